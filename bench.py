@@ -12,7 +12,10 @@ starts.  The timed region ROTATES over several distinct resident batches (``--ba
 steps never see the same scenes, the MLP geometry is tuned on batch 0 only, and the parity check is made on the
 LAST batch the timed region submitted.
 
-One JSON line on rank 0: the contract fields plus
+One JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the contract fields (metric, value,
+unit, higher_is_better, dtype, ms_per_step) with the run's configuration and step-time tail.  ``--dump-outputs DIR``
+writes the boxes of the last timed step to DIR/boxes.npy (float32; inputs are seeded, so two builds compare output for
+output).  ``--full`` adds everything else, each a pass of its own after the timed region:
   parity_check — the boxes of the last timed step against the CPU spec-oracle on the same scenes (<= 1e-4, labels
                  exact); a failure makes the exit code non-zero;
   roofline     — the dominant kernel (the fused gather+MLP+max / MLP launches of a step) against the dense MFMA
@@ -109,6 +112,24 @@ def parity_check(got, want):
             "ok": bool(rel <= PARITY_TOL and labels),
             "against": "CPU spec-oracle (oracle/sad_oracle.c) on the same scenes; parity with the upstream "
                        "reference is unpinned (README-only, no implementation)"}
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_boxes(out_dir: str, boxes) -> str:
+    """Write the boxes a caller of the timed path received in its last step as ``out_dir/boxes.npy`` (float32).  Above
+    DUMP_MAX_BYTES a fixed, seeded sample of whole scenes is kept, in scene order, so the same arguments write the same
+    rows."""
+    import numpy as np
+    b = np.ascontiguousarray(boxes, dtype=np.float32)
+    if b.nbytes > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES // b[0].nbytes
+        b = b[np.sort(np.random.default_rng(0).choice(b.shape[0], keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, "boxes.npy")
+    np.save(path, b)
+    return path
 
 
 def step_tail(gaps) -> dict:
@@ -504,9 +525,11 @@ def measure(w: Workload, steps: int, warmup: int, rank: int, world: int, dev, ar
     assert out.shape == (world * B, cfg.n_cand, 9) and (bool(torch.isfinite(out).all()) or bool(os.environ.get("SAD_BENCH_WHATIF")))
     got_boxes = out[:B].cpu().numpy()          # rank 0's own scenes come first in the gathered tensor; batch `last`
     points, points_np = batches[last], batches_np[last]
+    if detail and rank == 0 and args.dump_outputs:
+        dump_boxes(args.dump_outputs, out.cpu().numpy())
 
     quality = None
-    if w.dtype == "bf16" and rank == 0 and not getattr(args, "no_bf16_quality", False):
+    if args.full and w.dtype == "bf16" and rank == 0 and not getattr(args, "no_bf16_quality", False):
         # the bf16 mode against the f32 detector on the batch the timed region ended with (same weights; serial, traced passes)
         det32 = SADDetector(cfg, weights, dev, overlap_fps=False, n_main_streams=w.main_streams, dtype="f32", streams=streams)
         det.overlap_fps, ov = False, det.overlap_fps
@@ -524,7 +547,7 @@ def measure(w: Workload, steps: int, warmup: int, rank: int, world: int, dev, ar
         del det32, tr_b, tr_f, b_bf, b_32
         torch.cuda.empty_cache()
 
-    log = None if args.no_launch_timing else []
+    log = [] if args.full and not args.no_launch_timing else None
     timed_steps = 0
     if log is not None and detail:
         for i in range(16):
@@ -839,7 +862,7 @@ def measure(w: Workload, steps: int, warmup: int, rank: int, world: int, dev, ar
             res["mlp_launch_order"] = [n for k, n, _, _ in ser_log if k == "mlp"]
 
     # ---- dense leg: the same kernels with the padding skip off (every grouped row computed) ----
-    if detail and not args.no_dense_leg and w.dtype == "f32" and world == 1:
+    if args.full and detail and not args.no_dense_leg and w.dtype == "f32" and world == 1:
         _lib.set_option("mlp_nodedup", 1)
         try:
             for _ in range(2):
@@ -1033,15 +1056,15 @@ def main():
     ap.add_argument("--main-streams", type=int, default=2, help="main streams used round-robin by consecutive steps")
     ap.add_argument("--queue-depth", type=int, default=None,
                     help="steps in flight before the host waits for the oldest (default: max(6, sampling streams + 2))")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg (parity_check then uses 4 scenes)")
-    ap.add_argument("--cpu-scenes", type=int, default=32)
-    ap.add_argument("--no-launch-timing", action="store_true", help="skip the per-launch event passes (roofline / kernels)")
-    ap.add_argument("--no-dense-leg", action="store_true")
-    ap.add_argument("--no-legs", action="store_true", help="skip the secondary bf16_leg / configs4_leg / pipeline_leg of the default run")
-    ap.add_argument("--no-bf16-quality", action="store_true", help="bf16 runs: skip the comparison with the f32 detector on the last batch")
-    ap.add_argument("--pipeline-steps", type=int, default=150, help="timed steps of the pipeline_leg (files -> H2D -> subsample_pad -> detector -> NMS -> D2H)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg (parity_check then uses 4 scenes)")
+    ap.add_argument("--cpu-scenes", type=int, default=32, help="--full: scenes of the cpu_baseline sample")
+    ap.add_argument("--no-launch-timing", action="store_true", help="--full: skip the per-launch event passes (roofline / kernels)")
+    ap.add_argument("--no-dense-leg", action="store_true", help="--full: skip the dense_leg")
+    ap.add_argument("--no-legs", action="store_true", help="--full: skip the secondary bf16_leg / configs4_leg / pipeline_leg of the default run")
+    ap.add_argument("--no-bf16-quality", action="store_true", help="--full, bf16 runs: skip the comparison with the f32 detector on the last batch")
+    ap.add_argument("--pipeline-steps", type=int, default=150, help="--full: timed steps of the pipeline_leg (files -> H2D -> subsample_pad -> detector -> NMS -> D2H)")
     ap.add_argument("--leg-steps", type=int, nargs=2, default=(300, 80), metavar=("BF16", "CONFIGS4"),
-                    help="timed steps of the two secondary legs")
+                    help="--full: timed steps of the two secondary legs")
     ap.add_argument("--no-autotune", action="store_true", help="use the built-in geometry heuristic")
     ap.add_argument("--geometry-file", default=None,
                     help="JSON {launch name: geometry code} from --save-geometry: no autotune launches (rocprof runs)")
@@ -1056,7 +1079,14 @@ def main():
                     help="bf16 = SPEC.md 14 mode (configs[4]): MLPs on the bf16 matrix cores; "
                          "the headline metric is the f32 default")
     ap.add_argument("--opt", action="append", default=[], help="tuning knob key=value (sad_set_option)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the per-launch roofline / kernel passes, dense_leg, parity_check against the "
+                         "CPU oracle, cpu_baseline, bf16_quality and the secondary legs (the --no-* options above trim this)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the boxes of the last timed step to DIR/boxes.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` as the driver runs it: start the N ranks ourselves (as a child process, before
@@ -1111,7 +1141,7 @@ def main():
                     args.queue_depth, args.batches, overlap=not args.no_overlap, first_batch=args.first_batch)
     res, rc, ctx = measure(head, args.steps, args.warmup, rank, world, dev, args, detail=True)
 
-    if rank == 0:
+    if rank == 0 and args.full:
         cfg, weights, points_np = ctx["cfg"], ctx["weights"], ctx["points_np"]
         want = None
         if not args.no_cpu and world == 1:
@@ -1134,7 +1164,7 @@ def main():
 
     # ---- secondary legs of the default run (one GPU, the headline workload): the bf16 mode on the same scenes, and
     # BASELINE configs[4] on its own shape; short, after the headline, each a full measurement of its own detector
-    default_run = (world == 1 and args.config == "kitti" and args.scene == "kitti" and args.dtype == "f32"
+    default_run = (args.full and world == 1 and args.config == "kitti" and args.scene == "kitti" and args.dtype == "f32"
                    and not args.no_legs and not args.no_overlap and not args.opt)
     if default_run:
         import copy

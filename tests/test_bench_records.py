@@ -99,3 +99,17 @@ def test_dispatch_bound_picks_the_larger_roofline():
     d = bench.dispatch_bound(76e9, 300e6, 0.86, 157.3)
     assert d["bound"] == "mfma" and abs(d["frac_of_bound"] - 0.5618) < 1e-3
     assert bench.bytes_of("a+b", {"a": 3, "b": 4, "c": 9}) == 7
+
+
+def test_dump_boxes_is_float32_bounded_and_seeded(tmp_path, monkeypatch):
+    b = _boxes(np.random.default_rng(2), 40, 8)
+    b[:, 0, 0] = np.arange(40)                                          # scene i is told apart by its first value
+    got = np.load(bench.dump_boxes(str(tmp_path / "all"), b.astype(np.float64)))
+    assert got.dtype == np.float32 and np.array_equal(got, b)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 5 * b[0].nbytes)      # over the cap: a fixed sample of whole scenes
+    s1 = np.load(bench.dump_boxes(str(tmp_path / "s1"), b))
+    s2 = np.load(bench.dump_boxes(str(tmp_path / "s2"), b))
+    assert s1.shape == (5, 8, 9) and s1.nbytes <= bench.DUMP_MAX_BYTES and np.array_equal(s1, s2)
+    idx = s1[:, 0, 0].astype(int)
+    assert np.all(np.diff(idx) > 0)                                     # in scene order
+    assert np.array_equal(s1, b[idx])                                   # whole scenes, unchanged

@@ -5,8 +5,8 @@ out=gpurun_out/${1:-runs}
 n=${2:-3}
 mkdir -p $out
 for r in $(seq 1 $n); do
-  python bench.py > $out/default_$r.json 2> $out/default_$r.err
-  python bench.py --gpus 1 --steps 20 --warmup 5 > $out/driver_$r.json 2> $out/driver_$r.err
+  python bench.py --full > $out/default_$r.json 2> $out/default_$r.err
+  python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/driver_$r.json 2> $out/driver_$r.err
 done
 python - $out <<'P'
 import json, glob, sys

@@ -3,7 +3,7 @@
 for r in $(seq 1 ${1:-3}); do
   for m in fused split; do
     E=""; [ $m = split ] && E=1
-    SAD_F32_NO_FUSE_HEAD=$E timeout -k 10 300 python bench.py --no-cpu --no-dense-leg --no-launch-timing --no-legs --steps 200 --warmup 10 2>/dev/null | python -c "
+    SAD_F32_NO_FUSE_HEAD=$E timeout -k 10 300 python bench.py --full --no-cpu --no-dense-leg --no-launch-timing --no-legs --steps 200 --warmup 10 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$m round $r:', d['value'], d['ms_per_step'], d.get('parity_check',{}).get('ok'), {k:v for k,v in d['config']['mlp_geometry'].items() if 'agg' in k or 'head' in k})"
   done
 done

@@ -3,7 +3,7 @@ set -eo pipefail
 out=gpurun_out/${1:-light1}
 mkdir -p $out
 python bench.py --save-geometry $out/geom.json --no-legs --no-cpu --steps 20 --warmup 5 > $out/tune.json 2> $out/tune.err
-A="--geometry-file $out/geom.json --no-legs --no-cpu --no-dense-leg --no-launch-timing --steps 200 --warmup 14"
+A="--geometry-file $out/geom.json --no-legs --no-cpu --no-dense-leg --no-launch-timing --steps 200 --warmup 14 --full"
 for r in 1 2 3; do
   python bench.py $A > $out/plain_$r.json 2> $out/plain_$r.err
   SAD_LIGHT=0 python tools/probe/bench_light_events.py $A > $out/ctl_$r.json 2> $out/ctl_$r.err

@@ -3,7 +3,7 @@ set -eo pipefail
 out=gpurun_out/${1:-minst}
 mkdir -p $out
 python bench.py --save-geometry $out/g32.json --no-legs --no-cpu --steps 20 --warmup 5 > $out/t32.json 2> $out/t32.err
-C="--geometry-file $out/g32.json --no-legs --no-cpu --no-dense-leg"
+C="--geometry-file $out/g32.json --no-legs --no-cpu --no-dense-leg --full"
 for r in 1 2 3; do
   python bench.py $C > $out/all8_$r.json 2> $out/all8_$r.err
   python tools/probe/bench_min_streams.py $C --fps-streams 3 > $out/min3_$r.json 2> $out/min3_$r.err

@@ -8,7 +8,7 @@ if [ ! -f $geom ]; then
 fi
 for r in $(seq 1 $rounds); do
   for v in "$@"; do
-    timeout -k 10 300 python bench.py --no-cpu --no-dense-leg --no-launch-timing --no-legs --no-bf16-quality --steps ${STEPS:-400} --warmup 10 $bargs --geometry-file $geom --opt $key=$v > $out/${key}${v}_$r.json 2> $out/${key}${v}_$r.err
+    timeout -k 10 300 python bench.py --full --no-cpu --no-dense-leg --no-launch-timing --no-legs --no-bf16-quality --steps ${STEPS:-400} --warmup 10 $bargs --geometry-file $geom --opt $key=$v > $out/${key}${v}_$r.json 2> $out/${key}${v}_$r.err
     python - <<PY
 import json
 try:

@@ -5,7 +5,7 @@ set -eo pipefail
 out=gpurun_out/${1:-place1}
 mkdir -p $out
 python bench.py --save-geometry $out/geom.json --no-legs --no-cpu --steps 20 --warmup 5 > $out/tune.json 2> $out/tune.err
-A="--geometry-file $out/geom.json --no-cpu --no-dense-leg"
+A="--geometry-file $out/geom.json --no-cpu --no-dense-leg --full"
 for r in 1 2 3; do
   SAD_NO_STREAM_PLACEMENT=1 python bench.py $A > $out/off_$r.json 2> $out/off_$r.err
   python bench.py $A > $out/on_$r.json 2> $out/on_$r.err

@@ -3,10 +3,10 @@ tag=${1:-r02}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=gpurun_out/prof_$tag; rm -rf $out; mkdir -p $out
 # 1. the default bench line (autotuned), saving the geometry it used
-python3 bench.py --save-geometry $out/geometry.json > $out/bench.log 2>&1 || { tail -3 $out/bench.log; exit 1; }
+python3 bench.py --full --save-geometry $out/geometry.json > $out/bench.log 2>&1 || { tail -3 $out/bench.log; exit 1; }
 grep -E '^\{' $out/bench.log > $out/bench.json
 # 2. the same command under rocprofv3 (kernel stats of the timed configuration; geometry from the file: no autotune launches)
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/timed -- python3 bench.py --no-cpu --no-dense-leg --geometry-file $out/geometry.json > $out/timed.log 2>&1 || { tail -3 $out/timed.log; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/timed -- python3 bench.py --full --no-cpu --no-dense-leg --geometry-file $out/geometry.json > $out/timed.log 2>&1 || { tail -3 $out/timed.log; exit 1; }
 grep -E '^\{' $out/timed.log > $out/bench_under_rocprof.json
 # 3. serial run (one stream, nothing overlapped): kernel intervals = kernel durations
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/serial -- python3 bench.py --no-cpu --no-dense-leg --no-launch-timing --main-streams 1 --no-overlap --steps 20 --warmup 2 --geometry-file $out/geometry.json > $out/serial.log 2>&1 || { tail -3 $out/serial.log; exit 1; }

@@ -28,11 +28,11 @@ serial() {  # serial <name> <bench args...>: one stream, nothing overlapped -> k
 for part in $parts; do case $part in
 f32)
   # the default bench line (autotuned, with the CPU leg), saving the geometry it used; the driver's setting; rocprof of the timed configuration
-  python3 bench.py --save-geometry $out/geometry.json > $out/bench.log 2>&1 || { tail -3 $out/bench.log; exit 1; }
+  python3 bench.py --full --save-geometry $out/geometry.json > $out/bench.log 2>&1 || { tail -3 $out/bench.log; exit 1; }
   grep -E '^\{' $out/bench.log > $out/bench.json
-  python3 bench.py --steps 20 --warmup 5 --no-cpu --geometry-file $out/geometry.json 2>/dev/null | grep -E '^\{' > $out/bench_driver_setting.json
+  python3 bench.py --full --steps 20 --warmup 5 --no-cpu --geometry-file $out/geometry.json 2>/dev/null | grep -E '^\{' > $out/bench_driver_setting.json
   rm -rf $out/timed
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/timed -- python3 bench.py --no-cpu --no-dense-leg --geometry-file $out/geometry.json > $out/timed.log 2>&1 || { tail -3 $out/timed.log; exit 1; }
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/timed -- python3 bench.py --full --no-cpu --no-dense-leg --geometry-file $out/geometry.json > $out/timed.log 2>&1 || { tail -3 $out/timed.log; exit 1; }
   grep -E '^\{' $out/timed.log > $out/bench_under_rocprof.json
   cp $(ls $out/timed/*/*kernel_stats.csv | head -1) $out/timed_kernel_stats.csv
   serial serial --geometry-file $out/geometry.json || exit 1
@@ -48,7 +48,7 @@ pmc)
   run sq SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32
   ;;
 bf16)
-  python3 bench.py --dtype bf16 --no-cpu --save-geometry $out/bf16_geometry.json > $out/bf16_bench.log 2>&1 || { tail -3 $out/bf16_bench.log; exit 1; }
+  python3 bench.py --full --dtype bf16 --no-cpu --save-geometry $out/bf16_geometry.json > $out/bf16_bench.log 2>&1 || { tail -3 $out/bf16_bench.log; exit 1; }
   grep -E '^\{' $out/bf16_bench.log > $out/bf16_bench.json
   serial bf16_serial --dtype bf16 --geometry-file $out/bf16_geometry.json || exit 1
   python3 tools/roofline_from_profiles.py $out/bf16_serial_kernel_trace.csv $out/bf16_bench.json 20 | tee $out/bf16_roofline_from_profiles.txt
@@ -56,7 +56,7 @@ bf16)
   timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES --output-format csv -d $out/pmc_bf16sq -- python3 bench.py --dtype bf16 --no-cpu --geometry-file $out/bf16_geometry.json --no-launch-timing --main-streams 1 --no-overlap --steps 3 --warmup 1 > $out/pmc_bf16sq.log 2>&1 || tail -3 $out/pmc_bf16sq.log
   ;;
 nus)
-  python3 bench.py --config nuscenes --dtype bf16 --batch 32 --no-cpu --steps 40 --warmup 6 --save-geometry $out/nus_geometry.json > $out/nus_bench.log 2>&1 || { tail -3 $out/nus_bench.log; exit 1; }
+  python3 bench.py --full --config nuscenes --dtype bf16 --batch 32 --no-cpu --steps 40 --warmup 6 --save-geometry $out/nus_geometry.json > $out/nus_bench.log 2>&1 || { tail -3 $out/nus_bench.log; exit 1; }
   grep -E '^\{' $out/nus_bench.log > $out/nuscenes_bf16_bench.json
   serial nus_serial --config nuscenes --dtype bf16 --batch 32 --steps 4 --geometry-file $out/nus_geometry.json || exit 1
   python3 tools/roofline_from_profiles.py $out/nus_serial_kernel_trace.csv $out/nuscenes_bf16_bench.json 4 | tee $out/nuscenes_bf16_roofline_from_profiles.txt

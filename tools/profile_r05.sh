@@ -35,11 +35,11 @@ SQ="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIV
 for part in $parts; do case $part in
 f32)
   # the default bench line (rotating batches, legs, CPU leg), saving the geometry it used; the driver's setting; rocprof of the timed configuration
-  python3 bench.py --save-geometry $out/geometry.json > $out/bench.log 2>&1 || { tail -3 $out/bench.log; exit 1; }
+  python3 bench.py --full --save-geometry $out/geometry.json > $out/bench.log 2>&1 || { tail -3 $out/bench.log; exit 1; }
   grep -E '^\{' $out/bench.log > $out/bench.json
-  python3 bench.py --steps 20 --warmup 5 --geometry-file $out/geometry.json 2>/dev/null | grep -E '^\{' > $out/bench_driver_setting.json
+  python3 bench.py --full --steps 20 --warmup 5 --geometry-file $out/geometry.json 2>/dev/null | grep -E '^\{' > $out/bench_driver_setting.json
   rm -rf $out/timed
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/timed -- python3 bench.py --no-cpu --no-dense-leg --no-legs --geometry-file $out/geometry.json > $out/timed.log 2>&1 || { tail -3 $out/timed.log; exit 1; }
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/timed -- python3 bench.py --full --no-cpu --no-dense-leg --no-legs --geometry-file $out/geometry.json > $out/timed.log 2>&1 || { tail -3 $out/timed.log; exit 1; }
   grep -E '^\{' $out/timed.log > $out/bench_under_rocprof.json
   cp $(ls $out/timed/*/*kernel_stats.csv | head -1) $out/timed_kernel_stats.csv
   serial serial $out/bench.json --geometry-file $out/geometry.json || exit 1
@@ -50,7 +50,7 @@ pmc)
   pmc sq $SQ SQ_INSTS_VALU_MFMA_MOPS_F32 -- --geometry-file $out/geometry.json
   ;;
 bf16)
-  python3 bench.py --dtype bf16 --no-cpu --no-legs --save-geometry $out/bf16_geometry.json > $out/bf16_bench.log 2>&1 || { tail -3 $out/bf16_bench.log; exit 1; }
+  python3 bench.py --full --dtype bf16 --no-cpu --no-legs --save-geometry $out/bf16_geometry.json > $out/bf16_bench.log 2>&1 || { tail -3 $out/bf16_bench.log; exit 1; }
   grep -E '^\{' $out/bf16_bench.log > $out/bf16_bench.json
   serial bf16_serial $out/bf16_bench.json --dtype bf16 --geometry-file $out/bf16_geometry.json || exit 1
   python3 tools/roofline_from_profiles.py $out/bf16_serial_kernel_trace.csv $out/bf16_bench.json 20 | tee $out/bf16_roofline_from_profiles.txt
@@ -58,7 +58,7 @@ bf16)
   pmc bf16sq $SQ -- --dtype bf16 --no-overlap --geometry-file $out/bf16_geometry.json
   ;;
 nus)
-  python3 bench.py --config nuscenes --dtype bf16 --batch 32 --batches 2 --no-cpu --no-legs --steps 80 --warmup 8 --save-geometry $out/nus_geometry.json > $out/nus_bench.log 2>&1 || { tail -3 $out/nus_bench.log; exit 1; }
+  python3 bench.py --full --config nuscenes --dtype bf16 --batch 32 --batches 2 --no-cpu --no-legs --steps 80 --warmup 8 --save-geometry $out/nus_geometry.json > $out/nus_bench.log 2>&1 || { tail -3 $out/nus_bench.log; exit 1; }
   grep -E '^\{' $out/nus_bench.log > $out/nuscenes_bf16_bench.json
   rm -rf $out/nus_serial
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/nus_serial -- python3 bench.py --config nuscenes --dtype bf16 --batch 32 --no-cpu --no-dense-leg --no-legs --no-launch-timing --no-bf16-quality --main-streams 1 --no-overlap --batches 1 --first-batch $(pb $out/nuscenes_bf16_bench.json) --steps 4 --warmup 2 --geometry-file $out/nus_geometry.json > $out/nus_serial.log 2>&1 || { tail -3 $out/nus_serial.log; exit 1; }

@@ -109,6 +109,20 @@ def test_layer_streamed_chain_refuses_rows_beyond_4gib(sad):
     assert b"4 GiB" in L.sad_last_error()
 
 
+def test_nms_refuses_k_beyond_512(sad):
+    """SPEC §13 kernels rank at most 512 boxes per scene: K = 513 is refused with SAD_EUNSUPPORTED by both entry points
+    before anything is launched, and has no workspace size."""
+    from sad_amd import _lib
+    L = _lib.lib()
+    p = 0x10000                                               # never dereferenced: the call fails on the host
+    assert L.sad_nms_bev_f32(p, 1, 513, 0.5, 0.0, p, p, p, None) == -2
+    assert b"513" in L.sad_last_error()
+    assert L.sad_nms_bev_ws_f32(p, 1, 513, 0.5, 0.0, p, p, p, p, None) == -2
+    assert b"513" in L.sad_last_error()
+    assert L.sad_nms_bev_workspace_bytes(1, 513) == 0
+    assert L.sad_nms_bev_workspace_bytes(1, 512) > 0
+
+
 def test_split_pooling_boundary_checks(sad):
     """ABI 4 (split pooling): sizes and refusals that need no GPU.  A table grows by one int per group, a continuation buffer has one row per
     32-row tile + the zero row, and the layer that reads split-pooled rows is ONE plain layer of bf16 rows on the row-streaming kernel."""

@@ -19,6 +19,7 @@ _LAZY = {
     "fps": "ops", "ball_query": "ops", "ball_query_multi": "ops", "knn_query": "ops",
     "group_points": "ops", "gather_points": "ops", "gather_xyz": "ops",
     "mlp_chain": "ops", "PackedMLP": "ops", "nms_bev": "ops",
+    "three_nn": "ops", "three_interpolate": "ops", "FPModule": "fp_module",
     "SAModuleMSG": "sa_module", "SAModule": "sa_module", "sa_module": "sa_module",
     "SADDetector": "detector", "IngestPipeline": "pipeline",
     "shard_range": "dist", "all_gather_boxes": "dist", "run_sharded": "dist",

@@ -91,6 +91,9 @@ SIGNATURES = {
     "sad_subsample_pad_f32": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint, vp, vp]),
     "sad_copy_rows_u32": (ctypes.c_int, [vp, ctypes.c_longlong, vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, vp]),
     "sad_knn_f32": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 4 + [vp, vp]),
+    "sad_three_nn_f32": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 3 + [vp, vp, vp, vp]),
+    "sad_three_interpolate_f32": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 5 + [vp, ctypes.c_int, ctypes.c_int, vp]),
+    "sad_three_interpolate_grad_f32": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 5 + [vp, vp]),
     "sad_mlp_packed_floats": (ctypes.c_size_t, [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int]),
     "sad_mlp_pack_f32": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
                                        ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp]),

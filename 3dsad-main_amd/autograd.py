@@ -109,6 +109,46 @@ class MaxPoolS(torch.autograd.Function):
         return gx
 
 
+def three_interpolate_grad(grad_out: torch.Tensor, idx: torch.Tensor, w: torch.Tensor, m: int,
+                           point_major: bool = False) -> torch.Tensor:
+    """SPEC.md §18: grad_out [B,C,n] (or [B,n,C] with ``point_major=True``), idx / w [B,n,3] -> grad_feat [B,C,m] (or [B,m,C]):
+    ``grad_feat[.., idx_k] += w_k * grad_out``.  The sum is formed point-major (contiguous float atomics) and transposed at the
+    end for the channel-major layout.  idx and w get no gradient."""
+    grad_out = _f32(grad_out, "grad_out", 3)
+    if idx.dtype != torch.int32 or not idx.is_cuda:
+        raise TypeError("idx: expected a GPU int32 tensor")
+    w = _f32(w, "w", 3)
+    idx = idx.contiguous()
+    if point_major:
+        B, n, C = grad_out.shape
+    else:
+        B, C, n = grad_out.shape
+    if tuple(idx.shape) != (B, n, 3) or tuple(w.shape) != (B, n, 3):
+        raise ValueError("idx and w must be [B,n,3]")
+    g = torch.zeros((B, m, C), dtype=torch.float32, device=grad_out.device)
+    check(lib().sad_three_interpolate_grad_f32(grad_out.data_ptr(), idx.data_ptr(), w.data_ptr(), B, C, n, m, int(bool(point_major)),
+                                               g.data_ptr(), _stream()), "sad_three_interpolate_grad_f32")
+    return g if point_major else g.transpose(1, 2).contiguous()
+
+
+class ThreeInterpolate(torch.autograd.Function):
+    """features [B,C,m] f32 (or [B,m,C] with point_major), idx [B,n,3] int32, w [B,n,3] f32 -> [B,C,n] (or [B,n,C]).
+    Gradient for the features only: idx and w get none (as in the libraries this replaces)."""
+
+    @staticmethod
+    def forward(ctx, features, idx, w, point_major=False):
+        ctx.save_for_backward(idx, w)
+        ctx.point_major = bool(point_major)
+        ctx.m = features.shape[1] if point_major else features.shape[2]
+        return ops.three_interpolate(_f32(features, "features", 3), idx, w, point_major=point_major)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        idx, w = ctx.saved_tensors
+        return three_interpolate_grad(grad_out, idx, w, ctx.m, point_major=ctx.point_major), None, None, None
+
+
 group_points = GroupPoints.apply
 gather_points = GatherPoints.apply
 max_pool_s = MaxPoolS.apply
+three_interpolate = ThreeInterpolate.apply

@@ -45,6 +45,7 @@ SAD_API int sad_set_option(const char *key, int value) {
     if (!strcmp(key, "group_variant")) { sad::g_opt[sad::OPT_GROUP_VARIANT].store(value, std::memory_order_relaxed); return SAD_OK; }   // 1 = L2-gather kernel only
     if (!strcmp(key, "bq_variant")) { sad::g_opt[sad::OPT_BQ_VARIANT].store(value, std::memory_order_relaxed); return SAD_OK; }
     if (!strcmp(key, "fps_threads")) { sad::g_opt[sad::OPT_FPS_THREADS].store(value, std::memory_order_relaxed); return SAD_OK; }
+    if (!strcmp(key, "nn_variant")) { sad::g_opt[sad::OPT_NN_VARIANT].store(value, std::memory_order_relaxed); return SAD_OK; }   // three_nn: 1 = scalar loads, 2 = LDS with two points per lane
     if (!strcmp(key, "fps_variant")) { sad::g_opt[sad::OPT_FPS_VARIANT].store(value, std::memory_order_relaxed); return SAD_OK; }
     return sad::fail(SAD_EINVAL, "sad_set_option: unknown key '%s'", key);
 }

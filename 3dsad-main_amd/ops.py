@@ -420,6 +420,57 @@ def knn_query(k: int, xyz: torch.Tensor, new_xyz: torch.Tensor) -> torch.Tensor:
     return idx
 
 
+def three_nn(unknown: torch.Tensor, known: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The three nearest known points of every unknown point (SPEC.md §18).  unknown [B,n,3], known [B,m,3] f32, m >= 1 ->
+    (dist2 [B,n,3] f32 squared distances, idx [B,n,3] int32, w [B,n,3] f32 interpolation weights), ascending by (d2, j);
+    slots beyond m hold d2 = +inf, idx = 0, w = 0."""
+    unknown = _need(unknown, "unknown", torch.float32, 3)
+    known = _need(known, "known", torch.float32, 3)
+    B, n, three = unknown.shape
+    if three != 3 or known.shape[2] != 3 or known.shape[0] != B:
+        raise ValueError("unknown [B,n,3] and known [B,m,3] expected")
+    m = known.shape[1]
+    dist2 = _empty((B, n, 3), dtype=torch.float32, device=unknown.device)
+    idx = _empty((B, n, 3), dtype=torch.int32, device=unknown.device)
+    w = _empty((B, n, 3), dtype=torch.float32, device=unknown.device)
+    with _timed("three_nn", f"n{n}m{m}"):
+        check(lib().sad_three_nn_f32(unknown.data_ptr(), known.data_ptr(), B, n, m, dist2.data_ptr(), idx.data_ptr(),
+                                     w.data_ptr(), _stream()), "sad_three_nn_f32")
+    return dist2, idx, w
+
+
+def three_interpolate(feat: torch.Tensor, idx: torch.Tensor, w: torch.Tensor, point_major: bool = False,
+                      out: Optional[torch.Tensor] = None, col_off: int = 0) -> torch.Tensor:
+    """Weighted sum of three known features per unknown point (SPEC.md §18), exact.  idx [B,n,3] int32 in [0,m), w [B,n,3] f32
+    (from ``three_nn`` or computed by the caller).  Channel-major: feat [B,C,m] -> [B,C,n].  ``point_major``: feat [B,m,C] ->
+    [B,n,C], or written into columns [col_off, col_off + C) of a contiguous ``out`` [B,n,ld] (the other columns untouched)."""
+    feat = _need(feat, "feat", torch.float32, 3)
+    idx = _need(idx, "idx", torch.int32, 3)
+    w = _need(w, "w", torch.float32, 3)
+    B, n = idx.shape[0], idx.shape[1]
+    if idx.shape[2] != 3 or tuple(w.shape) != tuple(idx.shape) or feat.shape[0] != B:
+        raise ValueError("idx and w must be [B,n,3] and feat must have the same B")
+    C, m = (feat.shape[2], feat.shape[1]) if point_major else (feat.shape[1], feat.shape[2])
+    if point_major:
+        if out is None:
+            if col_off != 0:
+                raise ValueError("col_off needs an out buffer")
+            out = _empty((B, n, C), dtype=torch.float32, device=feat.device)
+        if (not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.dim() != 3
+                or tuple(out.shape[:2]) != (B, n) or out.device != feat.device):
+            raise ValueError("out: expected a contiguous float32 [B,n,ld] tensor on the device of feat")
+        ld = out.shape[2]
+    else:
+        if out is not None or col_off != 0:
+            raise ValueError("out / col_off apply to the point-major layout only")
+        out = _empty((B, C, n), dtype=torch.float32, device=feat.device)
+        ld = n
+    with _timed("three_interpolate", f"C{C}" + ("pm" if point_major else "cm")):
+        check(lib().sad_three_interpolate_f32(feat.data_ptr(), idx.data_ptr(), w.data_ptr(), B, C, m, n, int(bool(point_major)),
+                                              out.data_ptr(), ld, int(col_off), _stream()), "sad_three_interpolate_f32")
+    return out
+
+
 def nms_bev_buffers(B: int, K: int, device) -> tuple:
     """(keep [B,K], order [B,K], count [B], workspace) for ``nms_bev(..., out=...)``: a caller that runs NMS every step
     allocates them once (pipeline.py)."""

@@ -167,6 +167,25 @@ int sad_subsample_pad_f32(const float *points, const int32_t *offsets, int B, in
 int sad_copy_rows_u32(const void *src, long long src_stride_words, void *dst, long long dst_stride_words,
                       long long n_rows, long long row_words, sad_stream_t stream);
 
+/* SPEC.md §18 (feature propagation).  Additions of ABI 4: the version is unchanged.
+ * three_nn: unknown[B,n,3], known[B,m,3] (m >= 1) -> dist2[B,n,3], idx[B,n,3]: the three smallest (d2, j), ascending,
+ * ties -> lowest j; slots k >= m hold d2 = +inf, idx = 0.  w (may be NULL) -> [B,n,3] interpolation weights of §18.
+ * Option "nn_variant": 0 LDS tiles, one unknown point per lane (default); 1 scalar loads; 2 LDS tiles, two points per lane.
+ * three_interpolate: out = (w0*f[idx0] + w1*f[idx1]) + w2*f[idx2], exact.  point_major = 0: feat[B,C,m] -> out[B,C,n]
+ * (ld_out = n, col_off = 0); point_major = 1: feat[B,m,C] -> out[(b*n+i)*ld_out + col_off + c] (ld_out >= col_off + C):
+ * a column slice of wider rows, the other columns untouched.  Indices must be in [0,m) (one outside reads a zero feature).
+ * three_interpolate_grad: grad_out [B,C,n] (point_major = 0) or [B,n,C] (1), idx, w -> grad_feat_pm[B,m,C] += w_k * grad_out
+ * at idx_k (float atomics, order unspecified; zero or a gradient to accumulate into on entry).  Always point-major: transpose
+ * afterwards for [B,C,m].  idx and w get no gradient. */
+int sad_three_nn_f32(const float *unknown, const float *known, int B, int n, int m, float *dist2,
+                     int32_t *idx, float *w, sad_stream_t stream);
+int sad_three_interpolate_f32(const float *feat, const int32_t *idx, const float *w, int B, int C,
+                              int m, int n, int point_major, float *out, int ld_out, int col_off,
+                              sad_stream_t stream);
+int sad_three_interpolate_grad_f32(const float *grad_out, const int32_t *idx, const float *w, int B,
+                                   int C, int n, int m, int point_major, float *grad_feat_pm,
+                                   sad_stream_t stream);
+
 /* SPEC.md §4.  -> idx[B,M,K] sorted by (d2, index); K <= 64, K <= N. */
 int sad_knn_f32(const float *xyz, const float *new_xyz, int B, int N, int M, int K, int32_t *idx,
                 sad_stream_t stream);

@@ -115,19 +115,23 @@ __global__ __launch_bounds__(256) void knn_kernel(const float *__restrict__ xyz,
     float ld = __builtin_inff();  // sorted list, ascending (d2, j); lanes >= K stay +inf
     int lj = 0;
     float worst = __builtin_inff();
+    // entries of the list in use (wave-uniform).  A list that is not full takes any d2, +inf included: finite points whose
+    // squared distance overflows are ordinary candidates (SPEC.md §4 orders them by index behind the finite ones), and
+    // `d < worst` alone left index 0 in their place
+    int filled = 0;
     for (int base = 0; base < N; base += 64) {
         const int j = base + lane;
         const bool valid = j < N;
         const int jj = valid ? j : N - 1;
         const float d = sad::d2f(p[jj * 3 + 0], p[jj * 3 + 1], p[jj * 3 + 2], cx, cy, cz);
-        unsigned long long mask = __ballot(valid && d < worst);
+        unsigned long long mask = __ballot(valid && (d < worst || filled < K));
         while (mask) {
             const int l = __builtin_ctzll(mask);
             mask &= mask - 1;
             const float xd = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, d), l));
-            if (!(xd < worst)) continue;  // the list tightened since the ballot
+            if (!(xd < worst) && filled >= K) continue;  // the list tightened since the ballot
             // equal d2 with a lower index is already in the list -> the new entry goes after it
-            const int pos = __builtin_popcountll(__ballot(ld <= xd));
+            const int pos = __builtin_popcountll(__ballot(lane < filled && ld <= xd));
             const float ud = __shfl_up(ld, 1, 64);
             const int uj = __shfl_up(lj, 1, 64);
             if (lane > pos) {
@@ -138,7 +142,8 @@ __global__ __launch_bounds__(256) void knn_kernel(const float *__restrict__ xyz,
                 lj = base + l;
             }
             if (lane >= K) ld = __builtin_inff();
-            worst = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ld), K - 1));
+            filled = filled < K ? filled + 1 : K;
+            worst = filled < K ? __builtin_inff() : __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ld), K - 1));
         }
     }
     if (lane < K) idx[((size_t)b * M + m) * K + lane] = lj;

@@ -13,9 +13,21 @@
 // lock) and scans it in ascending bit order with a wave-wide popcount prefix.  Either way the first
 // `nsample` accepted indices come out in ascending index order, exactly what SPEC.md §3's scan produces.
 //
-// Exactness: the accept test is the same sad::d2f(point, centroid) < r*r.  Pruning is conservative:
-// cell = floor((x - x0) * inv) is a monotone function of x in binary32, the cell edge is r_max *
-// 1.001 (or larger), so a point within r_max of the centroid lies at most one cell away per axis.
+// Exactness: the accept test is the same sad::d2f(point, centroid) < r*r.  Pruning is conservative BY AN ERROR BOUND
+// that the build enforces (a constant margin on the cell edge is not enough: with 1.001 r_max and ~30 000 cells along one
+// axis an accepted point was found TWO cells from its centroid; tests/edge_regimes.py `thin_line` keeps that scene).
+// Per axis, with u = 2^-24, edge = the cell edge, inv = fl(1 / edge) and s(x) = (x - x0) * inv in real arithmetic:
+//   * the kernel's t(x) = fl(fl(x - x0) * inv) carries two roundings, |t(x) - s(x)| <= (2u + u^2) |s(x)|, and |s| <= g + 1
+//     for every point of the scene and every centroid that can accept one (g = cells along the axis);
+//   * an accepted pair has fl(p - c)^2 <= d2 < fl(r_max^2), hence |p - c| <= r_max (1 + 3u), and edge * inv <= 1 + u, so
+//     |s(p) - s(c)| <= (1 + u - slack)(1 + 3u) with slack = (edge - r_max) * inv;
+//   * therefore |t(p) - t(c)| < 1 - slack + 4u (g + 2) (1 + 2u): the four roundings (two subtractions, two products) of at
+//     most half an ulp of extent * inv each.  floor() of two numbers less than 1 apart differs by at most 1 (the clamp of
+//     cell_coord is monotone and keeps that), so the 27-cell neighbourhood is complete whenever
+//         slack = (edge - r_max) * inv  >=  GRID_SLACK * (g_max + 2),   GRID_SLACK = 8u = 2^-21
+//     (twice the bound: the second-order terms and the two roundings of the test itself fit in the spare factor).
+// grid_build_kernel keeps growing the edge while the largest per-axis cell count breaks that inequality.  The starting
+// edge 1.001 r_max satisfies it up to ~2 090 cells per axis: lidar scenes (a few hundred) keep the geometry they had.
 #include "common.h"
 
 namespace {
@@ -23,9 +35,10 @@ namespace {
 constexpr int GRID_MAXC = 32768;   // cells per scene (LDS histogram: 128 KB of the CU's 160 KB; the build runs one workgroup per CU)
 // The cell edge starts at 1.001 r_max and grows by this factor until the grid fits GRID_MAXC cells.  Round 1-3 doubled it
 // with 16 384 cells: a KITTI-shaped scene (70 x 80 x 2 m) at r_max = 0.8 ended with 1.6 m cells — 27 cells = a 4.8 m cube,
-// ~70 candidates per centroid of which ~3 are accepted — where 0.8 m cells (26 400 of them) give ~17.  Any edge >= r_max is
-// exact (header comment); the candidate count goes with its square.
+// ~70 candidates per centroid of which ~3 are accepted — where 0.8 m cells (26 400 of them) give ~17.  Any edge whose slack
+// covers the rounding of the cell coordinates is exact (header comment); the candidate count goes with its square.
 constexpr float GRID_GROW = 1.18920712f;   // 2^(1/4)
+constexpr float GRID_SLACK = 4.76837158203125e-07f;   // 2^-21 = 8u: (edge - r_max) * inv must reach GRID_SLACK * (cells along the longest axis + 2)
 constexpr int BUILD_T = 1024;
 
 struct GridHdr {      // 16 floats / ints at the start of each scene's workspace block
@@ -54,7 +67,7 @@ __device__ __forceinline__ int cell_coord(float x, float x0, float inv, int g) {
 // serves; larger scenes (N <= 65 536) walk global memory as before (PTS = 0).
 template <int PTS>
 __global__ __launch_bounds__(BUILD_T) void grid_build_kernel(const float *__restrict__ xyz, int N,
-                                                             float cs_min, char *__restrict__ ws) {
+                                                             float cs_min, float r_max, char *__restrict__ ws) {
     extern __shared__ int hist[];               // GRID_MAXC + 64 ints
     __shared__ float red[6][16];
     __shared__ int wsum[16];
@@ -137,11 +150,21 @@ __global__ __launch_bounds__(BUILD_T) void grid_build_kernel(const float *__rest
         gx = (int)fx + 1;
         gy = (int)fy + 1;
         gz = (int)fz + 1;
-        if ((long long)gx * gy * gz <= GRID_MAXC) break;
+        bool fits = (long long)gx * gy * gz <= GRID_MAXC, fl = false;
         // flat scenes (lidar: a few cells high): give up the z split before coarsening x and y — one cell in z keeps the
         // candidate count of the fine x-y grid (its three z layers were all visited anyway); 128 x 128 x 3 cells of a
         // 102 m nuScenes-shaped scene at r_max = 0.8 do not fit, 128 x 128 x 1 do
-        if (gz <= 4 && (long long)gx * gy <= GRID_MAXC) { gz = 1; flat = true; break; }
+        if (!fits && gz <= 4 && (long long)gx * gy <= GRID_MAXC) fits = fl = true;
+        if (fits) {
+            // the +-1-cell neighbourhood is complete only while the slack of the edge over r_max covers the rounding of the
+            // cell coordinates, which grows with the cell count along an axis (header comment); a given-up z axis has none
+            const int gzz = fl ? 1 : gz;
+            const int gm = gx > gy ? (gx > gzz ? gx : gzz) : (gy > gzz ? gy : gzz);
+            if ((cs - r_max) * inv >= GRID_SLACK * (float)(gm + 2)) {
+                if (fl) { gz = 1; flat = true; }
+                break;
+            }
+        }
         cs = cs * GRID_GROW;
     }
     if (!sane) {
@@ -770,18 +793,18 @@ SAD_API int sad_ball_query_grid_f32(const float *xyz, const float *new_xyz, int 
     const size_t blds = sizeof(int) * (GRID_MAXC + 64);
     if (N <= 4 * BUILD_T) {
         sad::lds_attr_once(attr_done4, reinterpret_cast<const void *>(&grid_build_kernel<4>), 144 * 1024);
-        hipLaunchKernelGGL(grid_build_kernel<4>, dim3(B), dim3(BUILD_T), blds, st, xyz, N, rmax * 1.001f, (char *)workspace);
+        hipLaunchKernelGGL(grid_build_kernel<4>, dim3(B), dim3(BUILD_T), blds, st, xyz, N, rmax * 1.001f, rmax, (char *)workspace);
     } else if (N <= 16 * BUILD_T) {
         sad::lds_attr_once(attr_done16, reinterpret_cast<const void *>(&grid_build_kernel<16>), 144 * 1024);
-        hipLaunchKernelGGL(grid_build_kernel<16>, dim3(B), dim3(BUILD_T), blds, st, xyz, N, rmax * 1.001f, (char *)workspace);
+        hipLaunchKernelGGL(grid_build_kernel<16>, dim3(B), dim3(BUILD_T), blds, st, xyz, N, rmax * 1.001f, rmax, (char *)workspace);
     } else {
         sad::lds_attr_once(attr_done0, reinterpret_cast<const void *>(&grid_build_kernel<0>), 144 * 1024);
-        hipLaunchKernelGGL(grid_build_kernel<0>, dim3(B), dim3(BUILD_T), blds, st, xyz, N, rmax * 1.001f, (char *)workspace);
+        hipLaunchKernelGGL(grid_build_kernel<0>, dim3(B), dim3(BUILD_T), blds, st, xyz, N, rmax * 1.001f, rmax, (char *)workspace);
     }
 #ifdef SAD_GRID_BUILD_TWICE  // measurement build: the grid build launched twice (idempotent: same tables) — what its time costs the pipelined step
-    if (N <= 4 * BUILD_T) hipLaunchKernelGGL(grid_build_kernel<4>, dim3(B), dim3(BUILD_T), blds, st, xyz, N, rmax * 1.001f, (char *)workspace);
-    else if (N <= 16 * BUILD_T) hipLaunchKernelGGL(grid_build_kernel<16>, dim3(B), dim3(BUILD_T), blds, st, xyz, N, rmax * 1.001f, (char *)workspace);
-    else hipLaunchKernelGGL(grid_build_kernel<0>, dim3(B), dim3(BUILD_T), blds, st, xyz, N, rmax * 1.001f, (char *)workspace);
+    if (N <= 4 * BUILD_T) hipLaunchKernelGGL(grid_build_kernel<4>, dim3(B), dim3(BUILD_T), blds, st, xyz, N, rmax * 1.001f, rmax, (char *)workspace);
+    else if (N <= 16 * BUILD_T) hipLaunchKernelGGL(grid_build_kernel<16>, dim3(B), dim3(BUILD_T), blds, st, xyz, N, rmax * 1.001f, rmax, (char *)workspace);
+    else hipLaunchKernelGGL(grid_build_kernel<0>, dim3(B), dim3(BUILD_T), blds, st, xyz, N, rmax * 1.001f, rmax, (char *)workspace);
 #endif
     if (int e = sad::check_launch("sad_ball_query_grid_f32 (build)")) return e;
     const char *ws = (const char *)workspace;

@@ -150,6 +150,15 @@ __device__ __forceinline__ unsigned wave_max_u32_bcast(unsigned v) {   // same, 
     v = o > v ? o : v;
     return __builtin_amdgcn_readlane(v, 63);
 }
+// A cell bucket's state (max min-distance, the lane that attains it) and its wave's best are made by the bucket's first update,
+// so the first step must update every real bucket.  Starting a bucket at +inf under the skip test dq < bmax was not enough:
+// for finite points far apart dq itself overflows to +inf, the bucket was skipped with lane 0 recorded as its best, and ties
+// at +inf then went to a lane instead of the lowest index.  A fresh bucket therefore holds a NaN pattern and the skip test
+// reads !(dq >= bmax): false for the NaN whatever dq is, and exactly dq < bmax afterwards (an update stores a real
+// min-distance; dq is never NaN for finite coordinates).  The NaN never reaches a key: it is overwritten before the wave's
+// first arg-max over the bucket maxima.
+constexpr unsigned BMAX_FRESH = 0x7fc00000u;
+
 __device__ __forceinline__ float clampf(float v, float lo, float hi) {
     v = v < lo ? lo : v;
     return v > hi ? hi : v;
@@ -391,7 +400,7 @@ __device__ __forceinline__ void fps_cell_body(const float *__restrict__ xyz, con
         if (lane == k) {
             blo0 = lo[0]; blo1 = lo[1]; blo2 = lo[2];
             bhi0 = hi[0]; bhi1 = hi[1]; bhi2 = hi[2];
-            bmax = any_real ? 0x7f800000u : 0u;   // +inf: the first step updates every real bucket
+            bmax = any_real ? BMAX_FRESH : 0u;   // +inf: the first step updates every real bucket
             bidx = 0x80000000u;
         }
     }
@@ -416,7 +425,7 @@ __device__ __forceinline__ void fps_cell_body(const float *__restrict__ xyz, con
         // all PPT skip tests at once: lane k tests bucket k (a never-active lane has bmax = 0)
         const float dq = sad::d2f(__builtin_amdgcn_fmed3f(cx, blo0, bhi0), __builtin_amdgcn_fmed3f(cy, blo1, bhi1),
                                   __builtin_amdgcn_fmed3f(cz, blo2, bhi2), cx, cy, cz);
-        unsigned act = __builtin_amdgcn_readfirstlane((unsigned)__ballot(dq < __builtin_bit_cast(float, bmax)));
+        unsigned act = __builtin_amdgcn_readfirstlane((unsigned)__ballot(!(dq >= __builtin_bit_cast(float, bmax))));   // (BMAX_FRESH is a NaN)
         FPS_T(tb);
         FPS_ACC(0, tb - ta);
         FPS_ACC(5, act ? 1 : 0);
@@ -713,7 +722,7 @@ __device__ __forceinline__ void cell2_step(Cell2<NW, PPT> &s, int lane, int *__r
     FPS2_ACC(6, 1);
     const float dq = sad::d2f(__builtin_amdgcn_fmed3f(s.cx, s.blo0, s.bhi0), __builtin_amdgcn_fmed3f(s.cy, s.blo1, s.bhi1),
                               __builtin_amdgcn_fmed3f(s.cz, s.blo2, s.bhi2), s.cx, s.cy, s.cz);
-    unsigned act = __builtin_amdgcn_readfirstlane((unsigned)__ballot(dq < __builtin_bit_cast(float, s.bmax)));
+    unsigned act = __builtin_amdgcn_readfirstlane((unsigned)__ballot(!(dq >= __builtin_bit_cast(float, s.bmax))));
 #if defined(SAD_FPS_ABL) && SAD_FPS_ABL == 1
     act = 0;                                  // ablation: no bucket updates (timing only, wrong results)
 #endif
@@ -828,7 +837,7 @@ __global__ __launch_bounds__(NW * 64) void fps_cell2_kernel(const float *__restr
         if (lane == k) {
             s.blo0 = lo[0]; s.blo1 = lo[1]; s.blo2 = lo[2];
             s.bhi0 = hi[0]; s.bhi1 = hi[1]; s.bhi2 = hi[2];
-            s.bmax = any_real ? 0x7f800000u : 0u;   // +inf: the first step updates every real bucket
+            s.bmax = any_real ? BMAX_FRESH : 0u;   // +inf: the first step updates every real bucket
         }
     }
     s.cx = p[0]; s.cy = p[1]; s.cz = p[2];
@@ -941,7 +950,7 @@ __global__ __launch_bounds__(NW * 64) void fps_cell3_kernel(const float *__restr
         if (lane == k) {
             blo0 = lo[0]; blo1 = lo[1]; blo2 = lo[2];
             bhi0 = hi[0]; bhi1 = hi[1]; bhi2 = hi[2];
-            bmax = any_real ? 0x7f800000u : 0u;   // +inf: the first round updates every real bucket
+            bmax = any_real ? BMAX_FRESH : 0u;   // +inf: the first round updates every real bucket
         }
     }
     if (tid < 32) {
@@ -987,7 +996,7 @@ __global__ __launch_bounds__(NW * 64) void fps_cell3_kernel(const float *__restr
         for (int i = 0; i < 4; ++i) {
             const float dq = sad::d2f(__builtin_amdgcn_fmed3f(cx[i], blo0, bhi0), __builtin_amdgcn_fmed3f(cy[i], blo1, bhi1),
                                       __builtin_amdgcn_fmed3f(cz[i], blo2, bhi2), cx[i], cy[i], cz[i]);
-            any = any || (dq < bmf);
+            any = any || !(dq >= bmf);
         }
         const bool more = P > 4;              // (wave-uniform)
         if (more) {
@@ -995,7 +1004,7 @@ __global__ __launch_bounds__(NW * 64) void fps_cell3_kernel(const float *__restr
             for (int i = 4; i < MP_KMAX; ++i) {
                 const float dq = sad::d2f(__builtin_amdgcn_fmed3f(cx[i], blo0, bhi0), __builtin_amdgcn_fmed3f(cy[i], blo1, bhi1),
                                           __builtin_amdgcn_fmed3f(cz[i], blo2, bhi2), cx[i], cy[i], cz[i]);
-                any = any || (dq < bmf);
+                any = any || !(dq >= bmf);
             }
         }
         unsigned rest = __builtin_amdgcn_readfirstlane((unsigned)__ballot(any));
@@ -1258,7 +1267,7 @@ __global__ __launch_bounds__(1024) void fps_cellg_kernel(const float4 *__restric
         if (lane == k) {
             blo0 = lo[0]; blo1 = lo[1]; blo2 = lo[2];
             bhi0 = hi[0]; bhi1 = hi[1]; bhi2 = hi[2];
-            bmax = any_real ? 0x7f800000u : 0u;
+            bmax = any_real ? BMAX_FRESH : 0u;
         }
     }
     float cx, cy, cz;
@@ -1282,7 +1291,7 @@ __global__ __launch_bounds__(1024) void fps_cellg_kernel(const float4 *__restric
     for (int i = 1; i < M; ++i) {
         const float dq = sad::d2f(__builtin_amdgcn_fmed3f(cx, blo0, bhi0), __builtin_amdgcn_fmed3f(cy, blo1, bhi1),
                                   __builtin_amdgcn_fmed3f(cz, blo2, bhi2), cx, cy, cz);
-        unsigned long long act = __ballot(dq < __builtin_bit_cast(float, bmax));
+        unsigned long long act = __ballot(!(dq >= __builtin_bit_cast(float, bmax)));
         if (act) {
             __builtin_amdgcn_s_setprio(3);       // (as in fps_cell_body: the disturbed wave's chain ahead of its idle siblings)
             do {
@@ -1460,7 +1469,7 @@ __global__ __launch_bounds__(1024) void fps_cellg_kernel(const float4 *__restric
     {                                                                                                                 \
         const float dq = sad::d2f(__builtin_amdgcn_fmed3f(cx, blo0, bhi0), __builtin_amdgcn_fmed3f(cy, blo1, bhi1),   \
                                   __builtin_amdgcn_fmed3f(cz, blo2, bhi2), cx, cy, cz);                               \
-        const unsigned long long act0 = __ballot(dq < __builtin_bit_cast(float, bmax));                               \
+        const unsigned long long act0 = __ballot(!(dq >= __builtin_bit_cast(float, bmax)));                            \
         unsigned long long act = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(act0 >> 32)) << 32) | \
                                  (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)act0);        \
         if ((act != 0ull) | (pending != 0u)) CELLG2_SLOW(BUF)                                                         \
@@ -1524,7 +1533,7 @@ __device__ __forceinline__ void cellg2_body(const float4 *__restrict__ rec_in, i
         if (lane == k) {
             blo0 = lo[0]; blo1 = lo[1]; blo2 = lo[2];
             bhi0 = hi[0]; bhi1 = hi[1]; bhi2 = hi[2];
-            bmax = any_real ? 0x7f800000u : 0u;
+            bmax = any_real ? BMAX_FRESH : 0u;
         }
     }
     float cx, cy, cz;

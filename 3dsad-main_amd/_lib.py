@@ -94,6 +94,9 @@ SIGNATURES = {
     "sad_three_nn_f32": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 3 + [vp, vp, vp, vp]),
     "sad_three_interpolate_f32": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 5 + [vp, ctypes.c_int, ctypes.c_int, vp]),
     "sad_three_interpolate_grad_f32": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 5 + [vp, vp]),
+    "sad_boxes_iou_f32": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 6 + [vp, vp]),
+    "sad_points_in_boxes_f32": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 4 + [vp, vp]),
+    "sad_roipoint_pool3d_f32": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_int, vp, vp, vp, vp]),
     "sad_mlp_packed_floats": (ctypes.c_size_t, [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int]),
     "sad_mlp_pack_f32": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
                                        ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp]),

@@ -471,6 +471,90 @@ def three_interpolate(feat: torch.Tensor, idx: torch.Tensor, w: torch.Tensor, po
     return out
 
 
+def _boxes(t: torch.Tensor, name: str, batched: bool = True) -> torch.Tensor:
+    """boxes [B,K,D] (or [K,D] when not ``batched``) f32 with D >= 7 fields (cx,cy,cz,l,w,h,yaw,...) (SPEC.md §19)."""
+    t = _need(t, name, torch.float32, 3 if batched else 2)
+    if t.shape[-1] < 7:
+        raise ValueError(f"{name}: box rows need at least 7 fields (cx,cy,cz,l,w,h,yaw), got {t.shape[-1]}")
+    return t
+
+
+def _boxes_iou(a: torch.Tensor, b: torch.Tensor, mode: int, kind: str) -> torch.Tensor:
+    batched = isinstance(a, torch.Tensor) and a.dim() == 3
+    a = _boxes(a, "a", batched)
+    b = _boxes(b, "b", batched)
+    if not batched:
+        a, b = a.unsqueeze(0), b.unsqueeze(0)
+    B, Ka, Da = a.shape
+    if b.shape[0] != B or b.device != a.device:
+        raise ValueError("a and b must have the same batch size and device")
+    Kb, Db = b.shape[1], b.shape[2]
+    iou = _empty((B, Ka, Kb), dtype=torch.float32, device=a.device)
+    with _timed("boxes_iou", f"{kind}Ka{Ka}Kb{Kb}"):
+        check(lib().sad_boxes_iou_f32(a.data_ptr(), b.data_ptr(), B, Ka, Kb, Da, Db, mode, iou.data_ptr(), _stream()),
+              "sad_boxes_iou_f32")
+    return iou if batched else iou[0]
+
+
+def boxes_iou_bev(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """Pairwise rotated BEV IoU (SPEC.md §19.3, = §13 ``iou_bev(a_i, b_j)``).  a [B,Ka,Da], b [B,Kb,Db] -> [B,Ka,Kb], or
+    unbatched a [Ka,Da], b [Kb,Db] -> [Ka,Kb]; rows of D >= 7 floats (cx,cy,cz,l,w,h,yaw,...).  No gradient."""
+    return _boxes_iou(a, b, 0, "bev")
+
+
+def boxes_iou3d(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """Pairwise rotated 3-D IoU (SPEC.md §19.3: the §13 BEV intersection times the z overlap over the union of the
+    volumes).  Shapes as ``boxes_iou_bev``.  No gradient."""
+    return _boxes_iou(a, b, 1, "3d")
+
+
+def points_in_boxes(xyz: torch.Tensor, boxes: torch.Tensor) -> torch.Tensor:
+    """For each point the lowest index of a box that contains it, else -1 (SPEC.md §19.1).  xyz [B,N,3] f32,
+    boxes [B,K,D] f32 (D >= 7, centre / size / yaw) -> box_idx [B,N] int32."""
+    xyz = _need(xyz, "xyz", torch.float32, 3)
+    boxes = _boxes(boxes, "boxes")
+    B, N, three = xyz.shape
+    if three != 3 or boxes.shape[0] != B or boxes.device != xyz.device:
+        raise ValueError("xyz [B,N,3] and boxes [B,K,D] on one device expected")
+    K, D = boxes.shape[1], boxes.shape[2]
+    box_idx = _empty((B, N), dtype=torch.int32, device=xyz.device)
+    with _timed("points_in_boxes", f"N{N}K{K}"):
+        check(lib().sad_points_in_boxes_f32(xyz.data_ptr(), boxes.data_ptr(), B, N, K, D, box_idx.data_ptr(), _stream()),
+              "sad_points_in_boxes_f32")
+    return box_idx
+
+
+def roipoint_pool3d(xyz: torch.Tensor, feat_pm: Optional[torch.Tensor], boxes: torch.Tensor, extra_width: float,
+                    num_sampled_points: int, return_idx: bool = False):
+    """RoI point pooling (SPEC.md §19.2).  Per box (enlarged by ``extra_width`` on every side) the first
+    ``num_sampled_points`` = S points in ascending index order, repeated cyclically when fewer fall inside.
+    xyz [B,N,3], feat_pm [B,N,C] point-major or None, boxes [B,K,D] -> (pooled [B,K,S,3+C] rows [xyz || feat],
+    empty [B,K] int32 1 = no point inside (rows zero)[, idx [B,K,S] int32]).  1 <= S <= 8192.  No gradient."""
+    xyz = _need(xyz, "xyz", torch.float32, 3)
+    boxes = _boxes(boxes, "boxes")
+    B, N, three = xyz.shape
+    if three != 3 or boxes.shape[0] != B or boxes.device != xyz.device:
+        raise ValueError("xyz [B,N,3] and boxes [B,K,D] on one device expected")
+    C = 0
+    if feat_pm is not None:
+        feat_pm = _need(feat_pm, "feat_pm", torch.float32, 3)
+        if tuple(feat_pm.shape[:2]) != (B, N) or feat_pm.device != xyz.device:
+            raise ValueError("feat_pm: expected [B,N,C] on the device of xyz")
+        C = feat_pm.shape[2]
+    S = int(num_sampled_points)
+    if S < 1:
+        raise ValueError(f"num_sampled_points={S} must be >= 1")
+    K, D = boxes.shape[1], boxes.shape[2]
+    pooled = _empty((B, K, S, 3 + C), dtype=torch.float32, device=xyz.device)
+    empty = _empty((B, K), dtype=torch.int32, device=xyz.device)
+    idx = _empty((B, K, S), dtype=torch.int32, device=xyz.device) if return_idx else None
+    with _timed("roipoint_pool3d", f"N{N}K{K}S{S}C{C}"):
+        check(lib().sad_roipoint_pool3d_f32(xyz.data_ptr(), feat_pm.data_ptr() if C else None, boxes.data_ptr(), B, N, K, D, C,
+                                            float(np.float32(extra_width)), S, pooled.data_ptr(), empty.data_ptr(),
+                                            idx.data_ptr() if return_idx else None, _stream()), "sad_roipoint_pool3d_f32")
+    return (pooled, empty, idx) if return_idx else (pooled, empty)
+
+
 def nms_bev_buffers(B: int, K: int, device) -> tuple:
     """(keep [B,K], order [B,K], count [B], workspace) for ``nms_bev(..., out=...)``: a caller that runs NMS every step
     allocates them once (pipeline.py)."""

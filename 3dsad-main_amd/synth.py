@@ -33,6 +33,26 @@ def make_scene(scene_id: int, n_points: int = 16384, extent=(0.0, 70.4, -40.0, 4
     return np.ascontiguousarray(pts.astype(np.float32))
 
 
+def scene_boxes(scene_id: int, n_points: int = 16384, extent=(0.0, 70.4, -40.0, 40.0), n_boxes: int = 40) -> np.ndarray:
+    """The ground-truth boxes of ``make_scene(scene_id, n_points, extent, n_boxes)`` -> float32 [n_boxes, 7] =
+    (cx, cy, cz, l, w, h, yaw), centre and size as in SPEC.md §19; rebuilt by replaying that function's random draws."""
+    rng = np.random.default_rng(1234 + scene_id)
+    x0, x1, y0, y1 = extent
+    n_obj = int(round(0.3 * n_points))
+    n_gnd = n_points - n_obj
+    rng.uniform(x0, x1, n_gnd)
+    rng.uniform(y0, y1, n_gnd)
+    rng.normal(-1.6, 0.1, n_gnd)
+    bc = np.stack([rng.uniform(x0 + 3, x1 - 3, n_boxes), rng.uniform(y0 + 3, y1 - 3, n_boxes)], 1)
+    yaw = rng.uniform(-np.pi, np.pi, n_boxes)
+    out = np.empty((n_boxes, 7), np.float32)
+    out[:, 0:2] = bc
+    out[:, 2] = -1.6 + 0.78
+    out[:, 3:6] = (3.9, 1.6, 1.56)
+    out[:, 6] = yaw
+    return out
+
+
 def make_batch(first_scene: int, batch: int, n_points: int = 16384, **kw) -> np.ndarray:
     """float32 [batch, n_points, 4]; scene ids first_scene .. first_scene+batch-1."""
     return np.stack([make_scene(first_scene + i, n_points, **kw) for i in range(batch)], 0)

@@ -186,6 +186,23 @@ int sad_three_interpolate_grad_f32(const float *grad_out, const int32_t *idx, co
                                    int C, int n, int m, int point_major, float *grad_feat_pm,
                                    sad_stream_t stream);
 
+/* SPEC.md §19 (box operators).  Additions of ABI 4: the version is unchanged.  Boxes are rows of D >= 7 floats
+ * (cx, cy, cz, l, w, h, yaw, ...), row stride D: the detector's 9-column boxes and 7-column boxes both pass.  No gradients.
+ * boxes_iou: a[B,Ka,Da], b[B,Kb,Db] -> iou[B,Ka,Kb]; mode SAD_IOU_BEV = §13 iou_bev(a_i, b_j), SAD_IOU_3D = §19.3.  Any K.
+ * points_in_boxes: xyz[B,N,3] -> box_idx[B,N] = the lowest k whose box contains the point (§19.1, e = 0), else -1.
+ * roipoint_pool3d: per box, the first S points (ascending n) inside the box enlarged by extra_width (§19.2), repeated
+ * cyclically -> pooled[B,K,S,3+C] rows [xyz || feat] (feat [B,N,C] point-major; NULL when C = 0), empty[B,K] (1: no point,
+ * rows and idx zero), idx[B,K,S] (may be NULL).  1 <= S <= 8192 (SAD_EUNSUPPORTED above: the selection is held in LDS). */
+#define SAD_IOU_BEV 0
+#define SAD_IOU_3D 1
+int sad_boxes_iou_f32(const float *a, const float *b, int B, int Ka, int Kb, int Da, int Db, int mode,
+                      float *iou, sad_stream_t stream);
+int sad_points_in_boxes_f32(const float *xyz, const float *boxes, int B, int N, int K, int D,
+                            int32_t *box_idx, sad_stream_t stream);
+int sad_roipoint_pool3d_f32(const float *xyz, const float *feat, const float *boxes, int B, int N,
+                            int K, int D, int C, float extra_width, int S, float *pooled,
+                            int32_t *empty, int32_t *idx, sad_stream_t stream);
+
 /* SPEC.md §4.  -> idx[B,M,K] sorted by (d2, index); K <= 64, K <= N. */
 int sad_knn_f32(const float *xyz, const float *new_xyz, int B, int N, int M, int K, int32_t *idx,
                 sad_stream_t stream);

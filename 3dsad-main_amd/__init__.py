@@ -21,6 +21,8 @@ _LAZY = {
     "mlp_chain": "ops", "PackedMLP": "ops", "nms_bev": "ops",
     "three_nn": "ops", "three_interpolate": "ops", "FPModule": "fp_module",
     "boxes_iou_bev": "ops", "boxes_iou3d": "ops", "points_in_boxes": "ops", "roipoint_pool3d": "ops",
+    "voxel_coords": "ops", "voxel_index": "ops", "voxelize": "ops", "voxel_reduce": "ops",
+    "Voxelization": "voxel", "DynamicScatter": "voxel",
     "SAModuleMSG": "sa_module", "SAModule": "sa_module", "sa_module": "sa_module",
     "SADDetector": "detector", "IngestPipeline": "pipeline",
     "shard_range": "dist", "all_gather_boxes": "dist", "run_sharded": "dist",

@@ -97,6 +97,12 @@ SIGNATURES = {
     "sad_boxes_iou_f32": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 6 + [vp, vp]),
     "sad_points_in_boxes_f32": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 4 + [vp, vp]),
     "sad_roipoint_pool3d_f32": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_int, vp, vp, vp, vp]),
+    "sad_voxel_workspace_bytes": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_size_t)]),
+    "sad_voxel_coords_f32": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 3 + [c_f32p, c_f32p, vp, vp]),
+    "sad_voxel_index_f32": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 3 + [c_f32p, c_f32p, ctypes.c_int, vp, vp, vp, vp, vp, vp]),
+    "sad_voxelize_f32": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 3 + [c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp]),
+    "sad_voxel_reduce_f32": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 5 + [vp, vp, vp, vp, vp]),
+    "sad_voxel_reduce_grad_f32": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 5 + [vp, vp, vp]),
     "sad_mlp_packed_floats": (ctypes.c_size_t, [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int]),
     "sad_mlp_pack_f32": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
                                        ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp]),

@@ -148,7 +148,34 @@ class ThreeInterpolate(torch.autograd.Function):
         return three_interpolate_grad(grad_out, idx, w, ctx.m, point_major=ctx.point_major), None, None, None
 
 
+class VoxelReduce(torch.autograd.Function):
+    """feat [total,Cf] f32, point2voxel [total] int32, offsets [B+1] int32 -> out [B,V,Cf] (SPEC.md §20.5).  Gradient for the
+    features only (a gather, exact); point2voxel and offsets get none.  ``mode`` "max" returns the values only."""
+
+    @staticmethod
+    def forward(ctx, feat, point2voxel, offsets, max_voxels, mode="mean"):
+        feat = _f32(feat, "feat", 2)
+        ctx.mode = mode
+        aux = None
+        if mode == "max":
+            out, aux = ops.voxel_reduce(feat, point2voxel, offsets, max_voxels, "max")
+        elif mode == "mean":
+            out, aux = ops.voxel_reduce(feat, point2voxel, offsets, max_voxels, "mean", return_count=True)
+        else:
+            out = ops.voxel_reduce(feat, point2voxel, offsets, max_voxels, mode)
+        ctx.has_aux = aux is not None
+        ctx.save_for_backward(*((point2voxel, offsets) + ((aux,) if aux is not None else ())))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        saved = ctx.saved_tensors
+        g = ops.voxel_reduce_grad(_f32(grad_out, "grad_out", 3), saved[0], saved[1], ctx.mode, saved[2] if ctx.has_aux else None)
+        return g, None, None, None, None
+
+
 group_points = GroupPoints.apply
+voxel_reduce = VoxelReduce.apply
 gather_points = GatherPoints.apply
 max_pool_s = MaxPoolS.apply
 three_interpolate = ThreeInterpolate.apply

@@ -1,0 +1,624 @@
+// Voxelization (SPEC.md §20): voxel_coords, the dynamic voxel index, hard voxelization and the ordered reduction over voxels.
+// Ragged input throughout: points[total, C] + offsets[B+1] (device).  Every result is a function of the input alone: atomics
+// are used only where their order cannot show (first row of a key = atomicMin, member counts = atomicAdd, placement inside
+// an UNORDERED member list that is ranked afterwards).
+//
+// voxel numbering (§20.2):
+//   insert   one lane per point: key = (gz*Gy + gy)*Gx + gx, inserted as (scene << 32 | key) into ONE open-addressing table
+//            of >= 2 * total slots (64-bit CAS, linear probing); the lowest row of a key is kept by atomicMin.
+//   flags    a point is an OPENER iff it is the first row of its key; per 64 rows a ballot's popcount.
+//   scan     one workgroup: exclusive scan of the per-64-row counts over ALL rows, then the prefix at every scene start: the
+//            voxel number of an opener is (openers before it) - (openers before its scene), numbers >= V are dropped — the
+//            walk-continues rule of §20.2 needs nothing more.
+//   number   openers write their number, the voxel's (z,y,x) and p2v; follow: the other points copy their opener's number
+//            and every taken point counts into count[b,v].
+// member order (§20.3 / §20.4 / §20.5): CSR over the voxels (segment starts = a scan of the counts), members placed with a
+// per-voxel cursor in arrival order, then RANKED: the rank of row i in its voxel is the number of members below i, so
+// sorted[start + rank] = i puts every list in ascending row order whatever the arrival order was (lists are a handful of
+// entries on LiDAR scenes; a list of length N costs N^2 compares of one broadcast load each and still comes out right).
+// voxelize writes voxels[B,V,T,C] exactly once, rows and zeros in the same pass.  voxel_reduce walks sorted lists, one
+// thread per (voxel, channel), one rounding per addition.  The backward is a gather.
+#include "common.h"
+#include <algorithm>
+#include <limits.h>
+#include <math.h>
+
+namespace {
+
+typedef unsigned long long u64;
+constexpr int VX_THREADS = 256;
+constexpr int VX_SCAN_THREADS = 1024;
+constexpr u64 VX_EMPTY = ~0ull;
+
+struct VoxGrid {
+    float lo[3], v[3], Gf[3];
+    int G[3];
+};
+
+// largest b in [0, B-1] with offsets[b] <= i: the scene that owns row i (empty scenes own nothing)
+__device__ __forceinline__ int scene_of(const int32_t *__restrict__ off, int B, int i) {
+    int lo = 0, hi = B - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// §20.1: one subtraction, one correctly rounded division, one floor per axis; validity compared as floats
+__device__ __forceinline__ bool voxel_of(const float *__restrict__ p, const VoxGrid &g, int &gx, int &gy, int &gz) {
+    const float dx = p[0] - g.lo[0], dy = p[1] - g.lo[1], dz = p[2] - g.lo[2];
+    const float qx = dx / g.v[0], qy = dy / g.v[1], qz = dz / g.v[2];
+    const float fx = floorf(qx), fy = floorf(qy), fz = floorf(qz);
+    const bool ok = fx >= 0.0f && fx < g.Gf[0] && fy >= 0.0f && fy < g.Gf[1] && fz >= 0.0f && fz < g.Gf[2];
+    gx = ok ? (int)fx : -1;
+    gy = ok ? (int)fy : -1;
+    gz = ok ? (int)fz : -1;
+    return ok;
+}
+
+__device__ __forceinline__ int wave_incl_scan(int x, int lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int t = __shfl_up(x, d);
+        if (lane >= d) x += t;
+    }
+    return x;
+}
+
+// exclusive scan over the VX_SCAN_THREADS threads of a workgroup; total = sum of all.  s_w: 17 ints of LDS
+__device__ __forceinline__ int block_excl_scan(int v, int *s_w, int &total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int inc = wave_incl_scan(v, lane);
+    __syncthreads();                                        // (s_w of a previous call is no longer read)
+    if (lane == 63) s_w[wave] = inc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int run = 0;
+        for (int w = 0; w < VX_SCAN_THREADS / 64; ++w) { const int t = s_w[w]; s_w[w] = run; run += t; }
+        s_w[VX_SCAN_THREADS / 64] = run;
+    }
+    __syncthreads();
+    total = s_w[VX_SCAN_THREADS / 64];
+    return s_w[wave] + inc - v;
+}
+
+// ---- voxel_coords ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(VX_THREADS) void voxel_coords_kernel(const float *__restrict__ points, const int32_t *__restrict__ offsets,
+                                                                  int total, int B, int C, VoxGrid g, int32_t *__restrict__ coors) {
+    const int i = blockIdx.x * VX_THREADS + threadIdx.x;
+    if (i >= total) return;
+    int gx, gy, gz;
+    voxel_of(points + (size_t)i * C, g, gx, gy, gz);
+    int4 *o = (int4 *)coors + i;
+    *o = make_int4(scene_of(offsets, B, i), gz, gy, gx);
+}
+
+// ---- numbering ------------------------------------------------------------------------------------------------
+// grid-stride fill of whatever is passed: the hash table (keys empty, first rows INT_MAX), per-voxel ints cnt / fill (0),
+// coors (-1)
+__global__ __launch_bounds__(VX_THREADS) void voxel_init_kernel(u64 *__restrict__ tkeys, int32_t *__restrict__ tvals, unsigned cap,
+                                                                int32_t *__restrict__ cnt, int32_t *__restrict__ fill,
+                                                                int32_t *__restrict__ coors, unsigned nvox) {
+    const unsigned stride = gridDim.x * VX_THREADS;
+    const unsigned t0 = blockIdx.x * VX_THREADS + threadIdx.x;
+    if (tkeys) {
+        for (unsigned s = t0; s < cap; s += stride) { tkeys[s] = VX_EMPTY; tvals[s] = INT_MAX; }
+    }
+    for (unsigned s = t0; s < nvox; s += stride) {
+        if (cnt) cnt[s] = 0;
+        if (fill) fill[s] = 0;
+    }
+    if (coors) {
+        for (unsigned s = t0; s < nvox; s += stride) {
+            coors[(size_t)s * 3 + 0] = -1;
+            coors[(size_t)s * 3 + 1] = -1;
+            coors[(size_t)s * 3 + 2] = -1;
+        }
+    }
+}
+
+__global__ __launch_bounds__(VX_THREADS) void voxel_insert_kernel(const float *__restrict__ points, const int32_t *__restrict__ offsets,
+                                                                  int total, int B, int C, VoxGrid g, u64 *tkeys, int32_t *tvals,
+                                                                  unsigned mask, int shift, int32_t *__restrict__ pslot) {
+    const int i = blockIdx.x * VX_THREADS + threadIdx.x;
+    if (i >= total) return;
+    int gx, gy, gz;
+    if (!voxel_of(points + (size_t)i * C, g, gx, gy, gz)) {
+        pslot[i] = -1;
+        return;
+    }
+    const int key = (gz * g.G[1] + gy) * g.G[0] + gx;
+    const u64 k64 = ((u64)(unsigned)scene_of(offsets, B, i) << 32) | (unsigned)key;
+    unsigned h = (unsigned)((k64 * 0x9E3779B97F4A7C15ull) >> shift);
+    int slot = -1;
+    // the table holds at most `total` keys in >= 2 * total slots: an empty slot is met long before a full round
+    for (unsigned n = 0; n <= mask; ++n) {
+        u64 cur = __hip_atomic_load(&tkeys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == VX_EMPTY) {
+            cur = atomicCAS(&tkeys[h], VX_EMPTY, k64);
+            if (cur == VX_EMPTY) cur = k64;
+        }
+        if (cur == k64) { slot = (int)h; break; }
+        h = (h + 1) & mask;
+    }
+    if (slot >= 0) {
+        // first rows only go down: a stale value is a larger one, so a point that sees a lower row can skip the atomic
+        if (__hip_atomic_load(&tvals[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > i) atomicMin(&tvals[slot], i);
+    }
+    pslot[i] = slot;
+}
+
+__device__ __forceinline__ bool is_opener(const int32_t *__restrict__ pslot, const int32_t *__restrict__ tvals, int i, int total) {
+    if (i >= total) return false;
+    const int s = pslot[i];
+    return s >= 0 && tvals[s] == i;
+}
+
+// wavecnt[w] = openers among rows 64 w .. 64 w + 63
+__global__ __launch_bounds__(VX_THREADS) void voxel_flags_kernel(const int32_t *__restrict__ pslot, const int32_t *__restrict__ tvals, int total,
+                                                                 int32_t *__restrict__ wavecnt) {
+    const int i = blockIdx.x * VX_THREADS + threadIdx.x;
+    const unsigned long long m = __ballot(is_opener(pslot, tvals, i, total));
+    if ((threadIdx.x & 63) == 0 && i < total) wavecnt[i >> 6] = __builtin_popcountll(m);
+}
+
+// one workgroup: a[0..n) -> exclusive prefix in place, a[n] = total
+__device__ __forceinline__ void scan_in_place(int32_t *a, int n, int *s_w) {
+    const int chunk = (n + VX_SCAN_THREADS - 1) / VX_SCAN_THREADS;
+    const int k0 = min(n, (int)threadIdx.x * chunk), k1 = min(n, k0 + chunk);
+    int sum = 0;
+    for (int k = k0; k < k1; ++k) sum += a[k];
+    int tot;
+    int run = block_excl_scan(sum, s_w, tot);
+    for (int k = k0; k < k1; ++k) { const int t = a[k]; a[k] = run; run += t; }
+    if (threadIdx.x == 0) a[n] = tot;
+    __syncthreads();
+}
+
+// wavecnt[nw + 1] -> exclusive prefixes; P[b] = openers in rows below offsets[b] (b = 0 .. B); voxel_num[b] = min(V, openers of b)
+__global__ __launch_bounds__(VX_SCAN_THREADS) void voxel_scan_kernel(int32_t *wavecnt, int nw, const int32_t *__restrict__ pslot,
+                                                                     const int32_t *__restrict__ tvals, const int32_t *__restrict__ offsets,
+                                                                     int total, int B, int V, int32_t *P, int32_t *__restrict__ voxel_num) {
+    __shared__ int s_w[VX_SCAN_THREADS / 64 + 1];
+    scan_in_place(wavecnt, nw, s_w);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int b = wave; b <= B; b += VX_SCAN_THREADS / 64) {
+        const int o = min(max(offsets[b], 0), total);
+        const int w = o >> 6, r = (w << 6) + lane;
+        const unsigned long long m = __ballot(r < o && is_opener(pslot, tvals, r, total));
+        if (lane == 0) P[b] = wavecnt[w] + __builtin_popcountll(m);      // (w <= nw: wavecnt[nw] is the total)
+    }
+    __syncthreads();
+    for (int b = threadIdx.x; b < B; b += VX_SCAN_THREADS) voxel_num[b] = min(max(P[b + 1] - P[b], 0), V);
+}
+
+// openers: voxel number, p2v and the voxel's (z,y,x); invalid points: p2v = -1
+__global__ __launch_bounds__(VX_THREADS) void voxel_number_kernel(const int32_t *__restrict__ pslot, const u64 *__restrict__ tkeys,
+                                                                  const int32_t *__restrict__ tvals, const int32_t *__restrict__ offsets,
+                                                                  const int32_t *__restrict__ wavepre, const int32_t *__restrict__ P, int total,
+                                                                  int B, int V, int Gx, int Gy, int32_t *__restrict__ p2v,
+                                                                  int32_t *__restrict__ coors) {
+    const int i = blockIdx.x * VX_THREADS + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const int slot = i < total ? pslot[i] : -1;
+    const bool open = slot >= 0 && tvals[slot] == i;
+    const unsigned long long m = __ballot(open);
+    if (i >= total) return;
+    if (slot < 0) { p2v[i] = -1; return; }
+    if (!open) return;
+    const int b = scene_of(offsets, B, i);
+    const int vn = wavepre[i >> 6] + __builtin_popcountll(m & ((1ull << lane) - 1ull)) - P[b];
+    if (vn < 0 || vn >= V) { p2v[i] = -1; return; }       // the voxel cap: this key is dropped, with every later point of it
+    p2v[i] = vn;
+    const int key = (int)(unsigned)(tkeys[slot] & 0xFFFFFFFFull);
+    const int gx = key % Gx, q = key / Gx;
+    int32_t *c = coors + ((size_t)b * V + vn) * 3;
+    c[0] = q / Gy;
+    c[1] = q % Gy;
+    c[2] = gx;
+}
+
+// the other valid points take their opener's number; every taken point counts
+__global__ __launch_bounds__(VX_THREADS) void voxel_follow_kernel(const int32_t *__restrict__ pslot, const int32_t *__restrict__ tvals,
+                                                                  const int32_t *__restrict__ offsets, int total, int B, int V, int32_t *p2v,
+                                                                  int32_t *count) {
+    const int i = blockIdx.x * VX_THREADS + threadIdx.x;
+    if (i >= total) return;
+    const int slot = pslot[i];
+    if (slot < 0) return;
+    const int first = tvals[slot];
+    int v;
+    if (first == i) v = p2v[i];
+    else {
+        v = (first >= 0 && first < total) ? p2v[first] : -1;   // (an opener: written by the previous launch, not by this one)
+        p2v[i] = v;
+    }
+    if (v >= 0 && v < V) atomicAdd(&count[(size_t)scene_of(offsets, B, i) * V + v], 1);
+}
+
+// ---- CSR of the members, in ascending row order ------------------------------------------------------------------
+// count[b,v] from a caller's p2v (voxel_reduce): numbers outside [0, V) count as -1
+__global__ __launch_bounds__(VX_THREADS) void voxel_count_kernel(const int32_t *__restrict__ p2v, const int32_t *__restrict__ offsets, int total,
+                                                                 int B, int V, int32_t *count) {
+    const int i = blockIdx.x * VX_THREADS + threadIdx.x;
+    if (i >= total) return;
+    const int v = p2v[i];
+    if (v >= 0 && v < V) atomicAdd(&count[(size_t)scene_of(offsets, B, i) * V + v], 1);
+}
+
+// blocksum[k] = members of voxels 1024 k .. 1024 k + 1023 (all scenes' voxels as one list of nvox)
+__global__ __launch_bounds__(VX_SCAN_THREADS) void voxel_blocksum_kernel(const int32_t *__restrict__ cnt, unsigned nvox, int32_t *__restrict__ blocksum) {
+    __shared__ int s_w[VX_SCAN_THREADS / 64 + 1];
+    const unsigned s = blockIdx.x * VX_SCAN_THREADS + threadIdx.x;
+    int tot;
+    block_excl_scan(s < nvox ? cnt[s] : 0, s_w, tot);
+    if (threadIdx.x == 0) blocksum[blockIdx.x] = tot;
+}
+
+// start[s] = members of the voxels below s; num_points (optional) = min(count, T)
+__global__ __launch_bounds__(VX_SCAN_THREADS) void voxel_start_kernel(const int32_t *__restrict__ cnt, unsigned nvox, const int32_t *__restrict__ blocksum,
+                                                                      int32_t *__restrict__ start, int T, int32_t *__restrict__ num_points) {
+    __shared__ int s_w[VX_SCAN_THREADS / 64 + 1];
+    int before = 0, tot;
+    for (unsigned k = threadIdx.x; k < blockIdx.x; k += VX_SCAN_THREADS) before += blocksum[k];
+    block_excl_scan(before, s_w, tot);
+    const int base = tot;
+    const unsigned s = blockIdx.x * VX_SCAN_THREADS + threadIdx.x;
+    const int c = s < nvox ? cnt[s] : 0;
+    const int ex = block_excl_scan(c, s_w, tot);
+    if (s < nvox) {
+        start[s] = base + ex;
+        if (num_points) num_points[s] = min(c, T);
+    }
+}
+
+// members[start + arrival order] = row (arrival order is arbitrary: the ranking below removes it)
+__global__ __launch_bounds__(VX_THREADS) void voxel_fill_kernel(const int32_t *__restrict__ p2v, const int32_t *__restrict__ offsets, int total, int B,
+                                                                int V, const int32_t *__restrict__ start, const int32_t *__restrict__ cnt,
+                                                                int32_t *fill, int32_t *__restrict__ members) {
+    const int i = blockIdx.x * VX_THREADS + threadIdx.x;
+    if (i >= total) return;
+    const int v = p2v[i];
+    if (v < 0 || v >= V) return;
+    const size_t s = (size_t)scene_of(offsets, B, i) * V + v;
+    const int k = atomicAdd(&fill[s], 1);
+    const long long pos = (long long)start[s] + k;
+    if (k < cnt[s] && pos < total) members[pos] = i;
+}
+
+// sorted[start + (members of the voxel below row i)] = i
+__global__ __launch_bounds__(VX_THREADS) void voxel_rank_kernel(const int32_t *__restrict__ p2v, const int32_t *__restrict__ offsets, int total, int B,
+                                                                int V, const int32_t *__restrict__ start, const int32_t *__restrict__ cnt,
+                                                                const int32_t *__restrict__ members, int32_t *__restrict__ sorted) {
+    const int i = blockIdx.x * VX_THREADS + threadIdx.x;
+    if (i >= total) return;
+    const int v = p2v[i];
+    if (v < 0 || v >= V) return;
+    const size_t s = (size_t)scene_of(offsets, B, i) * V + v;
+    const int st = start[s];
+    const int c = min(cnt[s], total - st);
+    int r = 0;
+    for (int k = 0; k < c; ++k) r += members[st + k] < i;
+    sorted[st + r] = i;
+}
+
+// ---- hard voxelization: every float of voxels[B,V,T,C] is written once ------------------------------------------
+// one thread per 4 consecutive floats of the output (nq chunks; the tail chunk may be short)
+template <bool VEC>
+__global__ __launch_bounds__(VX_THREADS) void voxelize_write_kernel(const float *__restrict__ points, const int32_t *__restrict__ start,
+                                                                    const int32_t *__restrict__ cnt, const int32_t *__restrict__ sorted, int C,
+                                                                    int T, unsigned TC, unsigned long long nfloats, float *__restrict__ voxels) {
+    const unsigned long long q = (unsigned long long)blockIdx.x * VX_THREADS + threadIdx.x;
+    const unsigned long long e0 = q * 4;
+    if (e0 >= nfloats) return;
+    unsigned s;                                         // voxel (b * V + v)
+    if (nfloats <= 0xFFFFFFFFull) s = (unsigned)e0 / TC;     // (uniform: 32-bit division whenever the output is below 16 GiB)
+    else s = (unsigned)(e0 / TC);
+    unsigned r = (unsigned)(e0 - (unsigned long long)s * TC);
+    unsigned t = r / (unsigned)C, c = r - t * (unsigned)C;
+    int n = min(cnt[s], T), st = start[s];
+    int row = (int)t < n ? sorted[st + t] : -1;
+    float v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        v[u] = row >= 0 ? points[(size_t)row * C + c] : 0.0f;
+        if (++c == (unsigned)C) {
+            c = 0;
+            if (++t == (unsigned)T) {
+                t = 0;
+                ++s;
+                if ((unsigned long long)s * TC >= nfloats) { n = 0; st = 0; }
+                else { n = min(cnt[s], T); st = start[s]; }
+            }
+            row = (int)t < n ? sorted[st + t] : -1;
+        }
+    }
+    if (VEC) {
+        *(float4 *)(voxels + e0) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (e0 + u < nfloats) voxels[e0 + u] = v[u];
+    }
+}
+
+// ---- reduction over voxels -----------------------------------------------------------------------------------
+// one thread per (voxel, channel): the members in ascending row order, one rounding per addition
+__global__ __launch_bounds__(VX_THREADS) void voxel_reduce_kernel(const float *__restrict__ feat, const int32_t *__restrict__ start,
+                                                                  const int32_t *__restrict__ cnt, const int32_t *__restrict__ sorted, int Cf,
+                                                                  unsigned long long nout, int total, int mode, float *__restrict__ out,
+                                                                  int32_t *__restrict__ arg, int32_t *__restrict__ count) {
+    const unsigned long long e = (unsigned long long)blockIdx.x * VX_THREADS + threadIdx.x;
+    if (e >= nout) return;
+    const unsigned s = (unsigned)(e / (unsigned)Cf);
+    const int c = (int)(e - (unsigned long long)s * (unsigned)Cf);
+    const int st = start[s];
+    const int n = min(cnt[s], total - st);
+    if (count && c == 0) count[s] = n;
+    if (n <= 0) {
+        out[e] = 0.0f;
+        if (arg) arg[e] = -1;
+        return;
+    }
+    const int32_t *m = sorted + st;
+    int best = m[0];
+    float acc = feat[(size_t)best * Cf + c];
+    if (mode == SAD_VOXEL_MAX) {
+#pragma unroll 4
+        for (int k = 1; k < n; ++k) {
+            const int j = m[k];
+            const float x = feat[(size_t)j * Cf + c];
+            if (x > acc) { acc = x; best = j; }
+        }
+        arg[e] = best;
+    } else {
+#pragma unroll 4
+        for (int k = 1; k < n; ++k) acc = acc + feat[(size_t)m[k] * Cf + c];
+        if (mode == SAD_VOXEL_MEAN) acc = acc / (float)n;
+    }
+    out[e] = acc;
+}
+
+// backward: a gather.  aux = count[B,V] (mean) or arg[B,V,Cf] (max)
+__global__ __launch_bounds__(VX_THREADS) void voxel_reduce_grad_kernel(const float *__restrict__ grad_out, const int32_t *__restrict__ p2v,
+                                                                       const int32_t *__restrict__ offsets, const int32_t *__restrict__ aux,
+                                                                       int total, int B, int Cf, int V, int mode, float *__restrict__ grad_feat) {
+    const unsigned long long e = (unsigned long long)blockIdx.x * VX_THREADS + threadIdx.x;
+    if (e >= (unsigned long long)total * Cf) return;
+    const int i = (int)(e / (unsigned)Cf), c = (int)(e - (unsigned long long)i * (unsigned)Cf);
+    const int v = p2v[i];
+    float g = 0.0f;
+    if (v >= 0 && v < V) {
+        const size_t s = (size_t)scene_of(offsets, B, i) * V + v;
+        const float go = grad_out[s * Cf + c];
+        if (mode == SAD_VOXEL_SUM) g = go;
+        else if (mode == SAD_VOXEL_MEAN) g = go / (float)aux[s];
+        else g = aux[s * Cf + c] == i ? go : 0.0f;
+    }
+    grad_feat[e] = g;
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------
+inline size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// workspace layout (bytes from the base)
+struct VoxWs {
+    unsigned cap;          // hash slots: a power of two >= 2 * total (>= 2)
+    int shift;
+    size_t tkeys, tvals, pslot, wavecnt, P, blocksum, start, fill, cnt, p2v, members, sorted, bytes;
+};
+
+VoxWs vox_ws(int total, int B, int V) {
+    VoxWs w;
+    unsigned cap = 2;
+    int lg = 1;
+    while ((unsigned long long)cap < 2ull * (unsigned long long)total) { cap <<= 1; ++lg; }
+    w.cap = cap;
+    w.shift = 64 - lg;
+    const size_t nvox = (size_t)B * V, nw = ((size_t)total + 63) / 64;
+    size_t o = 0;
+    w.tkeys = o;    o += al16((size_t)cap * 8);
+    w.tvals = o;    o += al16((size_t)cap * 4);
+    w.pslot = o;    o += al16((size_t)total * 4);
+    w.wavecnt = o;  o += al16((nw + 1) * 4);
+    w.P = o;        o += al16(((size_t)B + 1) * 4);
+    w.blocksum = o; o += al16((nvox / VX_SCAN_THREADS + 1) * 4);
+    w.start = o;    o += al16(nvox * 4);
+    w.fill = o;     o += al16(nvox * 4);
+    w.cnt = o;      o += al16(nvox * 4);
+    w.p2v = o;      o += al16((size_t)total * 4);
+    w.members = o;  o += al16((size_t)total * 4);
+    w.sorted = o;   o += al16((size_t)total * 4);
+    w.bytes = o + 16;
+    return w;
+}
+
+constexpr int VX_MAX_TOTAL = 1 << 30;
+
+int vox_sizes_ok(const char *fn, long long total, int B, long long V) {
+    SAD_REQUIRE(B >= 1 && B <= 65535, "%s: B must be in 1 .. 65535 (got %d)", fn, B);
+    SAD_REQUIRE(total >= 0 && total <= VX_MAX_TOTAL, "%s: total_points must be in 0 .. 2^30 (got %lld)", fn, total);
+    SAD_REQUIRE(V >= 1 && (long long)B * V < (1LL << 31), "%s: max_voxels must be >= 1 and B * max_voxels < 2^31 (got %lld)", fn, V);
+    return SAD_OK;
+}
+
+// §20.1 grid: G_d = (int)rintf((hi_d - lo_d) / v_d), every G_d >= 1, Gx * Gy * Gz <= 2^31 - 1
+int vox_grid(const char *fn, const float *voxel_size, const float *point_range, VoxGrid &g) {
+    SAD_REQUIRE(voxel_size && point_range, "%s: NULL voxel_size / point_range", fn);
+    long long cells = 1;
+    for (int d = 0; d < 3; ++d) {
+        const float v = voxel_size[d], lo = point_range[d], hi = point_range[3 + d];
+        SAD_REQUIRE(v > 0.0f && isfinite(v) && isfinite(lo) && isfinite(hi), "%s: voxel_size must be > 0 and the range finite (axis %d)", fn, d);
+        volatile float ext = hi - lo;
+        volatile float q = ext / v;
+        const float r = rintf(q);
+        if (!(r >= 1.0f)) return sad::fail(SAD_EUNSUPPORTED, "%s: grid dimension %d is %g (< 1)", fn, d, (double)r);
+        if (!(r < 2147483648.0f)) return sad::fail(SAD_EUNSUPPORTED, "%s: grid dimension %d is %g (> 2^31 - 1 cells)", fn, d, (double)r);
+        g.lo[d] = lo;
+        g.v[d] = v;
+        g.G[d] = (int)r;
+        g.Gf[d] = (float)g.G[d];
+        cells *= g.G[d];
+        if (cells > 2147483647LL)
+            return sad::fail(SAD_EUNSUPPORTED, "%s: grid %d x %d x %d exceeds 2^31 - 1 cells", fn, g.G[0], d > 0 ? g.G[1] : 1, d > 1 ? g.G[2] : 1);
+    }
+    return SAD_OK;
+}
+
+inline unsigned blocks_for(unsigned long long n, int threads) { return (unsigned)((n + threads - 1) / threads); }
+
+inline void launch_init(u64 *tkeys, int32_t *tvals, unsigned cap, int32_t *cnt, int32_t *fill, int32_t *coors, unsigned nvox, hipStream_t st) {
+    const unsigned long long n = tkeys ? (cap > nvox ? cap : nvox) : nvox;
+    const unsigned blocks = (unsigned)std::min<unsigned long long>(blocks_for(n, VX_THREADS), 16384ull);
+    hipLaunchKernelGGL(voxel_init_kernel, dim3(blocks ? blocks : 1), dim3(VX_THREADS), 0, st, tkeys, tvals, cap, cnt, fill, coors, nvox);
+}
+
+// §20.2: p2v[total], coors[B,V,3], count[B,V], voxel_num[B].  `fill` (optional): zeroed for a CSR that follows
+void launch_numbering(const float *points, const int32_t *offsets, int total, int B, int C, const VoxGrid &g, int V, char *ws, const VoxWs &w,
+                      int32_t *p2v, int32_t *coors, int32_t *count, int32_t *voxel_num, int32_t *fill, hipStream_t st) {
+    u64 *tkeys = (u64 *)(ws + w.tkeys);
+    int32_t *tvals = (int32_t *)(ws + w.tvals), *pslot = (int32_t *)(ws + w.pslot), *wavecnt = (int32_t *)(ws + w.wavecnt);
+    int32_t *P = (int32_t *)(ws + w.P);
+    const unsigned nvox = (unsigned)B * (unsigned)V;
+    const int nw = (total + 63) / 64;
+    const dim3 gp(blocks_for((unsigned long long)total, VX_THREADS)), tb(VX_THREADS);
+    launch_init(tkeys, tvals, w.cap, count, fill, coors, nvox, st);
+    if (total > 0) {
+        hipLaunchKernelGGL(voxel_insert_kernel, gp, tb, 0, st, points, offsets, total, B, C, g, tkeys, tvals, w.cap - 1, w.shift, pslot);
+        hipLaunchKernelGGL(voxel_flags_kernel, gp, tb, 0, st, pslot, tvals, total, wavecnt);
+    }
+    hipLaunchKernelGGL(voxel_scan_kernel, dim3(1), dim3(VX_SCAN_THREADS), 0, st, wavecnt, nw, pslot, tvals, offsets, total, B, V, P, voxel_num);
+    if (total > 0) {
+        hipLaunchKernelGGL(voxel_number_kernel, gp, tb, 0, st, pslot, tkeys, tvals, offsets, wavecnt, P, total, B, V, g.G[0], g.G[1], p2v, coors);
+        hipLaunchKernelGGL(voxel_follow_kernel, gp, tb, 0, st, pslot, tvals, offsets, total, B, V, p2v, count);
+    }
+}
+
+// count[B,V] (final) + p2v -> start, sorted (fill zeroed on entry).  num_points (optional) = min(count, T)
+void launch_csr(const int32_t *p2v, const int32_t *offsets, int total, int B, int V, const int32_t *cnt, char *ws, const VoxWs &w, int T,
+                int32_t *num_points, hipStream_t st) {
+    int32_t *blocksum = (int32_t *)(ws + w.blocksum), *start = (int32_t *)(ws + w.start), *fill = (int32_t *)(ws + w.fill);
+    int32_t *members = (int32_t *)(ws + w.members), *sorted = (int32_t *)(ws + w.sorted);
+    const unsigned nvox = (unsigned)B * (unsigned)V;
+    const dim3 gv(blocks_for(nvox, VX_SCAN_THREADS)), gp(blocks_for((unsigned long long)total, VX_THREADS));
+    hipLaunchKernelGGL(voxel_blocksum_kernel, gv, dim3(VX_SCAN_THREADS), 0, st, cnt, nvox, blocksum);
+    hipLaunchKernelGGL(voxel_start_kernel, gv, dim3(VX_SCAN_THREADS), 0, st, cnt, nvox, blocksum, start, T, num_points);
+    if (total > 0) {
+        hipLaunchKernelGGL(voxel_fill_kernel, gp, dim3(VX_THREADS), 0, st, p2v, offsets, total, B, V, start, cnt, fill, members);
+        hipLaunchKernelGGL(voxel_rank_kernel, gp, dim3(VX_THREADS), 0, st, p2v, offsets, total, B, V, start, cnt, members, sorted);
+    }
+}
+
+}  // namespace
+
+SAD_API int sad_voxel_workspace_bytes(int total_points, int B, int max_voxels, size_t *out) {
+    SAD_REQUIRE(out, "sad_voxel_workspace_bytes: NULL out");
+    *out = 0;
+    if (int rc = vox_sizes_ok("sad_voxel_workspace_bytes", total_points, B, max_voxels)) return rc;
+    *out = vox_ws(total_points, B, max_voxels).bytes;
+    return SAD_OK;
+}
+
+SAD_API int sad_voxel_coords_f32(const float *points, const int32_t *offsets, int total_points, int B, int C, const float *voxel_size,
+                                 const float *point_range, int32_t *coors, sad_stream_t stream) {
+    SAD_REQUIRE(offsets && (total_points == 0 || (points && coors)), "sad_voxel_coords_f32: NULL pointer");
+    SAD_REQUIRE(C >= 3, "sad_voxel_coords_f32: point rows need C >= 3 floats (got %d)", C);
+    if (int rc = vox_sizes_ok("sad_voxel_coords_f32", total_points, B, 1)) return rc;
+    SAD_REQUIRE(((uintptr_t)coors & 15) == 0, "sad_voxel_coords_f32: coors must be 16-byte aligned");
+    VoxGrid g;
+    if (int rc = vox_grid("sad_voxel_coords_f32", voxel_size, point_range, g)) return rc;
+    if (total_points == 0) return SAD_OK;
+    hipLaunchKernelGGL(voxel_coords_kernel, dim3(blocks_for((unsigned long long)total_points, VX_THREADS)), dim3(VX_THREADS), 0, (hipStream_t)stream,
+                       points, offsets, total_points, B, C, g, coors);
+    return sad::check_launch("sad_voxel_coords_f32");
+}
+
+SAD_API int sad_voxel_index_f32(const float *points, const int32_t *offsets, int total_points, int B, int C, const float *voxel_size,
+                                const float *point_range, int max_voxels, int32_t *point2voxel, int32_t *coors, int32_t *count,
+                                int32_t *voxel_num, void *workspace, sad_stream_t stream) {
+    SAD_REQUIRE(offsets && coors && count && voxel_num && workspace && (total_points == 0 || (points && point2voxel)),
+                "sad_voxel_index_f32: NULL pointer");
+    SAD_REQUIRE(C >= 3, "sad_voxel_index_f32: point rows need C >= 3 floats (got %d)", C);
+    if (int rc = vox_sizes_ok("sad_voxel_index_f32", total_points, B, max_voxels)) return rc;
+    SAD_REQUIRE(((uintptr_t)workspace & 15) == 0, "sad_voxel_index_f32: workspace must be 16-byte aligned");
+    VoxGrid g;
+    if (int rc = vox_grid("sad_voxel_index_f32", voxel_size, point_range, g)) return rc;
+    const VoxWs w = vox_ws(total_points, B, max_voxels);
+    launch_numbering(points, offsets, total_points, B, C, g, max_voxels, (char *)workspace, w, point2voxel, coors, count, voxel_num, nullptr,
+                     (hipStream_t)stream);
+    return sad::check_launch("sad_voxel_index_f32");
+}
+
+SAD_API int sad_voxelize_f32(const float *points, const int32_t *offsets, int total_points, int B, int C, const float *voxel_size,
+                             const float *point_range, int max_points, int max_voxels, float *voxels, int32_t *coors, int32_t *num_points,
+                             int32_t *voxel_num, void *workspace, sad_stream_t stream) {
+    SAD_REQUIRE(offsets && voxels && coors && num_points && voxel_num && workspace && (total_points == 0 || points), "sad_voxelize_f32: NULL pointer");
+    SAD_REQUIRE(C >= 3, "sad_voxelize_f32: point rows need C >= 3 floats (got %d)", C);
+    SAD_REQUIRE(max_points >= 1, "sad_voxelize_f32: max_points must be >= 1 (got %d)", max_points);
+    if (int rc = vox_sizes_ok("sad_voxelize_f32", total_points, B, max_voxels)) return rc;
+    SAD_REQUIRE(((uintptr_t)workspace & 15) == 0, "sad_voxelize_f32: workspace must be 16-byte aligned");
+    const unsigned long long TC = (unsigned long long)max_points * C;
+    const unsigned long long nfloats = (unsigned long long)B * max_voxels * TC;
+    if (TC >= (1ull << 31) || nfloats >= (1ull << 40))
+        return sad::fail(SAD_EUNSUPPORTED, "sad_voxelize_f32: voxels[B,V,T,C] of %llu floats is too large", nfloats);
+    VoxGrid g;
+    if (int rc = vox_grid("sad_voxelize_f32", voxel_size, point_range, g)) return rc;
+    const VoxWs w = vox_ws(total_points, B, max_voxels);
+    char *ws = (char *)workspace;
+    const hipStream_t st = (hipStream_t)stream;
+    int32_t *cnt = (int32_t *)(ws + w.cnt), *p2v = (int32_t *)(ws + w.p2v);
+    launch_numbering(points, offsets, total_points, B, C, g, max_voxels, ws, w, p2v, coors, cnt, voxel_num, (int32_t *)(ws + w.fill), st);
+    launch_csr(p2v, offsets, total_points, B, max_voxels, cnt, ws, w, max_points, num_points, st);
+    const unsigned nb = blocks_for((nfloats + 3) / 4, VX_THREADS);
+    const int32_t *start = (const int32_t *)(ws + w.start), *sorted = (const int32_t *)(ws + w.sorted);
+    if (((uintptr_t)voxels & 15) == 0 && nfloats % 4 == 0)
+        hipLaunchKernelGGL(voxelize_write_kernel<true>, dim3(nb), dim3(VX_THREADS), 0, st, points, start, cnt, sorted, C, max_points, (unsigned)TC,
+                           nfloats, voxels);
+    else
+        hipLaunchKernelGGL(voxelize_write_kernel<false>, dim3(nb), dim3(VX_THREADS), 0, st, points, start, cnt, sorted, C, max_points, (unsigned)TC,
+                           nfloats, voxels);
+    return sad::check_launch("sad_voxelize_f32");
+}
+
+SAD_API int sad_voxel_reduce_f32(const float *feat, const int32_t *point2voxel, const int32_t *offsets, int total_points, int B, int Cf,
+                                 int max_voxels, int mode, float *out, int32_t *arg, int32_t *count, void *workspace, sad_stream_t stream) {
+    SAD_REQUIRE(offsets && out && workspace && (total_points == 0 || (feat && point2voxel)), "sad_voxel_reduce_f32: NULL pointer");
+    SAD_REQUIRE(mode == SAD_VOXEL_SUM || mode == SAD_VOXEL_MEAN || mode == SAD_VOXEL_MAX, "sad_voxel_reduce_f32: mode must be 0 (sum), 1 (mean) or 2 (max), got %d",
+                mode);
+    SAD_REQUIRE(mode != SAD_VOXEL_MAX || arg, "sad_voxel_reduce_f32: mode max needs the arg output");
+    SAD_REQUIRE(Cf >= 1, "sad_voxel_reduce_f32: Cf must be >= 1 (got %d)", Cf);
+    if (int rc = vox_sizes_ok("sad_voxel_reduce_f32", total_points, B, max_voxels)) return rc;
+    SAD_REQUIRE(((uintptr_t)workspace & 15) == 0, "sad_voxel_reduce_f32: workspace must be 16-byte aligned");
+    const unsigned long long nout = (unsigned long long)B * max_voxels * Cf;
+    if (nout >= (1ull << 40)) return sad::fail(SAD_EUNSUPPORTED, "sad_voxel_reduce_f32: out[B,V,Cf] of %llu floats is too large", nout);
+    const VoxWs w = vox_ws(total_points, B, max_voxels);
+    char *ws = (char *)workspace;
+    const hipStream_t st = (hipStream_t)stream;
+    int32_t *cnt = (int32_t *)(ws + w.cnt);
+    const unsigned nvox = (unsigned)B * (unsigned)max_voxels;
+    launch_init(nullptr, nullptr, 0, cnt, (int32_t *)(ws + w.fill), nullptr, nvox, st);
+    if (total_points > 0)
+        hipLaunchKernelGGL(voxel_count_kernel, dim3(blocks_for((unsigned long long)total_points, VX_THREADS)), dim3(VX_THREADS), 0, st, point2voxel,
+                           offsets, total_points, B, max_voxels, cnt);
+    launch_csr(point2voxel, offsets, total_points, B, max_voxels, cnt, ws, w, 0, nullptr, st);
+    hipLaunchKernelGGL(voxel_reduce_kernel, dim3(blocks_for(nout, VX_THREADS)), dim3(VX_THREADS), 0, st, feat, (const int32_t *)(ws + w.start), cnt,
+                       (const int32_t *)(ws + w.sorted), Cf, nout, total_points, mode, out, mode == SAD_VOXEL_MAX ? arg : nullptr, count);
+    return sad::check_launch("sad_voxel_reduce_f32");
+}
+
+SAD_API int sad_voxel_reduce_grad_f32(const float *grad_out, const int32_t *point2voxel, const int32_t *offsets, int total_points, int B, int Cf,
+                                      int max_voxels, int mode, const int32_t *count_or_arg, float *grad_feat, sad_stream_t stream) {
+    SAD_REQUIRE(offsets && grad_out && (total_points == 0 || (point2voxel && grad_feat)), "sad_voxel_reduce_grad_f32: NULL pointer");
+    SAD_REQUIRE(mode == SAD_VOXEL_SUM || mode == SAD_VOXEL_MEAN || mode == SAD_VOXEL_MAX,
+                "sad_voxel_reduce_grad_f32: mode must be 0 (sum), 1 (mean) or 2 (max), got %d", mode);
+    SAD_REQUIRE(mode == SAD_VOXEL_SUM || count_or_arg, "sad_voxel_reduce_grad_f32: mean needs count[B,V], max needs arg[B,V,Cf]");
+    SAD_REQUIRE(Cf >= 1, "sad_voxel_reduce_grad_f32: Cf must be >= 1 (got %d)", Cf);
+    if (int rc = vox_sizes_ok("sad_voxel_reduce_grad_f32", total_points, B, max_voxels)) return rc;
+    if (total_points == 0) return SAD_OK;
+    const unsigned long long n = (unsigned long long)total_points * Cf;
+    SAD_REQUIRE(n < (1ull << 40), "sad_voxel_reduce_grad_f32: total_points * Cf too large");
+    hipLaunchKernelGGL(voxel_reduce_grad_kernel, dim3(blocks_for(n, VX_THREADS)), dim3(VX_THREADS), 0, (hipStream_t)stream, grad_out, point2voxel,
+                       offsets, count_or_arg, total_points, B, Cf, max_voxels, mode, grad_feat);
+    return sad::check_launch("sad_voxel_reduce_grad_f32");
+}

@@ -555,6 +555,173 @@ def roipoint_pool3d(xyz: torch.Tensor, feat_pm: Optional[torch.Tensor], boxes: t
     return (pooled, empty, idx) if return_idx else (pooled, empty)
 
 
+VOXEL_MODES = {"sum": 0, "mean": 1, "max": 2}
+
+
+def _voxel_points(points: torch.Tensor, offsets: Optional[torch.Tensor], name: str = "points", min_c: int = 3):
+    """Ragged ``points [total,C]`` + ``offsets [B+1]`` int32 on the GPU, or a batch ``points [B,N,C]`` with ``offsets=None``
+    (offsets[b] = b*N) -> (rows [total,C] contiguous, offsets, B) (SPEC.md §20)."""
+    if offsets is None:
+        points = _need(points, name, torch.float32, 3)
+        B, N, C = points.shape
+        if B < 1:
+            raise ValueError(f"{name}: empty batch")
+        if B * N >= 1 << 30:
+            raise ValueError(f"{name}: too many points")
+        offsets = torch.arange(0, (B + 1) * N, N, dtype=torch.int32, device=points.device) if N else \
+            torch.zeros((B + 1,), dtype=torch.int32, device=points.device)
+        points = points.view(B * N, C)
+    else:
+        points = _need(points, name, torch.float32, 2)
+        offsets = _need(offsets, "offsets", torch.int32, 1)
+        if offsets.device != points.device:
+            raise ValueError(f"offsets must be on the device of {name}")
+        B = offsets.shape[0] - 1
+        if B < 1:
+            raise ValueError("offsets must have B + 1 >= 2 entries")
+    if points.shape[1] < min_c:
+        raise ValueError(f"{name}: rows need at least {min_c} columns, got {points.shape[1]}")
+    return points, offsets, B
+
+
+def _voxel_grid(voxel_size, point_range):
+    """(vx,vy,vz), (x0,y0,z0,x1,y1,z1) -> two host float arrays, Python floats rounded to binary32."""
+    if len(voxel_size) != 3 or len(point_range) != 6:
+        raise ValueError("voxel_size must have 3 entries (vx,vy,vz) and point_range 6 (x0,y0,z0,x1,y1,z1)")
+    return ((ctypes.c_float * 3)(*[float(np.float32(v)) for v in voxel_size]),
+            (ctypes.c_float * 6)(*[float(np.float32(v)) for v in point_range]))
+
+
+def voxel_workspace(total_points: int, B: int, max_voxels: int, device) -> torch.Tensor:
+    """Scratch of the §20 operators for (total_points, B, max_voxels); contents arbitrary, reusable call after call on one stream."""
+    n = ctypes.c_size_t(0)
+    check(lib().sad_voxel_workspace_bytes(int(total_points), int(B), int(max_voxels), ctypes.byref(n)), "sad_voxel_workspace_bytes")
+    return _empty((n.value,), dtype=torch.uint8, device=device)
+
+
+def _voxel_ws(ws: Optional[torch.Tensor], total: int, B: int, V: int, device) -> torch.Tensor:
+    if ws is None:
+        return voxel_workspace(total, B, V, device)
+    n = ctypes.c_size_t(0)
+    check(lib().sad_voxel_workspace_bytes(int(total), int(B), int(V), ctypes.byref(n)), "sad_voxel_workspace_bytes")
+    if not ws.is_cuda or ws.device != device or not ws.is_contiguous() or ws.numel() * ws.element_size() < n.value or ws.data_ptr() % 16:
+        raise ValueError(f"workspace: expected a contiguous 16-byte aligned GPU buffer of at least {n.value} bytes (ops.voxel_workspace)")
+    return ws
+
+
+def voxel_coords(points: torch.Tensor, offsets: Optional[torch.Tensor], voxel_size, point_range) -> torch.Tensor:
+    """Voxel coordinate of every point (SPEC.md §20.1).  points [total,C] f32 + offsets [B+1] int32, or points [B,N,C] with
+    ``offsets=None`` -> coors [total,4] int32 = (b, z, y, x), or (b,-1,-1,-1) for a point outside ``point_range``."""
+    vs, pr = _voxel_grid(voxel_size, point_range)
+    points, offsets, B = _voxel_points(points, offsets)
+    total, C = points.shape
+    coors = _empty((total, 4), dtype=torch.int32, device=points.device)
+    with _timed("voxel_coords", f"n{total}"):
+        check(lib().sad_voxel_coords_f32(points.data_ptr(), offsets.data_ptr(), total, B, C, vs, pr, coors.data_ptr(), _stream()),
+              "sad_voxel_coords_f32")
+    return coors
+
+
+def voxel_index(points: torch.Tensor, offsets: Optional[torch.Tensor], voxel_size, point_range, max_voxels: int,
+                workspace: Optional[torch.Tensor] = None):
+    """Dynamic voxel index (SPEC.md §20.3): voxels numbered per scene in order of first appearance, at most ``max_voxels``.
+    -> (point2voxel [total] int32 (scene-local number, -1 = out of range or dropped), coors [B,V,3] int32 (z,y,x),
+    count [B,V] int32 (all members), voxel_num [B] int32).  Deterministic, bit-equal to the reference.  No gradient."""
+    vs, pr = _voxel_grid(voxel_size, point_range)
+    points, offsets, B = _voxel_points(points, offsets)
+    V = int(max_voxels)
+    if V < 1:
+        raise ValueError(f"max_voxels={V} must be >= 1")
+    total, C = points.shape
+    dev = points.device
+    ws = _voxel_ws(workspace, total, B, V, dev)
+    p2v = _empty((total,), dtype=torch.int32, device=dev)
+    coors = _empty((B, V, 3), dtype=torch.int32, device=dev)
+    count = _empty((B, V), dtype=torch.int32, device=dev)
+    voxel_num = _empty((B,), dtype=torch.int32, device=dev)
+    with _timed("voxel_index", f"n{total}V{V}"):
+        check(lib().sad_voxel_index_f32(points.data_ptr(), offsets.data_ptr(), total, B, C, vs, pr, V, p2v.data_ptr(), coors.data_ptr(),
+                                        count.data_ptr(), voxel_num.data_ptr(), ws.data_ptr(), _stream()), "sad_voxel_index_f32")
+    return p2v, coors, count, voxel_num
+
+
+def voxelize(points: torch.Tensor, offsets: Optional[torch.Tensor], voxel_size, point_range, max_points: int, max_voxels: int,
+             workspace: Optional[torch.Tensor] = None):
+    """Hard voxelization (SPEC.md §20.4): the first ``max_voxels`` voxels of each scene in order of first appearance, the
+    first ``max_points`` points of each in row order.  -> (voxels [B,V,T,C] f32 (unused slots 0), coors [B,V,3] int32 (z,y,x),
+    num_points [B,V] int32, voxel_num [B] int32).  Deterministic, bit-equal to the reference.  No gradient."""
+    vs, pr = _voxel_grid(voxel_size, point_range)
+    points, offsets, B = _voxel_points(points, offsets)
+    T, V = int(max_points), int(max_voxels)
+    if T < 1 or V < 1:
+        raise ValueError(f"max_points={T} and max_voxels={V} must be >= 1")
+    total, C = points.shape
+    dev = points.device
+    ws = _voxel_ws(workspace, total, B, V, dev)
+    voxels = _empty((B, V, T, C), dtype=torch.float32, device=dev)
+    coors = _empty((B, V, 3), dtype=torch.int32, device=dev)
+    num_points = _empty((B, V), dtype=torch.int32, device=dev)
+    voxel_num = _empty((B,), dtype=torch.int32, device=dev)
+    with _timed("voxelize", f"n{total}T{T}V{V}"):
+        check(lib().sad_voxelize_f32(points.data_ptr(), offsets.data_ptr(), total, B, C, vs, pr, T, V, voxels.data_ptr(), coors.data_ptr(),
+                                     num_points.data_ptr(), voxel_num.data_ptr(), ws.data_ptr(), _stream()), "sad_voxelize_f32")
+    return voxels, coors, num_points, voxel_num
+
+
+def voxel_reduce(feat: torch.Tensor, point2voxel: torch.Tensor, offsets: Optional[torch.Tensor], max_voxels: int, mode: str = "mean",
+                 workspace: Optional[torch.Tensor] = None, return_count: bool = False):
+    """Reduction of point features over voxels (SPEC.md §20.5).  feat [total,Cf] f32 + offsets, or feat [B,N,Cf] with
+    ``offsets=None``; point2voxel [total] int32 from ``voxel_index``.  ``mode`` "sum" / "mean" -> out [B,V,Cf]; "max" ->
+    (out, arg [B,V,Cf] int32 = row of the first member that attains the maximum, -1 for an empty voxel).  The sum runs over
+    the members in ascending row order (exact against the reference, unlike a float-atomic scatter).  ``return_count`` appends
+    count [B,V] int32.  No gradient here: ``autograd.voxel_reduce``."""
+    if mode not in VOXEL_MODES:
+        raise ValueError(f"mode must be one of {sorted(VOXEL_MODES)}, got {mode!r}")
+    feat, offsets, B = _voxel_points(feat, offsets, "feat", 1)
+    point2voxel = _need(point2voxel, "point2voxel", torch.int32, 1)
+    total, Cf = feat.shape
+    if point2voxel.shape[0] != total or point2voxel.device != feat.device:
+        raise ValueError("point2voxel must have one entry per row of feat, on its device")
+    V = int(max_voxels)
+    if V < 1:
+        raise ValueError(f"max_voxels={V} must be >= 1")
+    dev = feat.device
+    ws = _voxel_ws(workspace, total, B, V, dev)
+    out = _empty((B, V, Cf), dtype=torch.float32, device=dev)
+    arg = _empty((B, V, Cf), dtype=torch.int32, device=dev) if mode == "max" else None
+    count = _empty((B, V), dtype=torch.int32, device=dev) if return_count else None
+    with _timed("voxel_reduce", f"{mode}n{total}V{V}C{Cf}"):
+        check(lib().sad_voxel_reduce_f32(feat.data_ptr(), point2voxel.data_ptr(), offsets.data_ptr(), total, B, Cf, V, VOXEL_MODES[mode],
+                                         out.data_ptr(), arg.data_ptr() if arg is not None else None,
+                                         count.data_ptr() if count is not None else None, ws.data_ptr(), _stream()), "sad_voxel_reduce_f32")
+    res = (out,) + ((arg,) if arg is not None else ()) + ((count,) if return_count else ())
+    return res[0] if len(res) == 1 else res
+
+
+def voxel_reduce_grad(grad_out: torch.Tensor, point2voxel: torch.Tensor, offsets: torch.Tensor, mode: str,
+                      aux: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Backward of ``voxel_reduce`` (SPEC.md §20.5), a gather: grad_out [B,V,Cf] -> grad_feat [total,Cf].  ``aux``: count [B,V]
+    for "mean", arg [B,V,Cf] for "max".  Rows with point2voxel = -1 get 0."""
+    if mode not in VOXEL_MODES:
+        raise ValueError(f"mode must be one of {sorted(VOXEL_MODES)}, got {mode!r}")
+    grad_out = _need(grad_out, "grad_out", torch.float32, 3)
+    point2voxel = _need(point2voxel, "point2voxel", torch.int32, 1)
+    offsets = _need(offsets, "offsets", torch.int32, 1)
+    B, V, Cf = grad_out.shape
+    total = point2voxel.shape[0]
+    if offsets.shape[0] != B + 1:
+        raise ValueError("offsets must have B + 1 entries")
+    if mode != "sum":
+        aux = _need(aux, "aux", torch.int32, 2 if mode == "mean" else 3)
+        if tuple(aux.shape) != ((B, V) if mode == "mean" else (B, V, Cf)):
+            raise ValueError("aux: count [B,V] for mean, arg [B,V,Cf] for max")
+    grad_feat = _empty((total, Cf), dtype=torch.float32, device=grad_out.device)
+    check(lib().sad_voxel_reduce_grad_f32(grad_out.data_ptr(), point2voxel.data_ptr(), offsets.data_ptr(), total, B, Cf, V, VOXEL_MODES[mode],
+                                          aux.data_ptr() if mode != "sum" else None, grad_feat.data_ptr(), _stream()),
+          "sad_voxel_reduce_grad_f32")
+    return grad_feat
+
+
 def nms_bev_buffers(B: int, K: int, device) -> tuple:
     """(keep [B,K], order [B,K], count [B], workspace) for ``nms_bev(..., out=...)``: a caller that runs NMS every step
     allocates them once (pipeline.py)."""

@@ -203,6 +203,49 @@ int sad_roipoint_pool3d_f32(const float *xyz, const float *feat, const float *bo
                             int K, int D, int C, float extra_width, int S, float *pooled,
                             int32_t *empty, int32_t *idx, sad_stream_t stream);
 
+/* SPEC.md §20 (voxelization).  Additions of ABI 4: the version is unchanged.  Ragged input as in §17: points[total_points, C]
+ * (C >= 3 floats per row, columns 0..2 = x, y, z), offsets[B+1] (device, int32, non-decreasing, offsets[0] = 0, offsets[B] =
+ * total_points; a scene may be empty).  voxel_size[3] = (vx,vy,vz) and point_range[6] = (x0,y0,z0,x1,y1,z1) are HOST arrays.
+ * Grid G_d = (int)rintf((hi_d - lo_d) / v_d); a dimension below 1 or more than 2^31 - 1 cells in all: SAD_EUNSUPPORTED.
+ * A point is valid iff 0 <= floorf((p_d - lo_d) / v_d) < G_d on every axis (on lo: valid, on hi: not).  Every result is a
+ * function of the input alone (no dependence on the order of any atomic), bit for bit.
+ * voxel_coords: -> coors[total_points,4] = (b, gz, gy, gx), or (b,-1,-1,-1) for an invalid point; coors 16-byte aligned.
+ * voxel_index: voxels are numbered per scene in order of first appearance; a key first met when max_voxels exist is dropped
+ *   with all its later points, the walk continues (§20.2) -> point2voxel[total_points] (scene-local number or -1),
+ *   coors[B,V,3] (z,y,x), count[B,V] (all members, uncapped), voxel_num[B]; rows v >= voxel_num[b]: coors -1, count 0.
+ * voxelize: -> voxels[B,V,T,C]: slot t of voxel v = the row of its t-th member in ascending row order (t < min(count, T)),
+ *   every other float 0 — each float is written exactly once, no fill needed; coors[B,V,3], num_points[B,V] = min(count, T),
+ *   voxel_num[B].  T = max_points >= 1, V = max_voxels >= 1.
+ * voxel_reduce: feat[total_points,Cf], point2voxel (numbers outside [0,V) count as -1) -> out[B,V,Cf]: SAD_VOXEL_SUM adds the
+ *   members in ascending row order, one rounding per addition; SAD_VOXEL_MEAN divides that sum once by (float)count;
+ *   SAD_VOXEL_MAX the maximum, arg[B,V,Cf] = the global row of the first member that attains it (NULL for the other modes).
+ *   Empty voxels: 0 and arg -1.  count (may be NULL) -> [B,V] member counts (what the mean's backward needs).
+ * voxel_reduce_grad: grad_out[B,V,Cf] -> grad_feat[total_points,Cf], a gather: sum grad_out[b,p2v]; mean the same / (float)
+ *   count (count_or_arg = count[B,V]); max grad_out where arg == row, else 0 (count_or_arg = arg[B,V,Cf]); p2v = -1: 0.
+ * workspace: sad_voxel_workspace_bytes(total_points, B, max_voxels, &bytes) bytes of 16-byte aligned device scratch, contents
+ * arbitrary on entry, reusable by the next call on the same stream.  total_points <= 2^30, B <= 65535, B * max_voxels < 2^31. */
+#define SAD_VOXEL_SUM 0
+#define SAD_VOXEL_MEAN 1
+#define SAD_VOXEL_MAX 2
+int sad_voxel_workspace_bytes(int total_points, int B, int max_voxels, size_t *bytes);
+int sad_voxel_coords_f32(const float *points, const int32_t *offsets, int total_points, int B, int C,
+                         const float *voxel_size, const float *point_range, int32_t *coors,
+                         sad_stream_t stream);
+int sad_voxel_index_f32(const float *points, const int32_t *offsets, int total_points, int B, int C,
+                        const float *voxel_size, const float *point_range, int max_voxels,
+                        int32_t *point2voxel, int32_t *coors, int32_t *count, int32_t *voxel_num,
+                        void *workspace, sad_stream_t stream);
+int sad_voxelize_f32(const float *points, const int32_t *offsets, int total_points, int B, int C,
+                     const float *voxel_size, const float *point_range, int max_points, int max_voxels,
+                     float *voxels, int32_t *coors, int32_t *num_points, int32_t *voxel_num,
+                     void *workspace, sad_stream_t stream);
+int sad_voxel_reduce_f32(const float *feat, const int32_t *point2voxel, const int32_t *offsets,
+                         int total_points, int B, int Cf, int max_voxels, int mode, float *out,
+                         int32_t *arg, int32_t *count, void *workspace, sad_stream_t stream);
+int sad_voxel_reduce_grad_f32(const float *grad_out, const int32_t *point2voxel, const int32_t *offsets,
+                              int total_points, int B, int Cf, int max_voxels, int mode,
+                              const int32_t *count_or_arg, float *grad_feat, sad_stream_t stream);
+
 /* SPEC.md §4.  -> idx[B,M,K] sorted by (d2, index); K <= 64, K <= N. */
 int sad_knn_f32(const float *xyz, const float *new_xyz, int B, int N, int M, int K, int32_t *idx,
                 sad_stream_t stream);

@@ -23,6 +23,8 @@ _LAZY = {
     "boxes_iou_bev": "ops", "boxes_iou3d": "ops", "points_in_boxes": "ops", "roipoint_pool3d": "ops",
     "voxel_coords": "ops", "voxel_index": "ops", "voxelize": "ops", "voxel_reduce": "ops",
     "Voxelization": "voxel", "DynamicScatter": "voxel",
+    "sparse_conv_index": "ops", "sparse_conv": "ops", "sparse_to_dense": "ops", "PackedSparseWeight": "ops",
+    "SparseTensor": "spconv", "SubMConv3d": "spconv", "SparseConv3d": "spconv", "SparseSequential": "spconv",
     "SAModuleMSG": "sa_module", "SAModule": "sa_module", "sa_module": "sa_module",
     "SADDetector": "detector", "IngestPipeline": "pipeline",
     "shard_range": "dist", "all_gather_boxes": "dist", "run_sharded": "dist",

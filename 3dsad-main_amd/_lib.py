@@ -22,6 +22,7 @@ WS_REFILLS, WS_INUSE, WS_CONFLICT = 5, 6, 7
 c_f32p = ctypes.POINTER(ctypes.c_float)
 c_i32p = ctypes.POINTER(ctypes.c_int32)
 vp = ctypes.c_void_p
+c_i3p = ctypes.POINTER(ctypes.c_int)      # a host array of 3 ints (z,y,x): shapes, kernel sizes, strides, paddings
 
 
 class MlpArgs(ctypes.Structure):
@@ -103,6 +104,15 @@ SIGNATURES = {
     "sad_voxelize_f32": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 3 + [c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp]),
     "sad_voxel_reduce_f32": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 5 + [vp, vp, vp, vp, vp]),
     "sad_voxel_reduce_grad_f32": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 5 + [vp, vp, vp]),
+    "sad_spconv_workspace_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i3p, c_i3p, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
+    "sad_spconv_index_subm": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, c_i3p, c_i3p, vp, vp, vp]),
+    "sad_spconv_index_count": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, c_i3p, c_i3p, c_i3p, c_i3p, vp, vp, vp]),
+    "sad_spconv_index_fill": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, c_i3p, c_i3p, c_i3p, c_i3p, vp, ctypes.c_int, vp, vp, vp, vp]),
+    "sad_spconv_packed_floats": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "sad_spconv_pack_f32": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 3 + [vp, vp]),
+    "sad_spconv_f32": (ctypes.c_int, [vp, vp, vp, vp] + [ctypes.c_int] * 6 + [vp, vp]),
+    "sad_sparse_to_dense_workspace_bytes": (ctypes.c_int, [ctypes.c_int, c_i3p, ctypes.POINTER(ctypes.c_size_t)]),
+    "sad_sparse_to_dense_f32": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 3 + [c_i3p, vp, vp, vp]),
     "sad_mlp_packed_floats": (ctypes.c_size_t, [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int]),
     "sad_mlp_pack_f32": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
                                        ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp]),

@@ -25,25 +25,12 @@
 
 namespace {
 
-typedef unsigned long long u64;
-constexpr int VX_THREADS = 256;
-constexpr int VX_SCAN_THREADS = 1024;
-constexpr u64 VX_EMPTY = ~0ull;
+#include "vox_hash.h"
 
 struct VoxGrid {
     float lo[3], v[3], Gf[3];
     int G[3];
 };
-
-// largest b in [0, B-1] with offsets[b] <= i: the scene that owns row i (empty scenes own nothing)
-__device__ __forceinline__ int scene_of(const int32_t *__restrict__ off, int B, int i) {
-    int lo = 0, hi = B - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 // §20.1: one subtraction, one correctly rounded division, one floor per axis; validity compared as floats
 __device__ __forceinline__ bool voxel_of(const float *__restrict__ p, const VoxGrid &g, int &gx, int &gy, int &gz) {
@@ -55,32 +42,6 @@ __device__ __forceinline__ bool voxel_of(const float *__restrict__ p, const VoxG
     gy = ok ? (int)fy : -1;
     gz = ok ? (int)fz : -1;
     return ok;
-}
-
-__device__ __forceinline__ int wave_incl_scan(int x, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(x, d);
-        if (lane >= d) x += t;
-    }
-    return x;
-}
-
-// exclusive scan over the VX_SCAN_THREADS threads of a workgroup; total = sum of all.  s_w: 17 ints of LDS
-__device__ __forceinline__ int block_excl_scan(int v, int *s_w, int &total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int inc = wave_incl_scan(v, lane);
-    __syncthreads();                                        // (s_w of a previous call is no longer read)
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = 0;
-        for (int w = 0; w < VX_SCAN_THREADS / 64; ++w) { const int t = s_w[w]; s_w[w] = run; run += t; }
-        s_w[VX_SCAN_THREADS / 64] = run;
-    }
-    __syncthreads();
-    total = s_w[VX_SCAN_THREADS / 64];
-    return s_w[wave] + inc - v;
 }
 
 // ---- voxel_coords ---------------------------------------------------------------------------------------------
@@ -130,22 +91,8 @@ __global__ __launch_bounds__(VX_THREADS) void voxel_insert_kernel(const float *_
     }
     const int key = (gz * g.G[1] + gy) * g.G[0] + gx;
     const u64 k64 = ((u64)(unsigned)scene_of(offsets, B, i) << 32) | (unsigned)key;
-    unsigned h = (unsigned)((k64 * 0x9E3779B97F4A7C15ull) >> shift);
-    int slot = -1;
-    // the table holds at most `total` keys in >= 2 * total slots: an empty slot is met long before a full round
-    for (unsigned n = 0; n <= mask; ++n) {
-        u64 cur = __hip_atomic_load(&tkeys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == VX_EMPTY) {
-            cur = atomicCAS(&tkeys[h], VX_EMPTY, k64);
-            if (cur == VX_EMPTY) cur = k64;
-        }
-        if (cur == k64) { slot = (int)h; break; }
-        h = (h + 1) & mask;
-    }
-    if (slot >= 0) {
-        // first rows only go down: a stale value is a larger one, so a point that sees a lower row can skip the atomic
-        if (__hip_atomic_load(&tvals[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > i) atomicMin(&tvals[slot], i);
-    }
+    const int slot = hash_insert(tkeys, mask, shift, k64);
+    if (slot >= 0) hash_min(tvals, slot, i);
     pslot[i] = slot;
 }
 
@@ -161,19 +108,6 @@ __global__ __launch_bounds__(VX_THREADS) void voxel_flags_kernel(const int32_t *
     const int i = blockIdx.x * VX_THREADS + threadIdx.x;
     const unsigned long long m = __ballot(is_opener(pslot, tvals, i, total));
     if ((threadIdx.x & 63) == 0 && i < total) wavecnt[i >> 6] = __builtin_popcountll(m);
-}
-
-// one workgroup: a[0..n) -> exclusive prefix in place, a[n] = total
-__device__ __forceinline__ void scan_in_place(int32_t *a, int n, int *s_w) {
-    const int chunk = (n + VX_SCAN_THREADS - 1) / VX_SCAN_THREADS;
-    const int k0 = min(n, (int)threadIdx.x * chunk), k1 = min(n, k0 + chunk);
-    int sum = 0;
-    for (int k = k0; k < k1; ++k) sum += a[k];
-    int tot;
-    int run = block_excl_scan(sum, s_w, tot);
-    for (int k = k0; k < k1; ++k) { const int t = a[k]; a[k] = run; run += t; }
-    if (threadIdx.x == 0) a[n] = tot;
-    __syncthreads();
 }
 
 // wavecnt[nw + 1] -> exclusive prefixes; P[b] = openers in rows below offsets[b] (b = 0 .. B); voxel_num[b] = min(V, openers of b)
@@ -411,15 +345,11 @@ struct VoxWs {
 
 VoxWs vox_ws(int total, int B, int V) {
     VoxWs w;
-    unsigned cap = 2;
-    int lg = 1;
-    while ((unsigned long long)cap < 2ull * (unsigned long long)total) { cap <<= 1; ++lg; }
-    w.cap = cap;
-    w.shift = 64 - lg;
+    hash_capacity((unsigned long long)total, w.cap, w.shift);
     const size_t nvox = (size_t)B * V, nw = ((size_t)total + 63) / 64;
     size_t o = 0;
-    w.tkeys = o;    o += al16((size_t)cap * 8);
-    w.tvals = o;    o += al16((size_t)cap * 4);
+    w.tkeys = o;    o += al16((size_t)w.cap * 8);
+    w.tvals = o;    o += al16((size_t)w.cap * 4);
     w.pslot = o;    o += al16((size_t)total * 4);
     w.wavecnt = o;  o += al16((nw + 1) * 4);
     w.P = o;        o += al16(((size_t)B + 1) * 4);

@@ -722,6 +722,168 @@ def voxel_reduce_grad(grad_out: torch.Tensor, point2voxel: torch.Tensor, offsets
     return grad_feat
 
 
+def _int3(v, name: str, lo: int):
+    """int or 3 ints (z,y,x) -> (tuple of 3 Python ints, host int array)."""
+    t = (int(v),) * 3 if isinstance(v, (int, np.integer)) else tuple(int(x) for x in v)
+    if len(t) != 3:
+        raise ValueError(f"{name}: an int or 3 ints (z,y,x) expected, got {v!r}")
+    if min(t) < lo:
+        raise ValueError(f"{name}: entries must be >= {lo}, got {t}")
+    return t, (ctypes.c_int * 3)(*t)
+
+
+def sparse_conv_geometry(spatial_shape, kernel, stride=1, padding=0, subm: bool = False):
+    """Host arithmetic of SPEC.md §21: -> (spatial_shape, kernel, stride, padding, out_shape), tuples of 3 ints (z,y,x).
+    ``subm`` demands odd kernel sizes and fixes stride 1 and padding K // 2.  Needs no GPU."""
+    G, _ = _int3(spatial_shape, "spatial_shape", 1)
+    K, _ = _int3(kernel, "kernel", 1)
+    if max(K) > 3:
+        raise ValueError(f"kernel: sizes 1 .. 3 are implemented, got {K}")
+    if G[0] * G[1] * G[2] > 2 ** 31 - 1:
+        raise ValueError(f"spatial_shape {G} exceeds 2^31 - 1 cells")
+    if subm:
+        if any(k % 2 == 0 for k in K):
+            raise ValueError(f"a submanifold convolution needs odd kernel sizes, got {K}")
+        s, p = (1, 1, 1), tuple(k // 2 for k in K)
+        if _int3(stride, "stride", 1)[0] != s:
+            raise ValueError("a submanifold convolution has stride 1")
+        if padding not in (0, None) and _int3(padding, "padding", 0)[0] != p:
+            raise ValueError("a submanifold convolution has padding K // 2")
+    else:
+        s, _ = _int3(stride, "stride", 1)
+        p, _ = _int3(padding, "padding", 0)
+    if any(g + 2 * q - k < 0 for g, q, k in zip(G, p, K)):
+        raise ValueError(f"kernel {K} does not fit the padded grid {G} + 2 * {p}")
+    O = tuple((g + 2 * q - k) // t + 1 for g, q, k, t in zip(G, p, K, s))
+    return G, K, s, p, O
+
+
+def _sparse_coors(coors: torch.Tensor, offsets: torch.Tensor):
+    coors = _need(coors, "coors", torch.int32, 2)
+    offsets = _need(offsets, "offsets", torch.int32, 1)
+    if coors.shape[1] != 3:
+        raise ValueError(f"coors: [Nv,3] (z,y,x) expected, got {tuple(coors.shape)}")
+    if offsets.device != coors.device:
+        raise ValueError("offsets must be on the device of coors")
+    B = offsets.shape[0] - 1
+    if B < 1:
+        raise ValueError("offsets must have B + 1 >= 2 entries")
+    return coors, offsets, B
+
+
+def sparse_conv_index(coors: torch.Tensor, offsets: torch.Tensor, spatial_shape, kernel, stride=1, padding=0, subm: bool = False,
+                      capacity: Optional[int] = None):
+    """Rulebook of a sparse 3-D convolution (SPEC.md §21.1).  coors [Nv,3] int32 (z,y,x), offsets [B+1] int32, both on the GPU ->
+    (out_coors [No,3], out_offsets [B+1], nbr [No,Kvol] int32): nbr[o,kk] = the input row that output row o reads at kernel offset
+    kk, or -1.  ``subm``: out_coors / out_offsets ARE coors / offsets (the same tensors).  Otherwise the number of output rows is
+    known only on the device: with ``capacity=None`` it is read back once (ONE synchronisation of the current stream, as in the
+    libraries this replaces); with a ``capacity`` the call stays asynchronous, returns ``capacity`` rows (-1 beyond the true
+    total, which is out_offsets[B]) and drops the rows that do not fit.  Integer work, equal to the reference.  No gradient."""
+    _unrecordable("sparse_conv_index")
+    G, K, s, p, _ = sparse_conv_geometry(spatial_shape, kernel, stride, padding, subm)
+    coors, offsets, B = _sparse_coors(coors, offsets)
+    Nv, Kvol, dev = coors.shape[0], K[0] * K[1] * K[2], coors.device
+    cG, cK, cs, cp = [(ctypes.c_int * 3)(*t) for t in (G, K, s, p)]
+    n = ctypes.c_size_t(0)
+    check(lib().sad_spconv_workspace_bytes(Nv, B, cK, cs, int(subm), ctypes.byref(n)), "sad_spconv_workspace_bytes")
+    ws = torch.empty((n.value,), dtype=torch.uint8, device=dev)
+    if subm:
+        nbr = torch.empty((Nv, Kvol), dtype=torch.int32, device=dev)
+        with _timed("spconv_index", f"subm n{Nv}k{Kvol}"):
+            check(lib().sad_spconv_index_subm(coors.data_ptr(), offsets.data_ptr(), Nv, B, cG, cK, nbr.data_ptr(), ws.data_ptr(), _stream()),
+                  "sad_spconv_index_subm")
+        return coors, offsets, nbr
+    out_offsets = torch.empty((B + 1,), dtype=torch.int32, device=dev)
+    with _timed("spconv_index", f"count n{Nv}k{Kvol}"):
+        check(lib().sad_spconv_index_count(coors.data_ptr(), offsets.data_ptr(), Nv, B, cG, cK, cs, cp, out_offsets.data_ptr(), ws.data_ptr(),
+                                           _stream()), "sad_spconv_index_count")
+    No = int(out_offsets[B].item()) if capacity is None else int(capacity)
+    if No < 0:
+        raise ValueError(f"capacity={No} must be >= 0")
+    out_coors = torch.empty((No, 3), dtype=torch.int32, device=dev)
+    nbr = torch.empty((No, Kvol), dtype=torch.int32, device=dev)
+    with _timed("spconv_index", f"fill n{Nv}k{Kvol}"):
+        check(lib().sad_spconv_index_fill(coors.data_ptr(), offsets.data_ptr(), Nv, B, cG, cK, cs, cp, out_offsets.data_ptr(), No,
+                                          out_coors.data_ptr(), nbr.data_ptr(), ws.data_ptr(), _stream()), "sad_spconv_index_fill")
+    return out_coors, out_offsets, nbr
+
+
+class PackedSparseWeight:
+    """``W [Kvol,Cout,Cin]`` (+ ``bias [Cout]``) in the fragment layout the convolution kernel reads (``sad_spconv_pack_f32``);
+    BatchNorm is folded into W and bias beforehand, as for ``PackedMLP``."""
+
+    def __init__(self, weight: torch.Tensor, bias: Optional[torch.Tensor] = None):
+        weight = _need(weight, "weight", torch.float32, 3)
+        self.kvol, self.cout, self.cin = (int(x) for x in weight.shape)
+        if bias is not None:
+            bias = _need(bias, "bias", torch.float32, 1)
+            if bias.shape[0] != self.cout or bias.device != weight.device:
+                raise ValueError("bias: [Cout] on the device of weight expected")
+        if not (1 <= self.kvol <= 27):
+            raise ValueError(f"weight: Kvol = {self.kvol} must be in 1 .. 27")
+        n = lib().sad_spconv_packed_floats(self.kvol, self.cin, self.cout)
+        if n == 0:
+            raise RuntimeError(f"sparse_conv: Cin = {self.cin}, Cout = {self.cout} unsupported (1 .. 256 each)")
+        self.has_bias = bias is not None
+        self.packed = torch.empty((n,), dtype=torch.float32, device=weight.device)
+        check(lib().sad_spconv_pack_f32(weight.data_ptr(), bias.data_ptr() if bias is not None else None, self.kvol, self.cin, self.cout,
+                                        self.packed.data_ptr(), _stream()), "sad_spconv_pack_f32")
+
+
+def sparse_conv(feat: torch.Tensor, nbr: torch.Tensor, weight, bias: Optional[torch.Tensor] = None,
+                residual: Optional[torch.Tensor] = None, relu: bool = False) -> torch.Tensor:
+    """Sparse convolution over a rulebook (SPEC.md §21.2).  feat [Nv,Cin] f32, nbr [No,Kvol] int32 (``sparse_conv_index``),
+    ``weight`` [Kvol,Cout,Cin] f32 (packed on every call) or a ``PackedSparseWeight`` (then ``bias`` must be None: it is in the
+    pack) -> out [No,Cout] = act(bias + sum_kk W[kk] . feat[nbr[:,kk]] (+ residual [No,Cout])).  One accumulator per output
+    element, kk then ci ascending: equal to the CPU reference under ``==``.  No gradient."""
+    _unrecordable("sparse_conv")
+    feat = _need(feat, "feat", torch.float32, 2)
+    nbr = _need(nbr, "nbr", torch.int32, 2)
+    if isinstance(weight, PackedSparseWeight):
+        if bias is not None:
+            raise ValueError("bias: already part of the PackedSparseWeight")
+        pw = weight
+    else:
+        pw = PackedSparseWeight(weight, bias)
+    Nv, No, dev = feat.shape[0], nbr.shape[0], feat.device
+    if feat.shape[1] != pw.cin or nbr.shape[1] != pw.kvol:
+        raise ValueError(f"feat {tuple(feat.shape)} / nbr {tuple(nbr.shape)} do not fit weight [Kvol={pw.kvol},Cout={pw.cout},Cin={pw.cin}]")
+    if nbr.device != dev or pw.packed.device != dev:
+        raise ValueError("feat, nbr and weight must be on one device")
+    if residual is not None:
+        residual = _need(residual, "residual", torch.float32, 2)
+        if tuple(residual.shape) != (No, pw.cout) or residual.device != dev:
+            raise ValueError(f"residual: [{No},{pw.cout}] on the device of feat expected, got {tuple(residual.shape)}")
+    out = torch.empty((No, pw.cout), dtype=torch.float32, device=dev)
+    with _timed("spconv", f"n{No}k{pw.kvol}c{pw.cin}x{pw.cout}"):
+        check(lib().sad_spconv_f32(feat.data_ptr(), nbr.data_ptr(), pw.packed.data_ptr(), residual.data_ptr() if residual is not None else None,
+                                   int(bool(relu)), Nv, No, pw.kvol, pw.cin, pw.cout, out.data_ptr(), _stream()), "sad_spconv_f32")
+    return out
+
+
+def sparse_to_dense(feat: torch.Tensor, out_coors: torch.Tensor, out_offsets: torch.Tensor, out_shape) -> torch.Tensor:
+    """SPEC.md §21.3: feat [No,C] f32, out_coors [No,3] int32 (z,y,x), out_offsets [B+1] int32 -> dense [B,C,Oz,Oy,Ox] f32, zero
+    where no voxel is and an exact copy elsewhere (the lowest row on a duplicate; rows with a coordinate outside ``out_shape``,
+    such as the -1 rows of a fill with spare capacity, are skipped)."""
+    _unrecordable("sparse_to_dense")
+    feat = _need(feat, "feat", torch.float32, 2)
+    out_coors, out_offsets, B = _sparse_coors(out_coors, out_offsets)
+    O, cO = _int3(out_shape, "out_shape", 1)
+    No, C = feat.shape
+    if out_coors.shape[0] != No or out_coors.device != feat.device:
+        raise ValueError("out_coors must have one row per row of feat, on its device")
+    if C < 1:
+        raise ValueError("feat: at least one channel expected")
+    n = ctypes.c_size_t(0)
+    check(lib().sad_sparse_to_dense_workspace_bytes(B, cO, ctypes.byref(n)), "sad_sparse_to_dense_workspace_bytes")
+    ws = torch.empty((n.value,), dtype=torch.uint8, device=feat.device)
+    dense = torch.empty((B, C) + O, dtype=torch.float32, device=feat.device)
+    with _timed("sparse_to_dense", f"n{No}c{C}"):
+        check(lib().sad_sparse_to_dense_f32(feat.data_ptr(), out_coors.data_ptr(), out_offsets.data_ptr(), No, B, C, cO, dense.data_ptr(),
+                                            ws.data_ptr(), _stream()), "sad_sparse_to_dense_f32")
+    return dense
+
+
 def nms_bev_buffers(B: int, K: int, device) -> tuple:
     """(keep [B,K], order [B,K], count [B], workspace) for ``nms_bev(..., out=...)``: a caller that runs NMS every step
     allocates them once (pipeline.py)."""

@@ -1,0 +1,146 @@
+"""Sparse 3-D convolution layers (SPEC.md §21): ``SparseTensor`` and thin ``nn.Module``s over ``ops.sparse_conv_index`` /
+``ops.sparse_conv`` / ``ops.sparse_to_dense`` — the backbone step of a voxel detector, directly behind ``voxel.py``.
+
+A ``SparseTensor`` is ``feat [Nv,C]`` f32, ``coors [Nv,3]`` int32 (z,y,x), ``offsets [B+1]`` int32 (all on the GPU) and a host
+``spatial_shape`` (Gz,Gy,Gx).  It carries a rulebook cache: layers that name the same ``indice_key`` (the submanifold layers of
+one resolution) build ``nbr`` once.  Forward only (no gradients yet); everything is deterministic and equal to the reference
+restatement under ``==``; there is no CPU path."""
+from typing import Optional, Sequence
+
+import torch
+from torch import nn
+
+from . import ops
+
+
+class SparseTensor:
+    def __init__(self, feat: torch.Tensor, coors: torch.Tensor, offsets: torch.Tensor, spatial_shape: Sequence[int],
+                 rulebooks: Optional[dict] = None):
+        if feat.dim() != 2 or coors.dim() != 2 or coors.shape[1] != 3 or coors.shape[0] != feat.shape[0]:
+            raise ValueError(f"feat [Nv,C] and coors [Nv,3] expected, got {tuple(feat.shape)} and {tuple(coors.shape)}")
+        if offsets.dim() != 1 or offsets.shape[0] < 2:
+            raise ValueError("offsets [B+1] with B >= 1 expected")
+        if len(spatial_shape) != 3 or min(int(g) for g in spatial_shape) < 1:
+            raise ValueError(f"spatial_shape = (Gz,Gy,Gx), all >= 1, expected, got {spatial_shape!r}")
+        self.feat, self.coors, self.offsets = feat, coors, offsets
+        self.spatial_shape = tuple(int(g) for g in spatial_shape)
+        # indice_key -> (geometry, in_coors, out_coors, out_offsets, nbr, out_shape); shared by every tensor derived from this one
+        self.rulebooks = {} if rulebooks is None else rulebooks
+
+    @property
+    def batch_size(self) -> int:
+        return self.offsets.shape[0] - 1
+
+    @classmethod
+    def from_voxels(cls, feat: torch.Tensor, coors: torch.Tensor, voxel_num: torch.Tensor, spatial_shape: Sequence[int]) -> "SparseTensor":
+        """The bridge from §20.3 / §20.4: feat [B,V,C] (``voxel_reduce`` output, or any per-voxel feature), coors [B,V,3],
+        voxel_num [B] -> the rows v < voxel_num[b] of every scene, scene after scene.  Framework indexing; reads the row count
+        back (one synchronisation)."""
+        if feat.dim() != 3 or coors.dim() != 3 or tuple(coors.shape) != (feat.shape[0], feat.shape[1], 3) or voxel_num.shape != (feat.shape[0],):
+            raise ValueError(f"feat [B,V,C], coors [B,V,3], voxel_num [B] expected, got {tuple(feat.shape)}, {tuple(coors.shape)}, "
+                             f"{tuple(voxel_num.shape)}")
+        B, V, C = feat.shape
+        num = voxel_num.to(torch.int64).clamp(0, V)
+        keep = (torch.arange(V, device=feat.device)[None, :] < num[:, None]).reshape(-1)
+        offsets = torch.zeros((B + 1,), dtype=torch.int32, device=feat.device)
+        offsets[1:] = torch.cumsum(num, 0).to(torch.int32)
+        return cls(feat.reshape(B * V, C)[keep].to(torch.float32).contiguous(), coors.reshape(B * V, 3)[keep].to(torch.int32).contiguous(),
+                   offsets, spatial_shape)
+
+    def replace_feature(self, feat: torch.Tensor) -> "SparseTensor":
+        return SparseTensor(feat, self.coors, self.offsets, self.spatial_shape, self.rulebooks)
+
+    def dense(self) -> torch.Tensor:
+        """-> [B,C,Gz,Gy,Gx], zero where no voxel is (§21.3)."""
+        return ops.sparse_to_dense(self.feat, self.coors, self.offsets, self.spatial_shape)
+
+    def bev(self) -> torch.Tensor:
+        """The bird's-eye-view map of a voxel detector: ``dense()`` viewed as [B, C*Gz, Gy, Gx]."""
+        d = self.dense()
+        B, C, Gz, Gy, Gx = d.shape
+        return d.view(B, C * Gz, Gy, Gx)
+
+
+class _SparseConvBase(nn.Module):
+    subm = False
+
+    def __init__(self, in_channels: int, out_channels: int, kernel_size=3, stride=1, padding=0, bias: bool = True, relu: bool = False,
+                 indice_key: Optional[str] = None):
+        super().__init__()
+        # (shape checks on fixed sizes; the layer's own geometry is checked here so that a bad layer fails at construction)
+        _, self.kernel_size, self.stride, self.padding, _ = ops.sparse_conv_geometry((1 << 10,) * 3, kernel_size, stride, padding, self.subm)
+        self.in_channels, self.out_channels = int(in_channels), int(out_channels)
+        if not (1 <= self.in_channels <= 256 and 1 <= self.out_channels <= 256):
+            raise ValueError(f"channels must be in 1 .. 256, got {in_channels} -> {out_channels}")
+        self.relu = bool(relu)
+        self.indice_key = indice_key
+        kvol = self.kernel_size[0] * self.kernel_size[1] * self.kernel_size[2]
+        self.weight = nn.Parameter(torch.empty((kvol, self.out_channels, self.in_channels), dtype=torch.float32), requires_grad=False)
+        self.bias = nn.Parameter(torch.zeros((self.out_channels,), dtype=torch.float32), requires_grad=False) if bias else None
+        nn.init.uniform_(self.weight, -(kvol * in_channels) ** -0.5, (kvol * in_channels) ** -0.5)
+        self._packed = None         # (key of the parameters it was made from, ops.PackedSparseWeight)
+
+    @staticmethod
+    def from_conv3d_weight(w: torch.Tensor) -> torch.Tensor:
+        """``torch.nn.Conv3d`` weight [Cout,Cin,Kz,Ky,Kx] -> this module's [Kvol,Cout,Cin] (kk = (kz*Ky + ky)*Kx + kx)."""
+        if w.dim() != 5:
+            raise ValueError(f"[Cout,Cin,Kz,Ky,Kx] expected, got {tuple(w.shape)}")
+        co, ci = w.shape[:2]
+        return w.permute(2, 3, 4, 0, 1).reshape(-1, co, ci).contiguous()
+
+    def packed(self) -> "ops.PackedSparseWeight":
+        key = (self.weight.data_ptr(), self.weight._version, None if self.bias is None else (self.bias.data_ptr(), self.bias._version))
+        if self._packed is None or self._packed[0] != key:
+            self._packed = (key, ops.PackedSparseWeight(self.weight.data, None if self.bias is None else self.bias.data))
+        return self._packed[1]
+
+    def rulebook(self, x: SparseTensor):
+        geo = (self.subm, x.spatial_shape, self.kernel_size, self.stride, self.padding)
+        hit = x.rulebooks.get(self.indice_key) if self.indice_key is not None else None
+        if hit is not None:
+            if hit[0] != geo or hit[1] is not x.coors:
+                raise ValueError(f"indice_key {self.indice_key!r} was built for another geometry or another sparse tensor")
+            return hit[2:]
+        out_shape = ops.sparse_conv_geometry(x.spatial_shape, self.kernel_size, self.stride, self.padding, self.subm)[4]
+        out_coors, out_offsets, nbr = ops.sparse_conv_index(x.coors, x.offsets, x.spatial_shape, self.kernel_size, self.stride, self.padding, self.subm)
+        if self.indice_key is not None:
+            x.rulebooks[self.indice_key] = (geo, x.coors, out_coors, out_offsets, nbr, out_shape)
+        return out_coors, out_offsets, nbr, out_shape
+
+    def forward(self, x: SparseTensor, residual: Optional[torch.Tensor] = None) -> SparseTensor:
+        if x.feat.shape[1] != self.in_channels:
+            raise ValueError(f"{self.in_channels} input channels expected, got {x.feat.shape[1]}")
+        with torch.no_grad():
+            out_coors, out_offsets, nbr, out_shape = self.rulebook(x)
+            out = ops.sparse_conv(x.feat, nbr, self.packed(), None, residual, self.relu)
+        return SparseTensor(out, out_coors, out_offsets, out_shape, x.rulebooks)
+
+    def extra_repr(self) -> str:
+        return (f"{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, padding={self.padding}, "
+                f"bias={self.bias is not None}, relu={self.relu}, indice_key={self.indice_key!r}")
+
+
+class SubMConv3d(_SparseConvBase):
+    """Submanifold convolution: odd kernel, stride 1, padding K // 2; the active set does not grow (out rows = in rows)."""
+    subm = True
+
+    def __init__(self, in_channels: int, out_channels: int, kernel_size=3, bias: bool = True, relu: bool = False, indice_key: Optional[str] = None):
+        super().__init__(in_channels, out_channels, kernel_size, 1, 0, bias, relu, indice_key)
+
+
+class SparseConv3d(_SparseConvBase):
+    """Strided sparse convolution: an output site is active iff its window holds an active input; numbered per scene in order of
+    first appearance (§21.1).  Builds its rulebook with one synchronisation (the row count is read back)."""
+    subm = False
+
+
+class SparseSequential(nn.Sequential):
+    """``nn.Sequential`` over sparse layers; a dense module in the chain (e.g. an activation) is applied to ``.feat``."""
+
+    def forward(self, x: SparseTensor) -> SparseTensor:
+        for m in self:
+            if isinstance(m, (_SparseConvBase, SparseSequential)):
+                x = m(x)
+            else:
+                x = x.replace_feature(m(x.feat))
+        return x

@@ -246,6 +246,46 @@ int sad_voxel_reduce_grad_f32(const float *grad_out, const int32_t *point2voxel,
                               int total_points, int B, int Cf, int max_voxels, int mode,
                               const int32_t *count_or_arg, float *grad_feat, sad_stream_t stream);
 
+/* SPEC.md §21 (sparse 3-D convolution).  Additions of ABI 4: the version is unchanged.  A sparse tensor is feat[Nv,C] f32,
+ * coors[Nv,3] int32 (z,y,x), offsets[B+1] int32 on the device (scene b owns rows offsets[b] .. offsets[b+1]-1, offsets[0] = 0,
+ * offsets[B] = Nv, a scene may be empty) and a HOST spatial_shape[3] = (Gz,Gy,Gx), at most 2^31 - 1 cells.  kernel, stride and
+ * padding are HOST arrays of 3 ints in (z,y,x) order: kernel sizes 1 .. 3, stride >= 1, padding >= 0.  Coordinates outside the
+ * grid are undefined behaviour.  kk = (kz*Ky + ky)*Kx + kx; nbr[o,kk] = the lowest input row of o's scene at
+ * out_coors[o]*s - p + k, or -1.  Nv <= 2^30, Nv * Kvol < 2^31, B <= 65535.
+ *
+ * workspace: sad_spconv_workspace_bytes(Nv, B, kernel, stride, subm, &bytes) bytes of 16-byte aligned device scratch (stride is
+ *   ignored and may be NULL when subm != 0).  Contents arbitrary on entry.  index_count leaves in it what index_fill needs: the
+ *   two calls share one workspace, on one stream, with nothing of the library in between.
+ * index_subm: odd kernel sizes, stride 1, padding K/2: the outputs ARE the inputs (out_coors = coors, out_offsets = offsets);
+ *   -> nbr[Nv,Kvol].
+ * index_count: the strided form, first half -> out_offsets[B+1] on the device (out_offsets[B] = No, the number of active output
+ *   sites, numbered per scene in order of first appearance over the candidates (input row, kk) ascending).
+ * index_fill: second half, with the out_offsets of index_count -> out_coors[capacity,3], nbr[capacity,Kvol]: rows below
+ *   min(No, capacity) are filled, rows from No up to capacity get -1; nothing is written at or beyond capacity.
+ * pack: W[Kvol,Cout,Cin] row-major (+ bias[Cout] or NULL) -> packed[sad_spconv_packed_floats(Kvol,Cin,Cout)] floats, 16-byte
+ *   aligned: the fragment image the convolution reads.  1 <= Cin, Cout <= 256 (SAD_EUNSUPPORTED above; packed_floats returns 0).
+ * spconv: out[No,Cout] = bias + sum over kk ascending, ci ascending of W[kk][co][ci] * feat[nbr[o,kk]][ci] (fmaf chain, §21.2),
+ *   then + residual[No,Cout] (may be NULL), then ReLU if relu != 0.  nbr entries outside [0, Nv) count as -1.
+ * sparse_to_dense: -> dense[B,C,Oz,Oy,Ox], zero where no row is, the lowest row of a cell elsewhere; rows with a coordinate
+ *   outside out_shape are skipped.  workspace: sad_sparse_to_dense_workspace_bytes(B, out_shape, &bytes), B*Oz*Oy*Ox < 2^31. */
+int sad_spconv_workspace_bytes(int Nv, int B, const int *kernel, const int *stride, int subm, size_t *bytes);
+int sad_spconv_index_subm(const int32_t *coors, const int32_t *offsets, int Nv, int B, const int *spatial_shape,
+                          const int *kernel, int32_t *nbr, void *workspace, sad_stream_t stream);
+int sad_spconv_index_count(const int32_t *coors, const int32_t *offsets, int Nv, int B, const int *spatial_shape,
+                           const int *kernel, const int *stride, const int *padding, int32_t *out_offsets,
+                           void *workspace, sad_stream_t stream);
+int sad_spconv_index_fill(const int32_t *coors, const int32_t *offsets, int Nv, int B, const int *spatial_shape,
+                          const int *kernel, const int *stride, const int *padding, const int32_t *out_offsets,
+                          int capacity, int32_t *out_coors, int32_t *nbr, void *workspace, sad_stream_t stream);
+size_t sad_spconv_packed_floats(int Kvol, int Cin, int Cout);
+int sad_spconv_pack_f32(const float *W, const float *bias, int Kvol, int Cin, int Cout, float *packed,
+                        sad_stream_t stream);
+int sad_spconv_f32(const float *feat, const int32_t *nbr, const float *packed, const float *residual, int relu,
+                   int Nv, int No, int Kvol, int Cin, int Cout, float *out, sad_stream_t stream);
+int sad_sparse_to_dense_workspace_bytes(int B, const int *out_shape, size_t *bytes);
+int sad_sparse_to_dense_f32(const float *feat, const int32_t *out_coors, const int32_t *out_offsets, int No, int B,
+                            int C, const int *out_shape, float *dense, void *workspace, sad_stream_t stream);
+
 /* SPEC.md §4.  -> idx[B,M,K] sorted by (d2, index); K <= 64, K <= N. */
 int sad_knn_f32(const float *xyz, const float *new_xyz, int B, int N, int M, int K, int32_t *idx,
                 sad_stream_t stream);

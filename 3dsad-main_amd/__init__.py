@@ -24,6 +24,7 @@ _LAZY = {
     "voxel_coords": "ops", "voxel_index": "ops", "voxelize": "ops", "voxel_reduce": "ops",
     "Voxelization": "voxel", "DynamicScatter": "voxel",
     "sparse_conv_index": "ops", "sparse_conv": "ops", "sparse_to_dense": "ops", "PackedSparseWeight": "ops",
+    "sparse_conv_index_transpose": "ops", "sparse_conv_grad_weight": "ops", "sparse_conv_grad_input": "ops",
     "SparseTensor": "spconv", "SubMConv3d": "spconv", "SparseConv3d": "spconv", "SparseSequential": "spconv",
     "SAModuleMSG": "sa_module", "SAModule": "sa_module", "sa_module": "sa_module",
     "SADDetector": "detector", "IngestPipeline": "pipeline",

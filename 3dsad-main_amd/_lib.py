@@ -113,6 +113,9 @@ SIGNATURES = {
     "sad_spconv_f32": (ctypes.c_int, [vp, vp, vp, vp] + [ctypes.c_int] * 6 + [vp, vp]),
     "sad_sparse_to_dense_workspace_bytes": (ctypes.c_int, [ctypes.c_int, c_i3p, ctypes.POINTER(ctypes.c_size_t)]),
     "sad_sparse_to_dense_f32": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 3 + [c_i3p, vp, vp, vp]),
+    "sad_spconv_index_transpose": (ctypes.c_int, [vp] + [ctypes.c_int] * 3 + [vp, vp, vp]),
+    "sad_spconv_grad_weight_workspace_bytes": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_size_t)]),
+    "sad_spconv_grad_weight_f32": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 5 + [vp, vp, vp, vp]),
     "sad_mlp_packed_floats": (ctypes.c_size_t, [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int]),
     "sad_mlp_pack_f32": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
                                        ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp]),

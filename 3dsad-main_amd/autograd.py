@@ -1,11 +1,13 @@
 """Differentiable forms of the unfused operators (SPEC.md §16).
 
-``group_points`` / ``gather_points`` / ``max_pool_s`` as ``torch.autograd.Function``s whose forward
+``group_points`` / ``gather_points`` / ``max_pool_s`` (and ``three_interpolate`` §18, ``voxel_reduce`` §20.5, ``sparse_conv`` /
+``sparse_to_dense`` §21.4) as ``torch.autograd.Function``s whose forward
 AND backward are this package's HIP kernels (float32 only): the classic unfused
 ``group -> shared MLP (any torch layers) -> max over nsample`` stack becomes trainable without a
 PyTorch-side scatter.  The fused inference kernels (``PackedMLP.grouped``) have no backward.
 """
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import ops
 from ._lib import check, lib
@@ -174,7 +176,94 @@ class VoxelReduce(torch.autograd.Function):
         return g, None, None, None, None
 
 
+def _transposed(transposed, nbr, Nv):
+    """-> (nbrT, collisions as a Python int) from what ``SparseConv`` was given: None (built here, one synchronisation), a
+    callable that returns the pair (a layer's cache) or the pair itself."""
+    if transposed is None:
+        nbrT, col = ops.sparse_conv_index_transpose(nbr, Nv)
+        return nbrT, int(col.item())
+    nbrT, col = transposed() if callable(transposed) else transposed
+    return nbrT, int(col)
+
+
+class SparseConv(torch.autograd.Function):
+    """``ops.sparse_conv`` with its backward (SPEC.md §21.4): feat [Nv,Cin], weight [Kvol,Cout,Cin], bias [Cout] | None,
+    residual [No,Cout] | None, nbr [No,Kvol] int32, relu -> out [No,Cout].  Gradients for feat, weight, bias and residual, each
+    computed only where ``ctx.needs_input_grad`` asks: grad_W / grad_bias by ``sad_spconv_grad_weight_f32``, grad_feat by the
+    forward kernel over the transposed rulebook and the packed W^T.  Optional: ``transposed`` = (nbrT, collisions) or a callable
+    returning it (a layer's per-``indice_key`` cache; built on demand otherwise), ``packed`` = the ``PackedSparseWeight`` of
+    (weight, bias) and ``packed_t`` = a callable returning the one of W^T (what the layers cache per parameter version).
+    A transposed rulebook with collisions (an input that holds a coordinate twice, submanifold form) has no gradient for feat:
+    ``ValueError``.  nbr gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, feat, weight, bias, residual, nbr, relu=False, transposed=None, packed=None, packed_t=None):
+        feat = _f32(feat, "feat", 2)
+        weight = _f32(weight, "weight", 3)
+        if packed is None:
+            out = ops.sparse_conv(feat, nbr, weight, bias, residual, relu)
+        else:
+            out = ops.sparse_conv(feat, nbr, packed, None, residual, relu)
+        ctx.relu, ctx.transposed, ctx.packed_t = bool(relu), transposed, packed_t
+        ctx.save_for_backward(feat, weight, nbr, out if relu else None)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        feat, weight, nbr, out = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        g = _f32(grad_out, "grad_out", 2)
+        if ctx.relu:
+            g = g * (out > 0)                      # exact: g or 0
+        grad_feat = grad_w = grad_b = None
+        if need[0]:
+            nbrT, collisions = _transposed(ctx.transposed, nbr, feat.shape[0])
+            if collisions:
+                raise ValueError(f"sparse_conv backward: the rulebook maps {collisions} (output row, offset) pairs onto input rows that a "
+                                 "lower row already holds: the input has a duplicate coordinate inside a scene (submanifold form), "
+                                 "for which no gradient with respect to feat is defined (SPEC.md §21.4)")
+            grad_feat = ops.sparse_conv_grad_input(g, nbrT, ctx.packed_t() if ctx.packed_t is not None else weight)
+        if need[1] or need[2]:
+            grad_w, grad_b = ops.sparse_conv_grad_weight(feat, nbr, g, bias=need[2], weight=need[1])   # (a frozen weight: no GEMM)
+        return grad_feat, grad_w, grad_b, (g if need[3] else None), None, None, None, None, None
+
+
+class SparseToDense(torch.autograd.Function):
+    """``ops.sparse_to_dense`` (SPEC.md §21.3) with its backward: feat [No,C], out_coors [No,3], out_offsets [B+1], out_shape ->
+    dense [B,C,Oz,Oy,Ox].  grad_feat[o] = grad_dense at o's cell for the row that owns the cell (the lowest), zero for a shadowed
+    duplicate and for a row outside ``out_shape`` — a framework gather over out_coors (exact; not a hot path; its transient memory
+    is a few arrays of No entries, nothing of the size of the grid)."""
+
+    @staticmethod
+    def forward(ctx, feat, out_coors, out_offsets, out_shape):
+        ctx.save_for_backward(out_coors, out_offsets)
+        ctx.out_shape = tuple(int(v) for v in out_shape)
+        return ops.sparse_to_dense(_f32(feat, "feat", 2), out_coors, out_offsets, out_shape)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_dense):
+        coors, offsets = ctx.saved_tensors
+        Oz, Oy, Ox = ctx.out_shape
+        B = grad_dense.shape[0]
+        No, dev = coors.shape[0], coors.device
+        rows = torch.arange(No, device=dev)
+        scene = (torch.searchsorted(offsets.to(torch.int64), rows, right=True) - 1).clamp(0, B - 1)
+        z, y, x = (coors[:, d].to(torch.int64) for d in range(3))
+        inside = (z >= 0) & (z < Oz) & (y >= 0) & (y < Oy) & (x >= 0) & (x < Ox)
+        # the owner of a cell among the No rows only (nothing of the size of the grid is allocated): rows outside get ids of their own
+        cell = torch.where(inside, ((scene * Oz + z) * Oy + y) * Ox + x, -1 - rows)
+        _, group = torch.unique(cell, return_inverse=True)
+        owner = torch.full((No,), No, dtype=torch.int64, device=dev).scatter_reduce_(0, group, rows, "amin")
+        mine = inside & (owner[group] == rows)
+        picked = grad_dense[scene, :, z.clamp(0, Oz - 1), y.clamp(0, Oy - 1), x.clamp(0, Ox - 1)]      # [No, C]
+        return picked * mine[:, None].to(picked.dtype), None, None, None
+
+
 group_points = GroupPoints.apply
+sparse_conv = SparseConv.apply
+sparse_to_dense = SparseToDense.apply
 voxel_reduce = VoxelReduce.apply
 gather_points = GatherPoints.apply
 max_pool_s = MaxPoolS.apply

@@ -46,6 +46,7 @@ SAD_API int sad_set_option(const char *key, int value) {
     if (!strcmp(key, "bq_variant")) { sad::g_opt[sad::OPT_BQ_VARIANT].store(value, std::memory_order_relaxed); return SAD_OK; }
     if (!strcmp(key, "fps_threads")) { sad::g_opt[sad::OPT_FPS_THREADS].store(value, std::memory_order_relaxed); return SAD_OK; }
     if (!strcmp(key, "nn_variant")) { sad::g_opt[sad::OPT_NN_VARIANT].store(value, std::memory_order_relaxed); return SAD_OK; }   // three_nn: 1 = scalar loads, 2 = LDS with two points per lane
+    if (!strcmp(key, "spconv_grad_ranges")) { sad::g_opt[sad::OPT_SPCONV_GRAD_RANGES].store(value, std::memory_order_relaxed); return SAD_OK; }   // test knob: row ranges of the weight-gradient grid (0 = sized by the device)
     if (!strcmp(key, "fps_variant")) { sad::g_opt[sad::OPT_FPS_VARIANT].store(value, std::memory_order_relaxed); return SAD_OK; }
     return sad::fail(SAD_EINVAL, "sad_set_option: unknown key '%s'", key);
 }

@@ -861,6 +861,73 @@ def sparse_conv(feat: torch.Tensor, nbr: torch.Tensor, weight, bias: Optional[to
     return out
 
 
+def sparse_conv_index_transpose(nbr: torch.Tensor, Nv: int):
+    """Transposed rulebook (SPEC.md §21.4).  nbr [No,Kvol] int32, ``Nv`` input rows -> (nbrT [Nv,Kvol] int32, collisions: int32
+    scalar tensor on the device): nbrT[i,kk] = the lowest o with nbr[o,kk] == i, -1 if none; collisions = the entries (o,kk) that
+    another, lower row shadows.  ``sparse_conv_grad_input`` over nbrT is the true gradient iff collisions == 0.  Integer work,
+    equal to the reference.  No gradient."""
+    _unrecordable("sparse_conv_index_transpose")
+    nbr = _need(nbr, "nbr", torch.int32, 2)
+    Nv = int(Nv)
+    No, Kvol = nbr.shape
+    if Nv < 0:
+        raise ValueError(f"Nv={Nv} must be >= 0")
+    if not (1 <= Kvol <= 27):
+        raise ValueError(f"nbr: Kvol = {Kvol} must be in 1 .. 27")
+    nbrT = torch.empty((Nv, Kvol), dtype=torch.int32, device=nbr.device)
+    collisions = torch.empty((), dtype=torch.int32, device=nbr.device)
+    with _timed("spconv_index", f"transpose n{No}k{Kvol}"):
+        check(lib().sad_spconv_index_transpose(nbr.data_ptr(), No, Nv, Kvol, nbrT.data_ptr(), collisions.data_ptr(), _stream()),
+              "sad_spconv_index_transpose")
+    return nbrT, collisions
+
+
+def sparse_conv_grad_weight(feat: torch.Tensor, nbr: torch.Tensor, g: torch.Tensor, bias: bool = True, weight: bool = True):
+    """Weight gradient of ``sparse_conv`` (SPEC.md §21.4).  feat [Nv,Cin] f32 (the forward's input), nbr [No,Kvol] int32,
+    g [No,Cout] f32 (the output gradient AFTER the ReLU mask) -> (grad_W [Kvol,Cout,Cin], grad_bias [Cout] or None with
+    ``bias=False``; ``weight=False`` -> (None, grad_bias): the column sums only, no GEMM): grad_W[kk] = sum over the rows o with nbr[o,kk] >= 0 of g[o] (x) feat[nbr[o,kk]].  binary32 sums in an
+    order that is not specified (float atomics): within n * 2^-23 * sum |terms| of the exact sum, exact where every partial
+    sum is representable, not bit-equal from call to call."""
+    _unrecordable("sparse_conv_grad_weight")
+    feat = _need(feat, "feat", torch.float32, 2)
+    nbr = _need(nbr, "nbr", torch.int32, 2)
+    g = _need(g, "g", torch.float32, 2)
+    (Nv, cin), (No, kvol), cout, dev = feat.shape, nbr.shape, g.shape[1], feat.device
+    if g.shape[0] != No:
+        raise ValueError(f"g: one row per row of nbr expected, got {tuple(g.shape)} for nbr {tuple(nbr.shape)}")
+    if nbr.device != dev or g.device != dev:
+        raise ValueError("feat, nbr and g must be on one device")
+    if not (1 <= kvol <= 27 and 1 <= cin <= 256 and 1 <= cout <= 256):
+        raise ValueError(f"Kvol = {kvol} must be in 1 .. 27, Cin = {cin} and Cout = {cout} in 1 .. 256")
+    if not (bias or weight):
+        raise ValueError("sparse_conv_grad_weight: nothing asked for (bias=False, weight=False)")
+    n = ctypes.c_size_t(0)
+    check(lib().sad_spconv_grad_weight_workspace_bytes(No, kvol, cin, cout, ctypes.byref(n)), "sad_spconv_grad_weight_workspace_bytes")
+    ws = torch.empty((n.value,), dtype=torch.uint8, device=dev) if n.value else None
+    grad_w = torch.empty((kvol, cout, cin), dtype=torch.float32, device=dev) if weight else None
+    grad_b = torch.empty((cout,), dtype=torch.float32, device=dev) if bias else None
+    with _timed("spconv_grad_w", f"n{No}k{kvol}c{cin}x{cout}"):
+        check(lib().sad_spconv_grad_weight_f32(feat.data_ptr(), nbr.data_ptr(), g.data_ptr(), Nv, No, kvol, cin, cout, grad_w.data_ptr() if weight else None,
+                                               grad_b.data_ptr() if bias else None, ws.data_ptr() if ws is not None else None, _stream()),
+              "sad_spconv_grad_weight_f32")
+    return grad_w, grad_b
+
+
+def sparse_conv_grad_input(g: torch.Tensor, nbrT: torch.Tensor, weight) -> torch.Tensor:
+    """Input gradient of ``sparse_conv`` (SPEC.md §21.4).  g [No,Cout] f32 (after the ReLU mask), nbrT [Nv,Kvol] int32
+    (``sparse_conv_index_transpose``), ``weight`` = the forward's W [Kvol,Cout,Cin] (transposed and packed on every call) or a
+    ``PackedSparseWeight`` made from W.transpose(1, 2) without a bias -> grad_feat [Nv,Cin]: the §21.2 chain over
+    (g, nbrT, W^T) on the forward kernel, equal to the reference under ``==``.  The true gradient iff the transposed rulebook
+    has no collisions."""
+    if isinstance(weight, PackedSparseWeight):
+        if weight.has_bias:
+            raise ValueError("weight: the packed W^T of a gradient carries no bias")
+        pw = weight
+    else:
+        pw = PackedSparseWeight(_need(weight, "weight", torch.float32, 3).transpose(1, 2).contiguous(), None)
+    return sparse_conv(g, nbrT, pw, None, None, False)
+
+
 def sparse_to_dense(feat: torch.Tensor, out_coors: torch.Tensor, out_offsets: torch.Tensor, out_shape) -> torch.Tensor:
     """SPEC.md §21.3: feat [No,C] f32, out_coors [No,3] int32 (z,y,x), out_offsets [B+1] int32 -> dense [B,C,Oz,Oy,Ox] f32, zero
     where no voxel is and an exact copy elsewhere (the lowest row on a duplicate; rows with a coordinate outside ``out_shape``,

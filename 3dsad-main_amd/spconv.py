@@ -3,19 +3,27 @@
 
 A ``SparseTensor`` is ``feat [Nv,C]`` f32, ``coors [Nv,3]`` int32 (z,y,x), ``offsets [B+1]`` int32 (all on the GPU) and a host
 ``spatial_shape`` (Gz,Gy,Gx).  It carries a rulebook cache: layers that name the same ``indice_key`` (the submanifold layers of
-one resolution) build ``nbr`` once.  Forward only (no gradients yet); everything is deterministic and equal to the reference
-restatement under ``==``; there is no CPU path."""
+one resolution) build ``nbr`` once.  The forward is deterministic and equal to the reference restatement under ``==``; there is
+no CPU path.
+
+Training (SPEC.md §21.4).  Parameters are created with ``requires_grad=False`` and the layers then run the plain forward
+under ``no_grad``; ``module.requires_grad_(True)`` (or an input whose ``feat`` requires grad) routes a layer through
+``autograd.SparseConv``: grad_W / grad_bias by the weight-gradient kernel (float atomics: within the §21.4 bound, not bit-equal
+from run to run), grad_feat by the forward kernel over the transposed rulebook, which is built at the first backward that needs
+it and cached per ``indice_key`` beside the rulebook (``SparseTensor.transposed``; its collision count is read back once).
+``dense()`` / ``bev()`` are differentiable the same way.  A scene that holds a coordinate twice has no gradient through a
+submanifold layer (``ValueError`` in backward); ``from_voxels`` never produces one."""
 from typing import Optional, Sequence
 
 import torch
 from torch import nn
 
-from . import ops
+from . import autograd, ops
 
 
 class SparseTensor:
     def __init__(self, feat: torch.Tensor, coors: torch.Tensor, offsets: torch.Tensor, spatial_shape: Sequence[int],
-                 rulebooks: Optional[dict] = None):
+                 rulebooks: Optional[dict] = None, transposed: Optional[dict] = None):
         if feat.dim() != 2 or coors.dim() != 2 or coors.shape[1] != 3 or coors.shape[0] != feat.shape[0]:
             raise ValueError(f"feat [Nv,C] and coors [Nv,3] expected, got {tuple(feat.shape)} and {tuple(coors.shape)}")
         if offsets.dim() != 1 or offsets.shape[0] < 2:
@@ -26,6 +34,8 @@ class SparseTensor:
         self.spatial_shape = tuple(int(g) for g in spatial_shape)
         # indice_key -> (geometry, in_coors, out_coors, out_offsets, nbr, out_shape); shared by every tensor derived from this one
         self.rulebooks = {} if rulebooks is None else rulebooks
+        # indice_key -> (nbr, nbrT, collisions): the transposed rulebook of §21.4, made by the first backward that needs it; shared likewise
+        self.transposed = {} if transposed is None else transposed
 
     @property
     def batch_size(self) -> int:
@@ -48,10 +58,12 @@ class SparseTensor:
                    offsets, spatial_shape)
 
     def replace_feature(self, feat: torch.Tensor) -> "SparseTensor":
-        return SparseTensor(feat, self.coors, self.offsets, self.spatial_shape, self.rulebooks)
+        return SparseTensor(feat, self.coors, self.offsets, self.spatial_shape, self.rulebooks, self.transposed)
 
     def dense(self) -> torch.Tensor:
-        """-> [B,C,Gz,Gy,Gx], zero where no voxel is (§21.3)."""
+        """-> [B,C,Gz,Gy,Gx], zero where no voxel is (§21.3); differentiable with respect to ``feat`` (§21.4)."""
+        if torch.is_grad_enabled() and self.feat.requires_grad:
+            return autograd.sparse_to_dense(self.feat, self.coors, self.offsets, self.spatial_shape)
         return ops.sparse_to_dense(self.feat, self.coors, self.offsets, self.spatial_shape)
 
     def bev(self) -> torch.Tensor:
@@ -79,6 +91,7 @@ class _SparseConvBase(nn.Module):
         self.bias = nn.Parameter(torch.zeros((self.out_channels,), dtype=torch.float32), requires_grad=False) if bias else None
         nn.init.uniform_(self.weight, -(kvol * in_channels) ** -0.5, (kvol * in_channels) ** -0.5)
         self._packed = None         # (key of the parameters it was made from, ops.PackedSparseWeight)
+        self._packed_t = None       # the same for W^T (no bias): the weights of the input gradient (§21.4)
 
     @staticmethod
     def from_conv3d_weight(w: torch.Tensor) -> torch.Tensor:
@@ -93,6 +106,24 @@ class _SparseConvBase(nn.Module):
         if self._packed is None or self._packed[0] != key:
             self._packed = (key, ops.PackedSparseWeight(self.weight.data, None if self.bias is None else self.bias.data))
         return self._packed[1]
+
+    def packed_t(self) -> "ops.PackedSparseWeight":
+        key = (self.weight.data_ptr(), self.weight._version)
+        if self._packed_t is None or self._packed_t[0] != key:
+            self._packed_t = (key, ops.PackedSparseWeight(self.weight.data.transpose(1, 2).contiguous(), None))
+        return self._packed_t[1]
+
+    def transposed(self, x: SparseTensor, nbr: torch.Tensor):
+        """(nbrT, collisions) of this layer's rulebook on ``x``; cached under ``indice_key`` (one synchronisation at the build)."""
+        hit = x.transposed.get(self.indice_key) if self.indice_key is not None else None
+        if hit is not None and hit[0] is nbr:
+            return hit[1:]
+        with torch.no_grad():
+            nbrT, col = ops.sparse_conv_index_transpose(nbr, x.feat.shape[0])
+        col = int(col.item())
+        if self.indice_key is not None:
+            x.transposed[self.indice_key] = (nbr, nbrT, col)
+        return nbrT, col
 
     def rulebook(self, x: SparseTensor):
         geo = (self.subm, x.spatial_shape, self.kernel_size, self.stride, self.padding)
@@ -110,10 +141,15 @@ class _SparseConvBase(nn.Module):
     def forward(self, x: SparseTensor, residual: Optional[torch.Tensor] = None) -> SparseTensor:
         if x.feat.shape[1] != self.in_channels:
             raise ValueError(f"{self.in_channels} input channels expected, got {x.feat.shape[1]}")
+        train = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x.feat, self.weight, self.bias, residual))
         with torch.no_grad():
             out_coors, out_offsets, nbr, out_shape = self.rulebook(x)
-            out = ops.sparse_conv(x.feat, nbr, self.packed(), None, residual, self.relu)
-        return SparseTensor(out, out_coors, out_offsets, out_shape, x.rulebooks)
+            if not train:
+                out = ops.sparse_conv(x.feat, nbr, self.packed(), None, residual, self.relu)
+        if train:
+            out = autograd.sparse_conv(x.feat, self.weight, self.bias, residual, nbr, self.relu, lambda: self.transposed(x, nbr),
+                                       self.packed(), self.packed_t)
+        return SparseTensor(out, out_coors, out_offsets, out_shape, x.rulebooks, x.transposed)
 
     def extra_repr(self) -> str:
         return (f"{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, padding={self.padding}, "

@@ -285,6 +285,24 @@ int sad_spconv_f32(const float *feat, const int32_t *nbr, const float *packed, c
 int sad_sparse_to_dense_workspace_bytes(int B, const int *out_shape, size_t *bytes);
 int sad_sparse_to_dense_f32(const float *feat, const int32_t *out_coors, const int32_t *out_offsets, int No, int B,
                             int C, const int *out_shape, float *dense, void *workspace, sad_stream_t stream);
+/* SPEC.md §21.4 (backward of the sparse convolution; additions of ABI 4 as well).  g[No,Cout] is the gradient of the output AFTER
+ * the ReLU mask (g = out > 0 ? grad_out : 0 is the caller's).
+ * index_transpose: nbr[No,Kvol] -> nbrT[Nv,Kvol], nbrT[i,kk] = the lowest o with nbr[o,kk] == i or -1, and *collisions (device) =
+ *   the number of (o,kk) with i = nbr[o,kk] in [0, Nv) and nbrT[i,kk] != o.  Entries outside [0, Nv) count as -1.
+ *   No * Kvol, Nv * Kvol < 2^31.  grad_feat[Nv,Cin] is then sad_spconv_f32(g, nbrT, pack(W^T), NULL, 0, No, Nv, Kvol, Cout, Cin),
+ *   W^T[kk][ci][co] = W[kk][co][ci]: the true gradient iff *collisions == 0.
+ * grad_weight: grad_W[Kvol,Cout,Cin] = sum over o with nbr[o,kk] >= 0 of g[o][co] * feat[nbr[o,kk]][ci] and, unless NULL,
+ *   grad_bias[Cout] = sum over o of g[o][co]; both are OVERWRITTEN (zeros for No = 0 or Nv = 0).  either may be NULL (not both): a NULL grad_W
+ *   launches the column sums only.  binary32 sums whose order is not specified: float atomics, so two calls may differ in the last
+ *   bits.  Option "spconv_grad_ranges" (test knob): n > 0 = split the output rows into about n ranges of 64-row tiles (at most 1024
+ *   tiles each, more ranges beyond), 0 = sized by the device (default).  1 <= Cin, Cout <= 256, Kvol <= 27.  workspace:
+ *   sad_spconv_grad_weight_workspace_bytes(No, Kvol, Cin, Cout, &bytes) bytes of 16-byte aligned device scratch; this form needs
+ *   none (bytes = 0, workspace may then be NULL). */
+int sad_spconv_index_transpose(const int32_t *nbr, int No, int Nv, int Kvol, int32_t *nbrT, int32_t *collisions,
+                               sad_stream_t stream);
+int sad_spconv_grad_weight_workspace_bytes(int No, int Kvol, int Cin, int Cout, size_t *bytes);
+int sad_spconv_grad_weight_f32(const float *feat, const int32_t *nbr, const float *g, int Nv, int No, int Kvol, int Cin,
+                               int Cout, float *grad_W, float *grad_bias, void *workspace, sad_stream_t stream);
 
 /* SPEC.md §4.  -> idx[B,M,K] sorted by (d2, index); K <= 64, K <= N. */
 int sad_knn_f32(const float *xyz, const float *new_xyz, int B, int N, int M, int K, int32_t *idx,

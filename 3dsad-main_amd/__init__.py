@@ -25,6 +25,7 @@ _LAZY = {
     "Voxelization": "voxel", "DynamicScatter": "voxel",
     "sparse_conv_index": "ops", "sparse_conv": "ops", "sparse_to_dense": "ops", "PackedSparseWeight": "ops",
     "sparse_conv_index_transpose": "ops", "sparse_conv_grad_weight": "ops", "sparse_conv_grad_input": "ops",
+    "sparse_max_pool": "ops", "sparse_max_pool_grad": "ops", "SparseMaxPool3d": "spconv", "SparseInverseConv3d": "spconv",
     "SparseTensor": "spconv", "SubMConv3d": "spconv", "SparseConv3d": "spconv", "SparseSequential": "spconv",
     "SAModuleMSG": "sa_module", "SAModule": "sa_module", "sa_module": "sa_module",
     "SADDetector": "detector", "IngestPipeline": "pipeline",

@@ -116,6 +116,8 @@ SIGNATURES = {
     "sad_spconv_index_transpose": (ctypes.c_int, [vp] + [ctypes.c_int] * 3 + [vp, vp, vp]),
     "sad_spconv_grad_weight_workspace_bytes": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_size_t)]),
     "sad_spconv_grad_weight_f32": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 5 + [vp, vp, vp, vp]),
+    "sad_spconv_max_pool_f32": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 4 + [vp, vp, vp]),
+    "sad_spconv_max_pool_grad_f32": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 4 + [vp, vp]),
     "sad_mlp_packed_floats": (ctypes.c_size_t, [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int]),
     "sad_mlp_pack_f32": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
                                        ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp]),

@@ -1,7 +1,7 @@
 """Differentiable forms of the unfused operators (SPEC.md §16).
 
 ``group_points`` / ``gather_points`` / ``max_pool_s`` (and ``three_interpolate`` §18, ``voxel_reduce`` §20.5, ``sparse_conv`` /
-``sparse_to_dense`` §21.4) as ``torch.autograd.Function``s whose forward
+``sparse_to_dense`` §21.4, ``sparse_max_pool`` §22.2) as ``torch.autograd.Function``s whose forward
 AND backward are this package's HIP kernels (float32 only): the classic unfused
 ``group -> shared MLP (any torch layers) -> max over nsample`` stack becomes trainable without a
 PyTorch-side scatter.  The fused inference kernels (``PackedMLP.grouped``) have no backward.
@@ -229,6 +229,34 @@ class SparseConv(torch.autograd.Function):
         return grad_feat, grad_w, grad_b, (g if need[3] else None), None, None, None, None, None
 
 
+class SparseMaxPool(torch.autograd.Function):
+    """``ops.sparse_max_pool`` with its backward (SPEC.md §22.1, §22.2): feat [Nv,C], nbr [No,Kvol] int32 -> out [No,C]; the forward
+    keeps ``arg``.  Gradient for feat only, by ``ops.sparse_max_pool_grad`` over the transposed rulebook (a gather: exact and
+    bit-equal from call to call).  Optional ``transposed`` as for ``SparseConv``: (nbrT, collisions), a callable returning it, or
+    None (built at the backward, one synchronisation).  A transposed rulebook with collisions has no gradient: ``ValueError``."""
+
+    @staticmethod
+    def forward(ctx, feat, nbr, transposed=None):
+        feat = _f32(feat, "feat", 2)
+        out, arg = ops.sparse_max_pool(feat, nbr)
+        ctx.Nv, ctx.transposed = feat.shape[0], transposed
+        ctx.save_for_backward(arg, nbr)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        arg, nbr = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        nbrT, collisions = _transposed(ctx.transposed, nbr, ctx.Nv)
+        if collisions:
+            raise ValueError(f"sparse_max_pool backward: the rulebook maps {collisions} (output row, offset) pairs onto input rows that a "
+                             "lower row already holds: the input has a duplicate coordinate inside a scene (submanifold form), "
+                             "for which no gradient with respect to feat is defined (SPEC.md §22.2)")
+        return ops.sparse_max_pool_grad(_f32(grad_out, "grad_out", 2), arg, nbrT, ctx.Nv), None, None
+
+
 class SparseToDense(torch.autograd.Function):
     """``ops.sparse_to_dense`` (SPEC.md §21.3) with its backward: feat [No,C], out_coors [No,3], out_offsets [B+1], out_shape ->
     dense [B,C,Oz,Oy,Ox].  grad_feat[o] = grad_dense at o's cell for the row that owns the cell (the lowest), zero for a shadowed
@@ -263,6 +291,7 @@ class SparseToDense(torch.autograd.Function):
 
 group_points = GroupPoints.apply
 sparse_conv = SparseConv.apply
+sparse_max_pool = SparseMaxPool.apply
 sparse_to_dense = SparseToDense.apply
 voxel_reduce = VoxelReduce.apply
 gather_points = GatherPoints.apply

@@ -928,6 +928,60 @@ def sparse_conv_grad_input(g: torch.Tensor, nbrT: torch.Tensor, weight) -> torch
     return sparse_conv(g, nbrT, pw, None, None, False)
 
 
+def _pool_sizes(Nv: int, No: int, Kvol: int, C: int, what: str) -> None:
+    if not (1 <= Kvol <= 27):
+        raise ValueError(f"{what}: Kvol = {Kvol} must be in 1 .. 27")
+    if C < 1:
+        raise ValueError(f"{what}: at least one channel expected")
+    if Nv * C >= 2 ** 31 or No * C >= 2 ** 31:
+        raise ValueError(f"{what}: Nv * C and No * C must be below 2^31, got {Nv} and {No} rows of {C}")
+
+
+def sparse_max_pool(feat: torch.Tensor, nbr: torch.Tensor):
+    """Sparse max pool over a rulebook (SPEC.md §22.1).  feat [Nv,C] f32, nbr [No,Kvol] int32 (``sparse_conv_index``, or a
+    caller's: entries outside [0, Nv) count as -1) -> (out [No,C] f32, arg [No,C] int32): per channel the maximum over the valid
+    entries, ties to the lowest kk, and the global input row it came from; 0.0 and -1 for a row without a valid entry (an absent
+    neighbour is absent, not a zero).  Exact: ``out`` is a bit copy of one input element.  No gradient
+    (``autograd.sparse_max_pool``)."""
+    _unrecordable("sparse_max_pool")
+    feat = _need(feat, "feat", torch.float32, 2)
+    nbr = _need(nbr, "nbr", torch.int32, 2)
+    (Nv, C), (No, Kvol), dev = feat.shape, nbr.shape, feat.device
+    if nbr.device != dev:
+        raise ValueError("feat and nbr must be on one device")
+    _pool_sizes(Nv, No, Kvol, C, "sparse_max_pool")
+    out = torch.empty((No, C), dtype=torch.float32, device=dev)
+    arg = torch.empty((No, C), dtype=torch.int32, device=dev)
+    with _timed("spconv_pool", f"n{No}k{Kvol}c{C}"):
+        check(lib().sad_spconv_max_pool_f32(feat.data_ptr(), nbr.data_ptr(), Nv, No, Kvol, C, out.data_ptr(), arg.data_ptr(), _stream()),
+              "sad_spconv_max_pool_f32")
+    return out, arg
+
+
+def sparse_max_pool_grad(g: torch.Tensor, arg: torch.Tensor, nbrT: torch.Tensor, Nv: int) -> torch.Tensor:
+    """Backward of ``sparse_max_pool`` (SPEC.md §22.2).  g [No,C] f32, arg [No,C] int32 (the forward's), nbrT [Nv,Kvol] int32
+    (``sparse_conv_index_transpose`` of the forward's nbr) -> grad_feat [Nv,C]: per element the sum, kk ascending, of g[o][c] over
+    o = nbrT[i,kk] with arg[o][c] == i.  A gather: no atomics, bit-equal from call to call, equal to the reference under ``==``.
+    The true gradient iff the transposed rulebook has no collisions."""
+    _unrecordable("sparse_max_pool_grad")
+    g = _need(g, "g", torch.float32, 2)
+    arg = _need(arg, "arg", torch.int32, 2)
+    nbrT = _need(nbrT, "nbrT", torch.int32, 2)
+    (No, C), Kvol, dev, Nv = g.shape, nbrT.shape[1], g.device, int(Nv)
+    if tuple(arg.shape) != (No, C):
+        raise ValueError(f"arg: the shape of g expected, got {tuple(arg.shape)} for g {tuple(g.shape)}")
+    if nbrT.shape[0] != Nv:
+        raise ValueError(f"nbrT: {Nv} rows expected, got {tuple(nbrT.shape)}")
+    if arg.device != dev or nbrT.device != dev:
+        raise ValueError("g, arg and nbrT must be on one device")
+    _pool_sizes(Nv, No, Kvol, C, "sparse_max_pool_grad")
+    grad_feat = torch.empty((Nv, C), dtype=torch.float32, device=dev)
+    with _timed("spconv_pool_grad", f"n{Nv}k{Kvol}c{C}"):
+        check(lib().sad_spconv_max_pool_grad_f32(g.data_ptr(), arg.data_ptr(), nbrT.data_ptr(), Nv, No, Kvol, C, grad_feat.data_ptr(), _stream()),
+              "sad_spconv_max_pool_grad_f32")
+    return grad_feat
+
+
 def sparse_to_dense(feat: torch.Tensor, out_coors: torch.Tensor, out_offsets: torch.Tensor, out_shape) -> torch.Tensor:
     """SPEC.md §21.3: feat [No,C] f32, out_coors [No,3] int32 (z,y,x), out_offsets [B+1] int32 -> dense [B,C,Oz,Oy,Ox] f32, zero
     where no voxel is and an exact copy elsewhere (the lowest row on a duplicate; rows with a coordinate outside ``out_shape``,

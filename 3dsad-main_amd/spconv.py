@@ -1,5 +1,7 @@
-"""Sparse 3-D convolution layers (SPEC.md §21): ``SparseTensor`` and thin ``nn.Module``s over ``ops.sparse_conv_index`` /
-``ops.sparse_conv`` / ``ops.sparse_to_dense`` — the backbone step of a voxel detector, directly behind ``voxel.py``.
+"""Sparse 3-D convolution layers (SPEC.md §21, §22): ``SparseTensor`` and thin ``nn.Module``s over ``ops.sparse_conv_index`` /
+``ops.sparse_conv`` / ``ops.sparse_to_dense`` — the backbone step of a voxel detector, directly behind ``voxel.py`` — and the
+decoder side of a sparse U-Net: ``SparseMaxPool3d`` (§22.1) and ``SparseInverseConv3d`` (§22.3), which returns to the active set
+its partner layer (named by ``indice_key``) came from, by that layer's own rulebook.
 
 A ``SparseTensor`` is ``feat [Nv,C]`` f32, ``coors [Nv,3]`` int32 (z,y,x), ``offsets [B+1]`` int32 (all on the GPU) and a host
 ``spatial_shape`` (Gz,Gy,Gx).  It carries a rulebook cache: layers that name the same ``indice_key`` (the submanifold layers of
@@ -23,7 +25,7 @@ from . import autograd, ops
 
 class SparseTensor:
     def __init__(self, feat: torch.Tensor, coors: torch.Tensor, offsets: torch.Tensor, spatial_shape: Sequence[int],
-                 rulebooks: Optional[dict] = None, transposed: Optional[dict] = None):
+                 rulebooks: Optional[dict] = None, transposed: Optional[dict] = None, sources: Optional[dict] = None):
         if feat.dim() != 2 or coors.dim() != 2 or coors.shape[1] != 3 or coors.shape[0] != feat.shape[0]:
             raise ValueError(f"feat [Nv,C] and coors [Nv,3] expected, got {tuple(feat.shape)} and {tuple(coors.shape)}")
         if offsets.dim() != 1 or offsets.shape[0] < 2:
@@ -36,6 +38,9 @@ class SparseTensor:
         self.rulebooks = {} if rulebooks is None else rulebooks
         # indice_key -> (nbr, nbrT, collisions): the transposed rulebook of §21.4, made by the first backward that needs it; shared likewise
         self.transposed = {} if transposed is None else transposed
+        # indice_key -> (in_offsets,): what an inverse layer (§22.3) needs of its partner's INPUT tensor beside the rulebook entry
+        # (which holds in_coors and, in its geometry, the input's spatial_shape); shared likewise
+        self.sources = {} if sources is None else sources
 
     @property
     def batch_size(self) -> int:
@@ -58,7 +63,7 @@ class SparseTensor:
                    offsets, spatial_shape)
 
     def replace_feature(self, feat: torch.Tensor) -> "SparseTensor":
-        return SparseTensor(feat, self.coors, self.offsets, self.spatial_shape, self.rulebooks, self.transposed)
+        return SparseTensor(feat, self.coors, self.offsets, self.spatial_shape, self.rulebooks, self.transposed, self.sources)
 
     def dense(self) -> torch.Tensor:
         """-> [B,C,Gz,Gy,Gx], zero where no voxel is (§21.3); differentiable with respect to ``feat`` (§21.4)."""
@@ -71,6 +76,37 @@ class SparseTensor:
         d = self.dense()
         B, C, Gz, Gy, Gx = d.shape
         return d.view(B, C * Gz, Gy, Gx)
+
+
+def _rulebook(x: SparseTensor, indice_key, subm: bool, kernel_size, stride, padding):
+    """(out_coors, out_offsets, nbr, out_shape) of a layer geometry on ``x``, built once per ``indice_key``."""
+    geo = (subm, x.spatial_shape, kernel_size, stride, padding)
+    hit = x.rulebooks.get(indice_key) if indice_key is not None else None
+    if hit is not None:
+        if hit[0] != geo or hit[1] is not x.coors:
+            raise ValueError(f"indice_key {indice_key!r} was built for another geometry or another sparse tensor")
+        x.sources.setdefault(indice_key, (x.offsets,))
+        return hit[2:]
+    out_shape = ops.sparse_conv_geometry(x.spatial_shape, kernel_size, stride, padding, subm)[4]
+    out_coors, out_offsets, nbr = ops.sparse_conv_index(x.coors, x.offsets, x.spatial_shape, kernel_size, stride, padding, subm)
+    if indice_key is not None:
+        x.rulebooks[indice_key] = (geo, x.coors, out_coors, out_offsets, nbr, out_shape)
+        x.sources[indice_key] = (x.offsets,)
+    return out_coors, out_offsets, nbr, out_shape
+
+
+def _transposed(x: SparseTensor, indice_key, nbr: torch.Tensor, Nv: int):
+    """(nbrT, collisions) of the rulebook ``nbr`` over ``Nv`` input rows; cached under ``indice_key`` (one synchronisation at the
+    build), whichever layer asks first: the backward of the layer that owns the rulebook or the forward of its inverse."""
+    hit = x.transposed.get(indice_key) if indice_key is not None else None
+    if hit is not None and hit[0] is nbr:
+        return hit[1:]
+    with torch.no_grad():
+        nbrT, col = ops.sparse_conv_index_transpose(nbr, Nv)
+    col = int(col.item())
+    if indice_key is not None:
+        x.transposed[indice_key] = (nbr, nbrT, col)
+    return nbrT, col
 
 
 class _SparseConvBase(nn.Module):
@@ -115,28 +151,10 @@ class _SparseConvBase(nn.Module):
 
     def transposed(self, x: SparseTensor, nbr: torch.Tensor):
         """(nbrT, collisions) of this layer's rulebook on ``x``; cached under ``indice_key`` (one synchronisation at the build)."""
-        hit = x.transposed.get(self.indice_key) if self.indice_key is not None else None
-        if hit is not None and hit[0] is nbr:
-            return hit[1:]
-        with torch.no_grad():
-            nbrT, col = ops.sparse_conv_index_transpose(nbr, x.feat.shape[0])
-        col = int(col.item())
-        if self.indice_key is not None:
-            x.transposed[self.indice_key] = (nbr, nbrT, col)
-        return nbrT, col
+        return _transposed(x, self.indice_key, nbr, x.feat.shape[0])
 
     def rulebook(self, x: SparseTensor):
-        geo = (self.subm, x.spatial_shape, self.kernel_size, self.stride, self.padding)
-        hit = x.rulebooks.get(self.indice_key) if self.indice_key is not None else None
-        if hit is not None:
-            if hit[0] != geo or hit[1] is not x.coors:
-                raise ValueError(f"indice_key {self.indice_key!r} was built for another geometry or another sparse tensor")
-            return hit[2:]
-        out_shape = ops.sparse_conv_geometry(x.spatial_shape, self.kernel_size, self.stride, self.padding, self.subm)[4]
-        out_coors, out_offsets, nbr = ops.sparse_conv_index(x.coors, x.offsets, x.spatial_shape, self.kernel_size, self.stride, self.padding, self.subm)
-        if self.indice_key is not None:
-            x.rulebooks[self.indice_key] = (geo, x.coors, out_coors, out_offsets, nbr, out_shape)
-        return out_coors, out_offsets, nbr, out_shape
+        return _rulebook(x, self.indice_key, self.subm, self.kernel_size, self.stride, self.padding)
 
     def forward(self, x: SparseTensor, residual: Optional[torch.Tensor] = None) -> SparseTensor:
         if x.feat.shape[1] != self.in_channels:
@@ -149,7 +167,7 @@ class _SparseConvBase(nn.Module):
         if train:
             out = autograd.sparse_conv(x.feat, self.weight, self.bias, residual, nbr, self.relu, lambda: self.transposed(x, nbr),
                                        self.packed(), self.packed_t)
-        return SparseTensor(out, out_coors, out_offsets, out_shape, x.rulebooks, x.transposed)
+        return SparseTensor(out, out_coors, out_offsets, out_shape, x.rulebooks, x.transposed, x.sources)
 
     def extra_repr(self) -> str:
         return (f"{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, padding={self.padding}, "
@@ -170,12 +188,98 @@ class SparseConv3d(_SparseConvBase):
     subm = False
 
 
+class SparseInverseConv3d(_SparseConvBase):
+    """Inverse convolution (SPEC.md §22.3): the up-sampling layer of a sparse U-Net.  Applied to the tensor that the strided layer
+    named by ``indice_key`` (a ``SparseConv3d`` or a ``SparseMaxPool3d``) produced — possibly after submanifold layers or
+    ``replace_feature``, which keep ``coors`` — it writes the rows of that layer's INPUT: ``sparse_conv`` over the transposed
+    rulebook with this layer's own weights, the same ``kk`` in both directions (no flipped kernel).  The output carries the
+    partner's input ``coors`` / ``offsets`` (the same tensor objects) and ``spatial_shape``, so skip connections line up row for
+    row and a submanifold ``indice_key`` of that resolution is a cache hit.  An input row that no window of the partner covers gets
+    the bias (+ residual) alone."""
+    subm = False
+
+    def __init__(self, in_channels: int, out_channels: int, kernel_size, indice_key: str, bias: bool = True, relu: bool = False):
+        if indice_key is None:
+            raise ValueError("SparseInverseConv3d needs the indice_key of the strided layer it inverts")
+        super().__init__(in_channels, out_channels, kernel_size, 1, 0, bias, relu, indice_key)
+        self.stride = self.padding = None          # the partner's, found with its rulebook
+
+    def rulebook(self, x: SparseTensor):
+        """-> (in_coors, in_offsets, in_shape, nbr) of the partner layer's rulebook, after the checks of §22.3."""
+        key = self.indice_key
+        hit = x.rulebooks.get(key)
+        if hit is None:
+            raise ValueError(f"SparseInverseConv3d: no rulebook under indice_key {key!r} (the strided layer it inverts must run first, on "
+                             "a tensor this one derives from)")
+        (subm, in_shape, kernel_size, _, _), in_coors, out_coors, _, nbr, _ = hit
+        if subm:
+            raise ValueError(f"SparseInverseConv3d: indice_key {key!r} names a submanifold rulebook; a strided layer is expected")
+        if kernel_size != self.kernel_size:
+            raise ValueError(f"SparseInverseConv3d: kernel_size {self.kernel_size} differs from {kernel_size} of indice_key {key!r}")
+        if x.coors is not out_coors:
+            raise ValueError(f"SparseInverseConv3d: the input is not the tensor that the layer of indice_key {key!r} produced")
+        src = x.sources.get(key)
+        if src is None:
+            raise ValueError(f"SparseInverseConv3d: the input carries the rulebook of indice_key {key!r} but not its partner's offsets "
+                             "(a SparseTensor built by hand must be given the `sources` dict beside `rulebooks`)")
+        return in_coors, src[0], in_shape, nbr
+
+    def forward(self, x: SparseTensor, residual: Optional[torch.Tensor] = None) -> SparseTensor:
+        if x.feat.shape[1] != self.in_channels:
+            raise ValueError(f"{self.in_channels} input channels expected, got {x.feat.shape[1]}")
+        in_coors, in_offsets, in_shape, nbr = self.rulebook(x)
+        train = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x.feat, self.weight, self.bias, residual))
+        with torch.no_grad():
+            nbrT, collisions = _transposed(x, self.indice_key, nbr, in_coors.shape[0])
+            if not train:
+                out = ops.sparse_conv(x.feat, nbrT, self.packed(), None, residual, self.relu)
+        if train:
+            # (the roles of §21.4 swapped: the rulebook of this convolution is nbrT, and its transpose is nbr when nothing collided)
+            out = autograd.sparse_conv(x.feat, self.weight, self.bias, residual, nbrT, self.relu, (nbr, collisions), self.packed(), self.packed_t)
+        return SparseTensor(out, in_coors, in_offsets, in_shape, x.rulebooks, x.transposed, x.sources)
+
+    def extra_repr(self) -> str:
+        return (f"{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, indice_key={self.indice_key!r}, "
+                f"bias={self.bias is not None}, relu={self.relu}")
+
+
+class SparseMaxPool3d(nn.Module):
+    """Sparse max pool (SPEC.md §22.1): the active output sites and the windows of a ``SparseConv3d`` of the same geometry (the two
+    may share an ``indice_key``), per channel the maximum over the ACTIVE inputs of the window (an absent voxel is absent, not a
+    zero).  No parameters.  Exact; its backward is a gather over the transposed rulebook (§22.2), exact as well."""
+
+    def __init__(self, kernel_size, stride=None, padding=0, indice_key: Optional[str] = None):
+        super().__init__()
+        _, self.kernel_size, self.stride, self.padding, _ = ops.sparse_conv_geometry((1 << 10,) * 3, kernel_size,
+                                                                                      kernel_size if stride is None else stride, padding, False)
+        self.indice_key = indice_key
+
+    def rulebook(self, x: SparseTensor):
+        return _rulebook(x, self.indice_key, False, self.kernel_size, self.stride, self.padding)
+
+    def transposed(self, x: SparseTensor, nbr: torch.Tensor):
+        return _transposed(x, self.indice_key, nbr, x.feat.shape[0])
+
+    def forward(self, x: SparseTensor) -> SparseTensor:
+        train = torch.is_grad_enabled() and x.feat.requires_grad
+        with torch.no_grad():
+            out_coors, out_offsets, nbr, out_shape = self.rulebook(x)
+            if not train:
+                out = ops.sparse_max_pool(x.feat, nbr)[0]
+        if train:
+            out = autograd.sparse_max_pool(x.feat, nbr, lambda: self.transposed(x, nbr))
+        return SparseTensor(out, out_coors, out_offsets, out_shape, x.rulebooks, x.transposed, x.sources)
+
+    def extra_repr(self) -> str:
+        return f"kernel_size={self.kernel_size}, stride={self.stride}, padding={self.padding}, indice_key={self.indice_key!r}"
+
+
 class SparseSequential(nn.Sequential):
     """``nn.Sequential`` over sparse layers; a dense module in the chain (e.g. an activation) is applied to ``.feat``."""
 
     def forward(self, x: SparseTensor) -> SparseTensor:
         for m in self:
-            if isinstance(m, (_SparseConvBase, SparseSequential)):
+            if isinstance(m, (_SparseConvBase, SparseMaxPool3d, SparseSequential)):
                 x = m(x)
             else:
                 x = x.replace_feature(m(x.feat))

@@ -303,6 +303,19 @@ int sad_spconv_index_transpose(const int32_t *nbr, int No, int Nv, int Kvol, int
 int sad_spconv_grad_weight_workspace_bytes(int No, int Kvol, int Cin, int Cout, size_t *bytes);
 int sad_spconv_grad_weight_f32(const float *feat, const int32_t *nbr, const float *g, int Nv, int No, int Kvol, int Cin,
                                int Cout, float *grad_W, float *grad_bias, void *workspace, sad_stream_t stream);
+/* SPEC.md §22 (sparse max pool over a rulebook and its backward; additions of ABI 4 as well).  nbr[No,Kvol] is any rulebook of §21
+ * (Kvol <= 27), nbrT[Nv,Kvol] its transpose (sad_spconv_index_transpose).  1 <= C, Nv * C and No * C < 2^31 (SAD_EUNSUPPORTED above).
+ * max_pool: out[No,C] = per channel the maximum of feat[nbr[o,kk]][c] over the entries in [0, Nv), walked kk ascending, a later one
+ *   replacing the first only if strictly greater (ties, -0.0f against +0.0f included, stay with the lowest kk): a bit copy of one
+ *   input element; arg[No,C] = the GLOBAL input row it came from.  A row without a valid entry: 0.0f and -1.  NaN undefined.
+ * max_pool_grad: grad_feat[Nv,C] (OVERWRITTEN) = from +0.0f, kk ascending, + g[o][c] for o = nbrT[i,kk] in [0, No) with
+ *   arg[o][c] == i: a gather, no atomics, the same bits on every call; the true gradient iff the transpose has no collisions.
+ * The inverse convolution of §22.3 has no entry point of its own: it is sad_spconv_f32(feat, nbrT, packed, residual, relu, No, Nv,
+ *   Kvol, Cin, Cout, out) with the rows of the rulebook's output in the place of Nv and those of its input in the place of No. */
+int sad_spconv_max_pool_f32(const float *feat, const int32_t *nbr, int Nv, int No, int Kvol, int C, float *out, int32_t *arg,
+                            sad_stream_t stream);
+int sad_spconv_max_pool_grad_f32(const float *g, const int32_t *arg, const int32_t *nbrT, int Nv, int No, int Kvol, int C,
+                                 float *grad_feat, sad_stream_t stream);
 
 /* SPEC.md §4.  -> idx[B,M,K] sorted by (d2, index); K <= 64, K <= N. */
 int sad_knn_f32(const float *xyz, const float *new_xyz, int B, int N, int M, int K, int32_t *idx,

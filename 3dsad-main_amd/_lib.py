@@ -151,6 +151,9 @@ SIGNATURES = {
     "sad_nms_bev_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "sad_nms_bev_ws_f32": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float,
                                          vp, vp, vp, vp, vp]),
+    "sad_nms_boxes_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "sad_nms_boxes_f32": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float,
+                                        ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp]),
     "sad_decode_boxes_f32": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, c_f32p, vp, vp]),
 }
 

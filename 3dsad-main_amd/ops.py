@@ -1046,6 +1046,70 @@ def nms_bev(boxes: torch.Tensor, iou_thr: float, score_thr: float = 0.0, single_
     return keep, order, count
 
 
+def _nms_boxes_limits(K: int, pre_max: Optional[int], post_max: Optional[int]) -> Tuple[int, int, int]:
+    """(pre_max, post_max, P) as the C-ABI wants them: ``None`` = K; P = min(K, pre_max, post_max) = columns of ``order``."""
+    pre = K if pre_max is None else int(pre_max)
+    post = K if post_max is None else int(post_max)
+    if pre < 1 or post < 1:
+        raise ValueError(f"pre_max={pre_max} and post_max={post_max} must be >= 1 (or None)")
+    pre, post = min(pre, 2 ** 31 - 1), min(post, 2 ** 31 - 1)
+    return pre, post, min(K, pre, post)
+
+
+def nms_boxes_buffers(B: int, K: int, device, pre_max: Optional[int] = None, post_max: Optional[int] = None) -> tuple:
+    """(keep [B,K], order [B,P], count [B], workspace) for ``nms_boxes(..., out=...)`` with the same limits."""
+    pre, post, P = _nms_boxes_limits(K, pre_max, post_max)
+    nbytes = lib().sad_nms_boxes_workspace_bytes(B, K, pre)
+    if nbytes == 0:
+        raise ValueError(f"nms_boxes: unsupported shape B={B}, K={K}, pre_max={pre_max} (min(K, pre_max) <= 16384, B <= 65535, B*K < 2^31)")
+    return (torch.empty((B, K), dtype=torch.int32, device=device), torch.empty((B, P), dtype=torch.int32, device=device),
+            torch.empty((B,), dtype=torch.int32, device=device), torch.empty((nbytes,), dtype=torch.uint8, device=device))
+
+
+def nms_boxes(boxes: torch.Tensor, scores: Optional[torch.Tensor], labels: Optional[torch.Tensor], iou_thr: float,
+              score_thr: float = 0.0, pre_max: Optional[int] = None, post_max: Optional[int] = None,
+              out: Optional[tuple] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Box selection and rotated BEV NMS at scale (SPEC.md §23).  boxes [B,K,D] f32 (D >= 7: cx,cy,cz,l,w,h,yaw,...),
+    scores [B,K] f32 (``None`` with D >= 8: column 7 of the rows), labels [B,K] int32 or ``None`` (class-agnostic) ->
+    (keep [B,K] int32 0/1, order [B,P] int32 kept indices in rank order (-1 padded), count [B]), P = min(K, pre_max,
+    post_max).  Candidates (score >= score_thr) are ranked by (score desc, index asc); the best ``pre_max`` are walked
+    greedily with §13's IoU, suppressing within a class only, until ``post_max`` are kept.  min(K, pre_max) <= 16384.
+    No synchronisation; ``out`` = buffers from ``nms_boxes_buffers`` with the same limits."""
+    boxes = _boxes(boxes, "boxes")
+    B, K, D = boxes.shape
+    if scores is None:
+        if D < 8:
+            raise ValueError("scores=None needs box rows with a score column (D >= 8)")
+        scores = _empty((B, K), dtype=torch.float32, device=boxes.device)
+        copy_rows(boxes, 7, D, B * K, 1, scores)
+    else:
+        scores = _need(scores, "scores", torch.float32, 2)
+    if tuple(scores.shape) != (B, K) or scores.device != boxes.device:
+        raise ValueError("scores: expected [B,K] on the device of boxes")
+    if labels is not None:
+        labels = _need(labels, "labels", torch.int32, 2)
+        if tuple(labels.shape) != (B, K) or labels.device != boxes.device:
+            raise ValueError("labels: expected [B,K] on the device of boxes")
+    pre, post, P = _nms_boxes_limits(K, pre_max, post_max)
+    if out is not None:                 # buffers from nms_boxes_buffers(B, K, device, pre_max, post_max)
+        keep, order, count, ws = out
+        if (tuple(keep.shape) != (B, K) or tuple(order.shape) != (B, P) or tuple(count.shape) != (B,) or keep.device != boxes.device
+                or ws.numel() < lib().sad_nms_boxes_workspace_bytes(B, K, pre)):
+            raise ValueError("out: buffers of another shape, limits or device (nms_boxes_buffers(B, K, device, pre_max, post_max))")
+    else:
+        nbytes = lib().sad_nms_boxes_workspace_bytes(B, K, pre)
+        keep = _empty((B, K), dtype=torch.int32, device=boxes.device)
+        order = _empty((B, P), dtype=torch.int32, device=boxes.device)
+        count = _empty((B,), dtype=torch.int32, device=boxes.device)
+        ws = _empty((max(nbytes, 16),), dtype=torch.uint8, device=boxes.device)     # (0 bytes = unsupported: the call below says why)
+    with _timed("nms_boxes", f"K{K}P{min(K, pre)}"):
+        check(lib().sad_nms_boxes_f32(boxes.data_ptr(), D, scores.data_ptr(), labels.data_ptr() if labels is not None else None,
+                                      B, K, float(np.float32(iou_thr)), float(np.float32(score_thr)), pre, post,
+                                      keep.data_ptr(), order.data_ptr(), count.data_ptr(), ws.data_ptr(), _stream()),
+              "sad_nms_boxes_f32")
+    return keep, order, count
+
+
 class PackedMLP:
     """A shared-MLP chain (SPEC.md §6) with weights repacked once into MFMA A-fragment order.
 

@@ -532,6 +532,22 @@ size_t sad_nms_bev_workspace_bytes(int B, int K);
 int sad_nms_bev_ws_f32(const float *boxes, int B, int K, float iou_thr, float score_thr, int32_t *keep,
                        int32_t *order, int32_t *count, void *workspace, sad_stream_t stream);
 
+/* SPEC.md §23.  Box selection and rotated-box NMS at scale: any K, scores (and labels) in their own tensors.
+ * boxes[B,K,D] (D >= 7; only cx,cy,cz,l,w,h,yaw are read), scores[B,K], labels[B,K] or NULL (NULL = class-agnostic; any
+ * int32 is a class) -> keep[B,K] (0/1), order[B,P] (kept indices in rank order, -1 padded), count[B].
+ * Candidates (score >= score_thr) are ranked by (score desc, index asc), the best pre_max go on, the greedy walk of §13
+ * suppresses within a class only and stops after post_max kept boxes.  pre_max / post_max <= 0 are invalid (SAD_EINVAL):
+ * pass K for "no limit".  Shape rule: order has P = min(K, pre_max, post_max) columns.  Limits: 1 <= B <= 65535,
+ * B*K < 2^31, min(K, pre_max) <= 16384 (SAD_EUNSUPPORTED above; workspace_bytes then returns 0).
+ * Workspace law: sad_nms_boxes_workspace_bytes(B, K, pre_max) bytes, 16-byte aligned, contents irrelevant before and
+ * after the call: per scene, with P' = min(K, pre_max), 64 + 52 P' + 8 P' ceil(P'/64) bytes rounded up to 16 (the
+ * suppression matrix is P' x ceil(P'/64) words).  keep, order and count are fully written by the call.  Four launches
+ * whose dimensions depend on (B, K, pre_max) only; nothing is read back and nothing synchronises. */
+size_t sad_nms_boxes_workspace_bytes(int B, int K, int pre_max);
+int sad_nms_boxes_f32(const float *boxes, int D, const float *scores, const int32_t *labels, int B, int K,
+                      float iou_thr, float score_thr, int pre_max, int post_max, int32_t *keep, int32_t *order,
+                      int32_t *count, void *workspace, sad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -206,3 +206,110 @@ def test_null_labels_accepted(sad, dev):
                                       order.data_ptr(), count.data_ptr(), ws.data_ptr(), torch.cuda.current_stream().cuda_stream)
     assert rc == 0
     _same((keep.cpu().numpy(), order.cpu().numpy(), count.cpu().numpy()), ref.expected("layout:7"))
+
+
+# ---- score regimes: selection over the whole float32 score line (small crowded scenes, so the NMS behind it shows) -----
+def test_scores_logits(sad, dev):
+    """All scores negative and distinct, pre_max cutting inside them: the negative branch of the key orders by value."""
+    print(ref.cover_logits())                                                        # coverage
+    _same(_case(sad, dev, "logits"), ref.expected("logits"))
+    _same(_case(sad, dev, "logits", score_thr=-3.5, pre_max=None), ref.expected("logits", score_thr=-3.5, pre_max=None), "thr")
+
+
+def test_scores_mixed(sad, dev):
+    """Both signs and a block of +0.0 / -0.0: the cut among the positives, inside the zeros, among the negatives."""
+    print(ref.cover_mixed())                                                         # coverage
+    for p in ref.MIXED_CUTS:
+        _same(_case(sad, dev, "mixed", pre_max=p), ref.expected("mixed", pre_max=p), f"pre_max={p}")
+
+
+def test_scores_wide(sad, dev):
+    """Every exponent in both signs, subnormals, +-FLT_MAX, FLT_MIN, +-Inf (ordinary scores): >= 200 top digits in use."""
+    print(ref.cover_wide())                                                          # coverage
+    for p in ref.wide_cuts():
+        _same(_case(sad, dev, "wide", pre_max=p), ref.expected("wide", pre_max=p), f"pre_max={p}")
+
+
+@pytest.mark.parametrize("q", sorted(ref.LADDER))
+def test_scores_ladder(sad, dev, q):
+    """Consecutive floats across the carry into radix digit q, positive (scene 0) and negative (scene 1): pass q is the
+    first that separates the threshold from its neighbours; threshold keys end in 0x00 and 0xFF digits."""
+    print(ref.cover_ladder())                                                        # coverage
+    name = f"ladder:{q}"
+    for p in ref.ladder_cuts(name):
+        _same(_case(sad, dev, name, pre_max=p), ref.expected(name, pre_max=p), f"{name} pre_max={p}")
+
+
+@pytest.mark.parametrize("pattern", ref.RUNS)
+def test_scores_runs(sad, dev, pattern):
+    """All equal / ascending / descending / two values alternating, K = 1500, pre_max = 700: one run per thread, or none."""
+    print(ref.cover_runs())                                                          # coverage
+    got = _case(sad, dev, f"runs:{pattern}")
+    _same(got, ref.expected(f"runs:{pattern}"), pattern)
+    if pattern == "equal":
+        assert got[1].max() < 700                                                    # the lowest 700 indices went on
+
+
+@pytest.mark.parametrize("pre_max", [None, 300])
+def test_score_thresholds(sad, dev, pre_max):
+    """score_thr above / at the maximum, at and one ulp either side of the 300-th score, negative, -Inf, +Inf with a +Inf
+    score present (scene 1), +0.0 with -0.0 scores present."""
+    print(ref.cover_thresholds())                                                    # coverage
+    for tag, thr in ref.threshold_values():
+        want = ref.expected("thresholds", score_thr=float(thr), pre_max=pre_max)
+        _same(_case(sad, dev, "thresholds", score_thr=float(thr), pre_max=pre_max), want, tag)
+
+
+# ---- stage boundaries ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("K", ref.STRIDE_K)
+def test_select_strides(sad, dev, K):
+    """K at the strides of the two select kernels (256, 1024) and at the switch between them (4096); no limits."""
+    name = f"stride:{K}"
+    assert ref.selected_n(ref.case(name)["scores"][0], 0.0) == K and 0.2 < ref.kept_fraction(name) < 0.8     # coverage
+    _same(_case(sad, dev, name), ref.expected(name), name)
+
+
+def test_selected_count_boundaries(sad, dev):
+    """K = 5000, n at the rows-per-workgroup (16), chunk (64, 128), select-stride (256), rank-tile (2048) boundaries and
+    at 4096: once through pre_max (P = n) and once through score_thr (P = K, so surplus workgroups exit on n)."""
+    print(ref.cover_stages())                                                        # coverage
+    for n, thr in zip(ref.N5000, ref.n5000_thresholds()):
+        _same(_case(sad, dev, "n5000", pre_max=n), ref.expected("n5000", pre_max=n), f"pre_max={n}")
+        _same(_case(sad, dev, "n5000", score_thr=thr), ref.expected("n5000", score_thr=thr), f"n={n} by score_thr")
+    _same(_case(sad, dev, "n5000", pre_max=1), ref.expected("n5000", pre_max=1), "pre_max=1")
+    _same(_case(sad, dev, "n5000", post_max=1), ref.expected("n5000", post_max=1), "post_max=1")
+
+
+def test_post_cap_at_a_chunk_end(sad, dev):
+    """post_max reached exactly on the last rank of a 64-rank chunk, and on the first rank of a chunk."""
+    print(ref.cover_post_chunk())                                                    # coverage
+    for post in ref.post_chunk_cuts():
+        _same(_case(sad, dev, "post", post_max=post), ref.expected("post", post_max=post), f"post_max={post}")
+
+
+def test_batch_of_37_on_a_dirty_workspace(sad, dev):
+    """B = 37 in one launch, n = 0, 1, 17, 64, 65, 300 and P = 400 mixed over the scenes; every out= buffer filled with
+    0xFF bytes before the first call and with 0xA5 before the second."""
+    import torch
+    print(ref.cover_stages()["batch37_n"])                                           # coverage
+    c, want = ref.case("batch37"), ref.expected("batch37")
+    buf = sad.nms_boxes_buffers(37, 600, dev, pre_max=400)
+    for fill in (0xFF, 0xA5):
+        for t in buf:
+            t.view(torch.uint8).fill_(fill)
+        _same(_run(sad, dev, c["boxes"], c["scores"], None, out=buf, **c["kw"]), want, f"workspace filled with {fill:#x}")
+
+
+# ---- the walk at full reach ----------------------------------------------------------------------------------------------
+def test_walk_far(sad, dev):
+    """K = n = 16 384: copies planted 1 .. 16 000 ranks below their originals are suppressed from up to 250 chunks away;
+    a box whose only suppressor was itself suppressed 17 chunks earlier is kept."""
+    print(ref.cover_far())                                                           # coverage
+    _same(_case(sad, dev, "far"), ref.expected("far"))
+
+
+@pytest.mark.parametrize("name", ["crowded4k", "crowded4k:classes"])
+def test_walk_crowded_4096(sad, dev, name):
+    """K = n = 4096 crowded: suppression is dense across all 64 chunks, class-agnostic and with 3 labels."""
+    print(ref.cover_crowded4k())                                                     # coverage
+    _same(_case(sad, dev, name), ref.expected(name), name)

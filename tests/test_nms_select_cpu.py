@@ -133,3 +133,40 @@ def test_coverage_layout():
     other = ref.nms_boxes(c9["boxes"], c9["boxes"][..., 7], None, **c9["kw"])
     assert not np.array_equal(ref.expected("layout:7")[1], other[1])
     _eq(ref.expected("layout:9"), ref.expected("layout:7"))
+
+
+# ---- score regimes, stage boundaries and the walk's reach: the coverage (figures printed, then asserted by cover_*) -----
+@pytest.mark.parametrize("family", ["logits", "mixed", "wide", "ladder", "runs", "thresholds", "stages", "post_chunk", "far",
+                                    "crowded4k"])
+def test_coverage_of_the_new_families(family):
+    print(family, getattr(ref, f"cover_{family}")())
+
+
+def test_score_key_is_monotone_in_the_float():
+    """score_key_np orders as floats do, with both zeros on one key — over every score the new cases use."""
+    names = ["logits", "mixed", "wide", "thresholds"] + [f"ladder:{q}" for q in ref.LADDER] + [f"runs:{p}" for p in ref.RUNS]
+    s = np.unique(np.concatenate([ref.case(n)["scores"].ravel() for n in names]))        # ascending, -0.0 == +0.0 merged
+    k = ref.score_key_np(s).astype(np.int64)
+    assert len(s) > 5000 and (np.diff(k) > 0).all()
+    assert ref.score_key_np(np.array([-0.0], F))[0] == ref.score_key_np(np.array([0.0], F))[0] == 0x80000000
+    prof = ref.radix_profile(np.array([3.0, -1.0, 2.0, 2.0, -0.0, 0.0], F), 2.5, 2)
+    assert prof == dict(key=int(ref.score_key_np(np.array([2.0], F))[0]), shared=(3, 2, 2, 2), decides="thr")
+    assert ref.radix_profile(np.array([3.0, -1.0, 2.0], F), -2.0, 5)["key"] == int(ref.score_key_np(np.array([-1.0], F))[0])
+
+
+SCORE_CASES = (["logits", "mixed", "wide", "thresholds", "crowded4k", "n5000"] + [f"ladder:{q}" for q in ref.LADDER]
+               + [f"runs:{p}" for p in ref.RUNS] + [f"stride:{K}" for K in ref.STRIDE_K])
+
+
+@pytest.mark.parametrize("name", SCORE_CASES)
+def test_new_cases_equal_oracle_without_pre_max(orc, name):
+    """Every score regime, without pre_max, against the oracle's nms_bev (scores in column 7): the ranking of negative,
+    zero, subnormal, infinite and consecutive scores by the reference is the oracle's.  (`far` is left out: the oracle
+    clips all 1.3e8 pairs of its 16 384 kept boxes; its expected result is asserted box by box in cover_far.)"""
+    c = ref.case(name)
+    thrs = [v for _, v in ref.threshold_values()] if name == "thresholds" else [c["kw"]["score_thr"]]
+    for thr in thrs:
+        want = orc.nms_bev(ref.with_scores(c["boxes"], c["scores"]), ref.IOU_THR, thr)
+        got = ref.expected(name, pre_max=None, score_thr=float(thr)) if name == "thresholds" else \
+            ref.nms_boxes(c["boxes"], c["scores"], None, ref.IOU_THR, thr)
+        _eq(got, want, f"{name} score_thr={thr}")

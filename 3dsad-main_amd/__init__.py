@@ -22,7 +22,8 @@ _LAZY = {
     "three_nn": "ops", "three_interpolate": "ops", "FPModule": "fp_module",
     "boxes_iou_bev": "ops", "boxes_iou3d": "ops", "points_in_boxes": "ops", "roipoint_pool3d": "ops",
     "voxel_coords": "ops", "voxel_index": "ops", "voxelize": "ops", "voxel_reduce": "ops",
-    "Voxelization": "voxel", "DynamicScatter": "voxel",
+    "voxel_decorate": "ops", "voxel_encode": "ops",
+    "Voxelization": "voxel", "DynamicScatter": "voxel", "PillarFeatureNet": "voxel",
     "sparse_conv_index": "ops", "sparse_conv": "ops", "sparse_to_dense": "ops", "PackedSparseWeight": "ops",
     "sparse_conv_index_transpose": "ops", "sparse_conv_grad_weight": "ops", "sparse_conv_grad_input": "ops",
     "sparse_max_pool": "ops", "sparse_max_pool_grad": "ops", "SparseMaxPool3d": "spconv", "SparseInverseConv3d": "spconv",

@@ -104,6 +104,9 @@ SIGNATURES = {
     "sad_voxelize_f32": (ctypes.c_int, [vp, vp] + [ctypes.c_int] * 3 + [c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp]),
     "sad_voxel_reduce_f32": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 5 + [vp, vp, vp, vp, vp]),
     "sad_voxel_reduce_grad_f32": (ctypes.c_int, [vp, vp, vp] + [ctypes.c_int] * 5 + [vp, vp, vp]),
+    "sad_voxel_encode_workspace_bytes": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_size_t)]),
+    "sad_voxel_decorate_f32": (ctypes.c_int, [vp] * 5 + [ctypes.c_int] * 5 + [c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, vp, vp, vp]),
+    "sad_voxel_encode_f32": (ctypes.c_int, [vp] * 5 + [ctypes.c_int] * 5 + [c_f32p, c_f32p, vp, vp] + [ctypes.c_int] * 3 + [vp] * 5),
     "sad_spconv_workspace_bytes": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i3p, c_i3p, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
     "sad_spconv_index_subm": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, c_i3p, c_i3p, vp, vp, vp]),
     "sad_spconv_index_count": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, c_i3p, c_i3p, c_i3p, c_i3p, vp, vp, vp]),

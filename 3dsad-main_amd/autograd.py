@@ -176,6 +176,69 @@ class VoxelReduce(torch.autograd.Function):
         return g, None, None, None, None
 
 
+class VoxelEncode(torch.autograd.Function):
+    """The voxel feature encoder (SPEC.md §24) with gradients for points, weight, bias and vox_feat.  The forward is the fused
+    operator with ``arg``; the backward is a composition of existing operators: the routed gradient (``voxel_reduce_grad`` with
+    ``arg``), the decorated rows (``voxel_decorate``), two matrix products and the ordered sum for ``vox_feat``.  The mean and the
+    voxel centre are constants of the row: no gradient flows through them; point2voxel, offsets and coors get none."""
+
+    @staticmethod
+    def forward(ctx, points, point2voxel, offsets, max_voxels, weight, bias, coors, voxel_size, point_range, cluster_center, voxel_center,
+                relu, vox_feat, max_points, return_pointwise):
+        points = _f32(points, "points", 2)
+        res = ops.voxel_encode(points, point2voxel, offsets, max_voxels, weight, bias, coors, voxel_size, point_range, cluster_center,
+                               voxel_center, relu, vox_feat, max_points, return_arg=True, return_pointwise=return_pointwise)
+        pooled, arg = res[0], res[1]
+        pointwise = res[2] if return_pointwise else None
+        ctx.cfg = (int(max_voxels), voxel_size, point_range, bool(cluster_center), bool(voxel_center), bool(relu), max_points)
+        ctx.has = (coors is not None, vox_feat is not None, pointwise is not None)
+        ctx.save_for_backward(*[t for t in (points, point2voxel, offsets, weight, arg, pooled, coors, vox_feat, pointwise) if t is not None])
+        return (pooled, pointwise) if return_pointwise else pooled
+
+    @staticmethod
+    def backward(ctx, grad_pooled, grad_pointwise=None):
+        V, voxel_size, point_range, cc, vc, relu, T = ctx.cfg
+        saved = list(ctx.saved_tensors)
+        points, p2v, offsets, weight, arg, pooled = saved[:6]
+        rest = saved[6:]
+        coors = rest.pop(0) if ctx.has[0] else None
+        vox_feat = rest.pop(0) if ctx.has[1] else None
+        pointwise = rest.pop(0) if ctx.has[2] else None
+        total, C = points.shape
+        gp = _f32(grad_pooled, "grad_pooled", 3)
+        if relu:
+            gp = torch.where(pooled > 0, gp, torch.zeros_like(gp))      # y of the arg row IS the pooled value
+        g = ops.voxel_reduce_grad(gp, p2v, offsets, "max", arg)
+        if pointwise is not None and grad_pointwise is not None:
+            # rows that are not members have the constant output 0: a column of ones decorated alone marks the members
+            member = ops.voxel_decorate(torch.ones((total, 1), dtype=torch.float32, device=points.device), p2v, offsets, V,
+                                        cluster_center=False, voxel_center=False, max_points=T)
+            live = (member > 0) & (pointwise > 0) if relu else (member > 0)
+            g = g + torch.where(live, grad_pointwise, torch.zeros_like(grad_pointwise))
+        rows = ops.voxel_decorate(points, p2v, offsets, V, coors, voxel_size, point_range, cc, vc, vox_feat, T)
+        grad_w = g.t() @ rows if ctx.needs_input_grad[4] else None
+        grad_b = g.sum(0) if ctx.needs_input_grad[5] else None
+        grad_points = grad_vox = None
+        if ctx.needs_input_grad[0] or (vox_feat is not None and ctx.needs_input_grad[12]):
+            grad_rows = g @ weight
+            if ctx.needs_input_grad[0]:
+                grad_points = grad_rows[:, :C].clone()
+                for k in range(int(cc) + int(vc)):
+                    grad_points[:, :3] += grad_rows[:, C + 3 * k:C + 3 * k + 3]
+            if vox_feat is not None and ctx.needs_input_grad[12]:
+                Cv = vox_feat.shape[2]
+                grad_vox = ops.voxel_reduce(grad_rows[:, grad_rows.shape[1] - Cv:].contiguous(), p2v, offsets, V, "sum")
+        return (grad_points, None, None, None, grad_w, grad_b, None, None, None, None, None, None, grad_vox, None, None)
+
+
+def voxel_encode(points, point2voxel, offsets, max_voxels, weight, bias, coors=None, voxel_size=None, point_range=None,
+                 cluster_center=True, voxel_center=True, relu=True, vox_feat=None, max_points=None, return_pointwise=False):
+    """Differentiable ``ops.voxel_encode`` (SPEC.md §24): points [total,C] + offsets [B+1] -> pooled [B,V,Cout], or (pooled,
+    pointwise [total,Cout]) with ``return_pointwise``.  Gradients for points, weight, bias and vox_feat."""
+    return VoxelEncode.apply(points, point2voxel, offsets, max_voxels, weight, bias, coors, voxel_size, point_range, cluster_center,
+                             voxel_center, relu, vox_feat, max_points, return_pointwise)
+
+
 def _transposed(transposed, nbr, Nv):
     """-> (nbrT, collisions as a Python int) from what ``SparseConv`` was given: None (built here, one synchronisation), a
     callable that returns the pair (a layer's cache) or the pair itself."""

@@ -19,6 +19,7 @@
 // voxelize writes voxels[B,V,T,C] exactly once, rows and zeros in the same pass.  voxel_reduce walks sorted lists, one
 // thread per (voxel, channel), one rounding per addition.  The backward is a gather.
 #include "common.h"
+#include "voxel_csr.h"
 #include <algorithm>
 #include <limits.h>
 #include <math.h>
@@ -442,6 +443,29 @@ void launch_csr(const int32_t *p2v, const int32_t *offsets, int total, int B, in
 
 }  // namespace
 
+namespace sad {
+
+size_t voxel_ws_bytes(int total, int B, int V) { return vox_ws(total, B, V).bytes; }
+
+int voxel_sizes_ok(const char *fn, long long total, int B, long long V) { return vox_sizes_ok(fn, total, B, V); }
+
+void voxel_member_lists(const int32_t *p2v, const int32_t *offsets, int total, int B, int V, void *workspace, hipStream_t st,
+                        VoxLists &out) {
+    const VoxWs w = vox_ws(total, B, V);
+    char *ws = (char *)workspace;
+    int32_t *cnt = (int32_t *)(ws + w.cnt);
+    launch_init(nullptr, nullptr, 0, cnt, (int32_t *)(ws + w.fill), nullptr, (unsigned)B * (unsigned)V, st);
+    if (total > 0)
+        hipLaunchKernelGGL(voxel_count_kernel, dim3(blocks_for((unsigned long long)total, VX_THREADS)), dim3(VX_THREADS), 0, st, p2v, offsets,
+                           total, B, V, cnt);
+    launch_csr(p2v, offsets, total, B, V, cnt, ws, w, 0, nullptr, st);
+    out.start = (const int32_t *)(ws + w.start);
+    out.cnt = cnt;
+    out.sorted = (const int32_t *)(ws + w.sorted);
+}
+
+}  // namespace sad
+
 SAD_API int sad_voxel_workspace_bytes(int total_points, int B, int max_voxels, size_t *out) {
     SAD_REQUIRE(out, "sad_voxel_workspace_bytes: NULL out");
     *out = 0;
@@ -522,18 +546,11 @@ SAD_API int sad_voxel_reduce_f32(const float *feat, const int32_t *point2voxel, 
     SAD_REQUIRE(((uintptr_t)workspace & 15) == 0, "sad_voxel_reduce_f32: workspace must be 16-byte aligned");
     const unsigned long long nout = (unsigned long long)B * max_voxels * Cf;
     if (nout >= (1ull << 40)) return sad::fail(SAD_EUNSUPPORTED, "sad_voxel_reduce_f32: out[B,V,Cf] of %llu floats is too large", nout);
-    const VoxWs w = vox_ws(total_points, B, max_voxels);
-    char *ws = (char *)workspace;
     const hipStream_t st = (hipStream_t)stream;
-    int32_t *cnt = (int32_t *)(ws + w.cnt);
-    const unsigned nvox = (unsigned)B * (unsigned)max_voxels;
-    launch_init(nullptr, nullptr, 0, cnt, (int32_t *)(ws + w.fill), nullptr, nvox, st);
-    if (total_points > 0)
-        hipLaunchKernelGGL(voxel_count_kernel, dim3(blocks_for((unsigned long long)total_points, VX_THREADS)), dim3(VX_THREADS), 0, st, point2voxel,
-                           offsets, total_points, B, max_voxels, cnt);
-    launch_csr(point2voxel, offsets, total_points, B, max_voxels, cnt, ws, w, 0, nullptr, st);
-    hipLaunchKernelGGL(voxel_reduce_kernel, dim3(blocks_for(nout, VX_THREADS)), dim3(VX_THREADS), 0, st, feat, (const int32_t *)(ws + w.start), cnt,
-                       (const int32_t *)(ws + w.sorted), Cf, nout, total_points, mode, out, mode == SAD_VOXEL_MAX ? arg : nullptr, count);
+    sad::VoxLists ml;
+    sad::voxel_member_lists(point2voxel, offsets, total_points, B, max_voxels, workspace, st, ml);
+    hipLaunchKernelGGL(voxel_reduce_kernel, dim3(blocks_for(nout, VX_THREADS)), dim3(VX_THREADS), 0, st, feat, ml.start, ml.cnt, ml.sorted, Cf, nout,
+                       total_points, mode, out, mode == SAD_VOXEL_MAX ? arg : nullptr, count);
     return sad::check_launch("sad_voxel_reduce_f32");
 }
 

@@ -722,6 +722,119 @@ def voxel_reduce_grad(grad_out: torch.Tensor, point2voxel: torch.Tensor, offsets
     return grad_feat
 
 
+VFE_CLUSTER_CENTER, VFE_VOXEL_CENTER, VFE_RELU = 1, 2, 4
+
+
+def voxel_encode_workspace(total_points: int, B: int, max_voxels: int, cin: int, cout: int, device) -> torch.Tensor:
+    """Scratch of ``voxel_encode`` / ``voxel_decorate`` (``cout=0``) for these sizes; contents arbitrary, reusable call after call
+    on one stream."""
+    n = ctypes.c_size_t(0)
+    check(lib().sad_voxel_encode_workspace_bytes(int(total_points), int(B), int(max_voxels), int(cin), int(cout), ctypes.byref(n)),
+          "sad_voxel_encode_workspace_bytes")
+    return _empty((n.value,), dtype=torch.uint8, device=device)
+
+
+def _vfe_args(points, point2voxel, offsets, max_voxels, coors, voxel_size, point_range, cluster_center, voxel_center, vox_feat,
+              max_points, cout, workspace):
+    """The arguments ``voxel_decorate`` and ``voxel_encode`` share -> (points, p2v, offsets, coors, vox_feat, total, B, C, V, Cv, vs,
+    pr, flags, T, Cin, workspace)."""
+    cc, vc = bool(cluster_center), bool(voxel_center)
+    points, offsets, B = _voxel_points(points, offsets, "points", 3 if (cc or vc) else 1)
+    point2voxel = _need(point2voxel, "point2voxel", torch.int32, 1)
+    total, C = points.shape
+    dev = points.device
+    if point2voxel.shape[0] != total or point2voxel.device != dev:
+        raise ValueError("point2voxel must have one entry per row of points, on its device")
+    V = int(max_voxels)
+    if V < 1:
+        raise ValueError(f"max_voxels={V} must be >= 1")
+    vs = pr = None
+    if vc:
+        if coors is None or voxel_size is None or point_range is None:
+            raise ValueError("voxel_center needs coors [B,V,3], voxel_size and point_range")
+        vs, pr = _voxel_grid(voxel_size, point_range)
+        coors = _need(coors, "coors", torch.int32, 3)
+        if tuple(coors.shape) != (B, V, 3) or coors.device != dev:
+            raise ValueError(f"coors: [{B},{V},3] on the device of points expected")
+    else:
+        coors = None
+    Cv = 0
+    if vox_feat is not None:
+        vox_feat = _need(vox_feat, "vox_feat", torch.float32, 3)
+        if tuple(vox_feat.shape[:2]) != (B, V) or vox_feat.shape[2] < 1 or vox_feat.device != dev:
+            raise ValueError(f"vox_feat: [{B},{V},Cv >= 1] on the device of points expected")
+        Cv = vox_feat.shape[2]
+    T = 0
+    if max_points is not None:
+        T = int(max_points)
+        if T < 1:
+            raise ValueError(f"max_points={T} must be >= 1 (None: no cap)")
+    cin = C + 3 * cc + 3 * vc + Cv
+    n = ctypes.c_size_t(0)       # (Cin or Cout outside 1 .. 256: SAD_EUNSUPPORTED from here, before anything is launched)
+    check(lib().sad_voxel_encode_workspace_bytes(total, B, V, cin, cout, ctypes.byref(n)), "sad_voxel_encode_workspace_bytes")
+    if workspace is None:
+        workspace = _empty((n.value,), dtype=torch.uint8, device=dev)
+    elif (not workspace.is_cuda or workspace.device != dev or not workspace.is_contiguous()
+          or workspace.numel() * workspace.element_size() < n.value or workspace.data_ptr() % 16):
+        raise ValueError(f"workspace: expected a contiguous 16-byte aligned GPU buffer of at least {n.value} bytes "
+                         "(ops.voxel_encode_workspace)")
+    flags = (VFE_CLUSTER_CENTER if cc else 0) | (VFE_VOXEL_CENTER if vc else 0)
+    return points, point2voxel, offsets, coors, vox_feat, total, B, C, V, Cv, vs, pr, flags, T, cin, workspace
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return t.data_ptr() if t is not None else None
+
+
+def voxel_decorate(points: torch.Tensor, point2voxel: torch.Tensor, offsets: Optional[torch.Tensor], max_voxels: int,
+                   coors: Optional[torch.Tensor] = None, voxel_size=None, point_range=None, cluster_center: bool = True,
+                   voxel_center: bool = True, vox_feat: Optional[torch.Tensor] = None, max_points: Optional[int] = None,
+                   workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The decorated rows of the voxel feature encoder (SPEC.md §24), unfused: points [total,C] f32 + offsets (or [B,N,C] with
+    ``offsets=None``), point2voxel [total] int32 -> rows [total,Cin] = [points | xyz - mean of the voxel's members | xyz - voxel
+    centre | vox_feat[b,v]] as asked for; rows that are not members (point2voxel outside [0,V), or past the first ``max_points`` of
+    their voxel) are zero.  ``voxel_center`` needs coors [B,V,3] (z,y,x), ``voxel_size`` and ``point_range``.  No gradient."""
+    (points, point2voxel, offsets, coors, vox_feat, total, B, C, V, Cv, vs, pr, flags, T, cin, ws) = _vfe_args(
+        points, point2voxel, offsets, max_voxels, coors, voxel_size, point_range, cluster_center, voxel_center, vox_feat, max_points, 0,
+        workspace)
+    rows = _empty((total, cin), dtype=torch.float32, device=points.device)
+    with _timed("voxel_decorate", f"n{total}V{V}C{cin}"):
+        check(lib().sad_voxel_decorate_f32(points.data_ptr(), point2voxel.data_ptr(), offsets.data_ptr(), _ptr(coors), _ptr(vox_feat), total, B,
+                                           C, V, Cv, vs, pr, flags, T, rows.data_ptr(), ws.data_ptr(), _stream()), "sad_voxel_decorate_f32")
+    return rows
+
+
+def voxel_encode(points: torch.Tensor, point2voxel: torch.Tensor, offsets: Optional[torch.Tensor], max_voxels: int,
+                 weight: torch.Tensor, bias: torch.Tensor, coors: Optional[torch.Tensor] = None, voxel_size=None, point_range=None,
+                 cluster_center: bool = True, voxel_center: bool = True, relu: bool = True, vox_feat: Optional[torch.Tensor] = None,
+                 max_points: Optional[int] = None, return_arg: bool = False, return_pointwise: bool = False,
+                 workspace: Optional[torch.Tensor] = None):
+    """Voxel feature encoder (SPEC.md §24), fused: the rows of ``voxel_decorate``, one layer ``weight [Cout,Cin]``, ``bias [Cout]``
+    (+ ReLU) and the maximum over each voxel's members in one kernel, without the [total,Cout] intermediate.  -> pooled [B,V,Cout]
+    (0 for a voxel without members); ``return_arg`` appends arg [B,V,Cout] int32 (lowest member row that attains the maximum, -1
+    without members); ``return_pointwise`` appends pointwise [total,Cout] (the layer output of every member row, 0 elsewhere: what
+    the next layer of a stack reads).  Equal to the reference under ``==``, bit-equal from call to call.  No gradient here:
+    ``autograd.voxel_encode``."""
+    weight = _need(weight, "weight", torch.float32, 2)
+    bias = _need(bias, "bias", torch.float32, 1)
+    cout = weight.shape[0]
+    (points, point2voxel, offsets, coors, vox_feat, total, B, C, V, Cv, vs, pr, flags, T, cin, ws) = _vfe_args(
+        points, point2voxel, offsets, max_voxels, coors, voxel_size, point_range, cluster_center, voxel_center, vox_feat, max_points, cout,
+        workspace)
+    dev = points.device
+    if weight.shape[1] != cin or bias.shape[0] != cout or weight.device != dev or bias.device != dev:
+        raise ValueError(f"weight [Cout,{cin}] and bias [Cout] on the device of points expected, got {tuple(weight.shape)}, {tuple(bias.shape)}")
+    pooled = _empty((B, V, cout), dtype=torch.float32, device=dev)
+    arg = _empty((B, V, cout), dtype=torch.int32, device=dev) if return_arg else None
+    pointwise = _empty((total, cout), dtype=torch.float32, device=dev) if return_pointwise else None
+    with _timed("voxel_encode", f"n{total}V{V}C{cin}x{cout}"):
+        check(lib().sad_voxel_encode_f32(points.data_ptr(), point2voxel.data_ptr(), offsets.data_ptr(), _ptr(coors), _ptr(vox_feat), total, B, C,
+                                         V, Cv, vs, pr, weight.data_ptr(), bias.data_ptr(), cout, flags | (VFE_RELU if relu else 0), T,
+                                         pooled.data_ptr(), _ptr(arg), _ptr(pointwise), ws.data_ptr(), _stream()), "sad_voxel_encode_f32")
+    res = (pooled,) + ((arg,) if return_arg else ()) + ((pointwise,) if return_pointwise else ())
+    return res[0] if len(res) == 1 else res
+
+
 def _int3(v, name: str, lo: int):
     """int or 3 ints (z,y,x) -> (tuple of 3 Python ints, host int array)."""
     t = (int(v),) * 3 if isinstance(v, (int, np.integer)) else tuple(int(x) for x in v)

@@ -57,3 +57,67 @@ class DynamicScatter(nn.Module):
 
     def extra_repr(self) -> str:
         return f"mode={self.mode}"
+
+
+class PillarFeatureNet(nn.Module):
+    """Pillar / dynamic-voxel feature encoder (SPEC.md §24): a stack of fused decorate + linear (+ ReLU) + voxel-max layers.
+    The first layer reads the points decorated with the offset to the mean of the voxel's members (``with_cluster_center``)
+    and to the voxel's centre (``with_voxel_center``); a layer that is not the last has ``feat / 2`` output channels and hands
+    the next layer its pointwise output next to its per-voxel maximum (rows ``[y | max]``).  ``weight`` / ``bias`` hold the
+    linear layers with BatchNorm already folded in.  ``max_points`` = T keeps the first T points of a voxel (hard
+    voxelization); ``None`` is the dynamic form.
+
+    forward(points [total,C], point2voxel [total], offsets [B+1], coors [B,V,3]) -> [B,V,feat_channels[-1]], zero for a voxel
+    without points: what ``SparseTensor.from_voxels`` or a BEV scatter takes."""
+
+    def __init__(self, in_channels: int, feat_channels: Sequence[int] = (64,), voxel_size: Sequence[float] = (0.16, 0.16, 4),
+                 point_range: Sequence[float] = (0, -39.68, -3, 69.12, 39.68, 1), with_cluster_center: bool = True,
+                 with_voxel_center: bool = True, max_points: Optional[int] = None):
+        super().__init__()
+        if len(voxel_size) != 3 or len(point_range) != 6:
+            raise ValueError("voxel_size = (vx,vy,vz), point_range = (x0,y0,z0,x1,y1,z1)")
+        if len(feat_channels) < 1:
+            raise ValueError("feat_channels: at least one layer")
+        self.in_channels = int(in_channels)
+        self.feat_channels = tuple(int(c) for c in feat_channels)
+        self.voxel_size = tuple(float(v) for v in voxel_size)
+        self.point_range = tuple(float(v) for v in point_range)
+        self.with_cluster_center, self.with_voxel_center = bool(with_cluster_center), bool(with_voxel_center)
+        self.max_points = None if max_points is None else int(max_points)
+        cin = self.in_channels + 3 * self.with_cluster_center + 3 * self.with_voxel_center
+        self.weight, self.bias = nn.ParameterList(), nn.ParameterList()
+        for l, feat in enumerate(self.feat_channels):
+            last = l == len(self.feat_channels) - 1
+            if not last and feat % 2:
+                raise ValueError(f"feat_channels[{l}] = {feat}: a layer that is not the last must have an even width")
+            cout = feat if last else feat // 2
+            w = torch.empty(cout, cin)
+            nn.init.kaiming_uniform_(w, a=5 ** 0.5)
+            self.weight.append(nn.Parameter(w))
+            self.bias.append(nn.Parameter(torch.zeros(cout)))
+            cin = 2 * cout
+
+    def forward(self, points: torch.Tensor, point2voxel: torch.Tensor, offsets: Optional[torch.Tensor], coors: torch.Tensor):
+        if offsets is None:
+            if points.dim() != 3:
+                raise ValueError("points: [B,N,C] expected when offsets is None")
+            B, N, C = points.shape
+            offsets = torch.arange(0, (B + 1) * N, N, dtype=torch.int32, device=points.device) if N else \
+                torch.zeros((B + 1,), dtype=torch.int32, device=points.device)
+            points = points.reshape(B * N, C)
+        V = coors.shape[1]
+        x, pooled = points, None
+        n = len(self.feat_channels)
+        for l in range(n):
+            first, last = l == 0, l == n - 1
+            res = autograd.voxel_encode(x, point2voxel, offsets, V, self.weight[l], self.bias[l], coors if first else None,
+                                        self.voxel_size, self.point_range, first and self.with_cluster_center,
+                                        first and self.with_voxel_center, True, pooled, self.max_points, not last)
+            if last:
+                return res
+            pooled, x = res
+        return pooled
+
+    def extra_repr(self) -> str:
+        return (f"in_channels={self.in_channels}, feat_channels={self.feat_channels}, voxel_size={self.voxel_size}, "
+                f"point_range={self.point_range}, max_points={self.max_points}")

@@ -246,6 +246,36 @@ int sad_voxel_reduce_grad_f32(const float *grad_out, const int32_t *point2voxel,
                               int total_points, int B, int Cf, int max_voxels, int mode,
                               const int32_t *count_or_arg, float *grad_feat, sad_stream_t stream);
 
+/* SPEC.md §24 (voxel feature encoder).  Additions of ABI 4: the version is unchanged.  points[total_points, C], offsets[B+1] and
+ * point2voxel[total_points] as for voxel_reduce (numbers outside [0, max_voxels) count as -1).  The members of voxel (b,v) are
+ * the rows with point2voxel == v in ascending row order, with max_points = T >= 1 only the first T of them (0: no cap); there
+ * are no padding slots.  flags: SAD_VFE_CLUSTER_CENTER appends points[i,0:3] - mean (mean: §20.5 over the members),
+ * SAD_VFE_VOXEL_CENTER appends points[i,0:3] - ((float)g_d * v_d + (0.5f * v_d + lo_d)) with g from coors[B,V,3] (z,y,x) and
+ * the HOST arrays voxel_size[3], point_range[6] (all three may be NULL without that flag); vox_feat[B,V,Cv] (NULL with Cv = 0)
+ * is appended last.  Cin = C + 3 + 3 + Cv as flagged, 1 <= Cin <= 256 (SAD_EUNSUPPORTED above); decorations need C >= 3.
+ * voxel_decorate: -> rows[total_points, Cin], zeros for rows that are not members.
+ * voxel_encode: the fused form.  y = one §6 layer of the decorated row (acc = bias[o]; k ascending: acc = fmaf(W[o][k],
+ *   row[k], acc); SAD_VFE_RELU: acc > 0 ? acc : 0) with weight[Cout,Cin], bias[Cout] on the device, 1 <= Cout <= 256
+ *   (SAD_EUNSUPPORTED above) -> pooled[B,V,Cout] = the maximum over the members, 0 without members; arg[B,V,Cout] (may be
+ *   NULL) = the lowest member row that attains it, -1 without members; pointwise[total_points,Cout] (may be NULL) = y of every
+ *   member row, 0 for the others.  Every output float is written exactly once: no fill is needed before the call.
+ *   B * max_voxels * Cout < 2^40.  Bit-equal from call to call; equal to the reference under == (sign of a zero unspecified).
+ * workspace: sad_voxel_encode_workspace_bytes(total_points, B, max_voxels, Cin, Cout, &bytes) bytes of 16-byte aligned device
+ * scratch (Cout = 0: what voxel_decorate needs), contents arbitrary on entry, reusable by the next call on the same stream. */
+#define SAD_VFE_CLUSTER_CENTER 1
+#define SAD_VFE_VOXEL_CENTER 2
+#define SAD_VFE_RELU 4
+int sad_voxel_encode_workspace_bytes(int total_points, int B, int max_voxels, int Cin, int Cout, size_t *bytes);
+int sad_voxel_decorate_f32(const float *points, const int32_t *point2voxel, const int32_t *offsets,
+                           const int32_t *coors, const float *vox_feat, int total_points, int B, int C,
+                           int max_voxels, int Cv, const float *voxel_size, const float *point_range,
+                           int flags, int max_points, float *rows, void *workspace, sad_stream_t stream);
+int sad_voxel_encode_f32(const float *points, const int32_t *point2voxel, const int32_t *offsets,
+                         const int32_t *coors, const float *vox_feat, int total_points, int B, int C,
+                         int max_voxels, int Cv, const float *voxel_size, const float *point_range,
+                         const float *weight, const float *bias, int Cout, int flags, int max_points,
+                         float *pooled, int32_t *arg, float *pointwise, void *workspace, sad_stream_t stream);
+
 /* SPEC.md §21 (sparse 3-D convolution).  Additions of ABI 4: the version is unchanged.  A sparse tensor is feat[Nv,C] f32,
  * coors[Nv,3] int32 (z,y,x), offsets[B+1] int32 on the device (scene b owns rows offsets[b] .. offsets[b+1]-1, offsets[0] = 0,
  * offsets[B] = Nv, a scene may be empty) and a HOST spatial_shape[3] = (Gz,Gy,Gx), at most 2^31 - 1 cells.  kernel, stride and

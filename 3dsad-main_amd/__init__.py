@@ -18,7 +18,7 @@ HW_QUEUES_STATE = _runtime.ensure_hw_queues()
 _LAZY = {
     "fps": "ops", "ball_query": "ops", "ball_query_multi": "ops", "knn_query": "ops",
     "group_points": "ops", "gather_points": "ops", "gather_xyz": "ops",
-    "mlp_chain": "ops", "PackedMLP": "ops", "nms_bev": "ops", "nms_boxes": "ops", "nms_boxes_buffers": "ops",
+    "mlp_chain": "mlp", "PackedMLP": "mlp", "nms_bev": "ops", "nms_boxes": "ops", "nms_boxes_buffers": "ops",
     "three_nn": "ops", "three_interpolate": "ops", "FPModule": "fp_module",
     "boxes_iou_bev": "ops", "boxes_iou3d": "ops", "points_in_boxes": "ops", "roipoint_pool3d": "ops",
     "voxel_coords": "ops", "voxel_index": "ops", "voxelize": "ops", "voxel_reduce": "ops",

@@ -476,6 +476,7 @@ class SADDetector(nn.Module):
             ops._unrecordable("zero-filled cluster pooling buffer")
             cat = torch.zeros((B, K, self.cluster_cat), dtype=torch.float32, device=points.device)
         calls, off = [], 0
+        cwss = [None] * len(idxs)
         if ckont is not None:
             # split pooling: the tables come from an explicit scan (the same two launches the dispatch would make itself), the aggregation
             # layer needs them beside the continuation rows
@@ -484,8 +485,8 @@ class SADDetector(nn.Module):
                 outs.append((cat, o_, mlp.out_channels, k_))
                 o_ += mlp.out_channels
             cwss = ops.rowscan_multi(idxs, cnts, M3, outs)
-        for bi, (mlp, idx, cnt) in enumerate(zip(self.cluster_branches, idxs, cnts)):
-            calls.append((mlp, cur_xyz, cur_feat, cand, idx, cat, off, cnt) + ((cwss[bi], ckont[bi]) if ckont is not None else ()))
+        for mlp, idx, cnt, ws, k_ in zip(self.cluster_branches, idxs, cnts, cwss, ckont or [None] * len(idxs)):
+            calls.append(ops.GroupedCall(mlp, cur_xyz, cur_feat, cand, idx, out=cat, col_off=off, cnt=cnt, ws=ws, cont=k_))
             off += mlp.out_channels
         ops.grouped_multi(calls)
         # ---- head + decode (SPEC.md §9) -------------------------------------------------------

@@ -148,8 +148,8 @@ class SAModuleMSG(nn.Module):
             ops._unrecordable("group_and_pool: zero-filled pooling buffer")
             cat = torch.zeros((B, M, self.cat_channels), dtype=torch.float32, device=xyz.device)
         calls, off = [], 0               # all branches in one dispatch (ops.grouped_multi)
-        for bi, (mlp, idx, cnt, ws) in enumerate(zip(self.branches, idxs, cnts, wss)):
-            calls.append((mlp, xyz, feat_pm, new_xyz, idx, cat, off, cnt, ws) + ((conts[bi],) if conts is not None else ()))
+        for mlp, idx, cnt, ws, cont in zip(self.branches, idxs, cnts, wss, conts or [None] * len(idxs)):
+            calls.append(ops.GroupedCall(mlp, xyz, feat_pm, new_xyz, idx, out=cat, col_off=off, cnt=cnt, ws=ws, cont=cont))
             off += mlp.out_channels
         ops.grouped_multi(calls)
         if conts is not None:        # split-pooled rows: the aggregation layer takes the maximum with the continuation rows as it reads

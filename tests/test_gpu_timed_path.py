@@ -261,3 +261,44 @@ def test_unaligned_feature_view_with_poisoned_buffers(orc, sad, dev, pack_featur
         ws = ops.rowscan_multi(idxs[:1], cnts[:1], xyz.shape[1])[0]
         with pytest.raises(RuntimeError, match="packs for itself"):
             m.branches[0].grouped(xyz, view, new_xyz, idxs[0], out=torch.zeros_like(cat), cnt=cnts[0], ws=ws)
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_one_log_entry_per_dispatch_and_rerun_reproduces(sad, dev, dtype):
+    """The bookkeeping of an MLP dispatch, with the switches set through ``ops``: a single ``grouped`` call and a merged
+    ``grouped_multi`` each append exactly ONE entry to ``ops.LAUNCH_LOG`` and to ``ops.RERUN_LOG``, named ``name`` / ``"a+b"``,
+    and the RERUN_LOG entry's fn() enqueues the same dispatch again: onto a re-zeroed ``out`` it reproduces the result bit for
+    bit.  One scene of 128 points, 16 groups of up to 8 samples (some short), two 3-layer chains: what can go wrong here is
+    bookkeeping (a switch read from the wrong module, a closure that lost an object, a double append), not arithmetic."""
+    import torch
+    from sad_amd import ops, synth
+    rng = np.random.default_rng(128)
+    B, N, M, S, C = 1, 128, 16, 8, 4
+    xyz = rng.random((B, N, 3), dtype=np.float32)
+    X, F, Cn = _t(xyz, dev), _t(rng.normal(size=(B, N, C)).astype(np.float32), dev), _t(xyz[:, :M], dev)
+    (idx,), (cnt,) = ops.ball_query_multi([0.25], [S], X, Cn, return_counts=True)
+    assert bool((cnt < S).any()) and bool((cnt == S).any()), "want groups short of S beside full ones"
+    cls = ops.PackedMLP if dtype == "f32" else ops.PackedMLPBf16
+    nets = [cls(synth.make_mlp_weights([C + 3] + m, rng), True, dev, name=n) for n, m in (("a", [16, 16, 32]), ("b", [32, 32, 64]))]
+    one = torch.zeros(B, M, 32, device=dev)
+    both = torch.zeros(B, M, 96, device=dev)
+    assert ops.RERUN_LOG is None and ops.LAUNCH_LOG is None
+    try:
+        ops.RERUN_LOG, ops.LAUNCH_LOG = [], []
+        nets[0].grouped(X, F, Cn, idx, out=one, col_off=0, cnt=cnt)
+        assert [e[0] for e in ops.RERUN_LOG] == ["a"] and [e[:2] for e in ops.LAUNCH_LOG] == [("mlp", "a")]
+        ops.grouped_multi([(nets[0], X, F, Cn, idx, both, 0, cnt), (nets[1], X, F, Cn, idx, both, 32, cnt)])
+        assert [e[0] for e in ops.RERUN_LOG] == ["a", "a+b"]
+        assert [e[:2] for e in ops.LAUNCH_LOG] == [("mlp", "a"), ("mlp", "a+b")]
+        reruns, ops.RERUN_LOG, ops.LAUNCH_LOG = ops.RERUN_LOG, None, None
+        for (name, fn), out in zip(reruns, (one, both)):
+            first = out.clone()
+            assert bool((first > 0).any()), name
+            out.zero_()
+            fn()
+            torch.cuda.synchronize()
+            assert torch.equal(out, first), f"{dtype} {name}: the re-enqueued dispatch differs"
+        if dtype == "f32":      # (the merged dispatch writes the single launch's bits: test_multi_chain_dispatch_matches_single_launches)
+            assert torch.equal(both[:, :, :32], one)
+    finally:
+        ops.RERUN_LOG, ops.LAUNCH_LOG = None, None

@@ -23,6 +23,8 @@ _LAZY = {
     "boxes_iou_bev": "ops", "boxes_iou3d": "ops", "points_in_boxes": "ops", "roipoint_pool3d": "ops",
     "voxel_coords": "ops", "voxel_index": "ops", "voxelize": "ops", "voxel_reduce": "ops",
     "voxel_decorate": "ops", "voxel_encode": "ops",
+    "anchor_decode": "ops", "center_decode": "ops", "anchor_grid": "dense_head",
+    "AnchorHeadDecoder": "dense_head", "CenterHeadDecoder": "dense_head",
     "Voxelization": "voxel", "DynamicScatter": "voxel", "PillarFeatureNet": "voxel",
     "sparse_conv_index": "ops", "sparse_conv": "ops", "sparse_to_dense": "ops", "PackedSparseWeight": "ops",
     "sparse_conv_index_transpose": "ops", "sparse_conv_grad_weight": "ops", "sparse_conv_grad_input": "ops",

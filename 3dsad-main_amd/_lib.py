@@ -62,6 +62,35 @@ class MlpBf16Args(ctypes.Structure):
     ]
 
 
+LAYOUTS = {"nchw": 0, "nhwc": 1}      # SAD_LAYOUT_*
+
+
+class AnchorDecodeArgs(ctypes.Structure):
+    """``struct sad_anchor_decode_args`` (include/sad_amd.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("cls", vp), ("reg", vp), ("dir", vp), ("index", vp),
+        ("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("C", ctypes.c_int), ("nb", ctypes.c_int),
+        ("ns", ctypes.c_int), ("nr", ctypes.c_int), ("layout", ctypes.c_int), ("P", ctypes.c_int),
+        ("sizes", ctypes.c_float * 48), ("z_center", ctypes.c_float * 16), ("rotations", ctypes.c_float * 8),
+        ("x0", ctypes.c_float), ("y0", ctypes.c_float), ("sx", ctypes.c_float), ("sy", ctypes.c_float),
+        ("dir_offset", ctypes.c_float), ("dir_limit_offset", ctypes.c_float),
+        ("boxes", vp), ("scores", vp), ("labels", vp),
+    ]
+
+
+class CenterDecodeArgs(ctypes.Structure):
+    """``struct sad_center_decode_args`` (include/sad_amd.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("hm", vp), ("reg", vp), ("height", vp), ("dim", vp), ("rot", vp), ("vel", vp), ("index", vp),
+        ("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("C", ctypes.c_int), ("layout", ctypes.c_int),
+        ("P", ctypes.c_int), ("log_dim", ctypes.c_int), ("peak", ctypes.c_int),
+        ("lo_x", ctypes.c_float), ("lo_y", ctypes.c_float), ("sx", ctypes.c_float), ("sy", ctypes.c_float),
+        ("boxes", vp), ("scores", vp), ("labels", vp),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/sad_amd.h declares
 SIGNATURES = {
     "sad_version": (ctypes.c_int, []),
@@ -158,6 +187,8 @@ SIGNATURES = {
     "sad_nms_boxes_f32": (ctypes.c_int, [vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float,
                                         ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp]),
     "sad_decode_boxes_f32": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, c_f32p, vp, vp]),
+    "sad_anchor_decode_f32": (ctypes.c_int, [ctypes.POINTER(AnchorDecodeArgs), vp]),
+    "sad_center_decode_f32": (ctypes.c_int, [ctypes.POINTER(CenterDecodeArgs), vp]),
 }
 
 _lib = None

@@ -1,0 +1,77 @@
+"""Dense BEV heads (SPEC.md §25): the raw maps of an anchor head (SECOND, PointPillars, PV-RCNN's RPN) or a centre head
+(CenterPoint) -> ``(boxes, scores, labels)``, and on through ``ops.nms_boxes``.  The 2-D convolutions that produce the maps
+are torch's; these modules hold the decode configuration only and have no parameters.  Inference only."""
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import ops
+
+
+def anchor_grid(point_range: Sequence[float], H: int, W: int) -> Tuple[Tuple[float, float], Tuple[float, float]]:
+    """``(origin, step)`` of the corner-aligned anchor grid of OpenPCDet's AnchorGenerator on a feature map of H x W cells:
+    the first anchor stands on the low edge of ``point_range`` (x_lo, y_lo, z_lo, x_hi, y_hi, z_hi), the last on the high
+    edge, so step = (hi - lo) / (n - 1), computed in double and rounded to float32 once; 0 for a single cell."""
+    lo_x, lo_y, hi_x, hi_y = (float(point_range[i]) for i in (0, 1, 3, 4))
+    if H < 1 or W < 1:
+        raise ValueError(f"anchor_grid: need H, W >= 1 (got {H}, {W})")
+    sx = (hi_x - lo_x) / (W - 1) if W > 1 else 0.0
+    sy = (hi_y - lo_y) / (H - 1) if H > 1 else 0.0
+    f = lambda v: float(np.float32(v))  # noqa: E731
+    return (f(lo_x), f(lo_y)), (f(sx), f(sy))
+
+
+def _predict(boxes, scores, labels, iou_thr, score_thr, pre_max, post_max, class_aware):
+    keep, order, count = ops.nms_boxes(boxes, scores, labels if class_aware else None, iou_thr, score_thr, pre_max, post_max)
+    return boxes, scores, labels, order, count
+
+
+class AnchorHeadDecoder(nn.Module):
+    """Decode configuration of an anchor head.  ``sizes`` [ns,3] (l,w,h), ``z_center`` [ns] (the anchors' centre heights:
+    OpenPCDet's ``anchor_bottom_heights + h / 2``), ``rotations`` [nr]; ``origin`` / ``step`` from ``anchor_grid``."""
+
+    def __init__(self, sizes, z_center, rotations, origin, step, dir_offset: float = 0.78539, dir_limit_offset: float = 0.0,
+                 layout: str = "nchw"):
+        super().__init__()
+        self.sizes = np.asarray(sizes, dtype=np.float32).reshape(-1, 3)
+        self.z_center = np.asarray(z_center, dtype=np.float32).reshape(-1)
+        self.rotations = np.asarray(rotations, dtype=np.float32).reshape(-1)
+        self.origin, self.step = (float(origin[0]), float(origin[1])), (float(step[0]), float(step[1]))
+        self.dir_offset, self.dir_limit_offset, self.layout = float(dir_offset), float(dir_limit_offset), layout
+
+    @property
+    def num_anchors(self) -> int:
+        return self.sizes.shape[0] * self.rotations.shape[0]
+
+    def forward(self, cls: torch.Tensor, reg: torch.Tensor, dir: Optional[torch.Tensor] = None,
+                index: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        return ops.anchor_decode(cls, reg, dir, sizes=self.sizes, z_center=self.z_center, rotations=self.rotations,
+                                 origin=self.origin, step=self.step, dir_offset=self.dir_offset,
+                                 dir_limit_offset=self.dir_limit_offset, layout=self.layout, index=index)
+
+    def predict(self, cls: torch.Tensor, reg: torch.Tensor, dir: Optional[torch.Tensor] = None, *, iou_thr: float,
+                score_thr: float = 0.0, pre_max: Optional[int] = None, post_max: Optional[int] = None, class_aware: bool = True):
+        """(boxes [B,K,7], scores, labels, order [B,P], count [B]): the decode, then ``ops.nms_boxes`` on its three tensors.
+        ``order[b, :count[b]]`` are the kept rows of scene b, best first.  No synchronisation."""
+        return _predict(*self.forward(cls, reg, dir), iou_thr, score_thr, pre_max, post_max, class_aware)
+
+
+class CenterHeadDecoder(nn.Module):
+    """Decode configuration of one task of a centre head.  ``origin`` = (x_lo, y_lo) of the point range, ``cell`` =
+    ``out_stride * voxel_size`` in x and y."""
+
+    def __init__(self, origin, cell, log_dim: bool = True, peak: bool = False, layout: str = "nchw"):
+        super().__init__()
+        self.origin, self.cell = (float(origin[0]), float(origin[1])), (float(cell[0]), float(cell[1]))
+        self.log_dim, self.peak, self.layout = bool(log_dim), bool(peak), layout
+
+    def forward(self, hm, reg, height, dim, rot, vel=None, index: Optional[torch.Tensor] = None):
+        return ops.center_decode(hm, reg, height, dim, rot, vel, origin=self.origin, cell=self.cell, log_dim=self.log_dim,
+                                 peak=self.peak, layout=self.layout, index=index)
+
+    def predict(self, hm, reg, height, dim, rot, vel=None, *, iou_thr: float, score_thr: float = 0.0,
+                pre_max: Optional[int] = None, post_max: Optional[int] = None, class_aware: bool = True):
+        """(boxes [B,K,D], scores, labels, order [B,P], count [B]) as ``AnchorHeadDecoder.predict``."""
+        return _predict(*self.forward(hm, reg, height, dim, rot, vel), iou_thr, score_thr, pre_max, post_max, class_aware)

@@ -1141,6 +1141,181 @@ def nms_boxes(boxes: torch.Tensor, scores: Optional[torch.Tensor], labels: Optio
     return keep, order, count
 
 
+def _head_map(t: torch.Tensor, name: str, B: int, ch: int, H: int, W: int, layout: str) -> torch.Tensor:
+    """A head map [B,ch,H,W] (nchw) / [B,H,W,ch] (nhwc): contiguous f32, read where it is (no copy is ever made).  Shapes and
+    dtypes are judged before devices (``_head_devices``), so a wrong map is named whatever it lives on."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: expected a torch.Tensor")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name}: expected dtype torch.float32, got {t.dtype}")
+    want = (B, ch, H, W) if layout == "nchw" else (B, H, W, ch)
+    if tuple(t.shape) != want:
+        raise ValueError(f"{name}: expected shape {want} for layout {layout!r} ({ch} channels), got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: must be contiguous in layout {layout!r} (the kernel reads the map where it is)")
+    return t
+
+
+def _head_devices(named) -> torch.device:
+    """Every tensor of (name, tensor-or-None) pairs on the current GPU."""
+    dev = None
+    for name, t in named:
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise RuntimeError(f"{name}: expected a GPU tensor (sad_amd has no CPU path)")
+        _on_current_device(t, name)
+        dev = t.device
+    return dev
+
+
+def _head_index(index: Optional[torch.Tensor], B: int) -> int:
+    """P of index [B,P] int32 (0 without one)."""
+    if index is None:
+        return 0
+    if not isinstance(index, torch.Tensor):
+        raise TypeError("index: expected a torch.Tensor")
+    if index.dtype != torch.int32:
+        raise TypeError(f"index: expected dtype torch.int32, got {index.dtype}")
+    if index.dim() != 2 or index.shape[0] != B or index.shape[1] < 1:
+        raise ValueError(f"index: expected [B,P] with B = {B} and P >= 1, got {tuple(index.shape)}")
+    if not index.is_contiguous():
+        raise ValueError("index: must be contiguous")
+    return index.shape[1]
+
+
+def _head_grid(first: torch.Tensor, name: str, layout: str) -> Tuple[int, int, int, int]:
+    """(B, channels, H, W) of the first map of a head."""
+    if layout not in _lib.LAYOUTS:
+        raise ValueError(f"layout: expected 'nchw' or 'nhwc', got {layout!r}")
+    if not isinstance(first, torch.Tensor):
+        raise TypeError(f"{name}: expected a torch.Tensor")
+    if first.dim() != 4:
+        raise ValueError(f"{name}: expected 4 dims, got shape {tuple(first.shape)}")
+    B, d1, d2, d3 = first.shape
+    return (B, d1, d2, d3) if layout == "nchw" else (B, d3, d1, d2)
+
+
+def _head_outputs(B: int, rows: int, D: int, out: Optional[tuple], dev) -> tuple:
+    """(boxes [B,rows,D], scores [B,rows], labels [B,rows]) of a decode call: ``out`` checked, or new buffers."""
+    if out is None:
+        return (_empty((B, rows, D), dtype=torch.float32, device=dev), _empty((B, rows), dtype=torch.float32, device=dev),
+                _empty((B, rows), dtype=torch.int32, device=dev))
+    boxes, scores, labels = out
+    ok = (tuple(boxes.shape) == (B, rows, D) and tuple(scores.shape) == (B, rows) and tuple(labels.shape) == (B, rows)
+          and boxes.dtype == scores.dtype == torch.float32 and labels.dtype == torch.int32
+          and boxes.is_contiguous() and scores.is_contiguous() and labels.is_contiguous()
+          and boxes.device == scores.device == labels.device == dev)
+    if not ok:
+        raise ValueError(f"out: expected contiguous (boxes [{B},{rows},{D}] f32, scores [{B},{rows}] f32, labels [{B},{rows}] int32) "
+                         "on the device of the maps")
+    return boxes, scores, labels
+
+
+def _f32(v) -> float:
+    return float(np.float32(v))
+
+
+def anchor_decode(cls: torch.Tensor, reg: torch.Tensor, dir: Optional[torch.Tensor] = None, *, sizes, z_center, rotations,
+                  origin, step, dir_offset: float = 0.78539, dir_limit_offset: float = 0.0, layout: str = "nchw",
+                  index: Optional[torch.Tensor] = None, out: Optional[tuple] = None
+                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Anchor head decode (SPEC.md §25.1).  cls [B,A*C,H,W], reg [B,A*7,H,W], dir [B,A*nb,H,W] or ``None`` (``layout="nhwc"``:
+    channels last), contiguous f32, read where they are.  A = ns * nr anchors per cell from ``sizes`` [ns,3] (l,w,h),
+    ``z_center`` [ns], ``rotations`` [nr] (sizes outer, rotations inner); the anchor of cell (y, x) stands at
+    ``origin + (x, y) * step`` (``dense_head.anchor_grid``).  -> (boxes [B,K,7], scores [B,K], labels [B,K] int32), K = H*W*A,
+    k = (y*W + x)*A + a: ResidualCoder.decode, the direction bin applied when ``dir`` is given, score = sigmoid(max class
+    logit).  ``index`` [B,P] int32: only those rows, outputs [B,P,...]; an entry outside [0, K) gives (0..., -inf, -1).
+    One launch, no synchronisation, no gradients.  ``out`` = (boxes, scores, labels) to write into."""
+    sizes_np = np.asarray(sizes, dtype=np.float32).reshape(-1, 3)
+    zc = np.asarray(z_center, dtype=np.float32).reshape(-1)
+    rots = np.asarray(rotations, dtype=np.float32).reshape(-1)
+    ns, nr = sizes_np.shape[0], rots.shape[0]
+    if ns < 1 or nr < 1 or zc.shape[0] != ns:
+        raise ValueError(f"sizes [ns,3], z_center [ns], rotations [nr]: need ns, nr >= 1 and one z_center per size (ns = {ns}, "
+                         f"z_center: {zc.shape[0]}, nr = {nr})")
+    if ns > 16 or nr > 8:
+        raise ValueError(f"sizes / rotations: at most 16 sizes and 8 rotations (got {ns}, {nr})")
+    A = ns * nr
+    B, chc, H, W = _head_grid(cls, "cls", layout)
+    if chc < A or chc % A:
+        raise ValueError(f"cls: {chc} channels are not a multiple of A = ns * nr = {A}")
+    C = chc // A
+    cls = _head_map(cls, "cls", B, A * C, H, W, layout)
+    _, chr_, _, _ = _head_grid(reg, "reg", layout)
+    if chr_ != A * 7:
+        raise ValueError(f"reg: expected A * 7 = {A * 7} channels, got {chr_}")
+    reg = _head_map(reg, "reg", B, A * 7, H, W, layout)
+    nb = 0
+    if dir is not None:
+        _, chd, _, _ = _head_grid(dir, "dir", layout)
+        if chd < 2 * A or chd % A:
+            raise ValueError(f"dir: {chd} channels are not A * nb with nb >= 2 (A = {A})")
+        nb = chd // A
+        dir = _head_map(dir, "dir", B, chd, H, W, layout)
+    K = H * W * A
+    P = _head_index(index, B)
+    dev = _head_devices((("cls", cls), ("reg", reg), ("dir", dir), ("index", index)))
+    rows = P if index is not None else K
+    boxes, scores, labels = _head_outputs(B, rows, 7, out, dev)
+    a = _lib.AnchorDecodeArgs()
+    a.struct_size = ctypes.sizeof(_lib.AnchorDecodeArgs)
+    a.cls, a.reg, a.dir = cls.data_ptr(), reg.data_ptr(), dir.data_ptr() if dir is not None else None
+    a.index = index.data_ptr() if index is not None else None
+    a.B, a.H, a.W, a.C, a.nb, a.ns, a.nr, a.layout, a.P = B, H, W, C, nb, ns, nr, _lib.LAYOUTS[layout], P
+    a.sizes[:3 * ns] = sizes_np.reshape(-1).tolist()
+    a.z_center[:ns] = zc.tolist()
+    a.rotations[:nr] = rots.tolist()
+    a.x0, a.y0, a.sx, a.sy = _f32(origin[0]), _f32(origin[1]), _f32(step[0]), _f32(step[1])
+    a.dir_offset, a.dir_limit_offset = _f32(dir_offset), _f32(dir_limit_offset)
+    a.boxes, a.scores, a.labels = boxes.data_ptr(), scores.data_ptr(), labels.data_ptr()
+    with _timed("anchor_decode", f"K{K}R{rows}"):
+        check(lib().sad_anchor_decode_f32(ctypes.byref(a), _stream()), "sad_anchor_decode_f32")
+    return boxes, scores, labels
+
+
+def center_decode(hm: torch.Tensor, reg: torch.Tensor, height: torch.Tensor, dim: torch.Tensor, rot: torch.Tensor,
+                  vel: Optional[torch.Tensor] = None, *, origin, cell, log_dim: bool = True, peak: bool = False,
+                  layout: str = "nchw", index: Optional[torch.Tensor] = None, out: Optional[tuple] = None
+                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Centre head decode (SPEC.md §25.2, one CenterPoint task).  hm [B,C,H,W], reg [B,2,H,W], height [B,1,H,W], dim [B,3,H,W],
+    rot [B,2,H,W] (sine, cosine), vel [B,2,H,W] or ``None`` (``layout="nhwc"``: channels last), contiguous f32 ->
+    (boxes [B,K,D], scores [B,K], labels [B,K] int32), K = H*W, k = y*W + x, D = 9 with ``vel`` else 7:
+    cx = (x + reg0) * cell[0] + origin[0], cy likewise, cz = height, (l,w,h) = exp(dim) if ``log_dim`` else dim,
+    yaw = atan2(rot0, rot1), score = sigmoid(max class logit).  ``peak``: only the classes that are a 3x3 local maximum at the
+    cell take part; a cell without one gets score 0 and label -1.  ``index`` / ``out`` as in ``anchor_decode``."""
+    B, C, H, W = _head_grid(hm, "hm", layout)
+    if C < 1:
+        raise ValueError("hm: needs at least one class channel")
+    hm = _head_map(hm, "hm", B, C, H, W, layout)
+    maps = []
+    for t, name, ch in ((reg, "reg", 2), (height, "height", 1), (dim, "dim", 3), (rot, "rot", 2), (vel, "vel", 2)):
+        if t is None and name == "vel":
+            maps.append(None)
+            continue
+        if isinstance(t, torch.Tensor) and t.dim() == 4 and _head_grid(t, name, layout)[1] != ch:
+            raise ValueError(f"{name}: expected {ch} channels, got {_head_grid(t, name, layout)[1]}")
+        maps.append(_head_map(t, name, B, ch, H, W, layout))
+    reg, height, dim, rot, vel = maps
+    D = 9 if vel is not None else 7
+    K = H * W
+    P = _head_index(index, B)
+    dev = _head_devices((("hm", hm), ("reg", reg), ("height", height), ("dim", dim), ("rot", rot), ("vel", vel), ("index", index)))
+    rows = P if index is not None else K
+    boxes, scores, labels = _head_outputs(B, rows, D, out, dev)
+    a = _lib.CenterDecodeArgs()
+    a.struct_size = ctypes.sizeof(_lib.CenterDecodeArgs)
+    a.hm, a.reg, a.height, a.dim, a.rot = hm.data_ptr(), reg.data_ptr(), height.data_ptr(), dim.data_ptr(), rot.data_ptr()
+    a.vel = vel.data_ptr() if vel is not None else None
+    a.index = index.data_ptr() if index is not None else None
+    a.B, a.H, a.W, a.C, a.layout, a.P, a.log_dim, a.peak = B, H, W, C, _lib.LAYOUTS[layout], P, int(bool(log_dim)), int(bool(peak))
+    a.lo_x, a.lo_y, a.sx, a.sy = _f32(origin[0]), _f32(origin[1]), _f32(cell[0]), _f32(cell[1])
+    a.boxes, a.scores, a.labels = boxes.data_ptr(), scores.data_ptr(), labels.data_ptr()
+    with _timed("center_decode", f"K{K}R{rows}"):
+        check(lib().sad_center_decode_f32(ctypes.byref(a), _stream()), "sad_center_decode_f32")
+    return boxes, scores, labels
+
+
 # The fused MLP chains (PackedMLP / PackedMLPBf16, grouped_multi, rowscan_multi, the autotuner) live in mlp.py; they belong
 # to this operator surface, so their public names are re-exported here (the same objects).
 from .mlp import (GroupedCall, PackedMLP, PackedMLPBf16, check_workspace, choose_stage_assignment, cont_buffer,  # noqa: E402,F401

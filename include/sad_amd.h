@@ -578,6 +578,55 @@ int sad_nms_boxes_f32(const float *boxes, int D, const float *scores, const int3
                       float iou_thr, float score_thr, int pre_max, int post_max, int32_t *keep, int32_t *order,
                       int32_t *count, void *workspace, sad_stream_t stream);
 
+/* SPEC.md §25.  Dense head decode: the raw maps of a BEV head -> boxes[B,K,D], scores[B,K], labels[B,K], the inputs of
+ * sad_nms_boxes_f32.  Inference only.  Maps are contiguous f32 in the layout named by `layout` and are read where they are:
+ * SAD_LAYOUT_NCHW [B, channels, H, W] or SAD_LAYOUT_NHWC [B, H, W, channels], the same channel numbering in both.
+ * With index[B,P] (int32, may be NULL) only the rows k = index[b,p] are decoded and the outputs are [B,P,...]: an entry
+ * outside [0, K) gives a zero box, score -inf and label -1; duplicates are allowed.  Outputs are fully written by the call.
+ * One launch whose dimensions depend on the shapes only; nothing is read back and nothing synchronises.
+ * Common limits: 1 <= B <= 65535, 1 <= C <= 64, B*K < 2^31, B*P < 2^31 (SAD_EUNSUPPORTED above); a NULL pointer, a wrong
+ * struct_size, a size below 1 or another layout code: SAD_EINVAL.  NaN in a map is undefined behaviour. */
+#define SAD_LAYOUT_NCHW 0
+#define SAD_LAYOUT_NHWC 1
+
+/* §25.1 anchor head (SECOND, PointPillars, PV-RCNN's RPN).  A = ns * nr anchors per cell, a = s * nr + r (sizes outer);
+ * K = H*W*A, k = (y*W + x)*A + a.  cls has A*C channels (a*C + c), reg A*7 (a*7 + j), dir A*nb (a*nb + d); dir == NULL
+ * iff nb == 0, else 2 <= nb <= 8.  1 <= ns <= 16, 1 <= nr <= 8 (SAD_EUNSUPPORTED above).  The anchor of (y, x, s, r) is
+ * (x0 + x*sx, y0 + y*sy, z_center[s], sizes[3s .. 3s+2] = (l, w, h), rotations[r]); no anchor tensor is read.
+ * boxes[.,7] = (cx, cy, cz, l, w, h, yaw): ResidualCoder.decode, then the direction bin with period 2*pi/nb when dir is
+ * given; score = sigmoid(max class logit), label = the lowest class that attains it. */
+typedef struct sad_anchor_decode_args {
+    size_t struct_size;   /* = sizeof(sad_anchor_decode_args) */
+    const float *cls, *reg, *dir;
+    const int32_t *index; /* [B,P] or NULL */
+    int B, H, W, C, nb, ns, nr, layout, P;
+    float sizes[48];      /* [ns,3] (l, w, h) */
+    float z_center[16];   /* [ns] */
+    float rotations[8];   /* [nr] */
+    float x0, y0, sx, sy; /* centre of cell (0, 0) and the step between cell centres */
+    float dir_offset, dir_limit_offset;
+    float *boxes;         /* [B,K,7] or [B,P,7] */
+    float *scores;        /* [B,K] or [B,P] */
+    int32_t *labels;      /* [B,K] or [B,P] */
+} sad_anchor_decode_args;
+int sad_anchor_decode_f32(const sad_anchor_decode_args *args, sad_stream_t stream);
+
+/* §25.2 centre head (CenterPoint, one task per call).  hm[B,C,H,W], reg[.,2,.,.], height[.,1,.,.], dim[.,3,.,.],
+ * rot[.,2,.,.] (sine, cosine), vel[.,2,.,.] or NULL; K = H*W, k = y*W + x.  boxes[.,D], D = 9 with vel (columns 7, 8 = vel)
+ * else 7: cx = (x + reg0)*sx + lo_x, cy likewise, cz = height, (l, w, h) = exp(dim) if log_dim else dim, yaw =
+ * atan2(rot0, rot1).  score / label as in §25.1 over the C heat-map channels; with peak != 0 only the classes whose logit
+ * is >= its (up to 8) in-image neighbours take part, and a cell where none does gets score 0 and label -1. */
+typedef struct sad_center_decode_args {
+    size_t struct_size;   /* = sizeof(sad_center_decode_args) */
+    const float *hm, *reg, *height, *dim, *rot, *vel;
+    const int32_t *index; /* [B,P] or NULL */
+    int B, H, W, C, layout, P, log_dim, peak;
+    float lo_x, lo_y, sx, sy;
+    float *boxes, *scores;
+    int32_t *labels;
+} sad_center_decode_args;
+int sad_center_decode_f32(const sad_center_decode_args *args, sad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,10 +32,29 @@ struct ScanJob {
     void *cont0;
     int cont_cols;
 };
-// ints of a row-packing table in front of gstart (hdr, row_start, pass_first, block sums, row map: make_scan_job)
-inline long long scan_gstart_off(long long ng, int S) {
-    const long long o = 4 + (ng + 1) + (ng * S / 32 + 2) + (ng / 1024 + 2) + 2 * ng * S;
-    return (o + 3) & ~3LL;
+// Layout of a row-packing table (int offsets from its start):
+//   hdr[4] | row_start[ngroups+1] (item queues in its first 258 ints, else unused) | pass_first[ngroups*S/32+2] (holds the block sums:
+//   ngroups/256 + 1 of them) | [ngroups/1024+2] (unused: the block sums of 1 024-group blocks lived here) | row map: src[ngroups*S] |
+//   gid[ngroups*S] (only written when idx != NULL) | (from a multiple of 4 ints) gstart[ngroups+1] (written by a split-pooling scan only)
+struct ScanLayout { long long blk_sum, row_src, row_gid, gstart, ints; };
+inline ScanLayout scan_layout(long long ng, int S) {
+    ScanLayout t;
+    t.blk_sum = 4 + (ng + 1);
+    t.row_src = t.blk_sum + (ng * S / 32 + 2) + (ng / 1024 + 2);
+    t.row_gid = t.row_src + ng * S;
+    t.gstart = (t.row_gid + ng * S + 3) & ~3LL;
+    t.ints = t.gstart + ng + 1;
+    return t;
+}
+// a scan launched by a chain's own dispatch zero-fills the groups of the chain's output slice that need it (ScanJob::zout)
+inline void scan_zero_fill(ScanJob &jb, float *out, int ld_out, int col_off, int cols) { jb.zout = out + col_off; jb.zld = ld_out; jb.zcols = cols; }
+// order[0..n) = 0..n-1 by weight, heaviest first: the chains of a merged MLP dispatch (the workgroups of the heaviest start first, the light
+// chains fill its tail).  Only a strictly heavier later chain is exchanged forward: two chains of equal weight are never exchanged with each other.
+inline void heaviest_first(const double *weight, int n, int *order) {
+    for (int i = 0; i < n; ++i) order[i] = i;
+    for (int i = 0; i < n; ++i)
+        for (int k = i + 1; k < n; ++k)
+            if (weight[order[k]] > weight[order[i]]) { const int t = order[i]; order[i] = order[k]; order[k] = t; }
 }
 constexpr int CONT_BIT = 1 << 29;          // row map: this row's group began in an earlier tile (split pooling only)
 constexpr int GID_MASK = CONT_BIT - 1;

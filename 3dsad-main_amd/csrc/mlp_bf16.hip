@@ -465,20 +465,28 @@ inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 }  // namespace
 
-// bytes of the per-layer images (fragment image + padded bias of every layer); the stream image of the register-resident
-// chain kernel (mlp_bf16_reg.hip) follows them for grouped 3-layer chains with a compiled shape
-static size_t layer_images_bytes(int L, const int *dims) {
+// The packed image: per layer the fragment image ([channel tile][k-step of 16][lane] x 8 bf16 = CT * 32 * kp * 2 bytes) and the bias
+// padded to CT * 32 floats, each from a 16-byte boundary; the stream image of the register-resident chain kernel (mlp_bf16_reg.hip)
+// follows them for grouped 3-layer chains with a compiled shape.
+struct LayerImage { size_t w, bias; int kp, CT; };      // byte offsets in the packed image; padded input channels, output channel tiles of 32
+// fills im[0..L); returns the bytes of the layer images = the offset of the stream image
+static size_t layer_images(int L, const int *dims, LayerImage *im) {
     size_t n = 0;
     for (int l = 0; l < L; ++l) {
-        const int CT = (dims[l + 1] + 31) / 32;
-        n += align16((size_t)CT * 32 * kpad(l, dims[l]) * 2) + align16((size_t)CT * 32 * 4);
+        im[l].kp = kpad(l, dims[l]);
+        im[l].CT = (dims[l + 1] + 31) / 32;
+        im[l].w = n;
+        n += align16((size_t)im[l].CT * 32 * im[l].kp * 2);
+        im[l].bias = n;
+        n += align16((size_t)im[l].CT * 32 * 4);
     }
     return n;
 }
 
 SAD_API size_t sad_mlp_packed_bytes_bf16(int L, const int *dims, int first_has_xyz) {
     if (L < 1 || L > SAD_MAX_LAYERS || !dims) return 0;
-    size_t n = layer_images_bytes(L, dims);
+    LayerImage im[SAD_MAX_LAYERS];
+    size_t n = layer_images(L, dims, im);
     if (first_has_xyz) n += (size_t)sad::bfreg_stream_frags(sad::bfreg_shape_id(L, dims)) * 1024;
     return n;
 }
@@ -492,34 +500,31 @@ SAD_API int sad_mlp_pack_bf16(int L, const int *dims, int first_has_xyz, const f
     SAD_REQUIRE(L >= 1 && L <= SAD_MAX_LAYERS && dims && W && bias && packed, "sad_mlp_pack_bf16: bad argument");
     SAD_REQUIRE((uintptr_t)packed % 16 == 0, "sad_mlp_pack_bf16: packed must be 16-byte aligned");
     unsigned char *q = (unsigned char *)packed;
+    LayerImage im[SAD_MAX_LAYERS];
+    const size_t stream_image = layer_images(L, dims, im);
     for (int l = 0; l < L; ++l) {
         SAD_REQUIRE(dims[l] >= 1 && dims[l + 1] >= 1 && W[l] && bias[l], "sad_mlp_pack_bf16: bad layer %d", l);
         SAD_REQUIRE(!(l == 0 && first_has_xyz) || dims[0] >= 3, "sad_mlp_pack_bf16: first layer needs >= 3 inputs");
-        const int CT = (dims[l + 1] + 31) / 32, kp = kpad(l, dims[l]);
-        __bf16 *wout = (__bf16 *)q;
-        q += align16((size_t)CT * 32 * kp * 2);
-        float *bout = (float *)q;
-        q += align16((size_t)CT * 32 * 4);
         hipLaunchKernelGGL(pack_bf16_kernel, dim3(64), dim3(256), 0, (hipStream_t)stream, W[l], bias[l], dims[l],
-                           dims[l + 1], kp, (l == 0 && first_has_xyz) ? 1 : 0, wout, bout);
+                           dims[l + 1], im[l].kp, (l == 0 && first_has_xyz) ? 1 : 0, (__bf16 *)(q + im[l].w), (float *)(q + im[l].bias));
     }
     if (first_has_xyz) {
         const int shape = sad::bfreg_shape_id(L, dims);
         if (shape >= 0)
-            if (int e = sad::bfreg_pack(shape, dims, 1, W, (unsigned char *)packed + layer_images_bytes(L, dims), (hipStream_t)stream)) return e;
+            if (int e = sad::bfreg_pack(shape, dims, 1, W, q + stream_image, (hipStream_t)stream)) return e;
     }
     return sad::check_launch("sad_mlp_pack_bf16");
 }
 
 namespace {
+enum BfKind { BF_TILED, BF_ROWS, BF_REG };
 struct BfPrepared {
-    BfParams p;
+    BfKind kind;
+    BfParams p;             // BF_TILED: the tiled kernel of this file, with lds and grid
     size_t lds;
     int grid;
-    bool rows;              // plain single layer on the row-streaming kernel (mlp_bf16_rows.hip); `rj` is filled, p is not
-    sad::BfRowsJob rj;
-    bool reg;               // geometry 2: register-resident chain (mlp_bf16_reg.hip); `rc` is filled, p is not
-    sad::BfRegChain rc;
+    sad::BfRowsJob rj;      // BF_ROWS: plain single layer on the row-streaming kernel (mlp_bf16_rows.hip)
+    sad::BfRegChain rc;     // BF_REG (geometry 2): register-resident chain (mlp_bf16_reg.hip), with reg_shape, reg_tiles and scan
     int reg_shape;
     long long reg_tiles;
     sad::ScanJob scan;      // row-packing scan the chain needs before its kernel ...
@@ -527,8 +532,8 @@ struct BfPrepared {
 };
 }  // namespace
 
-// Validation, tile size, row-packing scan of one chain; fills `q` for the launch.
-static int prepare_bf16(const sad_mlp_bf16_args *a, sad_stream_t stream, BfPrepared &prep) {
+// Validation of one argument block; fills the parameters that do not depend on the kernel (p.rows among them).
+static int bf16_args(const sad_mlp_bf16_args *a, BfParams &p) {
     SAD_REQUIRE(a, "sad_mlp_chain_bf16: NULL args");
     SAD_REQUIRE(a->struct_size == sizeof(sad_mlp_bf16_args), "sad_mlp_chain_bf16: struct_size=%zu, this library's sad_mlp_bf16_args has %zu bytes "
                 "(caller built against another sad_amd.h; ABI version %d)", a->struct_size, sizeof(sad_mlp_bf16_args), SAD_ABI_VERSION);
@@ -536,7 +541,7 @@ static int prepare_bf16(const sad_mlp_bf16_args *a, sad_stream_t stream, BfPrepa
     SAD_REQUIRE((uintptr_t)a->packed % 16 == 0, "sad_mlp_chain_bf16: packed must be 16-byte aligned");
     SAD_REQUIRE(a->B >= 1 && a->M >= 1 && a->C >= 0, "sad_mlp_chain_bf16: bad sizes");
     const bool grouped = a->idx != nullptr;
-    BfParams p{};
+    p = BfParams{};
     if (grouped) {
         SAD_REQUIRE(a->xyz && a->new_xyz && a->N >= 1 && a->S >= 1, "sad_mlp_chain_bf16: grouped mode needs xyz, new_xyz, N, S");
         SAD_REQUIRE(a->dims[0] == a->C + 3, "sad_mlp_chain_bf16: dims[0]=%d != C+3=%d", a->dims[0], a->C + 3);
@@ -558,9 +563,6 @@ static int prepare_bf16(const sad_mlp_bf16_args *a, sad_stream_t stream, BfPrepa
     p.N = a->N; p.M = a->M; p.S = a->S; p.C = a->C;
     p.L = a->L; p.relu_mask = a->relu_mask;
     p.out = a->out; p.out_bf16 = a->out_bf16; p.ld_out = a->ld_out; p.col_off = a->col_off;
-    prep.reg = false;
-    prep.rows = false;
-    prep.prescanned = a->prescanned != 0;
     if (!grouped && a->n_pool) {
         // the input rows are split-pooled outputs (bf16 rows + continuation rows of n_pool chains side by side): one layer, row-streaming kernel only
         SAD_REQUIRE(a->n_pool >= 1 && a->n_pool <= SAD_MAX_RADII, "sad_mlp_chain_bf16: n_pool must be 0..%d", SAD_MAX_RADII);
@@ -580,103 +582,98 @@ static int prepare_bf16(const sad_mlp_bf16_args *a, sad_stream_t stream, BfPrepa
             SAD_REQUIRE(sad_mlp_cont_bytes(a->B, a->M, a->pool_S[i], a->pool_cols[i]) < (1ull << 32),
                         "sad_mlp_chain_bf16: continuation buffer %d of %zu bytes (limit 4 GB)", i, sad_mlp_cont_bytes(a->B, a->M, a->pool_S[i], a->pool_cols[i]));
     }
-    if (!grouped && a->L == 1 && (a->geometry == 0 || a->geometry == 3)) {
-        // ---- one plain layer: the row-streaming kernel (every input row read once per 128 output channels) ----
-        const size_t esz = a->feat_bf16 ? 2 : 4;
-        const bool ok = (a->C & 7) == 0 && ((size_t)a->ld_feat * esz) % 16 == 0 && (uintptr_t)a->feat % 16 == 0;
-        if (ok) {
-            sad::BfRowsJob &j = prep.rj;
-            j = sad::BfRowsJob{};
-            j.x = a->feat; j.x_bf16 = a->feat_bf16; j.ldx = a->ld_feat; j.kin = a->C; j.rows = p.rows;
-            const int kp = kpad(0, a->dims[0]), CT = (a->dims[1] + 31) / 32;
-            j.w = a->packed;
-            j.bias = (const float *)((const unsigned char *)a->packed + align16((size_t)CT * 32 * kp * 2));
-            j.ks = kp / 16; j.ct = CT; j.cout = a->dims[1];
-            j.relu = a->relu_mask & 1;
-            j.out = a->out; j.out_bf16 = a->out_bf16; j.ld_out = a->ld_out; j.col_off = a->col_off;
-            const size_t osz = a->out_bf16 ? 2 : 4;
-            j.vec_out = ((size_t)a->ld_out * osz) % (4 * osz) == 0 && ((size_t)a->col_off * osz) % (4 * osz) == 0 &&
-                        (uintptr_t)a->out % (4 * osz) == 0;
-            j.n_pool = a->n_pool;
-            for (int i = 0, c0 = 0; i < a->n_pool; ++i) {
-                j.pool_gstart[i] = (const int *)a->pool_ws[i] + sad::scan_gstart_off(p.rows, a->pool_S[i]);
-                j.pool_cont[i] = a->pool_cont[i];
-                j.pool_ld[i] = a->pool_cols[i];
-                j.pool_col0[i] = c0;
-                c0 += a->pool_cols[i];
-                for (int k = i + 1; k <= SAD_MAX_RADII; ++k) j.pool_col0[k] = c0;
-            }
-            prep.rows = true;
-            return SAD_OK;
-        }
-        if (a->n_pool) return sad::fail(SAD_EUNSUPPORTED, "sad_mlp_chain_bf16: split-pooled input rows need C %% 8 == 0 and 16-byte aligned rows");
-        if (a->geometry == 3) return sad::fail(SAD_EUNSUPPORTED, "sad_mlp_chain_bf16: geometry 3 (row-streaming layer) needs C %% 8 == 0 and 16-byte aligned rows");
+    return SAD_OK;
+}
+
+// One plain layer on the row-streaming kernel (every input row read once per 128 output channels): geometry 0 or 3.
+static void prepare_bf16_rows(const sad_mlp_bf16_args *a, long long rows, BfPrepared &prep) {
+    LayerImage im;
+    layer_images(1, a->dims, &im);
+    sad::BfRowsJob &j = prep.rj;
+    j = sad::BfRowsJob{};
+    j.x = a->feat; j.x_bf16 = a->feat_bf16; j.ldx = a->ld_feat; j.kin = a->C; j.rows = rows;
+    j.w = a->packed;
+    j.bias = (const float *)((const unsigned char *)a->packed + im.bias);
+    j.ks = im.kp / 16; j.ct = im.CT; j.cout = a->dims[1];
+    j.relu = a->relu_mask & 1;
+    j.out = a->out; j.out_bf16 = a->out_bf16; j.ld_out = a->ld_out; j.col_off = a->col_off;
+    const size_t osz = a->out_bf16 ? 2 : 4;
+    j.vec_out = ((size_t)a->ld_out * osz) % (4 * osz) == 0 && ((size_t)a->col_off * osz) % (4 * osz) == 0 &&
+                (uintptr_t)a->out % (4 * osz) == 0;
+    j.n_pool = a->n_pool;
+    for (int i = 0, c0 = 0; i < a->n_pool; ++i) {
+        j.pool_gstart[i] = (const int *)a->pool_ws[i] + sad::scan_layout(rows, a->pool_S[i]).gstart;
+        j.pool_cont[i] = a->pool_cont[i];
+        j.pool_ld[i] = a->pool_cols[i];
+        j.pool_col0[i] = c0;
+        c0 += a->pool_cols[i];
+        for (int k = i + 1; k <= SAD_MAX_RADII; ++k) j.pool_col0[k] = c0;
     }
-    if (a->geometry == 2) {
-        // ---- register-resident chain: one wave per 32-row tile, activations in registers, weights through an LDS ring ----
-        const int shape = grouped ? sad::bfreg_shape_id(a->L, a->dims) : -1;
-        const bool vec = a->feat_bf16 && (a->C & 7) == 0 && (a->ld_feat & 7) == 0 && a->C >= 8;
-        if (shape < 0 || !a->cnt || !a->workspace || (a->dims[0] > 16 && !vec))
-            return sad::fail(SAD_EUNSUPPORTED, "sad_mlp_chain_bf16: geometry 2 (register-resident chain) needs a compiled grouped 3-layer shape, "
-                                               "cnt + workspace and, for more than 13 feature channels, 16-byte bf16 feature rows");
-        SAD_REQUIRE((uintptr_t)a->workspace % 16 == 0, "sad_mlp_chain_bf16: workspace must be 16-byte aligned");
-        SAD_REQUIRE(!vec || (uintptr_t)a->feat % 16 == 0, "sad_mlp_chain_bf16: feat must be 16-byte aligned");
-        SAD_REQUIRE((long long)a->B * a->M < (long long)sad::CONT_BIT, "sad_mlp_chain_bf16: too many groups");
-        SAD_REQUIRE((long long)a->B * a->N < (1LL << 31), "sad_mlp_chain_bf16: B*N too large");
-        const int ngroups = a->B * a->M;
-        int *tab = (int *)a->workspace;
-        prep.scan = sad::make_scan_job(a->cnt, ngroups, a->S, 32, tab, 0, a->idx, a->N, a->M);
-        if (a->out_bf16) {
-            // split pooling: bf16 rows + continuation rows, plain stores only (nothing to zero; the table must come from a split scan:
-            // this dispatch's own, or sad_mlp_rowscan_split)
-            SAD_REQUIRE(a->dims[3] % 8 == 0 && a->ld_out % 8 == 0 && a->col_off % 8 == 0 && (uintptr_t)a->out % 16 == 0 && (uintptr_t)a->cont % 16 == 0,
-                        "sad_mlp_chain_bf16: split pooling needs cout, ld_out and col_off multiples of 8 and 16-byte aligned out / cont");
-            SAD_REQUIRE(sad_mlp_cont_bytes(a->B, a->M, a->S, a->dims[3]) < (1ull << 32), "sad_mlp_chain_bf16: continuation buffer of %zu bytes (limit 4 GB)",
-                        sad_mlp_cont_bytes(a->B, a->M, a->S, a->dims[3]));
-            prep.scan.split = 1;
-            prep.scan.cont0 = a->cont;
-            prep.scan.cont_cols = a->dims[3];
-        } else {
-            prep.scan.zout = (float *)a->out + a->col_off;     // (a scan launched by the dispatch itself zero-fills the groups that need it)
-            prep.scan.zld = a->ld_out;
-            prep.scan.zcols = a->dims[a->L];
-        }
-        sad::BfRegChain &rc = prep.rc;
-        rc = sad::BfRegChain{};
-        rc.xyz = a->xyz; rc.new_xyz = a->new_xyz; rc.feat = a->feat; rc.feat_bf16 = a->feat_bf16; rc.ld_feat = a->ld_feat; rc.C = a->C;
-        const unsigned char *q = (const unsigned char *)a->packed;
-        for (int l = 0; l < 3; ++l) {
-            const int CT = (a->dims[l + 1] + 31) / 32;
-            q += align16((size_t)CT * 32 * kpad(l, a->dims[l]) * 2);
-            rc.bias[l] = (const float *)q;
-            rc.np[l] = CT * 32;
-            q += align16((size_t)CT * 32 * 4);
-        }
-        rc.stream = q;
-        rc.out = (float *)a->out; rc.ld_out = a->ld_out; rc.col_off = a->col_off; rc.cout_last = a->dims[3];
-        rc.rowtab = tab; rc.row_src = prep.scan.row_src; rc.row_gid = prep.scan.row_gid;
-        rc.out_bf16 = a->out_bf16 ? 1 : 0; rc.cont = a->cont; rc.ld_cont = a->dims[3];
-        prep.reg = true;
-        prep.reg_shape = shape;
-        prep.reg_tiles = ((long long)ngroups * a->S + 31) / 32;
-        return SAD_OK;
+    prep.kind = BF_ROWS;
+}
+
+// Geometry 2: register-resident chain, one wave per 32-row tile, activations in registers, weights through an LDS ring.
+static int prepare_bf16_reg(const sad_mlp_bf16_args *a, BfPrepared &prep) {
+    const int shape = a->idx ? sad::bfreg_shape_id(a->L, a->dims) : -1;
+    const bool vec = a->feat_bf16 && (a->C & 7) == 0 && (a->ld_feat & 7) == 0 && a->C >= 8;
+    if (shape < 0 || !a->cnt || !a->workspace || (a->dims[0] > 16 && !vec))
+        return sad::fail(SAD_EUNSUPPORTED, "sad_mlp_chain_bf16: geometry 2 (register-resident chain) needs a compiled grouped 3-layer shape, "
+                                           "cnt + workspace and, for more than 13 feature channels, 16-byte bf16 feature rows");
+    SAD_REQUIRE((uintptr_t)a->workspace % 16 == 0, "sad_mlp_chain_bf16: workspace must be 16-byte aligned");
+    SAD_REQUIRE(!vec || (uintptr_t)a->feat % 16 == 0, "sad_mlp_chain_bf16: feat must be 16-byte aligned");
+    SAD_REQUIRE((long long)a->B * a->M < (long long)sad::CONT_BIT, "sad_mlp_chain_bf16: too many groups");
+    SAD_REQUIRE((long long)a->B * a->N < (1LL << 31), "sad_mlp_chain_bf16: B*N too large");
+    const int ngroups = a->B * a->M;
+    prep.scan = sad::make_scan_job(a->cnt, ngroups, a->S, 32, (int *)a->workspace, 0, a->idx, a->N, a->M);
+    if (a->out_bf16) {
+        // split pooling: bf16 rows + continuation rows, plain stores only (nothing to zero; the table must come from a split scan:
+        // this dispatch's own, or sad_mlp_rowscan_split)
+        SAD_REQUIRE(a->dims[3] % 8 == 0 && a->ld_out % 8 == 0 && a->col_off % 8 == 0 && (uintptr_t)a->out % 16 == 0 && (uintptr_t)a->cont % 16 == 0,
+                    "sad_mlp_chain_bf16: split pooling needs cout, ld_out and col_off multiples of 8 and 16-byte aligned out / cont");
+        SAD_REQUIRE(sad_mlp_cont_bytes(a->B, a->M, a->S, a->dims[3]) < (1ull << 32), "sad_mlp_chain_bf16: continuation buffer of %zu bytes (limit 4 GB)",
+                    sad_mlp_cont_bytes(a->B, a->M, a->S, a->dims[3]));
+        prep.scan.split = 1;
+        prep.scan.cont0 = a->cont;
+        prep.scan.cont_cols = a->dims[3];
+    } else {
+        sad::scan_zero_fill(prep.scan, (float *)a->out, a->ld_out, a->col_off, a->dims[a->L]);
     }
-    const bool packed = grouped && a->cnt && a->workspace;
+    sad::BfRegChain &rc = prep.rc;
+    rc = sad::BfRegChain{};
+    rc.xyz = a->xyz; rc.new_xyz = a->new_xyz; rc.feat = a->feat; rc.feat_bf16 = a->feat_bf16; rc.ld_feat = a->ld_feat; rc.C = a->C;
+    const unsigned char *packed = (const unsigned char *)a->packed;
+    LayerImage im[3];
+    rc.stream = packed + layer_images(3, a->dims, im);
+    for (int l = 0; l < 3; ++l) {
+        rc.bias[l] = (const float *)(packed + im[l].bias);
+        rc.np[l] = im[l].CT * 32;
+    }
+    rc.out = (float *)a->out; rc.ld_out = a->ld_out; rc.col_off = a->col_off; rc.cout_last = a->dims[3];
+    rc.rowtab = prep.scan.tab; rc.row_src = prep.scan.row_src; rc.row_gid = prep.scan.row_gid;
+    rc.out_bf16 = a->out_bf16 ? 1 : 0; rc.cont = a->cont; rc.ld_cont = a->dims[3];
+    prep.kind = BF_REG;
+    prep.reg_shape = shape;
+    prep.reg_tiles = ((long long)ngroups * a->S + 31) / 32;
+    return SAD_OK;
+}
+
+// The tiled kernel of this file: tile size (geometry = forced rows per tile, for autotuners: 32 / 64 / 128 / 256); launches the row-packing
+// scan itself when the chain comes with counts and a workspace.
+static int prepare_bf16_tiled(const sad_mlp_bf16_args *a, sad_stream_t stream, BfParams &p, BfPrepared &prep) {
+    const bool packed = a->idx && a->cnt && a->workspace;
     if (packed) {
         SAD_REQUIRE((uintptr_t)a->workspace % 16 == 0, "sad_mlp_chain_bf16: workspace must be 16-byte aligned");
         SAD_REQUIRE((long long)a->B * a->M < (1LL << 30) && p.rows < (1LL << 31), "sad_mlp_chain_bf16: too many groups");
         p.ngroups = a->B * a->M;
     }
-    const unsigned char *q = (const unsigned char *)a->packed;
+    LayerImage im[SAD_MAX_LAYERS];
+    layer_images(a->L, a->dims, im);
     int ldA = 0, ldB = 0;
     for (int l = 0; l < a->L; ++l) {
-        p.kp[l] = kpad(l, a->dims[l]);
+        p.kp[l] = im[l].kp;
         p.cout[l] = a->dims[l + 1];
-        const int CT = (a->dims[l + 1] + 31) / 32;
-        p.w[l] = (const bf16x8 *)q;
-        q += align16((size_t)CT * 32 * p.kp[l] * 2);
-        p.bias[l] = (const float *)q;
-        q += align16((size_t)CT * 32 * 4);
+        p.w[l] = (const bf16x8 *)((const unsigned char *)a->packed + im[l].w);
+        p.bias[l] = (const float *)((const unsigned char *)a->packed + im[l].bias);
         int &ld = (l & 1) ? ldB : ldA;
         ld = ld > p.kp[l] + 8 ? ld : p.kp[l] + 8;
     }
@@ -684,7 +681,7 @@ static int prepare_bf16(const sad_mlp_bf16_args *a, sad_stream_t stream, BfPrepa
     const size_t budget = 150 * 1024;
     int R = 128;
     auto lds_of = [&](int r) { return (((size_t)r * 2 * (ldA + ldB) + 15) & ~(size_t)15) + (size_t)(2 * r + 4) * sizeof(int); };
-    if (a->geometry) {     // forced rows per tile (autotuners): 32 / 64 / 128 / 256 (2 = the register-resident chain, 3 = the row-streaming layer, above)
+    if (a->geometry) {
         SAD_REQUIRE(a->geometry == 32 || a->geometry == 64 || a->geometry == 128 || a->geometry == 256,
                     "sad_mlp_chain_bf16: geometry (rows per tile) must be 32, 64, 128 or 256");
         R = a->geometry;
@@ -701,8 +698,9 @@ static int prepare_bf16(const sad_mlp_bf16_args *a, sad_stream_t stream, BfPrepa
         p.rowtab = (const int *)a->workspace;
         if (int e = sad::launch_rowscan(a->cnt, p.ngroups, a->S, R, (int *)a->workspace, (hipStream_t)stream, 0,
                                         a->idx, a->N, a->M)) return e;
-        p.row_src = p.rowtab + 4 + ((long long)p.ngroups + 1) + ((long long)p.ngroups * a->S / 32 + 2) + (p.ngroups / 1024 + 2);
-        p.row_gid = p.row_src + (long long)p.ngroups * a->S;
+        const sad::ScanLayout t = sad::scan_layout(p.ngroups, a->S);
+        p.row_src = p.rowtab + t.row_src;
+        p.row_gid = p.rowtab + t.row_gid;
     }
     SAD_REQUIRE(tiles < (1LL << 31), "sad_mlp_chain_bf16: too many rows");
     p.tiles = (int)tiles;
@@ -710,16 +708,41 @@ static int prepare_bf16(const sad_mlp_bf16_args *a, sad_stream_t stream, BfPrepa
     int per_cu = (int)((160 * 1024) / (lds_now > 0 ? lds_now : 1));
     per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
     p.noxcd = sad::get_option(sad::OPT_MLP_NOXCD);
+    prep.kind = BF_TILED;
     prep.p = p;
     prep.lds = lds_now;
     prep.grid = (int)(tiles < 256LL * per_cu ? tiles : 256LL * per_cu);
     return SAD_OK;
 }
 
+// Validation, then the preparer of the kernel that the geometry code and the shape of the call ask for; fills `prep` for the launch.
+static int prepare_bf16(const sad_mlp_bf16_args *a, sad_stream_t stream, BfPrepared &prep) {
+    BfParams p;
+    if (int e = bf16_args(a, p)) return e;
+    prep.prescanned = a->prescanned != 0;
+    if (!a->idx && a->L == 1 && (a->geometry == 0 || a->geometry == 3)) {
+        const size_t esz = a->feat_bf16 ? 2 : 4;
+        if ((a->C & 7) == 0 && ((size_t)a->ld_feat * esz) % 16 == 0 && (uintptr_t)a->feat % 16 == 0) {
+            prepare_bf16_rows(a, p.rows, prep);
+            return SAD_OK;
+        }
+        if (a->n_pool) return sad::fail(SAD_EUNSUPPORTED, "sad_mlp_chain_bf16: split-pooled input rows need C %% 8 == 0 and 16-byte aligned rows");
+        if (a->geometry == 3) return sad::fail(SAD_EUNSUPPORTED, "sad_mlp_chain_bf16: geometry 3 (row-streaming layer) needs C %% 8 == 0 and 16-byte aligned rows");
+    }
+    if (a->geometry == 2) return prepare_bf16_reg(a, prep);
+    return prepare_bf16_tiled(a, stream, p, prep);
+}
+
 static void bf16_attrs() {
     static std::atomic<uint64_t> attr_done1{0}, attr_done2{0};
     sad::lds_attr_once(attr_done1, reinterpret_cast<const void *>(&mlp_bf16_kernel), 160 * 1024);
     sad::lds_attr_once(attr_done2, reinterpret_cast<const void *>(&mlp_bf16_multi_kernel), 160 * 1024);
+}
+
+static int launch_bf16_tiled(const BfPrepared &q, hipStream_t st) {
+    bf16_attrs();
+    hipLaunchKernelGGL(mlp_bf16_kernel, dim3(q.grid), dim3(BF_T), q.lds, st, q.p);
+    return sad::check_launch("sad_mlp_chain_bf16");
 }
 
 // register-resident chains of one shape family (<= REG_MAX_CHAINS): pending scans in one pair of launches, then one dispatch
@@ -740,17 +763,16 @@ static int launch_bfreg_chains(const BfPrepared *const *qs, int n, hipStream_t s
     return sad::launch_bfreg(mp, st);
 }
 
+static int launch_bf16_prepared(const BfPrepared &q, hipStream_t st) {
+    const BfPrepared *one = &q;
+    if (q.kind == BF_ROWS) return sad::launch_bf16_rows(q.rj, st);
+    return q.kind == BF_REG ? launch_bfreg_chains(&one, 1, st) : launch_bf16_tiled(q, st);
+}
+
 SAD_API int sad_mlp_chain_bf16(const sad_mlp_bf16_args *a, sad_stream_t stream) {
     BfPrepared q;
     if (int e = prepare_bf16(a, stream, q)) return e;
-    if (q.rows) return sad::launch_bf16_rows(q.rj, (hipStream_t)stream);
-    if (q.reg) {
-        const BfPrepared *one = &q;
-        return launch_bfreg_chains(&one, 1, (hipStream_t)stream);
-    }
-    bf16_attrs();
-    hipLaunchKernelGGL(mlp_bf16_kernel, dim3(q.grid), dim3(BF_T), q.lds, (hipStream_t)stream, q.p);
-    return sad::check_launch("sad_mlp_chain_bf16");
+    return launch_bf16_prepared(q, (hipStream_t)stream);
 }
 
 SAD_API int sad_mlp_chain_multi_bf16(const sad_mlp_bf16_args *const *args, int n, sad_stream_t stream) {
@@ -760,56 +782,46 @@ SAD_API int sad_mlp_chain_multi_bf16(const sad_mlp_bf16_args *const *args, int n
             if (int e = sad_mlp_chain_multi_bf16(args + i, n - i < BF_MULTI_MAX ? n - i : BF_MULTI_MAX, stream)) return e;
         return SAD_OK;
     }
+    hipStream_t st = (hipStream_t)stream;
     BfPrepared q[BF_MULTI_MAX];
-    for (int i = 0; i < n; ++i)
+    bool all_tiled = true;
+    for (int i = 0; i < n; ++i) {
         if (int e = prepare_bf16(args[i], stream, q[i])) return e;
-    {   // register-resident chains: one dispatch per shape family, heaviest chain first
-        bool any_reg = false;
-        for (int i = 0; i < n; ++i) any_reg = any_reg || q[i].reg || q[i].rows;
-        if (any_reg) {
-            bool done[BF_MULTI_MAX] = {};
-            for (int i = 0; i < n; ++i) {
-                if (done[i]) continue;
-                if (q[i].rows) {
-                    if (int e = sad::launch_bf16_rows(q[i].rj, (hipStream_t)stream)) return e;
-                    done[i] = true;
-                    continue;
-                }
-                if (!q[i].reg) {
-                    bf16_attrs();
-                    hipLaunchKernelGGL(mlp_bf16_kernel, dim3(q[i].grid), dim3(BF_T), q[i].lds, (hipStream_t)stream, q[i].p);
-                    if (int e = sad::check_launch("sad_mlp_chain_bf16")) return e;
-                    done[i] = true;
-                    continue;
-                }
-                const BfPrepared *ord[sad::REG_MAX_CHAINS];
-                int m = 0;
-                for (int k = i; k < n && m < sad::REG_MAX_CHAINS; ++k)
-                    if (!done[k] && q[k].reg && sad::bfreg_family(q[k].reg_shape) == sad::bfreg_family(q[i].reg_shape)) { ord[m++] = &q[k]; done[k] = true; }
-                auto heavy = [](const BfPrepared *s) { return (double)sad::bfreg_stream_frags(s->reg_shape) * (double)s->reg_tiles; };
-                for (int x = 0; x < m; ++x)
-                    for (int y = x + 1; y < m; ++y)
-                        if (heavy(ord[y]) > heavy(ord[x])) { const BfPrepared *t = ord[x]; ord[x] = ord[y]; ord[y] = t; }
-                if (int e = launch_bfreg_chains(ord, m, (hipStream_t)stream)) return e;
-            }
-            return SAD_OK;
-        }
+        all_tiled = all_tiled && q[i].kind == BF_TILED;
     }
-    bf16_attrs();
-    if (n == 1) {
-        hipLaunchKernelGGL(mlp_bf16_kernel, dim3(q[0].grid), dim3(BF_T), q[0].lds, (hipStream_t)stream, q[0].p);
-        return sad::check_launch("sad_mlp_chain_bf16");
-    }
+    double weight[BF_MULTI_MAX];
     int order[BF_MULTI_MAX];
-    for (int i = 0; i < n; ++i) order[i] = i;
-    auto weight = [&](int i) {
+    if (!all_tiled || n == 1) {
+        // in argument order: every other chain on its own, register-resident chains one dispatch per shape family, heaviest chain first
+        bool done[BF_MULTI_MAX] = {};
+        for (int i = 0; i < n; ++i) {
+            if (done[i]) continue;
+            if (q[i].kind != BF_REG) {
+                if (int e = launch_bf16_prepared(q[i], st)) return e;
+                continue;
+            }
+            const BfPrepared *fam[sad::REG_MAX_CHAINS], *ord[sad::REG_MAX_CHAINS];
+            int m = 0;
+            for (int k = i; k < n && m < sad::REG_MAX_CHAINS; ++k)
+                if (!done[k] && q[k].kind == BF_REG && sad::bfreg_family(q[k].reg_shape) == sad::bfreg_family(q[i].reg_shape)) {
+                    weight[m] = (double)sad::bfreg_stream_frags(q[k].reg_shape) * (double)q[k].reg_tiles;
+                    fam[m++] = &q[k];
+                    done[k] = true;
+                }
+            sad::heaviest_first(weight, m, order);
+            for (int x = 0; x < m; ++x) ord[x] = fam[order[x]];
+            if (int e = launch_bfreg_chains(ord, m, st)) return e;
+        }
+        return SAD_OK;
+    }
+    // tiled chains: one dispatch, heaviest first
+    bf16_attrs();
+    for (int i = 0; i < n; ++i) {
         double m = 0;
         for (int l = 0; l < q[i].p.L; ++l) m += (double)q[i].p.kp[l] * q[i].p.cout[l];
-        return m * (double)q[i].p.rows;
-    };
-    for (int i = 0; i < n; ++i)
-        for (int k = i + 1; k < n; ++k)
-            if (weight(order[k]) > weight(order[i])) { const int t = order[i]; order[i] = order[k]; order[k] = t; }
+        weight[i] = m * (double)q[i].p.rows;
+    }
+    sad::heaviest_first(weight, n, order);
     BfMultiParams mp{};
     mp.n = n;
     size_t lds = 0;
@@ -821,6 +833,6 @@ SAD_API int sad_mlp_chain_multi_bf16(const sad_mlp_bf16_args *const *args, int n
         lds = q[order[i]].lds > lds ? q[order[i]].lds : lds;
     }
     mp.first[n] = (int)total;
-    hipLaunchKernelGGL(mlp_bf16_multi_kernel, dim3((unsigned)total), dim3(BF_T), lds, (hipStream_t)stream, mp);
+    hipLaunchKernelGGL(mlp_bf16_multi_kernel, dim3((unsigned)total), dim3(BF_T), lds, st, mp);
     return sad::check_launch("sad_mlp_chain_multi_bf16");
 }

@@ -175,19 +175,17 @@ __global__ __launch_bounds__(SCAN_T) void rowscan_write_kernel(const sad::ScanMu
 }  // namespace
 
 namespace sad {
-// Fills a ScanJob for one chain (table layout: see sad_mlp_workspace_bytes).
+// Fills a ScanJob for one chain (table layout: ScanLayout, common.h).
 ScanJob make_scan_job(const int32_t *cnt, int ngroups, int S, int R, int *tab, int nodedup, const int32_t *idx, int N, int M) {
     ScanJob jb{};
     jb.cnt = cnt; jb.idx = idx; jb.tab = tab; jb.ngroups = ngroups; jb.S = S; jb.N = N; jb.M = M; jb.nodedup = nodedup; jb.R = R;
-    // layout (ints): hdr[4] | row_start[ngroups+1] (item queues in its first 258 ints, else unused) | pass_first[ngroups*S/32+2]
-    //                (holds the block sums: ngroups/256 + 1 of them) | [ngroups/1024+2] (unused: the block sums of 1 024-group
-    //                blocks lived here) | row map: src[ngroups*S] | gid[ngroups*S]   (only written when idx != NULL)
-    jb.blk_sum = tab + 4 + (ngroups + 1);
+    const ScanLayout t = scan_layout(ngroups, S);
+    jb.blk_sum = tab + t.blk_sum;
     if (idx) {
-        jb.row_src = tab + 4 + (ngroups + 1) + ((long long)ngroups * S / 32 + 2) + (ngroups / 1024 + 2);
-        jb.row_gid = jb.row_src + (long long)ngroups * S;
+        jb.row_src = tab + t.row_src;
+        jb.row_gid = tab + t.row_gid;
     }
-    jb.gstart = tab + scan_gstart_off(ngroups, S);      // (written by a split-pooling scan only)
+    jb.gstart = tab + t.gstart;
     return jb;
 }
 
@@ -217,59 +215,55 @@ int launch_rowscan(const int32_t *cnt, int ngroups, int S, int R, int *tab, hipS
 }
 }  // namespace sad
 
+// The three sad_mlp_rowscan* entry points: the plain scan, the scan that also zero-fills the chains' output slices, and the split-pooling scan.
+enum ScanKind { SCAN_PLAIN, SCAN_INIT, SCAN_SPLIT };
+struct ScanArgs {                   // what they take; `fn` below: the one called, for the messages
+    int n; const int32_t *const *cnt, *const *idx; const int *S; int B, N, M; void *const *workspace;
+    float *const *out; const int *ld_out, *col_off;    // SCAN_INIT only: output slices [B*M][ld_out], columns col_off .. col_off + cout - 1
+    void *const *cont;              // SCAN_SPLIT only: continuation buffers, cout columns wide
+    const int *cout;                // SCAN_INIT and SCAN_SPLIT
+};
+static int rowscan_entry(const char *fn, ScanKind kind, const ScanArgs &a, sad_stream_t stream) {
+    const bool arrays = a.cnt && a.idx && a.S && a.workspace && (kind != SCAN_INIT || (a.out && a.ld_out && a.col_off && a.cout)) && (kind != SCAN_SPLIT || (a.cont && a.cout));
+    SAD_REQUIRE(a.n >= 1 && a.n <= sad::SCAN_MAX_CHAINS && arrays, "%s: need 1..%d chains and non-NULL arrays", fn, sad::SCAN_MAX_CHAINS);
+    const long long max_groups = kind == SCAN_SPLIT ? (long long)sad::CONT_BIT : 1LL << 30;      // (a split row map keeps CONT_BIT beside the group)
+    SAD_REQUIRE(a.B >= 1 && a.N >= 1 && a.M >= 1 && (long long)a.B * a.M < max_groups, "%s: bad B/N/M", fn);
+    sad::ScanJob jobs[sad::SCAN_MAX_CHAINS];
+    for (int i = 0; i < a.n; ++i) {
+        SAD_REQUIRE(a.cnt[i] && a.idx[i] && a.workspace[i] && a.S[i] >= 1 && a.S[i] <= 64, "%s: chain %d: NULL pointer or bad nsample", fn, i);
+        SAD_REQUIRE((uintptr_t)a.workspace[i] % 16 == 0, "%s: workspace must be 16-byte aligned", fn);
+        SAD_REQUIRE((long long)a.B * a.M * a.S[i] < (1LL << 31), "%s: B*M*S too large", fn);
+        if (kind == SCAN_INIT)
+            SAD_REQUIRE(a.out[i] && a.cout[i] >= 1 && a.col_off[i] >= 0 && a.ld_out[i] >= a.col_off[i] + a.cout[i],
+                        "%s: chain %d: need out != NULL and col_off + cout <= ld_out", fn, i);
+        if (kind == SCAN_SPLIT)
+            SAD_REQUIRE(a.cont[i] && (uintptr_t)a.cont[i] % 16 == 0 && a.cout[i] >= 8 && a.cout[i] % 8 == 0,
+                        "%s: chain %d: need a 16-byte aligned continuation buffer and cout %% 8 == 0", fn, i);
+        jobs[i] = sad::make_scan_job(a.cnt[i], a.B * a.M, a.S[i], 32, (int *)a.workspace[i], kind == SCAN_SPLIT ? 0 : sad::get_option(sad::OPT_MLP_NODEDUP), a.idx[i], a.N, a.M);
+        if (kind == SCAN_INIT) sad::scan_zero_fill(jobs[i], a.out[i], a.ld_out[i], a.col_off[i], a.cout[i]);
+        if (kind == SCAN_SPLIT) { jobs[i].split = 1; jobs[i].cont0 = a.cont[i]; jobs[i].cont_cols = a.cout[i]; }
+    }
+    return sad::launch_rowscan_multi(jobs, a.n, (hipStream_t)stream);
+}
+
 SAD_API int sad_mlp_rowscan(int n, const int32_t *const *cnt, const int32_t *const *idx, const int *S, int B, int N,
                             int M, void *const *workspace, sad_stream_t stream) {
-    SAD_REQUIRE(n >= 1 && n <= sad::SCAN_MAX_CHAINS && cnt && idx && S && workspace, "sad_mlp_rowscan: need 1..%d chains and non-NULL arrays", sad::SCAN_MAX_CHAINS);
-    SAD_REQUIRE(B >= 1 && N >= 1 && M >= 1 && (long long)B * M < (1LL << 30), "sad_mlp_rowscan: bad B/N/M");
-    sad::ScanJob jobs[sad::SCAN_MAX_CHAINS];
-    for (int i = 0; i < n; ++i) {
-        SAD_REQUIRE(cnt[i] && idx[i] && workspace[i] && S[i] >= 1 && S[i] <= 64, "sad_mlp_rowscan: chain %d: NULL pointer or bad nsample", i);
-        SAD_REQUIRE((uintptr_t)workspace[i] % 16 == 0, "sad_mlp_rowscan: workspace must be 16-byte aligned");
-        SAD_REQUIRE((long long)B * M * S[i] < (1LL << 31), "sad_mlp_rowscan: B*M*S too large");
-        jobs[i] = sad::make_scan_job(cnt[i], B * M, S[i], 32, (int *)workspace[i], sad::get_option(sad::OPT_MLP_NODEDUP), idx[i], N, M);
-    }
-    return sad::launch_rowscan_multi(jobs, n, (hipStream_t)stream);
+    return rowscan_entry("sad_mlp_rowscan", SCAN_PLAIN, ScanArgs{n, cnt, idx, S, B, N, M, workspace}, stream);
 }
 
 SAD_API int sad_mlp_rowscan_init(int n, const int32_t *const *cnt, const int32_t *const *idx, const int *S, int B, int N,
                                  int M, void *const *workspace, float *const *out, const int *ld_out, const int *col_off,
                                  const int *cout, sad_stream_t stream) {
-    SAD_REQUIRE(n >= 1 && n <= sad::SCAN_MAX_CHAINS && cnt && idx && S && workspace && out && ld_out && col_off && cout,
-                "sad_mlp_rowscan_init: need 1..%d chains and non-NULL arrays", sad::SCAN_MAX_CHAINS);
-    SAD_REQUIRE(B >= 1 && N >= 1 && M >= 1 && (long long)B * M < (1LL << 30), "sad_mlp_rowscan_init: bad B/N/M");
-    sad::ScanJob jobs[sad::SCAN_MAX_CHAINS];
-    for (int i = 0; i < n; ++i) {
-        SAD_REQUIRE(cnt[i] && idx[i] && workspace[i] && S[i] >= 1 && S[i] <= 64, "sad_mlp_rowscan_init: chain %d: NULL pointer or bad nsample", i);
-        SAD_REQUIRE((uintptr_t)workspace[i] % 16 == 0, "sad_mlp_rowscan_init: workspace must be 16-byte aligned");
-        SAD_REQUIRE((long long)B * M * S[i] < (1LL << 31), "sad_mlp_rowscan_init: B*M*S too large");
-        SAD_REQUIRE(out[i] && cout[i] >= 1 && col_off[i] >= 0 && ld_out[i] >= col_off[i] + cout[i],
-                    "sad_mlp_rowscan_init: chain %d: need out != NULL and col_off + cout <= ld_out", i);
-        jobs[i] = sad::make_scan_job(cnt[i], B * M, S[i], 32, (int *)workspace[i], sad::get_option(sad::OPT_MLP_NODEDUP), idx[i], N, M);
-        jobs[i].zout = out[i] + col_off[i];
-        jobs[i].zld = ld_out[i];
-        jobs[i].zcols = cout[i];
-    }
-    return sad::launch_rowscan_multi(jobs, n, (hipStream_t)stream);
+    ScanArgs a{n, cnt, idx, S, B, N, M, workspace};
+    a.out = out; a.ld_out = ld_out; a.col_off = col_off; a.cout = cout;
+    return rowscan_entry("sad_mlp_rowscan_init", SCAN_INIT, a, stream);
 }
 
 SAD_API int sad_mlp_rowscan_split(int n, const int32_t *const *cnt, const int32_t *const *idx, const int *S, int B, int N,
                                   int M, void *const *workspace, void *const *cont, const int *cout, sad_stream_t stream) {
-    SAD_REQUIRE(n >= 1 && n <= sad::SCAN_MAX_CHAINS && cnt && idx && S && workspace && cont && cout,
-                "sad_mlp_rowscan_split: need 1..%d chains and non-NULL arrays", sad::SCAN_MAX_CHAINS);
-    SAD_REQUIRE(B >= 1 && N >= 1 && M >= 1 && (long long)B * M < (long long)sad::CONT_BIT, "sad_mlp_rowscan_split: bad B/N/M");
-    sad::ScanJob jobs[sad::SCAN_MAX_CHAINS];
-    for (int i = 0; i < n; ++i) {
-        SAD_REQUIRE(cnt[i] && idx[i] && workspace[i] && S[i] >= 1 && S[i] <= 64, "sad_mlp_rowscan_split: chain %d: NULL pointer or bad nsample", i);
-        SAD_REQUIRE((uintptr_t)workspace[i] % 16 == 0, "sad_mlp_rowscan_split: workspace must be 16-byte aligned");
-        SAD_REQUIRE((long long)B * M * S[i] < (1LL << 31), "sad_mlp_rowscan_split: B*M*S too large");
-        SAD_REQUIRE(cont[i] && (uintptr_t)cont[i] % 16 == 0 && cout[i] >= 8 && cout[i] % 8 == 0,
-                    "sad_mlp_rowscan_split: chain %d: need a 16-byte aligned continuation buffer and cout %% 8 == 0", i);
-        jobs[i] = sad::make_scan_job(cnt[i], B * M, S[i], 32, (int *)workspace[i], 0, idx[i], N, M);
-        jobs[i].split = 1;
-        jobs[i].cont0 = cont[i];
-        jobs[i].cont_cols = cout[i];
-    }
-    return sad::launch_rowscan_multi(jobs, n, (hipStream_t)stream);
+    ScanArgs a{n, cnt, idx, S, B, N, M, workspace};
+    a.cont = cont; a.cout = cout;
+    return rowscan_entry("sad_mlp_rowscan_split", SCAN_SPLIT, a, stream);
 }
 
 SAD_API size_t sad_mlp_cont_bytes(int B, int M, int S, int cout) {
@@ -280,7 +274,5 @@ SAD_API size_t sad_mlp_cont_bytes(int B, int M, int S, int cout) {
 
 SAD_API size_t sad_mlp_workspace_bytes(int B, int M, int S) {
     if (B < 1 || M < 1 || S < 1) return 0;
-    const size_t ng = (size_t)B * M;
-    // hdr, row_start, pass_first (R >= 32), block sums of the two-launch scan, row map, first packed row of every group (split pooling)
-    return sizeof(int) * ((size_t)sad::scan_gstart_off((long long)ng, S) + ng + 1) + 64;
+    return sizeof(int) * (size_t)sad::scan_layout(B * (long long)M, S).ints + 64;
 }

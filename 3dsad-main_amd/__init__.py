@@ -25,6 +25,8 @@ _LAZY = {
     "voxel_decorate": "ops", "voxel_encode": "ops",
     "anchor_decode": "ops", "center_decode": "ops", "anchor_grid": "dense_head",
     "AnchorHeadDecoder": "dense_head", "CenterHeadDecoder": "dense_head",
+    "anchor_targets": "ops", "center_targets": "ops",
+    "AnchorTargetAssigner": "dense_head", "CenterTargetAssigner": "dense_head",
     "Voxelization": "voxel", "DynamicScatter": "voxel", "PillarFeatureNet": "voxel",
     "sparse_conv_index": "ops", "sparse_conv": "ops", "sparse_to_dense": "ops", "PackedSparseWeight": "ops",
     "sparse_conv_index_transpose": "ops", "sparse_conv_grad_weight": "ops", "sparse_conv_grad_input": "ops",

@@ -91,6 +91,34 @@ class CenterDecodeArgs(ctypes.Structure):
     ]
 
 
+class AnchorTargetsArgs(ctypes.Structure):
+    """``struct sad_anchor_targets_args`` (include/sad_amd.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("gt_boxes", vp), ("gt_labels", vp),
+        ("B", ctypes.c_int), ("G", ctypes.c_int), ("D", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
+        ("ns", ctypes.c_int), ("nr", ctypes.c_int), ("nb", ctypes.c_int), ("use_size_class", ctypes.c_int),
+        ("sizes", ctypes.c_float * 48), ("z_center", ctypes.c_float * 16), ("rotations", ctypes.c_float * 8),
+        ("pos_thr", ctypes.c_float * 16), ("neg_thr", ctypes.c_float * 16), ("size_class", ctypes.c_int32 * 16),
+        ("x0", ctypes.c_float), ("y0", ctypes.c_float), ("sx", ctypes.c_float), ("sy", ctypes.c_float),
+        ("dir_offset", ctypes.c_float),
+        ("labels", vp), ("match", vp), ("reg_target", vp), ("max_iou", vp), ("dir_target", vp), ("workspace", vp),
+    ]
+
+
+class CenterTargetsArgs(ctypes.Structure):
+    """``struct sad_center_targets_args`` (include/sad_amd.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("gt_boxes", vp), ("gt_labels", vp),
+        ("B", ctypes.c_int), ("G", ctypes.c_int), ("D", ctypes.c_int), ("C", ctypes.c_int), ("H", ctypes.c_int),
+        ("W", ctypes.c_int), ("layout", ctypes.c_int), ("min_radius", ctypes.c_int), ("vel", ctypes.c_int),
+        ("lo_x", ctypes.c_float), ("lo_y", ctypes.c_float), ("sx", ctypes.c_float), ("sy", ctypes.c_float),
+        ("min_overlap", ctypes.c_float),
+        ("heatmap", vp), ("ind", vp), ("anno", vp),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/sad_amd.h declares
 SIGNATURES = {
     "sad_version": (ctypes.c_int, []),
@@ -189,6 +217,9 @@ SIGNATURES = {
     "sad_decode_boxes_f32": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, c_f32p, vp, vp]),
     "sad_anchor_decode_f32": (ctypes.c_int, [ctypes.POINTER(AnchorDecodeArgs), vp]),
     "sad_center_decode_f32": (ctypes.c_int, [ctypes.POINTER(CenterDecodeArgs), vp]),
+    "sad_anchor_targets_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "sad_anchor_targets_f32": (ctypes.c_int, [ctypes.POINTER(AnchorTargetsArgs), vp]),
+    "sad_center_targets_f32": (ctypes.c_int, [ctypes.POINTER(CenterTargetsArgs), vp]),
 }
 
 _lib = None

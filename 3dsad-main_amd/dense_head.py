@@ -1,6 +1,9 @@
 """Dense BEV heads (SPEC.md §25): the raw maps of an anchor head (SECOND, PointPillars, PV-RCNN's RPN) or a centre head
 (CenterPoint) -> ``(boxes, scores, labels)``, and on through ``ops.nms_boxes``.  The 2-D convolutions that produce the maps
-are torch's; these modules hold the decode configuration only and have no parameters.  Inference only."""
+are torch's; these modules hold the decode configuration only and have no parameters.  Inference only.
+
+The way back (SPEC.md §26): ``AnchorTargetAssigner`` / ``CenterTargetAssigner`` turn ground-truth boxes into what such a head
+is trained against, from the same configuration (``decoder.assigner(...)``).  No gradients: the losses are torch's."""
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -51,6 +54,11 @@ class AnchorHeadDecoder(nn.Module):
                                  origin=self.origin, step=self.step, dir_offset=self.dir_offset,
                                  dir_limit_offset=self.dir_limit_offset, layout=self.layout, index=index)
 
+    def assigner(self, pos_thr, neg_thr, size_class=None, nb: int = 0) -> "AnchorTargetAssigner":
+        """The target assigner on this decoder's anchors."""
+        return AnchorTargetAssigner(self.sizes, self.z_center, self.rotations, self.origin, self.step, pos_thr, neg_thr, size_class,
+                                    nb=nb, dir_offset=self.dir_offset)
+
     def predict(self, cls: torch.Tensor, reg: torch.Tensor, dir: Optional[torch.Tensor] = None, *, iou_thr: float,
                 score_thr: float = 0.0, pre_max: Optional[int] = None, post_max: Optional[int] = None, class_aware: bool = True):
         """(boxes [B,K,7], scores, labels, order [B,P], count [B]): the decode, then ``ops.nms_boxes`` on its three tensors.
@@ -71,7 +79,53 @@ class CenterHeadDecoder(nn.Module):
         return ops.center_decode(hm, reg, height, dim, rot, vel, origin=self.origin, cell=self.cell, log_dim=self.log_dim,
                                  peak=self.peak, layout=self.layout, index=index)
 
+    def assigner(self, C: int, min_overlap: float = 0.1, min_radius: int = 2, vel: bool = False) -> "CenterTargetAssigner":
+        """The target assigner on this decoder's map geometry (C classes of the task)."""
+        return CenterTargetAssigner(C, self.origin, self.cell, min_overlap, min_radius, vel, self.layout)
+
     def predict(self, hm, reg, height, dim, rot, vel=None, *, iou_thr: float, score_thr: float = 0.0,
                 pre_max: Optional[int] = None, post_max: Optional[int] = None, class_aware: bool = True):
         """(boxes [B,K,D], scores, labels, order [B,P], count [B]) as ``AnchorHeadDecoder.predict``."""
         return _predict(*self.forward(hm, reg, height, dim, rot, vel), iou_thr, score_thr, pre_max, post_max, class_aware)
+
+
+class AnchorTargetAssigner(nn.Module):
+    """Target assignment of an anchor head (``ops.anchor_targets``): the anchor fields of ``AnchorHeadDecoder`` plus
+    ``pos_thr`` / ``neg_thr`` (a scalar or one per size) and ``size_class`` (the class each size is matched against; ``None``:
+    class-agnostic).  ``nb`` >= 2 adds the direction-bin target."""
+
+    def __init__(self, sizes, z_center, rotations, origin, step, pos_thr, neg_thr, size_class=None, nb: int = 0,
+                 dir_offset: float = 0.78539):
+        super().__init__()
+        self.sizes = np.asarray(sizes, dtype=np.float32).reshape(-1, 3)
+        self.z_center = np.asarray(z_center, dtype=np.float32).reshape(-1)
+        self.rotations = np.asarray(rotations, dtype=np.float32).reshape(-1)
+        self.origin, self.step = (float(origin[0]), float(origin[1])), (float(step[0]), float(step[1]))
+        self.pos_thr, self.neg_thr, self.size_class = pos_thr, neg_thr, size_class
+        self.nb, self.dir_offset = int(nb), float(dir_offset)
+
+    @property
+    def num_anchors(self) -> int:
+        return self.sizes.shape[0] * self.rotations.shape[0]
+
+    def forward(self, gt_boxes: torch.Tensor, gt_labels: torch.Tensor, H: int, W: int, out: Optional[tuple] = None) -> tuple:
+        """(labels, match, reg_target, max_iou[, dir_target]) for a feature map of H x W cells."""
+        return ops.anchor_targets(gt_boxes, gt_labels, H=H, W=W, sizes=self.sizes, z_center=self.z_center, rotations=self.rotations,
+                                  origin=self.origin, step=self.step, pos_thr=self.pos_thr, neg_thr=self.neg_thr,
+                                  size_class=self.size_class, nb=self.nb, dir_offset=self.dir_offset, out=out)
+
+
+class CenterTargetAssigner(nn.Module):
+    """Target assignment of one task of a centre head (``ops.center_targets``): ``origin`` / ``cell`` / ``layout`` as
+    ``CenterHeadDecoder``, ``C`` classes."""
+
+    def __init__(self, C: int, origin, cell, min_overlap: float = 0.1, min_radius: int = 2, vel: bool = False, layout: str = "nchw"):
+        super().__init__()
+        self.C = int(C)
+        self.origin, self.cell = (float(origin[0]), float(origin[1])), (float(cell[0]), float(cell[1]))
+        self.min_overlap, self.min_radius, self.vel, self.layout = float(min_overlap), int(min_radius), bool(vel), layout
+
+    def forward(self, gt_boxes: torch.Tensor, gt_labels: torch.Tensor, H: int, W: int, out: Optional[tuple] = None):
+        """(heatmap, ind, anno) for a map of H x W cells."""
+        return ops.center_targets(gt_boxes, gt_labels, C=self.C, H=H, W=W, origin=self.origin, cell=self.cell,
+                                  min_overlap=self.min_overlap, min_radius=self.min_radius, vel=self.vel, layout=self.layout, out=out)

@@ -1316,6 +1316,153 @@ def center_decode(hm: torch.Tensor, reg: torch.Tensor, height: torch.Tensor, dim
     return boxes, scores, labels
 
 
+def _gt_inputs(gt_boxes: torch.Tensor, gt_labels: torch.Tensor, min_d: int = 7) -> Tuple[int, int, int, torch.device]:
+    """(B, G, D, device) of gt_boxes [B,G,D] f32 / gt_labels [B,G] int32, both contiguous on the current GPU."""
+    for t, name, dt in ((gt_boxes, "gt_boxes", torch.float32), (gt_labels, "gt_labels", torch.int32)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: expected a torch.Tensor")
+        if t.dtype != dt:
+            raise TypeError(f"{name}: expected dtype {dt}, got {t.dtype}")
+    if gt_boxes.dim() != 3 or gt_boxes.shape[0] < 1 or gt_boxes.shape[2] < min_d:
+        raise ValueError(f"gt_boxes: expected [B,G,D] with B >= 1 and D >= {min_d}, got {tuple(gt_boxes.shape)}")
+    B, G, D = gt_boxes.shape
+    if tuple(gt_labels.shape) != (B, G):
+        raise ValueError(f"gt_labels: expected shape {(B, G)}, got {tuple(gt_labels.shape)}")
+    if G > 1024:
+        raise ValueError(f"gt_boxes: at most 1024 boxes per scene (got G = {G})")
+    if not gt_boxes.is_contiguous() or not gt_labels.is_contiguous():
+        raise ValueError("gt_boxes / gt_labels: must be contiguous")
+    return B, G, D, _head_devices((("gt_boxes", gt_boxes), ("gt_labels", gt_labels)))
+
+
+def _target_outputs(spec, out: Optional[tuple], dev) -> tuple:
+    """Buffers of a target call.  ``spec`` = ((name, shape, dtype), ...); ``out`` checked against it, or new buffers."""
+    if out is None:
+        return tuple(_empty(shape, dtype=dt, device=dev) for _, shape, dt in spec)
+    ok = len(out) == len(spec) and all(isinstance(t, torch.Tensor) and tuple(t.shape) == tuple(shape) and t.dtype == dt
+                                       and t.is_contiguous() and t.device == dev for t, (_, shape, dt) in zip(out, spec))
+    if not ok:
+        want = ", ".join(f"{n} {list(shape)} {str(dt).replace('torch.', '')}" for n, shape, dt in spec)
+        raise ValueError(f"out: expected contiguous ({want}) on the device of gt_boxes")
+    return tuple(out)
+
+
+def _per_size(v, ns: int, name: str, dtype) -> np.ndarray:
+    a = np.asarray(v, dtype=dtype).reshape(-1)
+    if a.shape[0] == 1 and ns > 1:
+        a = np.repeat(a, ns)
+    if a.shape[0] != ns:
+        raise ValueError(f"{name}: expected one value per anchor size (ns = {ns}), got {a.shape[0]}")
+    return a
+
+
+def anchor_targets_workspace(B: int, G: int, device) -> Optional[torch.Tensor]:
+    """The workspace of ``anchor_targets(..., workspace=...)`` for a caller that keeps it (``None`` when G = 0)."""
+    nbytes = lib().sad_anchor_targets_workspace_bytes(B, G)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
+
+
+def anchor_targets(gt_boxes: torch.Tensor, gt_labels: torch.Tensor, *, H: int, W: int, sizes, z_center, rotations, origin, step,
+                   pos_thr, neg_thr, size_class=None, nb: int = 0, dir_offset: float = 0.78539, out: Optional[tuple] = None,
+                   workspace: Optional[torch.Tensor] = None) -> tuple:
+    """Anchor head target assignment (SPEC.md §26.1), the inverse of ``anchor_decode`` on the same anchor scalars.
+    gt_boxes [B,G,D>=7] f32 rows (cx,cy,cz,l,w,h,yaw,...), gt_labels [B,G] int32 (negative: padding row), G <= 1024 ->
+    (labels [B,K] int32, match [B,K] int32, reg_target [B,K,7], max_iou [B,K][, dir_target [B,K] int32 when nb >= 2]),
+    K = H*W*A, k = (y*W + x)*A + a.  The max-IoU assigner of SECOND / PointPillars on the nearest-BEV IoU: anchor k of size s
+    is positive when its best IoU over the boxes of class ``size_class[s]`` (``None``: of any class) reaches ``pos_thr[s]``, or
+    when it attains some box's best IoU over the scene; background (-1) below ``neg_thr[s]``, else ignored (-2).  A positive
+    gets the class, the index and the residual encoding of its own best box.  Two launches and a memset, no anchor tensor, no
+    IoU matrix, no synchronisation, no gradients, bit-identical from call to call.  ``out``: the tuple to write into."""
+    sizes_np = np.asarray(sizes, dtype=np.float32).reshape(-1, 3)
+    zc = np.asarray(z_center, dtype=np.float32).reshape(-1)
+    rots = np.asarray(rotations, dtype=np.float32).reshape(-1)
+    ns, nr = sizes_np.shape[0], rots.shape[0]
+    if ns < 1 or nr < 1 or zc.shape[0] != ns:
+        raise ValueError(f"sizes [ns,3], z_center [ns], rotations [nr]: need ns, nr >= 1 and one z_center per size (ns = {ns}, "
+                         f"z_center: {zc.shape[0]}, nr = {nr})")
+    if ns > 16 or nr > 8:
+        raise ValueError(f"sizes / rotations: at most 16 sizes and 8 rotations (got {ns}, {nr})")
+    if not (sizes_np > 0).all():
+        raise ValueError("sizes: every anchor extent must be > 0")
+    if H < 1 or W < 1:
+        raise ValueError(f"H, W: need >= 1 (got {H}, {W})")
+    if nb != 0 and not 2 <= nb <= 8:
+        raise ValueError(f"nb: 0 (no direction target) or 2 .. 8 (got {nb})")
+    pos, neg = _per_size(pos_thr, ns, "pos_thr", np.float32), _per_size(neg_thr, ns, "neg_thr", np.float32)
+    sc = None if size_class is None else _per_size(size_class, ns, "size_class", np.int32)
+    B, G, D, dev = _gt_inputs(gt_boxes, gt_labels)
+    A = ns * nr
+    K = H * W * A
+    spec = [("labels", (B, K), torch.int32), ("match", (B, K), torch.int32), ("reg_target", (B, K, 7), torch.float32),
+            ("max_iou", (B, K), torch.float32)]
+    if nb:
+        spec.append(("dir_target", (B, K), torch.int32))
+    outs = _target_outputs(spec, out, dev)
+    nbytes = lib().sad_anchor_targets_workspace_bytes(B, G)
+    if workspace is None and nbytes:
+        workspace = _empty(nbytes, dtype=torch.uint8, device=dev)
+    if nbytes and (not workspace.is_cuda or workspace.device != dev or not workspace.is_contiguous()
+                   or workspace.numel() * workspace.element_size() < nbytes):
+        raise ValueError(f"workspace: expected at least {nbytes} contiguous bytes on {dev}")
+    a = _lib.AnchorTargetsArgs()
+    a.struct_size = ctypes.sizeof(_lib.AnchorTargetsArgs)
+    a.gt_boxes, a.gt_labels = (gt_boxes.data_ptr(), gt_labels.data_ptr()) if G else (None, None)
+    a.B, a.G, a.D, a.H, a.W, a.ns, a.nr, a.nb, a.use_size_class = B, G, D, H, W, ns, nr, nb, int(sc is not None)
+    a.sizes[:3 * ns] = sizes_np.reshape(-1).tolist()
+    a.z_center[:ns] = zc.tolist()
+    a.rotations[:nr] = rots.tolist()
+    a.pos_thr[:ns] = pos.tolist()
+    a.neg_thr[:ns] = neg.tolist()
+    if sc is not None:
+        a.size_class[:ns] = sc.tolist()
+    a.x0, a.y0, a.sx, a.sy = _f32(origin[0]), _f32(origin[1]), _f32(step[0]), _f32(step[1])
+    a.dir_offset = _f32(dir_offset)
+    a.labels, a.match, a.reg_target, a.max_iou = (t.data_ptr() for t in outs[:4])
+    a.dir_target = outs[4].data_ptr() if nb else None
+    a.workspace = workspace.data_ptr() if nbytes else None
+    with _timed("anchor_targets", f"K{K}G{G}"):
+        check(lib().sad_anchor_targets_f32(ctypes.byref(a), _stream()), "sad_anchor_targets_f32")
+    return outs
+
+
+def center_targets(gt_boxes: torch.Tensor, gt_labels: torch.Tensor, *, C: int, H: int, W: int, origin, cell,
+                   min_overlap: float = 0.1, min_radius: int = 2, vel: bool = False, layout: str = "nchw",
+                   out: Optional[tuple] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Centre head target assignment (SPEC.md §26.2, one CenterPoint task), the inverse of ``center_decode``.
+    gt_boxes [B,G,D>=7] f32, gt_labels [B,G] int32 (outside [0, C): padding), G <= 1024 -> (heatmap [B,C,H,W] f32 (``nhwc``:
+    [B,H,W,C]), ind [B,G] int32, anno [B,G,8 | 10] f32).  A box whose centre falls into cell (iy, ix) of the map draws
+    CenterNet's Gaussian of radius max(min_radius, int(gaussian_radius((w, l) in cells, min_overlap))) into the plane of its
+    class (maximum where boxes overlap, centre cell exactly 1); ind = iy*W + ix, anno = (dx, dy, z, log l, log w, log h,
+    sin yaw, cos yaw[, vx, vy]).  A box whose centre lies outside the map, whose l or w is <= 0 or whose label is padding is
+    unassigned: ind -1, anno 0, nothing drawn.  Two launches, every element stored once, no synchronisation, no gradients."""
+    if layout not in _lib.LAYOUTS:
+        raise ValueError(f"layout: expected 'nchw' or 'nhwc', got {layout!r}")
+    if C < 1 or C > 64 or H < 1 or W < 1:
+        raise ValueError(f"C, H, W: need 1 <= C <= 64 and H, W >= 1 (got {C}, {H}, {W})")
+    if not 0.0 < float(min_overlap) < 1.0:
+        raise ValueError(f"min_overlap: expected a value in (0, 1), got {min_overlap}")
+    if not 0 <= int(min_radius) <= 64:
+        raise ValueError(f"min_radius: expected 0 .. 64, got {min_radius}")
+    if not (float(cell[0]) > 0 and float(cell[1]) > 0):
+        raise ValueError(f"cell: must be positive, got {tuple(cell)}")
+    B, G, D, dev = _gt_inputs(gt_boxes, gt_labels, 9 if vel else 7)
+    na = 10 if vel else 8
+    spec = (("heatmap", (B, C, H, W) if layout == "nchw" else (B, H, W, C), torch.float32), ("ind", (B, G), torch.int32),
+            ("anno", (B, G, na), torch.float32))
+    heatmap, ind, anno = _target_outputs(spec, out, dev)
+    a = _lib.CenterTargetsArgs()
+    a.struct_size = ctypes.sizeof(_lib.CenterTargetsArgs)
+    a.gt_boxes, a.gt_labels = (gt_boxes.data_ptr(), gt_labels.data_ptr()) if G else (None, None)
+    a.B, a.G, a.D, a.C, a.H, a.W, a.layout, a.min_radius, a.vel = B, G, D, C, H, W, _lib.LAYOUTS[layout], int(min_radius), int(bool(vel))
+    a.lo_x, a.lo_y, a.sx, a.sy = _f32(origin[0]), _f32(origin[1]), _f32(cell[0]), _f32(cell[1])
+    a.min_overlap = _f32(min_overlap)
+    a.heatmap = heatmap.data_ptr()
+    a.ind, a.anno = (ind.data_ptr(), anno.data_ptr()) if G else (None, None)
+    with _timed("center_targets", f"K{H * W}G{G}"):
+        check(lib().sad_center_targets_f32(ctypes.byref(a), _stream()), "sad_center_targets_f32")
+    return heatmap, ind, anno
+
+
 # The fused MLP chains (PackedMLP / PackedMLPBf16, grouped_multi, rowscan_multi, the autotuner) live in mlp.py; they belong
 # to this operator surface, so their public names are re-exported here (the same objects).
 from .mlp import (GroupedCall, PackedMLP, PackedMLPBf16, check_workspace, choose_stage_assignment, cont_buffer,  # noqa: E402,F401

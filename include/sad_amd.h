@@ -627,6 +627,59 @@ typedef struct sad_center_decode_args {
 } sad_center_decode_args;
 int sad_center_decode_f32(const sad_center_decode_args *args, sad_stream_t stream);
 
+/* SPEC.md §26.  Dense head target assignment: ground-truth boxes -> what a dense head is trained against; the inverse of
+ * §25 with the same anchor scalars, K, k numbering and layouts.  No gradients.  gt_boxes[B,G,D] f32 (D >= 7, rows
+ * (cx,cy,cz,l,w,h,yaw,...)), gt_labels[B,G] int32 (0-based classes; a negative label marks a padding row).
+ * 0 <= G <= 1024 (SAD_EUNSUPPORTED above); with G == 0 the two pointers may be NULL.  Outputs are fully written by the
+ * call.  A fixed sequence of launches whose dimensions depend on the shapes only; nothing is read back, nothing
+ * synchronises, and two calls are bit-equal.  NaN in gt_boxes is undefined behaviour. */
+
+/* §26.1 anchor head targets: the per-class (size_class) or class-agnostic max-IoU assigner of SECOND / PointPillars on
+ * the nearest-BEV (axis-aligned) IoU, anchors generated from the scalars below as in §25.1 (no anchor tensor, no [K,G]
+ * matrix).  labels[B,K]: class of the matched box for a positive, -1 background, -2 ignored; match[B,K]: the matched g or
+ * -1; reg_target[B,K,7]: ResidualCoder.encode for a positive, else 0; max_iou[B,K]; dir_target[B,K] (NULL iff nb == 0,
+ * else 2 <= nb <= 8): the direction bin of a positive, else -1.  1 <= ns <= 16, 1 <= nr <= 8, B <= 65535, B*K < 2^31
+ * (SAD_EUNSUPPORTED above); an anchor size <= 0: SAD_EINVAL.  workspace: sad_anchor_targets_workspace_bytes(B, G) bytes
+ * (0: may be NULL), zeroed by the call itself. */
+typedef struct sad_anchor_targets_args {
+    size_t struct_size;   /* = sizeof(sad_anchor_targets_args) */
+    const float *gt_boxes;
+    const int32_t *gt_labels;
+    int B, G, D, H, W, ns, nr, nb;
+    int use_size_class;   /* 0: every size takes every class (size_class is not read) */
+    float sizes[48];      /* [ns,3] (l, w, h) */
+    float z_center[16];   /* [ns] */
+    float rotations[8];   /* [nr] */
+    float pos_thr[16], neg_thr[16]; /* [ns] */
+    int32_t size_class[16];         /* [ns]: the class size s is matched against */
+    float x0, y0, sx, sy; /* centre of cell (0, 0) and the step between cell centres */
+    float dir_offset;
+    int32_t *labels, *match;
+    float *reg_target, *max_iou;
+    int32_t *dir_target;
+    void *workspace;
+} sad_anchor_targets_args;
+size_t sad_anchor_targets_workspace_bytes(int B, int G);   /* 4*B*G; 0 outside B >= 1, 0 <= G <= 1024 */
+int sad_anchor_targets_f32(const sad_anchor_targets_args *args, sad_stream_t stream);
+
+/* §26.2 centre head targets (CenterPoint, one task per call).  A label outside [0, C) is padding.  heatmap[B,C,H,W]
+ * (SAD_LAYOUT_NHWC: [B,H,W,C]): the maximum over the boxes of a class of the CenterNet Gaussian drawn around the box's
+ * cell, 0 where no box reaches; ind[B,G]: iy*W + ix of an assigned box, else -1; anno[B,G,8 (vel: 10)] =
+ * (fx - ix, fy - iy, cz, log l, log w, log h, sin yaw, cos yaw[, vx, vy]), zero for an unassigned box.  A box whose
+ * centre lies outside the map is unassigned (not clamped onto the border).  1 <= C <= 64, B <= 65535, B*H*W < 2^31
+ * (SAD_EUNSUPPORTED above); sx, sy > 0, 0 < min_overlap < 1, 0 <= min_radius <= 64, vel needs D >= 9 (SAD_EINVAL). */
+typedef struct sad_center_targets_args {
+    size_t struct_size;   /* = sizeof(sad_center_targets_args) */
+    const float *gt_boxes;
+    const int32_t *gt_labels;
+    int B, G, D, C, H, W, layout, min_radius, vel;
+    float lo_x, lo_y, sx, sy, min_overlap;
+    float *heatmap;
+    int32_t *ind;
+    float *anno;
+} sad_center_targets_args;
+int sad_center_targets_f32(const sad_center_targets_args *args, sad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -229,6 +229,11 @@ inline void lds_attr_once(std::atomic<uint64_t> &done, const void *fn, int bytes
     done.fetch_or(bit, std::memory_order_release);
 }
 
+// x rounded up to a multiple of 16: the alignment of every slice of a workspace (and of LDS images read 16 bytes at a time)
+__host__ __device__ inline size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
+// workgroups of `threads` that cover n items
+inline unsigned blocks_for(unsigned long long n, int threads) { return (unsigned)((n + threads - 1) / threads); }
+
 inline int check_launch(const char *what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(SAD_ELAUNCH, "%s: %s", what, hipGetErrorString(e));

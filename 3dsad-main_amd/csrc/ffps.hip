@@ -15,7 +15,8 @@
 
 namespace {
 
-typedef unsigned long long u64;
+#include "prims.h"       // u64, wave_max_u32_bcast
+
 constexpr int PD_TILE = 64, PD_CK = 32;
 
 __global__ __launch_bounds__(256) void pairdist_kernel(const float *__restrict__ xyz, const float *__restrict__ feat,
@@ -81,23 +82,6 @@ __global__ __launch_bounds__(256) void pairdist_kernel(const float *__restrict__
     }
 }
 
-template <int CTRL>
-__device__ __forceinline__ unsigned dpp_max_u32(unsigned v) {
-    const unsigned o = __builtin_amdgcn_update_dpp(0u, v, CTRL, 0xF, 0xF, false);
-    return o > v ? o : v;
-}
-__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {   // full-wave max, wave-uniform result
-    v = dpp_max_u32<0xB1>(v);    // quad_perm [1,0,3,2]
-    v = dpp_max_u32<0x4E>(v);    // quad_perm [2,3,0,1]
-    v = dpp_max_u32<0x141>(v);   // row_half_mirror
-    v = dpp_max_u32<0x140>(v);   // row_mirror
-    unsigned o = __builtin_amdgcn_update_dpp(v, v, 0x142, 0xA, 0xF, false);   // row_bcast:15
-    v = o > v ? o : v;
-    o = __builtin_amdgcn_update_dpp(v, v, 0x143, 0xC, 0xF, false);            // row_bcast:31
-    v = o > v ? o : v;
-    return __builtin_amdgcn_readlane(v, 63);
-}
-
 // The chain per step: one coalesced row of the matrix, min, per-thread best, a two-phase 32-bit DPP
 // wave max (distance bits, then ~index among the ties), one LDS atomic max per wave into a rotating
 // slot, one barrier, one broadcast read.
@@ -131,8 +115,8 @@ __global__ __launch_bounds__(1024) void fps_dmat_kernel(const float *__restrict_
                 blo = better ? lo : blo;
             }
         }
-        const unsigned whi = wave_max_u32(bhi);
-        const unsigned wlo = wave_max_u32(bhi == whi ? blo : 0u);
+        const unsigned whi = wave_max_u32_bcast(bhi);
+        const unsigned wlo = wave_max_u32_bcast(bhi == whi ? blo : 0u);
         const int b3n = b3 == 2 ? 0 : b3 + 1;
         if (lane == 0) {
             atomicMax(&s_gkey[b3], ((u64)whi << 32) | wlo);

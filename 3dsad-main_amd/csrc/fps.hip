@@ -10,6 +10,8 @@
 
 namespace {
 
+#include "prims.h"
+
 // (d, i) is better than (bd, bi): larger distance, ties -> lower index (SPEC.md §2).
 __device__ __forceinline__ bool better(float d, int i, float bd, int bi) {
     return d > bd || (d == bd && i < bi);
@@ -138,27 +140,7 @@ __global__ __launch_bounds__(THREADS) void fps_reg_kernel(const float *__restric
 // updates per lane, a wave arg-max (4 DPP butterflies + 4 readlanes), the wave's winning lane puts
 // its key and its point's coordinates into LDS, ONE barrier, every wave reduces the 16 keys and
 // reads the winner's coordinates back from LDS — no global access on the serial chain.
-typedef unsigned long long u64;
-
-template <int CTRL>
-__device__ __forceinline__ u64 dpp_u64(u64 v) {
-    const unsigned lo = __builtin_amdgcn_update_dpp(0u, (unsigned)v, CTRL, 0xF, 0xF, false);
-    const unsigned hi = __builtin_amdgcn_update_dpp(0u, (unsigned)(v >> 32), CTRL, 0xF, 0xF, false);
-    return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ u64 umax64(u64 a, u64 b) { return a > b ? a : b; }
-__device__ __forceinline__ u64 row_max_u64(u64 k) {  // max over each row of 16 lanes
-    k = umax64(k, dpp_u64<0xB1>(k));
-    k = umax64(k, dpp_u64<0x4E>(k));
-    k = umax64(k, dpp_u64<0x141>(k));
-    k = umax64(k, dpp_u64<0x140>(k));
-    return k;
-}
-__device__ __forceinline__ u64 readlane_u64(u64 v, int l) {
-    const unsigned lo = __builtin_amdgcn_readlane((unsigned)v, l);
-    const unsigned hi = __builtin_amdgcn_readlane((unsigned)(v >> 32), l);
-    return ((u64)hi << 32) | lo;
-}
+// (u64 and the 64-bit DPP / readlane maxima: prims.h)
 
 template <int THREADS, int PPT>
 __global__ __launch_bounds__(THREADS) void fps_key_kernel(const float *__restrict__ xyz, int N,
@@ -295,7 +277,7 @@ SAD_API size_t sad_fps_workspace_bytes(int B, int N) {
     if (B <= 0 || N < 2048) return 0;
     size_t n = (size_t)B * (size_t)N * sizeof(float);
     // + sorted float4 records (used above 16384 points, or for any N with fps_variant = 5)
-    if (N <= 65536) n = ((n + 15) & ~(size_t)15) + (size_t)B * 65536 * 16;
+    if (N <= 65536) n = sad::al16(n) + (size_t)B * 65536 * 16;
     return n;
 }
 

@@ -15,7 +15,8 @@
 
 namespace {
 
-typedef unsigned long long u64;
+#include "prims.h"       // u64 and the DPP / readlane maxima, among them the three forms of the 64-lane u32 max
+
 constexpr int SORT_T = 1024;
 constexpr int SORT_CELLS = 16384;   // 32 x 32 (Z-order) x 16
 
@@ -96,60 +97,6 @@ __global__ __launch_bounds__(SORT_T) void fps_sort_kernel(const float *__restric
     for (int j = tid; j < N; j += SORT_T) perm[atomicAdd(&hist[cell_of(j)], 1)] = j;
 }
 
-template <int CTRL>
-__device__ __forceinline__ u64 dpp_u64(u64 v) {
-    const unsigned lo = __builtin_amdgcn_update_dpp(0u, (unsigned)v, CTRL, 0xF, 0xF, false);
-    const unsigned hi = __builtin_amdgcn_update_dpp(0u, (unsigned)(v >> 32), CTRL, 0xF, 0xF, false);
-    return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ u64 umax64(u64 a, u64 b) { return a > b ? a : b; }
-__device__ __forceinline__ u64 row_max_u64(u64 k) {
-    k = umax64(k, dpp_u64<0xB1>(k));
-    k = umax64(k, dpp_u64<0x4E>(k));
-    k = umax64(k, dpp_u64<0x141>(k));
-    k = umax64(k, dpp_u64<0x140>(k));
-    return k;
-}
-__device__ __forceinline__ u64 readlane_u64(u64 v, int l) {
-    const unsigned lo = __builtin_amdgcn_readlane((unsigned)v, l);
-    const unsigned hi = __builtin_amdgcn_readlane((unsigned)(v >> 32), l);
-    return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ u64 wave_max_u64(u64 k) {
-    k = row_max_u64(k);
-    return umax64(umax64(readlane_u64(k, 0), readlane_u64(k, 16)), umax64(readlane_u64(k, 32), readlane_u64(k, 48)));
-}
-// 32-bit building blocks: a 64-bit key max is done as max(high words), then max of the low words
-// among the lanes that hold that high word — two cheap v_max_u32 butterflies instead of 64-bit
-// compare/select chains.
-template <int CTRL>
-__device__ __forceinline__ unsigned dpp_max_u32(unsigned v) {
-    const unsigned o = __builtin_amdgcn_update_dpp(0u, v, CTRL, 0xF, 0xF, false);
-    return o > v ? o : v;
-}
-template <int STEPS>
-__device__ __forceinline__ unsigned row_max_u32(unsigned v) {   // max over aligned groups of 2^STEPS lanes (<= 16)
-    if constexpr (STEPS >= 1) v = dpp_max_u32<0xB1>(v);
-    if constexpr (STEPS >= 2) v = dpp_max_u32<0x4E>(v);
-    if constexpr (STEPS >= 3) v = dpp_max_u32<0x141>(v);
-    if constexpr (STEPS >= 4) v = dpp_max_u32<0x140>(v);
-    return v;
-}
-__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {  // wave-uniform result
-    v = row_max_u32<4>(v);
-    const unsigned a = __builtin_amdgcn_readlane(v, 0), b = __builtin_amdgcn_readlane(v, 16);
-    const unsigned c = __builtin_amdgcn_readlane(v, 32), d = __builtin_amdgcn_readlane(v, 48);
-    const unsigned ab = a > b ? a : b, cd = c > d ? c : d;
-    return ab > cd ? ab : cd;
-}
-__device__ __forceinline__ unsigned wave_max_u32_bcast(unsigned v) {   // same, cross-row part by row_bcast DPP
-    v = row_max_u32<4>(v);
-    unsigned o = __builtin_amdgcn_update_dpp(v, v, 0x142, 0xA, 0xF, false);   // row_bcast:15 -> rows 1,3
-    v = o > v ? o : v;
-    o = __builtin_amdgcn_update_dpp(v, v, 0x143, 0xC, 0xF, false);            // row_bcast:31 -> rows 2,3
-    v = o > v ? o : v;
-    return __builtin_amdgcn_readlane(v, 63);
-}
 // A cell bucket's state (max min-distance, the lane that attains it) and its wave's best are made by the bucket's first update,
 // so the first step must update every real bucket.  Starting a bucket at +inf under the skip test dq < bmax was not enough:
 // for finite points far apart dq itself overflows to +inf, the bucket was skipped with lane 0 recorded as its best, and ties
@@ -542,17 +489,9 @@ __global__ __launch_bounds__(NW * 64) void fps_cell_kernel(const float *__restri
 //    its key lives on in lane wl's registers: an undisturbed wave's step is the skip test, one LDS atomic, the
 //    barrier and the read of the winner;
 //  * the wave best is recomputed only when the best bucket itself was updated or an updated bucket reaches its key;
-//  * the 64-lane max uses single-instruction row_bcast DPP steps (hipcc expands the builtin into mov + mov_dpp + max).
+//  * the 64-lane max uses single-instruction row_bcast DPP steps (wave_max_u32_b, prims.h; hipcc expands the builtin into mov + mov_dpp + max).
 typedef float f4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ unsigned lds_off(const void *p) { return (unsigned)(size_t)p; }   // low half of a flat LDS address
-__device__ __forceinline__ unsigned wave_max_u32_b(unsigned v) {   // wave-uniform result (SGPR)
-    v = row_max_u32<4>(v);
-    // row_bcast:15 -> rows 1, 3; row_bcast:31 -> rows 2, 3; dst == src1, so the rows left out keep their value
-    // (no wait states are inserted inside asm: two after the VALU write of v, two between the DPP steps)
-    asm("s_nop 1\n\tv_max_u32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-        "s_nop 1\n\tv_max_u32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf" : "+v"(v));
-    return __builtin_amdgcn_readlane(v, 63);
-}
 
 #ifdef SAD_FPS_STAMPS2
 // measurement build of the second form: s_memtime ticks per phase, summed by every wave of workgroup 0 over the steps in
@@ -1602,7 +1541,7 @@ int launch_fps_cellg(const float *xyz, int B, int N, int M, int32_t *idx, void *
     lds_attr_once(attr_done, reinterpret_cast<const void *>(&fps_sort_kernel), 80 * 1024);
     const int NP = N <= 16384 ? 16384 : 65536;
     int *perm = (int *)workspace;
-    const size_t off = (((size_t)B * N * sizeof(int)) + 15) & ~(size_t)15;
+    const size_t off = sad::al16((size_t)B * N * sizeof(int));
     float4 *rec = (float4 *)((unsigned char *)workspace + off);
     hipLaunchKernelGGL(fps_sort_kernel, dim3(B), dim3(SORT_T), sizeof(int) * SORT_CELLS, st, xyz, N, perm);
     hipLaunchKernelGGL(fps_records_kernel, dim3(64, B), dim3(256), 0, st, xyz, perm, N, NP, rec);

@@ -22,9 +22,7 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "prims.h"       // bf16x8, bf16x4, f32x16, atomic_max_pos
 
 constexpr int BF_T = 256;   // threads per workgroup (4 waves)
 
@@ -57,10 +55,6 @@ struct BfParams {
     int meta_off;              // byte offset of the per-tile row maps (s_pt[R], s_grp[R]) in LDS
     int noxcd;                 // A/B switch (option mlp_noxcd): plain tile stride
 };
-
-__device__ __forceinline__ void atomic_max_pos(float *addr, float v) {
-    atomicMax(reinterpret_cast<unsigned *>(addr), __builtin_bit_cast(unsigned, v));
-}
 
 __device__ __forceinline__ __bf16 load_feat(const void *feat, int is_bf16, size_t i) {
     return is_bf16 ? reinterpret_cast<const __bf16 *>(feat)[i] : (__bf16) reinterpret_cast<const float *>(feat)[i];
@@ -461,7 +455,6 @@ __global__ void pack_bf16_kernel(const float *__restrict__ W, const float *__res
 }
 
 inline int kpad(int l, int width) { return l == 0 ? (width + 15) & ~15 : (width + 31) & ~31; }
-inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 }  // namespace
 
@@ -476,9 +469,9 @@ static size_t layer_images(int L, const int *dims, LayerImage *im) {
         im[l].kp = kpad(l, dims[l]);
         im[l].CT = (dims[l + 1] + 31) / 32;
         im[l].w = n;
-        n += align16((size_t)im[l].CT * 32 * im[l].kp * 2);
+        n += sad::al16((size_t)im[l].CT * 32 * im[l].kp * 2);
         im[l].bias = n;
-        n += align16((size_t)im[l].CT * 32 * 4);
+        n += sad::al16((size_t)im[l].CT * 32 * 4);
     }
     return n;
 }
@@ -680,7 +673,7 @@ static int prepare_bf16_tiled(const sad_mlp_bf16_args *a, sad_stream_t stream, B
     p.kp[a->L] = kpad(a->L, a->dims[a->L]);
     const size_t budget = 150 * 1024;
     int R = 128;
-    auto lds_of = [&](int r) { return (((size_t)r * 2 * (ldA + ldB) + 15) & ~(size_t)15) + (size_t)(2 * r + 4) * sizeof(int); };
+    auto lds_of = [&](int r) { return sad::al16((size_t)r * 2 * (ldA + ldB)) + (size_t)(2 * r + 4) * sizeof(int); };
     if (a->geometry) {
         SAD_REQUIRE(a->geometry == 32 || a->geometry == 64 || a->geometry == 128 || a->geometry == 256,
                     "sad_mlp_chain_bf16: geometry (rows per tile) must be 32, 64, 128 or 256");
@@ -692,7 +685,7 @@ static int prepare_bf16_tiled(const sad_mlp_bf16_args *a, sad_stream_t stream, B
     while (!a->geometry && R > 32 && p.rows <= R / 2) R >>= 1;
     p.R = R;
     p.bufA_elems = R * ldA;
-    p.meta_off = (int)(((size_t)R * 2 * (ldA + ldB) + 15) & ~(size_t)15);
+    p.meta_off = (int)sad::al16((size_t)R * 2 * (ldA + ldB));
     const long long tiles = (p.rows + R - 1) / R;       // packed mode: an upper bound, the kernel reads the real count
     if (packed) {
         p.rowtab = (const int *)a->workspace;

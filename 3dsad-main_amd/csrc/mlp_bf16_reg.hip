@@ -25,9 +25,7 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "prims.h"       // bf16x8, bf16x4, f32x16, glds16, wait_vm, atomic_max_pos
 using sad::BfRegChain;
 using sad::BfRegMulti;
 
@@ -68,19 +66,6 @@ __host__ __device__ constexpr int pfd_of(int family) { return family == 2 ? SAD_
 // instruction rate.
 constexpr int STAGE_F = 1024;        // floats of pooled-output staging per wave
 __host__ __device__ constexpr int stage_cb(int no2) { return no2 * 32 < 128 ? no2 * 32 : 128; }
-
-// One wave-wide 16-byte LDS-DMA (1 KB lands at lds_dst + 16 * lane; cdna_hip_programming.md: M0 carries the LDS address and is the compiler's,
-// so it is saved and restored in the statement that uses it).  The compiler keeps no count of these loads: they are retired by wait_vm.
-__device__ __forceinline__ void glds16(const void *gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(__builtin_amdgcn_readfirstlane(lds_dst)));
-}
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N)); }
-
-__device__ __forceinline__ void atomic_max_pos(float *addr, float v) {
-    atomicMax(reinterpret_cast<unsigned *>(addr), __builtin_bit_cast(unsigned, v));
-}
 
 __device__ __forceinline__ bf16x8 as_bf(const float4 v) { return __builtin_bit_cast(bf16x8, v); }
 
@@ -211,8 +196,8 @@ __device__ __forceinline__ void br_tile(const BfRegChain &c, const int tile, con
     float4 *const ring = rs.ring;
     int slot = rs.slot;
     int srel = 0;
-    static_assert(FPW == 2 || FPW == 4, "two or four fragments per wave and stage");   // (FPW == 2: T2, T3 stay unused)
-    float4 T0, T1, T2, T3;                          // this wave's fragments of stage srel + 2, in flight (named: an array
+    static_assert(FPW == 2 || FPW == 4, "two or four fragments per wave and stage");   // (FPW == 2: T2, T3 stay unused; SAD_BR_DMA: all four)
+    [[maybe_unused]] float4 T0, T1, T2, T3;         // this wave's fragments of stage srel + 2, in flight (named: an array
     T2 = T3 = make_float4(0.f, 0.f, 0.f, 0.f);      // captured by the lambdas below may end up in scratch)
     const unsigned ulane = (unsigned)lane;
     auto stage_begin = [&]() {

@@ -19,9 +19,7 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "prims.h"       // bf16x8, bf16x4, f32x16, glds16, wait_vm
 typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 using sad::BfRowsJob;
 
@@ -370,13 +368,7 @@ __global__ __launch_bounds__(256) void bf16_rows_kernel(const BfRowsJob jb) {
 //     chunk later and published by a raw s_barrier — a stage is read in the chunk AFTER the barrier that follows its wait, and refilled
 //     after the barrier that follows its last read (cdna_hip_programming.md, "Read a staged buffer one phase after the wait that retires it").
 // Same products and the same k order per accumulator as the first form: bit-identical results (tests/test_gpu_bf16.py).
-__device__ __forceinline__ void glds16(const void *gsrc, unsigned lds_dst) {
-    unsigned keep;       // (M0 is the compiler's: saved and restored in the statement that uses it)
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(__builtin_amdgcn_readfirstlane(lds_dst)));      // (lds_dst is wave-uniform)
-    // (no "memory" clobber: with one, the by-value argument block is kept in scratch and re-read through it; the statements are volatile,
-    // so they keep their order among themselves and relative to the barriers, which is all the ring needs)
-}
+// (glds16 and wait_vm: prims.h)
 // byte offset of the k-th continuation row (k = 1, 2) of group `row` in its chain's buffer (row stride ld elements), 0 = none: the group's
 // packed rows begin in tile gstart[row] >> 5 and its continuation rows are those of the following tiles it reaches
 __device__ __forceinline__ unsigned cont_off(const int *gstart, int ld, long long row, int k) {
@@ -384,7 +376,6 @@ __device__ __forceinline__ unsigned cont_off(const int *gstart, int ld, long lon
     const int t0 = r0 >> 5, n = ((r1 - 1) >> 5) - t0;
     return n >= k ? (unsigned)(t0 + k) * (unsigned)ld * 2u : 0u;
 }
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N)); }
 
 template <int NTW, bool XCONT>
 __global__ __launch_bounds__(512) void bf16_rows2_kernel(const BfRowsJob jb) {

@@ -22,7 +22,7 @@ namespace {
 
 using namespace sad::chain;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "prims.h"       // f32x16, atomic_max_pos
 
 #ifndef SAD_MLP_BDEPTH
 #define SAD_MLP_BDEPTH 2
@@ -196,12 +196,6 @@ __device__ __forceinline__ int s_off_last_group(const int *s_off, int G, int T) 
         if (s_off[mid] <= T - 1) lo = mid; else hi = mid;
     }
     return lo;
-}
-
-// Atomic max on floats that are known to be >= +0 (outputs of a ReLU): their bit patterns order
-// like unsigned integers.
-__device__ __forceinline__ void atomic_max_pos(float *addr, float v) {
-    atomicMax(reinterpret_cast<unsigned *>(addr), __builtin_bit_cast(unsigned, v));
 }
 
 template <int W, int RW, int CW = 1>

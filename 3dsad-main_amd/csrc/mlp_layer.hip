@@ -21,7 +21,7 @@
 namespace {
 
 // MFMA operand shuffles (swap32 / to_operands / mma4), the two-operation DPP segmented max-scan (pool_masks / seg_max16)
-// and atomic_max_pos are the register-resident kernels' (reg_common.h): one copy of each
+// are the register-resident kernels' (reg_common.h), atomic_max_pos comes with it from prims.h: one copy of each
 #include "reg_common.h"
 
 constexpr int LWAVES = 4;         // waves per workgroup (independent)

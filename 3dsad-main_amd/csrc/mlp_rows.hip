@@ -137,12 +137,7 @@ __global__ __launch_bounds__(256, NT == 2 ? 4 : 2) void mlp_rows_kernel(const Ro
 // channel groups; lane (j, h) reads c0..c3 / c4..c7 of its row per k-group and two v_permlane32_swap make the four B operands, exactly as
 // in the first form.  The DMA goes through inline asm (the compiler keeps no count of it), is retired by a counted vmcnt one chunk later and
 // published by the chunk's barrier.  Same MFMAs in the same k order from the same bias: SPEC section 6's fmaf chains bit for bit.
-__device__ __forceinline__ void glds16(const void *gsrc, unsigned lds_dst) {
-    unsigned keep;       // (M0 is the compiler's: saved and restored in the statement that uses it)
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(__builtin_amdgcn_readfirstlane(lds_dst)));
-}
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N)); }
+// (glds16 and wait_vm: prims.h, through reg_common.h)
 
 template <int NTW>
 __global__ __launch_bounds__(512) void mlp_rows2_kernel(const RowsJob jb) {

@@ -15,7 +15,7 @@
 
 namespace {
 
-typedef unsigned long long u64;
+#include "prims.h"       // u64
 
 constexpr int NMSX_MAXP = 16384;
 constexpr int NMSX_MAXW = NMSX_MAXP / 64;        // 256 removed-words per scene, held in LDS by the walk
@@ -42,7 +42,7 @@ struct NmsxWs {           // per-scene slices of the workspace (8-byte items fir
 __host__ __device__ inline size_t nmsx_ws_scene_bytes(int P) {
     const size_t W = (size_t)(P + 63) / 64;
     const size_t b = 64 + (size_t)P * 8 + (size_t)P * W * 8 + (size_t)P * 16 * 2 + (size_t)P * 4 * 3;
-    return (b + 15) & ~(size_t)15;
+    return sad::al16(b);
 }
 __device__ __forceinline__ NmsxWs nmsx_ws(void *base, int scene, int P) {
     unsigned char *q = (unsigned char *)base + (size_t)scene * nmsx_ws_scene_bytes(P);

@@ -2,8 +2,8 @@
 // the DPP segmented max-scan and the staged pooled-output path.  Included inside each file's anonymous namespace.
 // No reference source exists (/root/reference/README.md:1-2).
 #pragma once
+#include "prims.h"       // f32x16, atomic_max_pos; mlp_rows.hip also takes glds16 and wait_vm from it
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int WHOLE_BIT = 1 << 30;
 using sad::RegChain;
 using sad::RegMulti;
@@ -115,10 +115,6 @@ __device__ __forceinline__ f32x16 seg_max16(f32x16 t, const PoolMasks &pm) {
 #pragma unroll
     for (int g = 0; g < 16; ++g) t[g] = __builtin_bit_cast(float, x[g]);
     return t;
-}
-
-__device__ __forceinline__ void atomic_max_pos(float *addr, float v) {
-    atomicMax(reinterpret_cast<unsigned *>(addr), __builtin_bit_cast(unsigned, v));
 }
 
 // max-pool of one finished 32-channel tile over the rows of each group + store (whole groups) / atomic max (groups

@@ -376,8 +376,8 @@ __global__ __launch_bounds__(VX_THREADS) void dense_write_kernel(const float *__
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
-inline size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
-inline unsigned blocks_for(unsigned long long n, int threads) { return (unsigned)((n + threads - 1) / threads); }
+using sad::al16;
+using sad::blocks_for;
 constexpr int SP_MAX_C = 256;
 
 // kernel / stride / padding / shapes of §21: subm ignores stride and padding (1 and K / 2)

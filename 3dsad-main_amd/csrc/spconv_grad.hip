@@ -23,7 +23,7 @@ namespace {
 #include "vox_hash.h"
 #include "reg_common.h"
 
-inline unsigned blocks_for(unsigned long long n, int threads) { return (unsigned)((n + threads - 1) / threads); }
+using sad::blocks_for;
 constexpr int SG_MAX_C = 256, SG_TR = 64, SG_MAX_TILES = 1024, SG_BIAS_ROWS = 1024;
 
 // ---- transposed rulebook ------------------------------------------------------------------------------------------

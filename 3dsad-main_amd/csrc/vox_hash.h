@@ -6,8 +6,8 @@
 //          back depends on the order of an atomic.
 // scans    exclusive scans over the 1024 threads of a workgroup, and of an int array in place by one workgroup.
 #pragma once
+#include "prims.h"       // u64
 
-typedef unsigned long long u64;
 constexpr int VX_THREADS = 256;
 constexpr int VX_SCAN_THREADS = 1024;
 constexpr u64 VX_EMPTY = ~0ull;

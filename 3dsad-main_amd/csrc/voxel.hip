@@ -335,7 +335,8 @@ __global__ __launch_bounds__(VX_THREADS) void voxel_reduce_grad_kernel(const flo
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
-inline size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
+using sad::al16;
+using sad::blocks_for;
 
 // workspace layout (bytes from the base)
 struct VoxWs {
@@ -396,8 +397,6 @@ int vox_grid(const char *fn, const float *voxel_size, const float *point_range, 
     }
     return SAD_OK;
 }
-
-inline unsigned blocks_for(unsigned long long n, int threads) { return (unsigned)((n + threads - 1) / threads); }
 
 inline void launch_init(u64 *tkeys, int32_t *tvals, unsigned cap, int32_t *cnt, int32_t *fill, int32_t *coors, unsigned nvox, hipStream_t st) {
     const unsigned long long n = tkeys ? (cap > nvox ? cap : nvox) : nvox;

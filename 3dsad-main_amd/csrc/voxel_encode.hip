@@ -278,7 +278,7 @@ EncWs enc_ws(int total, int B, int V, int Cin, int Cout) {
     EncWs w;
     w.lists = 0;
     w.mean = sad::voxel_ws_bytes(total, B, V);
-    w.wimg = w.mean + (((size_t)B * V * 3 * 4 + 15) & ~(size_t)15);
+    w.wimg = w.mean + sad::al16((size_t)B * V * 3 * 4);
     const size_t NP = ((size_t)Cout + 31) / 32 * 32, KP = ((size_t)Cin + 7) / 8 * 8;
     w.bytes = w.wimg + (Cout > 0 ? (NP + NP * KP) * 4 : 0) + 16;
     return w;

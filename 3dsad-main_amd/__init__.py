@@ -27,6 +27,8 @@ _LAZY = {
     "AnchorHeadDecoder": "dense_head", "CenterHeadDecoder": "dense_head",
     "anchor_targets": "ops", "center_targets": "ops",
     "AnchorTargetAssigner": "dense_head", "CenterTargetAssigner": "dense_head",
+    "anchor_head_loss": "ops", "center_head_loss": "ops", "anchor_head_loss_workspace": "ops", "center_head_loss_workspace": "ops",
+    "AnchorHeadLoss": "dense_head", "CenterHeadLoss": "dense_head",
     "Voxelization": "voxel", "DynamicScatter": "voxel", "PillarFeatureNet": "voxel",
     "sparse_conv_index": "ops", "sparse_conv": "ops", "sparse_to_dense": "ops", "PackedSparseWeight": "ops",
     "sparse_conv_index_transpose": "ops", "sparse_conv_grad_weight": "ops", "sparse_conv_grad_input": "ops",

@@ -119,6 +119,35 @@ class CenterTargetsArgs(ctypes.Structure):
     ]
 
 
+class AnchorHeadLossArgs(ctypes.Structure):
+    """``struct sad_anchor_head_loss_args`` (include/sad_amd.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("cls", vp), ("reg", vp), ("dir", vp), ("labels", vp), ("reg_target", vp), ("dir_target", vp),
+        ("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("A", ctypes.c_int), ("C", ctypes.c_int),
+        ("nb", ctypes.c_int), ("layout", ctypes.c_int), ("sin_diff", ctypes.c_int), ("normalize", ctypes.c_int),
+        ("alpha", ctypes.c_float), ("beta", ctypes.c_float),
+        ("code_weights", ctypes.c_float * 7), ("scale", ctypes.c_float * 3),
+        ("loss", vp), ("num_pos", vp), ("grad_cls", vp), ("grad_reg", vp), ("grad_dir", vp), ("per_anchor", vp),
+        ("workspace", vp),
+    ]
+
+
+class CenterHeadLossArgs(ctypes.Structure):
+    """``struct sad_center_head_loss_args`` (include/sad_amd.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("hm", vp), ("reg", vp), ("height", vp), ("dim", vp), ("rot", vp), ("vel", vp),
+        ("heatmap", vp), ("ind", vp), ("anno", vp),
+        ("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("C", ctypes.c_int), ("G", ctypes.c_int),
+        ("layout", ctypes.c_int), ("normalize", ctypes.c_int),
+        ("code_weights", ctypes.c_float * 10), ("scale", ctypes.c_float * 2),
+        ("loss", vp), ("num_pos", vp),
+        ("grad_hm", vp), ("grad_reg", vp), ("grad_height", vp), ("grad_dim", vp), ("grad_rot", vp), ("grad_vel", vp),
+        ("workspace", vp),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/sad_amd.h declares
 SIGNATURES = {
     "sad_version": (ctypes.c_int, []),
@@ -220,6 +249,10 @@ SIGNATURES = {
     "sad_anchor_targets_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "sad_anchor_targets_f32": (ctypes.c_int, [ctypes.POINTER(AnchorTargetsArgs), vp]),
     "sad_center_targets_f32": (ctypes.c_int, [ctypes.POINTER(CenterTargetsArgs), vp]),
+    "sad_anchor_head_loss_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "sad_anchor_head_loss_f32": (ctypes.c_int, [ctypes.POINTER(AnchorHeadLossArgs), vp]),
+    "sad_center_head_loss_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "sad_center_head_loss_f32": (ctypes.c_int, [ctypes.POINTER(CenterHeadLossArgs), vp]),
 }
 
 _lib = None

@@ -360,3 +360,47 @@ voxel_reduce = VoxelReduce.apply
 gather_points = GatherPoints.apply
 max_pool_s = MaxPoolS.apply
 three_interpolate = ThreeInterpolate.apply
+
+
+def _scaled(grad: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """grad [B,...] times w [B], broadcast per scene."""
+    return grad * w.view(-1, *([1] * (grad.dim() - 1)))
+
+
+class AnchorHeadLoss(torch.autograd.Function):
+    """(cls, reg, dir | None, labels, reg_target, dir_target | None, cfg) -> loss [B,3] (SPEC.md §27.1), differentiable in the maps.
+    The forward is ``ops.anchor_head_loss``, which already produced d loss[b, i] / d map for every component i: the backward
+    multiplies the saved gradients by ``grad_loss[:, i]`` per scene (a torch multiply).  ``cfg``: the operator's keywords."""
+
+    @staticmethod
+    def forward(ctx, cls, reg, dir, labels, reg_target, dir_target, cfg):
+        outs = ops.anchor_head_loss(cls, reg, dir, labels, reg_target, dir_target, **cfg)
+        ctx.save_for_backward(*outs[2:5 if dir is not None else 4])
+        ctx.mark_non_differentiable(outs[1])
+        return outs[0], outs[1]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss, _grad_num_pos):
+        saved = ctx.saved_tensors
+        grads = [_scaled(g, grad_loss[:, i]) for i, g in enumerate(saved)]
+        return grads[0], grads[1], grads[2] if len(grads) == 3 else None, None, None, None, None
+
+
+class CenterHeadLoss(torch.autograd.Function):
+    """(hm, reg, height, dim, rot, vel | None, heatmap, ind, anno, cfg) -> loss [B,2] (SPEC.md §27.2), differentiable in the maps:
+    grad_hm scales with ``grad_loss[:, 0]``, the regression gradients with ``grad_loss[:, 1]``."""
+
+    @staticmethod
+    def forward(ctx, hm, reg, height, dim, rot, vel, heatmap, ind, anno, cfg):
+        outs = ops.center_head_loss(hm, reg, height, dim, rot, vel, heatmap, ind, anno, **cfg)
+        ctx.save_for_backward(*outs[2:])
+        ctx.mark_non_differentiable(outs[1])
+        return outs[0], outs[1]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss, _grad_num_pos):
+        saved = ctx.saved_tensors
+        grads = [_scaled(g, grad_loss[:, 0 if i == 0 else 1]) for i, g in enumerate(saved)]
+        return (*grads, *([None] if len(grads) == 5 else []), None, None, None, None)

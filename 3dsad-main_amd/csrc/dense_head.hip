@@ -19,6 +19,8 @@
 
 namespace {
 
+#include "prims.h"       // flush_spans
+
 constexpr int DH_THREADS = 256;
 constexpr int TC = 64;             // cells of an anchor tile
 constexpr int AC = 8;              // anchors of an anchor tile
@@ -147,16 +149,6 @@ __device__ __forceinline__ void load_tab(const AncP &p, float *tab) {
     __syncthreads();
 }
 
-// tile image -> memory: `ncell` spans of `seg` elements, span c at dst[c * stride]; the image holds them back to back
-template <class T>
-__device__ __forceinline__ void flush_spans(const T *img, T *dst, int ncell, int seg, size_t stride) {
-    const int n = ncell * seg;
-    for (int i = threadIdx.x; i < n; i += DH_THREADS) {
-        const int c = i / seg;
-        dst[(size_t)c * stride + (i - c * seg)] = img[i];
-    }
-}
-
 template <bool NHWC>
 __global__ __launch_bounds__(DH_THREADS) void anchor_dense_kernel(const AncP p) {
     __shared__ float tab[72];
@@ -199,18 +191,18 @@ __global__ __launch_bounds__(DH_THREADS) void anchor_dense_kernel(const AncP p) 
     }
     __syncthreads();
     const size_t k0 = ((size_t)b * p.HW + cell0) * p.A + a0;
-    flush_spans(obox, p.boxes + k0 * 7, ncell, acn * 7, (size_t)p.A * 7);
-    flush_spans(oscore, p.scores + k0, ncell, acn, (size_t)p.A);
-    flush_spans(olabel, p.labels + k0, ncell, acn, (size_t)p.A);
+    flush_spans<DH_THREADS>(obox, p.boxes + k0 * 7, ncell, acn * 7, (size_t)p.A * 7);
+    flush_spans<DH_THREADS>(oscore, p.scores + k0, ncell, acn, (size_t)p.A);
+    flush_spans<DH_THREADS>(olabel, p.labels + k0, ncell, acn, (size_t)p.A);
 }
 
 // the rows of 256 consecutive output positions, decoded by their threads into rows[], go out in memory order
 __device__ __forceinline__ void flush_block(const float *obox, const float *oscore, const int32_t *olabel, float *boxes, float *scores,
                                             int32_t *labels, size_t row0, int n, int D) {
     __syncthreads();
-    flush_spans(obox, boxes + row0 * D, 1, n * D, 0);
-    flush_spans(oscore, scores + row0, 1, n, 0);
-    flush_spans(olabel, labels + row0, 1, n, 0);
+    flush_spans<DH_THREADS>(obox, boxes + row0 * D, 1, n * D, 0);
+    flush_spans<DH_THREADS>(oscore, scores + row0, 1, n, 0);
+    flush_spans<DH_THREADS>(olabel, labels + row0, 1, n, 0);
 }
 
 __global__ __launch_bounds__(DH_THREADS) void anchor_index_kernel(const AncP p) {

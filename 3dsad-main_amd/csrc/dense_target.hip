@@ -25,6 +25,8 @@
 
 namespace {
 
+#include "prims.h"       // flush_spans
+
 constexpr int DT_THREADS = 256;
 constexpr int TC = 64;             // cells of an anchor tile
 constexpr int AC = 8;              // anchors of an anchor tile
@@ -187,16 +189,6 @@ __global__ __launch_bounds__(DT_THREADS) void anchor_best_kernel(const TgtP p) {
         if (sbest[g]) atomicMax(&p.best[(size_t)b * p.G + g], sbest[g]);
 }
 
-// tile image -> memory: `ncell` spans of `seg` elements, span c at dst[c * stride]; the image holds them back to back
-template <class T>
-__device__ __forceinline__ void flush_spans(const T *img, T *dst, int ncell, int seg, size_t stride) {
-    const int n = ncell * seg;
-    for (int i = threadIdx.x; i < n; i += DT_THREADS) {
-        const int c = i / seg;
-        dst[(size_t)c * stride + (i - c * seg)] = img[i];
-    }
-}
-
 __global__ __launch_bounds__(DT_THREADS) void anchor_assign_kernel(const TgtP p) {
     __shared__ float tab[T_N];
     __shared__ float4 grect[MAXG];
@@ -280,11 +272,11 @@ __global__ __launch_bounds__(DT_THREADS) void anchor_assign_kernel(const TgtP p)
     }
     __syncthreads();
     const size_t k0 = ((size_t)b * p.HW + cell0) * p.A + a0;
-    flush_spans(oreg, p.reg + k0 * 7, ncell, acn * 7, (size_t)p.A * 7);
-    flush_spans(omax, p.max_iou + k0, ncell, acn, (size_t)p.A);
-    flush_spans(olabel, p.labels + k0, ncell, acn, (size_t)p.A);
-    flush_spans(omatch, p.match + k0, ncell, acn, (size_t)p.A);
-    if (p.nb) flush_spans(odir, p.dir_target + k0, ncell, acn, (size_t)p.A);
+    flush_spans<DT_THREADS>(oreg, p.reg + k0 * 7, ncell, acn * 7, (size_t)p.A * 7);
+    flush_spans<DT_THREADS>(omax, p.max_iou + k0, ncell, acn, (size_t)p.A);
+    flush_spans<DT_THREADS>(olabel, p.labels + k0, ncell, acn, (size_t)p.A);
+    flush_spans<DT_THREADS>(omatch, p.match + k0, ncell, acn, (size_t)p.A);
+    if (p.nb) flush_spans<DT_THREADS>(odir, p.dir_target + k0, ncell, acn, (size_t)p.A);
 }
 
 // §26.2: one box.  false: unassigned

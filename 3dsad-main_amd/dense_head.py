@@ -1,9 +1,11 @@
 """Dense BEV heads (SPEC.md §25): the raw maps of an anchor head (SECOND, PointPillars, PV-RCNN's RPN) or a centre head
 (CenterPoint) -> ``(boxes, scores, labels)``, and on through ``ops.nms_boxes``.  The 2-D convolutions that produce the maps
-are torch's; these modules hold the decode configuration only and have no parameters.  Inference only.
+are torch's; these modules hold the decode configuration only and have no parameters.  The decode is inference only.
 
 The way back (SPEC.md §26): ``AnchorTargetAssigner`` / ``CenterTargetAssigner`` turn ground-truth boxes into what such a head
-is trained against, from the same configuration (``decoder.assigner(...)``).  No gradients: the losses are torch's."""
+is trained against, from the same configuration (``decoder.assigner(...)``), and ``AnchorHeadLoss`` / ``CenterHeadLoss``
+(SPEC.md §27, ``decoder.loss(...)``) are the losses on those targets: one fused pass that also writes the gradient of every
+map, wrapped in an autograd Function, so ``loss.sum().backward()`` reaches the convolutions."""
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -59,6 +61,10 @@ class AnchorHeadDecoder(nn.Module):
         return AnchorTargetAssigner(self.sizes, self.z_center, self.rotations, self.origin, self.step, pos_thr, neg_thr, size_class,
                                     nb=nb, dir_offset=self.dir_offset)
 
+    def loss(self, **cfg) -> "AnchorHeadLoss":
+        """The loss module in this decoder's layout (keywords of ``AnchorHeadLoss``)."""
+        return AnchorHeadLoss(layout=self.layout, **cfg)
+
     def predict(self, cls: torch.Tensor, reg: torch.Tensor, dir: Optional[torch.Tensor] = None, *, iou_thr: float,
                 score_thr: float = 0.0, pre_max: Optional[int] = None, post_max: Optional[int] = None, class_aware: bool = True):
         """(boxes [B,K,7], scores, labels, order [B,P], count [B]): the decode, then ``ops.nms_boxes`` on its three tensors.
@@ -82,6 +88,10 @@ class CenterHeadDecoder(nn.Module):
     def assigner(self, C: int, min_overlap: float = 0.1, min_radius: int = 2, vel: bool = False) -> "CenterTargetAssigner":
         """The target assigner on this decoder's map geometry (C classes of the task)."""
         return CenterTargetAssigner(C, self.origin, self.cell, min_overlap, min_radius, vel, self.layout)
+
+    def loss(self, **cfg) -> "CenterHeadLoss":
+        """The loss module in this decoder's layout (keywords of ``CenterHeadLoss``)."""
+        return CenterHeadLoss(layout=self.layout, **cfg)
 
     def predict(self, hm, reg, height, dim, rot, vel=None, *, iou_thr: float, score_thr: float = 0.0,
                 pre_max: Optional[int] = None, post_max: Optional[int] = None, class_aware: bool = True):
@@ -129,3 +139,40 @@ class CenterTargetAssigner(nn.Module):
         """(heatmap, ind, anno) for a map of H x W cells."""
         return ops.center_targets(gt_boxes, gt_labels, C=self.C, H=H, W=W, origin=self.origin, cell=self.cell,
                                   min_overlap=self.min_overlap, min_radius=self.min_radius, vel=self.vel, layout=self.layout, out=out)
+
+
+class AnchorHeadLoss(nn.Module):
+    """Losses of an anchor head (``ops.anchor_head_loss``, SPEC.md §27.1): the configuration only, no parameters.
+    ``forward(cls, reg, dir, labels, reg_target, dir_target) -> loss [B,3]`` (classification, regression, direction), each
+    already divided by the scene's positive count, differentiable in the maps.  The operator's second output is not returned:
+    the module keeps ``num_pos`` [B] int32 of its LAST call as an attribute (``None`` before the first), for logging."""
+
+    def __init__(self, alpha: float = 0.25, beta: float = 1.0 / 9.0, code_weights=None, sin_diff: bool = True, scale=(1.0, 1.0, 1.0),
+                 normalize: bool = True, layout: str = "nchw"):
+        super().__init__()
+        self.cfg = dict(alpha=float(alpha), beta=float(beta), code_weights=None if code_weights is None else [float(v) for v in code_weights],
+                        sin_diff=bool(sin_diff), scale=tuple(float(v) for v in scale), normalize=bool(normalize), layout=layout)
+        self.num_pos = None
+
+    def forward(self, cls: torch.Tensor, reg: torch.Tensor, dir: Optional[torch.Tensor], labels: torch.Tensor, reg_target: torch.Tensor,
+                dir_target: Optional[torch.Tensor] = None) -> torch.Tensor:
+        from .autograd import AnchorHeadLoss as _Fn
+        loss, self.num_pos = _Fn.apply(cls, reg, dir, labels, reg_target, dir_target, self.cfg)
+        return loss
+
+
+class CenterHeadLoss(nn.Module):
+    """Losses of one task of a centre head (``ops.center_head_loss``, SPEC.md §27.2).
+    ``forward(hm, reg, height, dim, rot, vel, heatmap, ind, anno) -> loss [B,2]`` (heat map, regression), differentiable in the
+    maps.  ``num_pos`` [B,2] int32 of the LAST call is kept as an attribute (``None`` before the first)."""
+
+    def __init__(self, code_weights=None, scale=(1.0, 1.0), normalize: bool = True, layout: str = "nchw"):
+        super().__init__()
+        self.cfg = dict(code_weights=None if code_weights is None else [float(v) for v in code_weights],
+                        scale=tuple(float(v) for v in scale), normalize=bool(normalize), layout=layout)
+        self.num_pos = None
+
+    def forward(self, hm, reg, height, dim, rot, vel, heatmap, ind, anno) -> torch.Tensor:
+        from .autograd import CenterHeadLoss as _Fn
+        loss, self.num_pos = _Fn.apply(hm, reg, height, dim, rot, vel, heatmap, ind, anno, self.cfg)
+        return loss

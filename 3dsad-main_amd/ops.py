@@ -1335,7 +1335,7 @@ def _gt_inputs(gt_boxes: torch.Tensor, gt_labels: torch.Tensor, min_d: int = 7) 
     return B, G, D, _head_devices((("gt_boxes", gt_boxes), ("gt_labels", gt_labels)))
 
 
-def _target_outputs(spec, out: Optional[tuple], dev) -> tuple:
+def _target_outputs(spec, out: Optional[tuple], dev, of: str = "gt_boxes") -> tuple:
     """Buffers of a target call.  ``spec`` = ((name, shape, dtype), ...); ``out`` checked against it, or new buffers."""
     if out is None:
         return tuple(_empty(shape, dtype=dt, device=dev) for _, shape, dt in spec)
@@ -1343,7 +1343,7 @@ def _target_outputs(spec, out: Optional[tuple], dev) -> tuple:
                                        and t.is_contiguous() and t.device == dev for t, (_, shape, dt) in zip(out, spec))
     if not ok:
         want = ", ".join(f"{n} {list(shape)} {str(dt).replace('torch.', '')}" for n, shape, dt in spec)
-        raise ValueError(f"out: expected contiguous ({want}) on the device of gt_boxes")
+        raise ValueError(f"out: expected contiguous ({want}) on the device of {of}")
     return tuple(out)
 
 
@@ -1461,6 +1461,179 @@ def center_targets(gt_boxes: torch.Tensor, gt_labels: torch.Tensor, *, C: int, H
     with _timed("center_targets", f"K{H * W}G{G}"):
         check(lib().sad_center_targets_f32(ctypes.byref(a), _stream()), "sad_center_targets_f32")
     return heatmap, ind, anno
+
+
+def _dense_targets(named, dev) -> None:
+    """(name, tensor, shape, dtype) rows of a loss call: contiguous tensors of that shape and dtype on the maps' device."""
+    for name, t, shape, dt in named:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: expected a torch.Tensor")
+        if t.dtype != dt:
+            raise TypeError(f"{name}: expected dtype {dt}, got {t.dtype}")
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: must be contiguous")
+        if not t.is_cuda or t.device != dev:
+            raise RuntimeError(f"{name}: expected a tensor on {dev} (sad_amd has no CPU path)")
+
+
+def _loss_workspace(nbytes: int, workspace: Optional[torch.Tensor], dev) -> torch.Tensor:
+    if workspace is None:
+        return _empty(nbytes, dtype=torch.uint8, device=dev)
+    if (not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or workspace.device != dev or not workspace.is_contiguous()
+            or workspace.numel() * workspace.element_size() < nbytes):
+        raise ValueError(f"workspace: expected at least {nbytes} contiguous bytes on {dev}")
+    return workspace
+
+
+def _weights(v, n: int, name: str) -> list:
+    a = np.ones(n, np.float32) if v is None else np.asarray(v, dtype=np.float32).reshape(-1)
+    if a.shape[0] != n:
+        raise ValueError(f"{name}: expected {n} values, got {a.shape[0]}")
+    return a.tolist()
+
+
+def anchor_head_loss_workspace(B: int, H: int, W: int, A: int, device) -> torch.Tensor:
+    """The workspace of ``anchor_head_loss(..., workspace=...)`` for a caller that keeps it."""
+    nbytes = lib().sad_anchor_head_loss_workspace_bytes(B, H, W, A)
+    if not nbytes:
+        raise ValueError(f"anchor_head_loss_workspace: unsupported shape B = {B}, H = {H}, W = {W}, A = {A}")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def anchor_head_loss(cls: torch.Tensor, reg: torch.Tensor, dir: Optional[torch.Tensor], labels: torch.Tensor,
+                     reg_target: torch.Tensor, dir_target: Optional[torch.Tensor] = None, *, alpha: float = 0.25,
+                     beta: float = 1.0 / 9.0, code_weights=None, sin_diff: bool = True, scale=(1.0, 1.0, 1.0), normalize: bool = True,
+                     layout: str = "nchw", per_anchor: bool = False, out: Optional[tuple] = None,
+                     workspace: Optional[torch.Tensor] = None) -> tuple:
+    """Anchor head losses with their gradients (SPEC.md §27.1).  cls [B,A*C,H,W], reg [B,A*7,H,W], dir [B,A*nb,H,W] or ``None``
+    (``layout="nhwc"``: channels last), contiguous f32; labels [B,K] int32 (>= 0 class, -1 background, -2 ignored), reg_target
+    [B,K,7] f32 and dir_target [B,K] int32 as ``anchor_targets`` makes them, K = H*W*A ->
+    (loss [B,3] = (cls, reg, dir), num_pos [B] int32, grad_cls, grad_reg[, grad_dir][, per_anchor [B,K,3]]): OpenPCDet's sigmoid
+    focal loss (gamma = 2) over the rows that are not ignored, smooth-L1 with the sine-difference yaw and softmax cross-entropy
+    of the direction bins over the positives, each scaled by ``scale[i] / max(num_pos[b], 1)`` per scene (``normalize=False``:
+    by ``scale[i]``); the gradients are those of ``loss[b, i]`` summed over i, in the shape and layout of the maps.  Two small
+    launches around one pass over the maps, no synchronisation, bit-identical from call to call.  ``out``: the tuple to write into."""
+    B, chc, H, W = _head_grid(cls, "cls", layout)
+    _, chr_, _, _ = _head_grid(reg, "reg", layout)
+    if chr_ < 7 or chr_ % 7:
+        raise ValueError(f"reg: {chr_} channels are not A * 7")
+    A = chr_ // 7
+    if A > 128:
+        raise ValueError(f"reg: at most 128 anchors per cell (got A = {A})")
+    if chc < A or chc % A:
+        raise ValueError(f"cls: {chc} channels are not a multiple of A = {A}")
+    C = chc // A
+    if C > 64:
+        raise ValueError(f"cls: at most 64 classes (got C = {C})")
+    cls = _head_map(cls, "cls", B, A * C, H, W, layout)
+    reg = _head_map(reg, "reg", B, A * 7, H, W, layout)
+    nb = 0
+    if dir is not None:
+        _, chd, _, _ = _head_grid(dir, "dir", layout)
+        if chd < 2 * A or chd % A or chd // A > 8:
+            raise ValueError(f"dir: {chd} channels are not A * nb with 2 <= nb <= 8 (A = {A})")
+        nb = chd // A
+        dir = _head_map(dir, "dir", B, chd, H, W, layout)
+    if (dir is None) != (dir_target is None):
+        raise ValueError("dir and dir_target must be given together")
+    if not float(beta) > 0.0:
+        raise ValueError(f"beta: must be > 0, got {beta}")
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError(f"alpha: expected a value in [0, 1], got {alpha}")
+    cw, sc = _weights(code_weights, 7, "code_weights"), _weights(scale, 3, "scale")
+    K = H * W * A
+    dev = _head_devices((("cls", cls), ("reg", reg), ("dir", dir)))
+    _dense_targets([("labels", labels, (B, K), torch.int32), ("reg_target", reg_target, (B, K, 7), torch.float32)]
+                   + ([("dir_target", dir_target, (B, K), torch.int32)] if nb else []), dev)
+    spec = [("loss", (B, 3), torch.float32), ("num_pos", (B,), torch.int32), ("grad_cls", tuple(cls.shape), torch.float32),
+            ("grad_reg", tuple(reg.shape), torch.float32)]
+    if nb:
+        spec.append(("grad_dir", tuple(dir.shape), torch.float32))
+    if per_anchor:
+        spec.append(("per_anchor", (B, K, 3), torch.float32))
+    outs = _target_outputs(spec, out, dev, "the maps")
+    nbytes = lib().sad_anchor_head_loss_workspace_bytes(B, H, W, A)
+    if not nbytes:
+        raise ValueError(f"anchor_head_loss: unsupported shape (B = {B}, K = {K}: B <= 65535 and B * K < 2^31)")
+    workspace = _loss_workspace(nbytes, workspace, dev)
+    a = _lib.AnchorHeadLossArgs()
+    a.struct_size = ctypes.sizeof(_lib.AnchorHeadLossArgs)
+    a.cls, a.reg, a.dir = cls.data_ptr(), reg.data_ptr(), dir.data_ptr() if nb else None
+    a.labels, a.reg_target, a.dir_target = labels.data_ptr(), reg_target.data_ptr(), dir_target.data_ptr() if nb else None
+    a.B, a.H, a.W, a.A, a.C, a.nb, a.layout = B, H, W, A, C, nb, _lib.LAYOUTS[layout]
+    a.sin_diff, a.normalize = int(bool(sin_diff)), int(bool(normalize))
+    a.alpha, a.beta = _f32(alpha), _f32(beta)
+    a.code_weights[:], a.scale[:] = cw, sc
+    a.loss, a.num_pos, a.grad_cls, a.grad_reg = (t.data_ptr() for t in outs[:4])
+    a.grad_dir = outs[4].data_ptr() if nb else None
+    a.per_anchor = outs[-1].data_ptr() if per_anchor else None
+    a.workspace = workspace.data_ptr()
+    with _timed("anchor_head_loss", f"K{K}C{C}"):
+        check(lib().sad_anchor_head_loss_f32(ctypes.byref(a), _stream()), "sad_anchor_head_loss_f32")
+    return outs
+
+
+def center_head_loss_workspace(B: int, H: int, W: int, G: int, device) -> torch.Tensor:
+    """The workspace of ``center_head_loss(..., workspace=...)`` for a caller that keeps it."""
+    nbytes = lib().sad_center_head_loss_workspace_bytes(B, H, W, G)
+    if not nbytes:
+        raise ValueError(f"center_head_loss_workspace: unsupported shape B = {B}, H = {H}, W = {W}, G = {G}")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def center_head_loss(hm: torch.Tensor, reg: torch.Tensor, height: torch.Tensor, dim: torch.Tensor, rot: torch.Tensor,
+                     vel: Optional[torch.Tensor], heatmap: torch.Tensor, ind: torch.Tensor, anno: torch.Tensor, *, code_weights=None,
+                     scale=(1.0, 1.0), normalize: bool = True, layout: str = "nchw", out: Optional[tuple] = None,
+                     workspace: Optional[torch.Tensor] = None) -> tuple:
+    """Centre head losses with their gradients (SPEC.md §27.2, one CenterPoint task).  The maps of ``center_decode`` and the
+    (heatmap, ind, anno) of ``center_targets`` (heatmap in the maps' layout) ->
+    (loss [B,2] = (hm, reg), num_pos [B,2] int32 = (cells with heatmap == 1, assigned boxes), grad_hm, grad_reg, grad_height,
+    grad_dim, grad_rot[, grad_vel]): CenterNet's penalty-reduced focal loss of the clamped sigmoid over every cell and class,
+    and L1 of the regression channels at the boxes' cells against anno, weighted by ``code_weights`` (one per anno column);
+    component i of scene b is scaled by ``scale[i] / max(num_pos[b, i], 1)`` (``normalize=False``: by ``scale[i]``).  Boxes
+    that share a cell add their gradients in ascending g.  No synchronisation, bit-identical from call to call."""
+    B, C, H, W = _head_grid(hm, "hm", layout)
+    if C < 1 or C > 64:
+        raise ValueError(f"hm: expected 1 .. 64 class channels, got {C}")
+    hm = _head_map(hm, "hm", B, C, H, W, layout)
+    maps = []
+    for t, name, ch in ((reg, "reg", 2), (height, "height", 1), (dim, "dim", 3), (rot, "rot", 2), (vel, "vel", 2)):
+        maps.append(None if t is None and name == "vel" else _head_map(t, name, B, ch, H, W, layout))
+    reg, height, dim, rot, vel = maps
+    na = 10 if vel is not None else 8
+    dev = _head_devices((("hm", hm), ("reg", reg), ("height", height), ("dim", dim), ("rot", rot), ("vel", vel)))
+    if not isinstance(ind, torch.Tensor) or ind.dim() != 2 or ind.shape[0] != B:
+        raise ValueError(f"ind: expected [B,G] with B = {B}")
+    G = ind.shape[1]
+    if G > 1024:
+        raise ValueError(f"ind: at most 1024 boxes per scene (got G = {G})")
+    _dense_targets((("heatmap", heatmap, tuple(hm.shape), torch.float32), ("ind", ind, (B, G), torch.int32),
+                    ("anno", anno, (B, G, na), torch.float32)), dev)
+    cw, sc = _weights(code_weights, na, "code_weights"), _weights(scale, 2, "scale")
+    spec = [("loss", (B, 2), torch.float32), ("num_pos", (B, 2), torch.int32), ("grad_hm", tuple(hm.shape), torch.float32)]
+    spec += [(f"grad_{n}", tuple(t.shape), torch.float32) for n, t in (("reg", reg), ("height", height), ("dim", dim), ("rot", rot), ("vel", vel))
+             if t is not None]
+    outs = _target_outputs(spec, out, dev, "the maps")
+    nbytes = lib().sad_center_head_loss_workspace_bytes(B, H, W, G)
+    if not nbytes:
+        raise ValueError(f"center_head_loss: unsupported shape (B = {B}, H * W = {H * W}: B <= 65535 and B * H * W < 2^31)")
+    workspace = _loss_workspace(nbytes, workspace, dev)
+    a = _lib.CenterHeadLossArgs()
+    a.struct_size = ctypes.sizeof(_lib.CenterHeadLossArgs)
+    a.hm, a.reg, a.height, a.dim, a.rot = hm.data_ptr(), reg.data_ptr(), height.data_ptr(), dim.data_ptr(), rot.data_ptr()
+    a.vel = vel.data_ptr() if vel is not None else None
+    a.heatmap = heatmap.data_ptr()
+    a.ind, a.anno = (ind.data_ptr(), anno.data_ptr()) if G else (None, None)
+    a.B, a.H, a.W, a.C, a.G, a.layout, a.normalize = B, H, W, C, G, _lib.LAYOUTS[layout], int(bool(normalize))
+    a.code_weights[:na], a.scale[:] = cw, sc
+    a.loss, a.num_pos, a.grad_hm, a.grad_reg, a.grad_height, a.grad_dim, a.grad_rot = (t.data_ptr() for t in outs[:7])
+    a.grad_vel = outs[7].data_ptr() if vel is not None else None
+    a.workspace = workspace.data_ptr()
+    with _timed("center_head_loss", f"K{H * W}G{G}"):
+        check(lib().sad_center_head_loss_f32(ctypes.byref(a), _stream()), "sad_center_head_loss_f32")
+    return outs
 
 
 # The fused MLP chains (PackedMLP / PackedMLPBf16, grouped_multi, rowscan_multi, the autotuner) live in mlp.py; they belong

@@ -680,6 +680,62 @@ typedef struct sad_center_targets_args {
 } sad_center_targets_args;
 int sad_center_targets_f32(const sad_center_targets_args *args, sad_stream_t stream);
 
+/* SPEC.md §27.  Dense head losses: the maps of a dense head and the targets of §26 -> per-scene losses and the gradient with
+ * respect to every map, written in the map's own layout (no permuted copy); K, the k numbering, the channel numbering and
+ * the layouts are §25's.  Component i of scene b is weighted by wq_i = scale[i] / (float)max(n_b, 1) (normalize != 0) or
+ * scale[i] (normalize == 0): scenes are independent; a batch-wide normaliser is normalize = 0 and a division by the caller.
+ * Outputs are fully written by the call.  A fixed sequence of memsets and launches whose dimensions depend on the shapes
+ * only; nothing is read back, nothing synchronises, no float atomics: two calls are bit-equal.  NaN in an input is
+ * undefined behaviour.  Limits: 1 <= B <= 65535, 1 <= C <= 64, A <= 128, nb 0 or 2 .. 8, G <= 1024, B*K < 2^31
+ * (SAD_EUNSUPPORTED above); a NULL pointer, a wrong struct_size, beta <= 0, alpha outside [0, 1], another layout code, dir
+ * without nb or the reverse: SAD_EINVAL. */
+
+/* §27.1 anchor head: sigmoid focal classification (gamma = 2) over the rows with labels != -2, smooth-L1 regression with
+ * the sine-difference yaw (sin_diff != 0) and softmax cross-entropy over the nb direction bins, both over the positives
+ * (labels >= 0); num_pos[b] = the scene's positives.  labels / reg_target / dir_target are §26.1's.  dir, dir_target and
+ * grad_dir are NULL iff nb == 0 (loss[.,2] = 0).  per_anchor[B,K,3] (may be NULL): the row's terms per component.
+ * workspace: sad_anchor_head_loss_workspace_bytes(B, H, W, A) bytes (the workgroups' partial sums), contents irrelevant. */
+typedef struct sad_anchor_head_loss_args {
+    size_t struct_size;   /* = sizeof(sad_anchor_head_loss_args) */
+    const float *cls, *reg, *dir;  /* maps: A*C, A*7, A*nb channels */
+    const int32_t *labels;         /* [B,K] */
+    const float *reg_target;       /* [B,K,7] */
+    const int32_t *dir_target;     /* [B,K] */
+    int B, H, W, A, C, nb, layout, sin_diff, normalize;
+    float alpha, beta;
+    float code_weights[7];
+    float scale[3];       /* cls, reg, dir */
+    float *loss;          /* [B,3] */
+    int32_t *num_pos;     /* [B] */
+    float *grad_cls, *grad_reg, *grad_dir; /* shapes and layout of the maps */
+    float *per_anchor;
+    void *workspace;
+} sad_anchor_head_loss_args;
+size_t sad_anchor_head_loss_workspace_bytes(int B, int H, int W, int A);   /* 12*B*ceil(H*W/64)*ceil(A/8); 0 outside the limits */
+int sad_anchor_head_loss_f32(const sad_anchor_head_loss_args *args, sad_stream_t stream);
+
+/* §27.2 centre head (CenterPoint, one task per call): CenterNet's penalty-reduced focal loss of the clamped sigmoid of hm
+ * against heatmap (same layout), and L1 of the regression maps at the cells ind[B,G] against anno[B,G,8 (vel: 10)], the
+ * outputs of §26.2.  num_pos[B,2] = (cells with heatmap == 1, boxes with 0 <= ind < H*W): the two normalisers.  The
+ * regression gradients are zero outside the boxes' cells; boxes that share a cell add up in ascending g.  vel and grad_vel
+ * are NULL together.  With G == 0 ind and anno may be NULL.  workspace: sad_center_head_loss_workspace_bytes(B, H, W, G). */
+typedef struct sad_center_head_loss_args {
+    size_t struct_size;   /* = sizeof(sad_center_head_loss_args) */
+    const float *hm, *reg, *height, *dim, *rot, *vel;
+    const float *heatmap;
+    const int32_t *ind;
+    const float *anno;
+    int B, H, W, C, G, layout, normalize;
+    float code_weights[10];
+    float scale[2];       /* hm, reg */
+    float *loss;          /* [B,2] */
+    int32_t *num_pos;     /* [B,2] */
+    float *grad_hm, *grad_reg, *grad_height, *grad_dim, *grad_rot, *grad_vel;
+    void *workspace;
+} sad_center_head_loss_args;
+size_t sad_center_head_loss_workspace_bytes(int B, int H, int W, int G);   /* 4*B*(ceil(H*W/256) + ceil(G/256)); 0 outside the limits */
+int sad_center_head_loss_f32(const sad_center_head_loss_args *args, sad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,7 +19,7 @@
 
 namespace {
 
-#include "prims.h"       // flush_spans
+#include "prims.h"       // flush_spans, stage_rows
 
 constexpr int DH_THREADS = 256;
 constexpr int TC = 64;             // cells of an anchor tile
@@ -61,18 +61,6 @@ struct AncDirect {
     __device__ __forceinline__ float cls(int c) const { return p.cls[map_at(p.nhwc, b, a * p.C + c, cell, p.A * p.C, p.HW)]; }
 };
 
-// rows (al, cell) of a pass -> lds[(al * 64 + cell) * ld + e], e < len: channels ch0 .. ch0 + len - 1 of anchor a0 + al out of CHA
-// per anchor; all 256 threads walk the floats of the pass in memory order
-__device__ __forceinline__ void stage_rows(float *lds, int ld, const float *scene, int CHA, int ch0, int len, int A, int cell0, int ncell, int a0,
-                                           int na) {
-    const int n = ncell * na * len;
-    for (int i = threadIdx.x; i < n; i += DH_THREADS) {
-        const int row = i / len, e = i - row * len;
-        const int cell = row / na, al = row - cell * na;
-        lds[(al * TC + cell) * ld + e] = scene[((size_t)(cell0 + cell) * A + a0 + al) * CHA + ch0 + e];
-    }
-}
-
 // values of the thread's row from the staged pass (nhwc).  Every thread of the workgroup makes the same calls: cls() stages
 // the next chunk of classes between two barriers.
 struct AncStaged {
@@ -85,7 +73,7 @@ struct AncStaged {
     __device__ __forceinline__ float cls(int c) const {
         if ((c & (CCH - 1)) == 0) {
             __syncthreads();
-            stage_rows(su, CCH + 1, scene_cls, p.C, c, min(CCH, p.C - c), p.A, cell0, ncell, a0, na);
+            stage_rows<DH_THREADS, TC, false>(su, CCH + 1, scene_cls, p.C, c, min(CCH, p.C - c), p.A, cell0, ncell, a0, na);
             __syncthreads();
         }
         return su[threadIdx.x * (CCH + 1) + (c & (CCH - 1))];
@@ -172,8 +160,11 @@ __global__ __launch_bounds__(DH_THREADS) void anchor_dense_kernel(const AncP p) 
             const int na = min(4, acn - 4 * pass);
             const AncStaged f{p, sreg, su, p.cls + (size_t)b * p.HW * p.A * p.C, cell0, ncell, a0 + 4 * pass, na};
             __syncthreads();
-            stage_rows(sreg, 7, p.reg + (size_t)b * p.HW * p.A * 7, 7, 0, 7, p.A, cell0, ncell, a0 + 4 * pass, na);
-            if (p.nb) stage_rows(su, CCH + 1, p.dir + (size_t)b * p.HW * p.A * p.nb, p.nb, 0, p.nb, p.A, cell0, ncell, a0 + 4 * pass, na);
+            stage_rows<DH_THREADS, TC, false>(sreg, 7, p.reg + (size_t)b * p.HW * p.A * 7, 7, 0, 7, p.A, cell0, ncell, a0 + 4 * pass,
+                                              na);
+            if (p.nb)
+                stage_rows<DH_THREADS, TC, false>(su, CCH + 1, p.dir + (size_t)b * p.HW * p.A * p.nb, p.nb, 0, p.nb, p.A, cell0, ncell,
+                                                  a0 + 4 * pass, na);
             __syncthreads();
             // (rows that are not active read stale LDS; their results are dropped below)
             anchor_row(p, tab, active ? a0 + al : a0, active ? cell0 + lane : cell0, f, box, score, label);

@@ -11,7 +11,7 @@
 //                 through LDS in memory order (load_spans, the inverse of flush_spans); per_anchor leaves the same way.
 //     nchw        channel planes are unit-stride in the cell: loads and gradient stores of a wave are 256 contiguous bytes.
 //     nhwc        a pass (64 cells x 4 anchors) is staged through LDS in memory order (stage_rows), the thread that owns a row
-//                 overwrites its values with their gradients, and the image goes back in memory order (stage_rows<true>): class
+//                 overwrites its values with their gradients, and the image goes back in memory order (stage_rows, OUT): class
 //                 logits in chunks of 8 classes.
 // centre head     memset(num_pos) | count | heat map | boxes | finish.
 //   heat map      a workgroup owns 256 consecutive cells, one per thread, classes ascending; nhwc staged 16 classes at a time.
@@ -23,7 +23,7 @@
 
 namespace {
 
-#include "prims.h"       // load_spans, flush_spans
+#include "prims.h"       // load_spans, flush_spans, stage_rows
 
 constexpr int DL_THREADS = 256;
 constexpr int TC = 64;             // cells of an anchor tile
@@ -87,20 +87,6 @@ __device__ __forceinline__ void sigmoid2(float x, float e, float &p, float &pc) 
     const float big = 1.0f / den, small = e / den;
     p = x >= 0.0f ? big : small;
     pc = x >= 0.0f ? small : big;
-}
-
-// rows (al, cell) of a pass <-> lds[(al * 64 + cell) * ld + e], e < len: channels ch0 .. ch0 + len - 1 of anchor a0 + al out of
-// CHA per anchor; all 256 threads walk the floats of the pass in memory order (nhwc)
-template <bool OUT, class P>
-__device__ __forceinline__ void stage_rows(float *lds, int ld, P *scene, int CHA, int ch0, int len, int A, int cell0, int ncell, int a0, int na) {
-    const int n = ncell * na * len;
-    for (int i = threadIdx.x; i < n; i += DL_THREADS) {
-        const int row = i / len, e = i - row * len;
-        const int cell = row / na, al = row - cell * na;
-        P *g = scene + ((size_t)(cell0 + cell) * A + a0 + al) * CHA + ch0 + e;
-        if constexpr (OUT) *g = lds[(al * TC + cell) * ld + e];
-        else lds[(al * TC + cell) * ld + e] = *g;
-    }
 }
 
 __global__ __launch_bounds__(DL_THREADS) void anchor_count_kernel(const int32_t *labels, int K, int32_t *num_pos) {
@@ -231,8 +217,8 @@ __global__ __launch_bounds__(DL_THREADS) void anchor_loss_kernel(const AncL p) {
         for (int j = 0; j < 7; ++j) t[j] = stgt[slot * 7 + j];
         if (NHWC) {
             __syncthreads();
-            stage_rows<false>(sreg, 7, sregm, 7, 0, 7, p.A, cell0, ncell, pa0, na);
-            if (p.nb) stage_rows<false>(su, CCH + 1, sdir, p.nb, 0, p.nb, p.A, cell0, ncell, pa0, na);
+            stage_rows<DL_THREADS, TC, false>(sreg, 7, sregm, 7, 0, 7, p.A, cell0, ncell, pa0, na);
+            if (p.nb) stage_rows<DL_THREADS, TC, false>(su, CCH + 1, sdir, p.nb, 0, p.nb, p.A, cell0, ncell, pa0, na);
             __syncthreads();
 #pragma unroll
             for (int j = 0; j < 7; ++j) r[j] = sreg[tid * 7 + j];
@@ -283,8 +269,8 @@ __global__ __launch_bounds__(DL_THREADS) void anchor_loss_kernel(const AncL p) {
         }
         if (NHWC) {
             __syncthreads();
-            stage_rows<true>(sreg, 7, gregm, 7, 0, 7, p.A, cell0, ncell, pa0, na);
-            if (p.nb) stage_rows<true>(su, CCH + 1, gdirm, p.nb, 0, p.nb, p.A, cell0, ncell, pa0, na);
+            stage_rows<DL_THREADS, TC, true>(sreg, 7, gregm, 7, 0, 7, p.A, cell0, ncell, pa0, na);
+            if (p.nb) stage_rows<DL_THREADS, TC, true>(su, CCH + 1, gdirm, p.nb, 0, p.nb, p.A, cell0, ncell, pa0, na);
         }
         // ---- classification, classes ascending
         const bool live = label != -2;
@@ -293,7 +279,7 @@ __global__ __launch_bounds__(DL_THREADS) void anchor_loss_kernel(const AncL p) {
             const int len = min(CCH, p.C - c0);
             if (NHWC) {
                 __syncthreads();
-                stage_rows<false>(su, CCH + 1, scls, p.C, c0, len, p.A, cell0, ncell, pa0, na);
+                stage_rows<DL_THREADS, TC, false>(su, CCH + 1, scls, p.C, c0, len, p.A, cell0, ncell, pa0, na);
                 __syncthreads();
             }
             if (NHWC || c0) {
@@ -311,7 +297,7 @@ __global__ __launch_bounds__(DL_THREADS) void anchor_loss_kernel(const AncL p) {
             }
             if (NHWC) {
                 __syncthreads();
-                stage_rows<true>(su, CCH + 1, gcls, p.C, c0, len, p.A, cell0, ncell, pa0, na);
+                stage_rows<DL_THREADS, TC, true>(su, CCH + 1, gcls, p.C, c0, len, p.A, cell0, ncell, pa0, na);
             }
         }
         if (active) {

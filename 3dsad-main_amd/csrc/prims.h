@@ -1,7 +1,8 @@
 // Device primitives that more than one translation unit needs: the vector types of the MFMA kernels, the cross-lane
 // (DPP / readlane) unsigned maxima of the samplers, the LDS-DMA load with its wait, the float atomic max of the pooled
-// outputs, and the tile-image span copies of the dense head kernels.  Included inside each file's anonymous namespace, like reg_common.h and vox_hash.h (which include it).  ONE
-// definition of each: a helper moves here when a second file needs it; a helper with a single user stays in that file.
+// outputs, and the tile-image span copies and the pass staging of the dense head kernels.  Included inside each file's
+// anonymous namespace, like reg_common.h and vox_hash.h (which include it).  ONE definition of each: a helper moves here when
+// a second file needs it; a helper with a single user stays in that file.
 #pragma once
 
 typedef unsigned long long u64;
@@ -138,5 +139,21 @@ __device__ __forceinline__ void load_spans(T *img, const T *src, int ncell, int 
     for (int i = threadIdx.x; i < n; i += THREADS) {
         const int c = i / seg;
         img[i] = src[(size_t)c * stride + (i - c * seg)];
+    }
+}
+
+// The channels-last (nhwc) passes of the anchor head (dense_head.hip, dense_loss.hip): rows (al, cell) of a pass <->
+// lds[(al * CELLS + cell) * ld + e], e < len: channels ch0 .. ch0 + len - 1 of anchor a0 + al out of CHA per anchor, CELLS the
+// cells of an anchor tile.  All THREADS threads walk the floats of the pass in memory order; OUT: the image goes back to memory.
+template <int THREADS, int CELLS, bool OUT, class P>
+__device__ __forceinline__ void stage_rows(float *lds, int ld, P *scene, int CHA, int ch0, int len, int A, int cell0, int ncell, int a0,
+                                           int na) {
+    const int n = ncell * na * len;
+    for (int i = threadIdx.x; i < n; i += THREADS) {
+        const int row = i / len, e = i - row * len;
+        const int cell = row / na, al = row - cell * na;
+        P *g = scene + ((size_t)(cell0 + cell) * A + a0 + al) * CHA + ch0 + e;
+        if constexpr (OUT) *g = lds[(al * CELLS + cell) * ld + e];
+        else lds[(al * CELLS + cell) * ld + e] = *g;
     }
 }

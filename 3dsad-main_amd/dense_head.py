@@ -8,7 +8,6 @@ is trained against, from the same configuration (``decoder.assigner(...)``), and
 map, wrapped in an autograd Function, so ``loss.sum().backward()`` reaches the convolutions."""
 from typing import Optional, Sequence, Tuple
 
-import numpy as np
 import torch
 from torch import nn
 
@@ -24,8 +23,7 @@ def anchor_grid(point_range: Sequence[float], H: int, W: int) -> Tuple[Tuple[flo
         raise ValueError(f"anchor_grid: need H, W >= 1 (got {H}, {W})")
     sx = (hi_x - lo_x) / (W - 1) if W > 1 else 0.0
     sy = (hi_y - lo_y) / (H - 1) if H > 1 else 0.0
-    f = lambda v: float(np.float32(v))  # noqa: E731
-    return (f(lo_x), f(lo_y)), (f(sx), f(sy))
+    return (ops._f32(lo_x), ops._f32(lo_y)), (ops._f32(sx), ops._f32(sy))
 
 
 def _predict(boxes, scores, labels, iou_thr, score_thr, pre_max, post_max, class_aware):
@@ -40,9 +38,7 @@ class AnchorHeadDecoder(nn.Module):
     def __init__(self, sizes, z_center, rotations, origin, step, dir_offset: float = 0.78539, dir_limit_offset: float = 0.0,
                  layout: str = "nchw"):
         super().__init__()
-        self.sizes = np.asarray(sizes, dtype=np.float32).reshape(-1, 3)
-        self.z_center = np.asarray(z_center, dtype=np.float32).reshape(-1)
-        self.rotations = np.asarray(rotations, dtype=np.float32).reshape(-1)
+        self.sizes, self.z_center, self.rotations = ops._anchor_arrays(sizes, z_center, rotations)
         self.origin, self.step = (float(origin[0]), float(origin[1])), (float(step[0]), float(step[1]))
         self.dir_offset, self.dir_limit_offset, self.layout = float(dir_offset), float(dir_limit_offset), layout
 
@@ -107,9 +103,7 @@ class AnchorTargetAssigner(nn.Module):
     def __init__(self, sizes, z_center, rotations, origin, step, pos_thr, neg_thr, size_class=None, nb: int = 0,
                  dir_offset: float = 0.78539):
         super().__init__()
-        self.sizes = np.asarray(sizes, dtype=np.float32).reshape(-1, 3)
-        self.z_center = np.asarray(z_center, dtype=np.float32).reshape(-1)
-        self.rotations = np.asarray(rotations, dtype=np.float32).reshape(-1)
+        self.sizes, self.z_center, self.rotations = ops._anchor_arrays(sizes, z_center, rotations)
         self.origin, self.step = (float(origin[0]), float(origin[1])), (float(step[0]), float(step[1]))
         self.pos_thr, self.neg_thr, self.size_class = pos_thr, neg_thr, size_class
         self.nb, self.dir_offset = int(nb), float(dir_offset)

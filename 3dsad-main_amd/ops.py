@@ -151,6 +151,61 @@ def _need(t: torch.Tensor, name: str, dtype, ndim: int) -> torch.Tensor:
     return t.contiguous()
 
 
+def _f32(v) -> float:
+    return float(np.float32(v))
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return t.data_ptr() if t is not None else None
+
+
+def _results(*ts):
+    """The results that were asked for (the others are ``None``): the only one alone, several as a tuple."""
+    res = tuple(t for t in ts if t is not None)
+    return res[0] if len(res) == 1 else res
+
+
+def _offsets(offsets: torch.Tensor, dev, of: str) -> int:
+    """B of offsets [B+1] (already through ``_need``), which live on ``dev``, the device of ``of``."""
+    if offsets.device != dev:
+        raise ValueError(f"offsets must be on the device of {of}")
+    B = offsets.shape[0] - 1
+    if B < 1:
+        raise ValueError("offsets must have B + 1 >= 2 entries")
+    return B
+
+
+def _outputs(spec, out: Optional[tuple], dev, of: str) -> tuple:
+    """The buffers a call writes.  ``spec`` = ((name, shape, dtype), ...); ``out`` checked against it, or new buffers."""
+    if out is None:
+        return tuple(_empty(shape, dtype=dt, device=dev) for _, shape, dt in spec)
+    ok = len(out) == len(spec) and all(isinstance(t, torch.Tensor) and tuple(t.shape) == tuple(shape) and t.dtype == dt
+                                       and t.is_contiguous() and t.device == dev for t, (_, shape, dt) in zip(out, spec))
+    if not ok:
+        want = ", ".join(f"{n} {list(shape)} {str(dt).replace('torch.', '')}" for n, shape, dt in spec)
+        raise ValueError(f"out: expected contiguous ({want}) on the device of {of}")
+    return tuple(out)
+
+
+def _bytes(fn_name: str, *args) -> int:
+    """The byte count of a workspace query of the library that answers through a size_t (and refuses sizes it does not support)."""
+    n = ctypes.c_size_t(0)
+    check(getattr(lib(), fn_name)(*args, ctypes.byref(n)), fn_name)
+    return n.value
+
+
+def _workspace(nbytes: int, given: Optional[torch.Tensor], dev, maker: str, align: int = 1) -> torch.Tensor:
+    """Scratch of ``nbytes`` bytes on ``dev``: a new buffer, or the caller's (from ``maker``), which a kernel will write over its
+    whole length: a tensor, on that GPU, contiguous, long enough and aligned, or the call is refused."""
+    if given is None:
+        return _empty((nbytes,), dtype=torch.uint8, device=dev)
+    if (not isinstance(given, torch.Tensor) or not given.is_cuda or given.device != dev or not given.is_contiguous()
+            or given.numel() * given.element_size() < nbytes or given.data_ptr() % align):
+        raise ValueError(f"workspace: expected a contiguous GPU buffer of at least {nbytes} bytes on {dev}"
+                         + (f", {align}-byte aligned" if align > 1 else "") + f" ({maker})")
+    return given
+
+
 def fps(xyz: torch.Tensor, npoint: int) -> torch.Tensor:
     """Farthest point sampling (SPEC.md §2).  xyz [B,N,3] f32 -> idx [B,npoint] int32."""
     xyz = _need(xyz, "xyz", torch.float32, 3)
@@ -163,8 +218,7 @@ def fps(xyz: torch.Tensor, npoint: int) -> torch.Tensor:
     ws_bytes = lib().sad_fps_workspace_bytes(B, N)
     ws = _empty((ws_bytes,), dtype=torch.uint8, device=xyz.device) if ws_bytes else None
     with _timed("fps", f"N{N}"):
-        check(lib().sad_fps_f32(xyz.data_ptr(), B, N, npoint, idx.data_ptr(),
-                                ws.data_ptr() if ws is not None else None, _stream()), "sad_fps_f32")
+        check(lib().sad_fps_f32(xyz.data_ptr(), B, N, npoint, idx.data_ptr(), _ptr(ws), _stream()), "sad_fps_f32")
     return idx
 
 
@@ -247,14 +301,9 @@ def subsample_pad(points: torch.Tensor, offsets: torch.Tensor, n_points: int, se
     repeats, empty = zeros.  Same rows as the host loader ``io.fix_size(points_b, n_points, seed, scene=b)``."""
     points = _need(points, "points", torch.float32, 2)
     offsets = _need(offsets, "offsets", torch.int32, 1)
-    B = offsets.shape[0] - 1
-    if B < 1:
-        raise ValueError("offsets must have B + 1 >= 2 entries")
+    B = _offsets(offsets, points.device, "points")
     C = points.shape[1]
-    if out is None:
-        out = _empty((B, n_points, C), dtype=torch.float32, device=points.device)
-    elif tuple(out.shape) != (B, n_points, C) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != points.device:
-        raise ValueError(f"out: expected a contiguous float32 [{B},{n_points},{C}] tensor on {points.device}")
+    out, = _outputs((("out", (B, n_points, C), torch.float32),), None if out is None else (out,), points.device, "points")
     check(lib().sad_subsample_pad_f32(points.data_ptr(), offsets.data_ptr(), B, C, int(n_points),
                                       int(seed) & 0xFFFFFFFF, out.data_ptr(), _stream()), "sad_subsample_pad_f32")
     return out
@@ -278,8 +327,7 @@ def ball_query(radius: Union[float, torch.Tensor], nsample: int, xyz: torch.Tens
         check(lib().sad_ball_query_f32(xyz.data_ptr(), new_xyz.data_ptr(), 0.0, rad.data_ptr(), B, N, M,
                                        nsample, idx.data_ptr(), _stream()), "sad_ball_query_f32")
     else:
-        check(lib().sad_ball_query_f32(xyz.data_ptr(), new_xyz.data_ptr(), float(np.float32(radius)),
-                                       None, B, N, M, nsample, idx.data_ptr(), _stream()),
+        check(lib().sad_ball_query_f32(xyz.data_ptr(), new_xyz.data_ptr(), _f32(radius), None, B, N, M, nsample, idx.data_ptr(), _stream()),
               "sad_ball_query_f32")
     return idx
 
@@ -300,7 +348,7 @@ def ball_query_multi(radii: Sequence[float], nsamples: Sequence[int], xyz: torch
     if n != len(nsamples) or not 1 <= n <= _lib.MAX_RADII:
         raise ValueError(f"need 1..{_lib.MAX_RADII} radii with matching nsamples")
     outs = [_empty((B, M, s), dtype=torch.int32, device=xyz.device) for s in nsamples]
-    r_arr = (ctypes.c_float * n)(*[float(np.float32(r)) for r in radii])
+    r_arr = (ctypes.c_float * n)(*[_f32(r) for r in radii])
     s_arr = (ctypes.c_int * n)(*[int(s) for s in nsamples])
     p_arr = (vp * n)(*[o.data_ptr() for o in outs])
     cnts = [_empty((B, M), dtype=torch.int32, device=xyz.device) for _ in nsamples] if return_counts else None
@@ -426,15 +474,20 @@ def boxes_iou3d(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return _boxes_iou(a, b, 1, "3d")
 
 
-def points_in_boxes(xyz: torch.Tensor, boxes: torch.Tensor) -> torch.Tensor:
-    """For each point the lowest index of a box that contains it, else -1 (SPEC.md §19.1).  xyz [B,N,3] f32,
-    boxes [B,K,D] f32 (D >= 7, centre / size / yaw) -> box_idx [B,N] int32."""
+def _xyz_boxes(xyz: torch.Tensor, boxes: torch.Tensor):
+    """xyz [B,N,3] and boxes [B,K,D] of one batch on one device -> (xyz, boxes, B, N, K, D)."""
     xyz = _need(xyz, "xyz", torch.float32, 3)
     boxes = _boxes(boxes, "boxes")
     B, N, three = xyz.shape
     if three != 3 or boxes.shape[0] != B or boxes.device != xyz.device:
         raise ValueError("xyz [B,N,3] and boxes [B,K,D] on one device expected")
-    K, D = boxes.shape[1], boxes.shape[2]
+    return xyz, boxes, B, N, boxes.shape[1], boxes.shape[2]
+
+
+def points_in_boxes(xyz: torch.Tensor, boxes: torch.Tensor) -> torch.Tensor:
+    """For each point the lowest index of a box that contains it, else -1 (SPEC.md §19.1).  xyz [B,N,3] f32,
+    boxes [B,K,D] f32 (D >= 7, centre / size / yaw) -> box_idx [B,N] int32."""
+    xyz, boxes, B, N, K, D = _xyz_boxes(xyz, boxes)
     box_idx = _empty((B, N), dtype=torch.int32, device=xyz.device)
     with _timed("points_in_boxes", f"N{N}K{K}"):
         check(lib().sad_points_in_boxes_f32(xyz.data_ptr(), boxes.data_ptr(), B, N, K, D, box_idx.data_ptr(), _stream()),
@@ -448,11 +501,7 @@ def roipoint_pool3d(xyz: torch.Tensor, feat_pm: Optional[torch.Tensor], boxes: t
     ``num_sampled_points`` = S points in ascending index order, repeated cyclically when fewer fall inside.
     xyz [B,N,3], feat_pm [B,N,C] point-major or None, boxes [B,K,D] -> (pooled [B,K,S,3+C] rows [xyz || feat],
     empty [B,K] int32 1 = no point inside (rows zero)[, idx [B,K,S] int32]).  1 <= S <= 8192.  No gradient."""
-    xyz = _need(xyz, "xyz", torch.float32, 3)
-    boxes = _boxes(boxes, "boxes")
-    B, N, three = xyz.shape
-    if three != 3 or boxes.shape[0] != B or boxes.device != xyz.device:
-        raise ValueError("xyz [B,N,3] and boxes [B,K,D] on one device expected")
+    xyz, boxes, B, N, K, D = _xyz_boxes(xyz, boxes)
     C = 0
     if feat_pm is not None:
         feat_pm = _need(feat_pm, "feat_pm", torch.float32, 3)
@@ -462,14 +511,13 @@ def roipoint_pool3d(xyz: torch.Tensor, feat_pm: Optional[torch.Tensor], boxes: t
     S = int(num_sampled_points)
     if S < 1:
         raise ValueError(f"num_sampled_points={S} must be >= 1")
-    K, D = boxes.shape[1], boxes.shape[2]
     pooled = _empty((B, K, S, 3 + C), dtype=torch.float32, device=xyz.device)
     empty = _empty((B, K), dtype=torch.int32, device=xyz.device)
     idx = _empty((B, K, S), dtype=torch.int32, device=xyz.device) if return_idx else None
     with _timed("roipoint_pool3d", f"N{N}K{K}S{S}C{C}"):
         check(lib().sad_roipoint_pool3d_f32(xyz.data_ptr(), feat_pm.data_ptr() if C else None, boxes.data_ptr(), B, N, K, D, C,
-                                            float(np.float32(extra_width)), S, pooled.data_ptr(), empty.data_ptr(),
-                                            idx.data_ptr() if return_idx else None, _stream()), "sad_roipoint_pool3d_f32")
+                                            _f32(extra_width), S, pooled.data_ptr(), empty.data_ptr(), _ptr(idx), _stream()),
+              "sad_roipoint_pool3d_f32")
     return (pooled, empty, idx) if return_idx else (pooled, empty)
 
 
@@ -492,11 +540,7 @@ def _voxel_points(points: torch.Tensor, offsets: Optional[torch.Tensor], name: s
     else:
         points = _need(points, name, torch.float32, 2)
         offsets = _need(offsets, "offsets", torch.int32, 1)
-        if offsets.device != points.device:
-            raise ValueError(f"offsets must be on the device of {name}")
-        B = offsets.shape[0] - 1
-        if B < 1:
-            raise ValueError("offsets must have B + 1 >= 2 entries")
+        B = _offsets(offsets, points.device, name)
     if points.shape[1] < min_c:
         raise ValueError(f"{name}: rows need at least {min_c} columns, got {points.shape[1]}")
     return points, offsets, B
@@ -506,25 +550,12 @@ def _voxel_grid(voxel_size, point_range):
     """(vx,vy,vz), (x0,y0,z0,x1,y1,z1) -> two host float arrays, Python floats rounded to binary32."""
     if len(voxel_size) != 3 or len(point_range) != 6:
         raise ValueError("voxel_size must have 3 entries (vx,vy,vz) and point_range 6 (x0,y0,z0,x1,y1,z1)")
-    return ((ctypes.c_float * 3)(*[float(np.float32(v)) for v in voxel_size]),
-            (ctypes.c_float * 6)(*[float(np.float32(v)) for v in point_range]))
+    return (ctypes.c_float * 3)(*[_f32(v) for v in voxel_size]), (ctypes.c_float * 6)(*[_f32(v) for v in point_range])
 
 
 def voxel_workspace(total_points: int, B: int, max_voxels: int, device) -> torch.Tensor:
     """Scratch of the §20 operators for (total_points, B, max_voxels); contents arbitrary, reusable call after call on one stream."""
-    n = ctypes.c_size_t(0)
-    check(lib().sad_voxel_workspace_bytes(int(total_points), int(B), int(max_voxels), ctypes.byref(n)), "sad_voxel_workspace_bytes")
-    return _empty((n.value,), dtype=torch.uint8, device=device)
-
-
-def _voxel_ws(ws: Optional[torch.Tensor], total: int, B: int, V: int, device) -> torch.Tensor:
-    if ws is None:
-        return voxel_workspace(total, B, V, device)
-    n = ctypes.c_size_t(0)
-    check(lib().sad_voxel_workspace_bytes(int(total), int(B), int(V), ctypes.byref(n)), "sad_voxel_workspace_bytes")
-    if not ws.is_cuda or ws.device != device or not ws.is_contiguous() or ws.numel() * ws.element_size() < n.value or ws.data_ptr() % 16:
-        raise ValueError(f"workspace: expected a contiguous 16-byte aligned GPU buffer of at least {n.value} bytes (ops.voxel_workspace)")
-    return ws
+    return _workspace(_bytes("sad_voxel_workspace_bytes", int(total_points), int(B), int(max_voxels)), None, device, "ops.voxel_workspace")
 
 
 def voxel_coords(points: torch.Tensor, offsets: Optional[torch.Tensor], voxel_size, point_range) -> torch.Tensor:
@@ -552,7 +583,7 @@ def voxel_index(points: torch.Tensor, offsets: Optional[torch.Tensor], voxel_siz
         raise ValueError(f"max_voxels={V} must be >= 1")
     total, C = points.shape
     dev = points.device
-    ws = _voxel_ws(workspace, total, B, V, dev)
+    ws = _workspace(_bytes("sad_voxel_workspace_bytes", total, B, V), workspace, dev, "ops.voxel_workspace", 16)
     p2v = _empty((total,), dtype=torch.int32, device=dev)
     coors = _empty((B, V, 3), dtype=torch.int32, device=dev)
     count = _empty((B, V), dtype=torch.int32, device=dev)
@@ -575,7 +606,7 @@ def voxelize(points: torch.Tensor, offsets: Optional[torch.Tensor], voxel_size, 
         raise ValueError(f"max_points={T} and max_voxels={V} must be >= 1")
     total, C = points.shape
     dev = points.device
-    ws = _voxel_ws(workspace, total, B, V, dev)
+    ws = _workspace(_bytes("sad_voxel_workspace_bytes", total, B, V), workspace, dev, "ops.voxel_workspace", 16)
     voxels = _empty((B, V, T, C), dtype=torch.float32, device=dev)
     coors = _empty((B, V, 3), dtype=torch.int32, device=dev)
     num_points = _empty((B, V), dtype=torch.int32, device=dev)
@@ -604,16 +635,14 @@ def voxel_reduce(feat: torch.Tensor, point2voxel: torch.Tensor, offsets: Optiona
     if V < 1:
         raise ValueError(f"max_voxels={V} must be >= 1")
     dev = feat.device
-    ws = _voxel_ws(workspace, total, B, V, dev)
+    ws = _workspace(_bytes("sad_voxel_workspace_bytes", total, B, V), workspace, dev, "ops.voxel_workspace", 16)
     out = _empty((B, V, Cf), dtype=torch.float32, device=dev)
     arg = _empty((B, V, Cf), dtype=torch.int32, device=dev) if mode == "max" else None
     count = _empty((B, V), dtype=torch.int32, device=dev) if return_count else None
     with _timed("voxel_reduce", f"{mode}n{total}V{V}C{Cf}"):
         check(lib().sad_voxel_reduce_f32(feat.data_ptr(), point2voxel.data_ptr(), offsets.data_ptr(), total, B, Cf, V, VOXEL_MODES[mode],
-                                         out.data_ptr(), arg.data_ptr() if arg is not None else None,
-                                         count.data_ptr() if count is not None else None, ws.data_ptr(), _stream()), "sad_voxel_reduce_f32")
-    res = (out,) + ((arg,) if arg is not None else ()) + ((count,) if return_count else ())
-    return res[0] if len(res) == 1 else res
+                                         out.data_ptr(), _ptr(arg), _ptr(count), ws.data_ptr(), _stream()), "sad_voxel_reduce_f32")
+    return _results(out, arg, count)
 
 
 def voxel_reduce_grad(grad_out: torch.Tensor, point2voxel: torch.Tensor, offsets: torch.Tensor, mode: str,
@@ -646,10 +675,8 @@ VFE_CLUSTER_CENTER, VFE_VOXEL_CENTER, VFE_RELU = 1, 2, 4
 def voxel_encode_workspace(total_points: int, B: int, max_voxels: int, cin: int, cout: int, device) -> torch.Tensor:
     """Scratch of ``voxel_encode`` / ``voxel_decorate`` (``cout=0``) for these sizes; contents arbitrary, reusable call after call
     on one stream."""
-    n = ctypes.c_size_t(0)
-    check(lib().sad_voxel_encode_workspace_bytes(int(total_points), int(B), int(max_voxels), int(cin), int(cout), ctypes.byref(n)),
-          "sad_voxel_encode_workspace_bytes")
-    return _empty((n.value,), dtype=torch.uint8, device=device)
+    return _workspace(_bytes("sad_voxel_encode_workspace_bytes", int(total_points), int(B), int(max_voxels), int(cin), int(cout)), None, device,
+                      "ops.voxel_encode_workspace")
 
 
 def _vfe_args(points, point2voxel, offsets, max_voxels, coors, voxel_size, point_range, cluster_center, voxel_center, vox_feat,
@@ -688,20 +715,10 @@ def _vfe_args(points, point2voxel, offsets, max_voxels, coors, voxel_size, point
         if T < 1:
             raise ValueError(f"max_points={T} must be >= 1 (None: no cap)")
     cin = C + 3 * cc + 3 * vc + Cv
-    n = ctypes.c_size_t(0)       # (Cin or Cout outside 1 .. 256: SAD_EUNSUPPORTED from here, before anything is launched)
-    check(lib().sad_voxel_encode_workspace_bytes(total, B, V, cin, cout, ctypes.byref(n)), "sad_voxel_encode_workspace_bytes")
-    if workspace is None:
-        workspace = _empty((n.value,), dtype=torch.uint8, device=dev)
-    elif (not workspace.is_cuda or workspace.device != dev or not workspace.is_contiguous()
-          or workspace.numel() * workspace.element_size() < n.value or workspace.data_ptr() % 16):
-        raise ValueError(f"workspace: expected a contiguous 16-byte aligned GPU buffer of at least {n.value} bytes "
-                         "(ops.voxel_encode_workspace)")
+    # (Cin or Cout outside 1 .. 256: SAD_EUNSUPPORTED from the size query, before anything is launched)
+    workspace = _workspace(_bytes("sad_voxel_encode_workspace_bytes", total, B, V, cin, cout), workspace, dev, "ops.voxel_encode_workspace", 16)
     flags = (VFE_CLUSTER_CENTER if cc else 0) | (VFE_VOXEL_CENTER if vc else 0)
     return points, point2voxel, offsets, coors, vox_feat, total, B, C, V, Cv, vs, pr, flags, T, cin, workspace
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return t.data_ptr() if t is not None else None
 
 
 def voxel_decorate(points: torch.Tensor, point2voxel: torch.Tensor, offsets: Optional[torch.Tensor], max_voxels: int,
@@ -749,8 +766,7 @@ def voxel_encode(points: torch.Tensor, point2voxel: torch.Tensor, offsets: Optio
         check(lib().sad_voxel_encode_f32(points.data_ptr(), point2voxel.data_ptr(), offsets.data_ptr(), _ptr(coors), _ptr(vox_feat), total, B, C,
                                          V, Cv, vs, pr, weight.data_ptr(), bias.data_ptr(), cout, flags | (VFE_RELU if relu else 0), T,
                                          pooled.data_ptr(), _ptr(arg), _ptr(pointwise), ws.data_ptr(), _stream()), "sad_voxel_encode_f32")
-    res = (pooled,) + ((arg,) if return_arg else ()) + ((pointwise,) if return_pointwise else ())
-    return res[0] if len(res) == 1 else res
+    return _results(pooled, arg, pointwise)
 
 
 def _int3(v, name: str, lo: int):
@@ -794,12 +810,7 @@ def _sparse_coors(coors: torch.Tensor, offsets: torch.Tensor):
     offsets = _need(offsets, "offsets", torch.int32, 1)
     if coors.shape[1] != 3:
         raise ValueError(f"coors: [Nv,3] (z,y,x) expected, got {tuple(coors.shape)}")
-    if offsets.device != coors.device:
-        raise ValueError("offsets must be on the device of coors")
-    B = offsets.shape[0] - 1
-    if B < 1:
-        raise ValueError("offsets must have B + 1 >= 2 entries")
-    return coors, offsets, B
+    return coors, offsets, _offsets(offsets, coors.device, "coors")
 
 
 def sparse_conv_index(coors: torch.Tensor, offsets: torch.Tensor, spatial_shape, kernel, stride=1, padding=0, subm: bool = False,
@@ -815,9 +826,7 @@ def sparse_conv_index(coors: torch.Tensor, offsets: torch.Tensor, spatial_shape,
     coors, offsets, B = _sparse_coors(coors, offsets)
     Nv, Kvol, dev = coors.shape[0], K[0] * K[1] * K[2], coors.device
     cG, cK, cs, cp = [(ctypes.c_int * 3)(*t) for t in (G, K, s, p)]
-    n = ctypes.c_size_t(0)
-    check(lib().sad_spconv_workspace_bytes(Nv, B, cK, cs, int(subm), ctypes.byref(n)), "sad_spconv_workspace_bytes")
-    ws = torch.empty((n.value,), dtype=torch.uint8, device=dev)
+    ws = torch.empty((_bytes("sad_spconv_workspace_bytes", Nv, B, cK, cs, int(subm)),), dtype=torch.uint8, device=dev)
     if subm:
         nbr = torch.empty((Nv, Kvol), dtype=torch.int32, device=dev)
         with _timed("spconv_index", f"subm n{Nv}k{Kvol}"):
@@ -857,7 +866,7 @@ class PackedSparseWeight:
             raise RuntimeError(f"sparse_conv: Cin = {self.cin}, Cout = {self.cout} unsupported (1 .. 256 each)")
         self.has_bias = bias is not None
         self.packed = torch.empty((n,), dtype=torch.float32, device=weight.device)
-        check(lib().sad_spconv_pack_f32(weight.data_ptr(), bias.data_ptr() if bias is not None else None, self.kvol, self.cin, self.cout,
+        check(lib().sad_spconv_pack_f32(weight.data_ptr(), _ptr(bias), self.kvol, self.cin, self.cout,
                                         self.packed.data_ptr(), _stream()), "sad_spconv_pack_f32")
 
 
@@ -887,8 +896,8 @@ def sparse_conv(feat: torch.Tensor, nbr: torch.Tensor, weight, bias: Optional[to
             raise ValueError(f"residual: [{No},{pw.cout}] on the device of feat expected, got {tuple(residual.shape)}")
     out = torch.empty((No, pw.cout), dtype=torch.float32, device=dev)
     with _timed("spconv", f"n{No}k{pw.kvol}c{pw.cin}x{pw.cout}"):
-        check(lib().sad_spconv_f32(feat.data_ptr(), nbr.data_ptr(), pw.packed.data_ptr(), residual.data_ptr() if residual is not None else None,
-                                   int(bool(relu)), Nv, No, pw.kvol, pw.cin, pw.cout, out.data_ptr(), _stream()), "sad_spconv_f32")
+        check(lib().sad_spconv_f32(feat.data_ptr(), nbr.data_ptr(), pw.packed.data_ptr(), _ptr(residual), int(bool(relu)), Nv, No, pw.kvol,
+                                   pw.cin, pw.cout, out.data_ptr(), _stream()), "sad_spconv_f32")
     return out
 
 
@@ -932,15 +941,13 @@ def sparse_conv_grad_weight(feat: torch.Tensor, nbr: torch.Tensor, g: torch.Tens
         raise ValueError(f"Kvol = {kvol} must be in 1 .. 27, Cin = {cin} and Cout = {cout} in 1 .. 256")
     if not (bias or weight):
         raise ValueError("sparse_conv_grad_weight: nothing asked for (bias=False, weight=False)")
-    n = ctypes.c_size_t(0)
-    check(lib().sad_spconv_grad_weight_workspace_bytes(No, kvol, cin, cout, ctypes.byref(n)), "sad_spconv_grad_weight_workspace_bytes")
-    ws = torch.empty((n.value,), dtype=torch.uint8, device=dev) if n.value else None
+    nbytes = _bytes("sad_spconv_grad_weight_workspace_bytes", No, kvol, cin, cout)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
     grad_w = torch.empty((kvol, cout, cin), dtype=torch.float32, device=dev) if weight else None
     grad_b = torch.empty((cout,), dtype=torch.float32, device=dev) if bias else None
     with _timed("spconv_grad_w", f"n{No}k{kvol}c{cin}x{cout}"):
-        check(lib().sad_spconv_grad_weight_f32(feat.data_ptr(), nbr.data_ptr(), g.data_ptr(), Nv, No, kvol, cin, cout, grad_w.data_ptr() if weight else None,
-                                               grad_b.data_ptr() if bias else None, ws.data_ptr() if ws is not None else None, _stream()),
-              "sad_spconv_grad_weight_f32")
+        check(lib().sad_spconv_grad_weight_f32(feat.data_ptr(), nbr.data_ptr(), g.data_ptr(), Nv, No, kvol, cin, cout, _ptr(grad_w), _ptr(grad_b),
+                                               _ptr(ws), _stream()), "sad_spconv_grad_weight_f32")
     return grad_w, grad_b
 
 
@@ -1026,14 +1033,21 @@ def sparse_to_dense(feat: torch.Tensor, out_coors: torch.Tensor, out_offsets: to
         raise ValueError("out_coors must have one row per row of feat, on its device")
     if C < 1:
         raise ValueError("feat: at least one channel expected")
-    n = ctypes.c_size_t(0)
-    check(lib().sad_sparse_to_dense_workspace_bytes(B, cO, ctypes.byref(n)), "sad_sparse_to_dense_workspace_bytes")
-    ws = torch.empty((n.value,), dtype=torch.uint8, device=feat.device)
+    ws = torch.empty((_bytes("sad_sparse_to_dense_workspace_bytes", B, cO),), dtype=torch.uint8, device=feat.device)
     dense = torch.empty((B, C) + O, dtype=torch.float32, device=feat.device)
     with _timed("sparse_to_dense", f"n{No}c{C}"):
         check(lib().sad_sparse_to_dense_f32(feat.data_ptr(), out_coors.data_ptr(), out_offsets.data_ptr(), No, B, C, cO, dense.data_ptr(),
                                             ws.data_ptr(), _stream()), "sad_sparse_to_dense_f32")
     return dense
+
+
+def _nms_outputs(B: int, K: int, P: int, out: Optional[tuple], dev) -> tuple:
+    """(keep [B,K], order [B,P], count [B], the caller's workspace or ``None``) of an NMS call; ``out`` = (keep, order, count,
+    workspace): the three through ``_outputs``, the fourth is for ``_workspace``."""
+    spec = (("keep", (B, K), torch.int32), ("order", (B, P), torch.int32), ("count", (B,), torch.int32))
+    if out is not None and len(out) != 4:
+        raise ValueError("out: expected (keep, order, count, workspace)")
+    return _outputs(spec, None if out is None else out[:3], dev, "boxes") + (None if out is None else out[3],)
 
 
 def nms_bev_buffers(B: int, K: int, device) -> tuple:
@@ -1054,25 +1068,15 @@ def nms_bev(boxes: torch.Tensor, iou_thr: float, score_thr: float = 0.0, single_
     B, K, nine = boxes.shape
     if nine != 9:
         raise ValueError("boxes: last dim must be 9 (x,y,z,l,w,h,yaw,score,label)")
-    ws = None
-    if out is not None:                 # buffers from nms_bev_buffers(B, K, device)
-        keep, order, count, ws = out
-        if tuple(keep.shape) != (B, K) or tuple(order.shape) != (B, K) or tuple(count.shape) != (B,) or keep.device != boxes.device:
-            raise ValueError("out: buffers of another shape or device (nms_bev_buffers(B, K, device))")
-    else:
-        keep = _empty((B, K), dtype=torch.int32, device=boxes.device)
-        order = _empty((B, K), dtype=torch.int32, device=boxes.device)
-        count = _empty((B,), dtype=torch.int32, device=boxes.device)
+    keep, order, count, ws = _nms_outputs(B, K, K, out, boxes.device)   # out: buffers from nms_bev_buffers(B, K, device)
+    if not single_kernel:
+        ws = _workspace(lib().sad_nms_bev_workspace_bytes(B, K), ws, boxes.device, "ops.nms_bev_buffers")
     with _timed("nms", f"K{K}"):
         if single_kernel:
-            check(lib().sad_nms_bev_f32(boxes.data_ptr(), B, K, float(np.float32(iou_thr)),
-                                        float(np.float32(score_thr)), keep.data_ptr(), order.data_ptr(),
+            check(lib().sad_nms_bev_f32(boxes.data_ptr(), B, K, _f32(iou_thr), _f32(score_thr), keep.data_ptr(), order.data_ptr(),
                                         count.data_ptr(), _stream()), "sad_nms_bev_f32")
         else:
-            if ws is None:
-                ws = _empty((lib().sad_nms_bev_workspace_bytes(B, K),), dtype=torch.uint8, device=boxes.device)
-            check(lib().sad_nms_bev_ws_f32(boxes.data_ptr(), B, K, float(np.float32(iou_thr)),
-                                           float(np.float32(score_thr)), keep.data_ptr(), order.data_ptr(),
+            check(lib().sad_nms_bev_ws_f32(boxes.data_ptr(), B, K, _f32(iou_thr), _f32(score_thr), keep.data_ptr(), order.data_ptr(),
                                            count.data_ptr(), ws.data_ptr(), _stream()), "sad_nms_bev_ws_f32")
     return keep, order, count
 
@@ -1122,38 +1126,40 @@ def nms_boxes(boxes: torch.Tensor, scores: Optional[torch.Tensor], labels: Optio
         if tuple(labels.shape) != (B, K) or labels.device != boxes.device:
             raise ValueError("labels: expected [B,K] on the device of boxes")
     pre, post, P = _nms_boxes_limits(K, pre_max, post_max)
-    if out is not None:                 # buffers from nms_boxes_buffers(B, K, device, pre_max, post_max)
-        keep, order, count, ws = out
-        if (tuple(keep.shape) != (B, K) or tuple(order.shape) != (B, P) or tuple(count.shape) != (B,) or keep.device != boxes.device
-                or ws.numel() < lib().sad_nms_boxes_workspace_bytes(B, K, pre)):
-            raise ValueError("out: buffers of another shape, limits or device (nms_boxes_buffers(B, K, device, pre_max, post_max))")
-    else:
-        nbytes = lib().sad_nms_boxes_workspace_bytes(B, K, pre)
-        keep = _empty((B, K), dtype=torch.int32, device=boxes.device)
-        order = _empty((B, P), dtype=torch.int32, device=boxes.device)
-        count = _empty((B,), dtype=torch.int32, device=boxes.device)
-        ws = _empty((max(nbytes, 16),), dtype=torch.uint8, device=boxes.device)     # (0 bytes = unsupported: the call below says why)
+    keep, order, count, ws = _nms_outputs(B, K, P, out, boxes.device)   # out: buffers from nms_boxes_buffers(B, K, device, pre_max, post_max)
+    # 0 bytes = unsupported shape: the call below refuses it and says why, so a caller's workspace of any length passes here,
+    # and a new buffer gets 16 bytes so that it has an address
+    nbytes = lib().sad_nms_boxes_workspace_bytes(B, K, pre)
+    ws = _workspace(nbytes if ws is not None else max(nbytes, 16), ws, boxes.device, "ops.nms_boxes_buffers")
     with _timed("nms_boxes", f"K{K}P{min(K, pre)}"):
-        check(lib().sad_nms_boxes_f32(boxes.data_ptr(), D, scores.data_ptr(), labels.data_ptr() if labels is not None else None,
-                                      B, K, float(np.float32(iou_thr)), float(np.float32(score_thr)), pre, post,
+        check(lib().sad_nms_boxes_f32(boxes.data_ptr(), D, scores.data_ptr(), _ptr(labels), B, K, _f32(iou_thr), _f32(score_thr), pre, post,
                                       keep.data_ptr(), order.data_ptr(), count.data_ptr(), ws.data_ptr(), _stream()),
               "sad_nms_boxes_f32")
     return keep, order, count
 
 
-def _head_map(t: torch.Tensor, name: str, B: int, ch: int, H: int, W: int, layout: str) -> torch.Tensor:
-    """A head map [B,ch,H,W] (nchw) / [B,H,W,ch] (nhwc): contiguous f32, read where it is (no copy is ever made).  Shapes and
-    dtypes are judged before devices (``_head_devices``), so a wrong map is named whatever it lives on."""
+def _strict(t: torch.Tensor, name: str, dtype, shape, want: Optional[str] = None, how: str = "", dev=None) -> torch.Tensor:
+    """The strict policy of the dense family: a tensor of ``dtype`` and ``shape`` (``None``: any extent; ``want`` says it in the
+    caller's words), contiguous, read where it is (no copy is ever made).  Shapes and dtypes are judged before devices
+    (``_head_devices``; for a target, ``dev``: the maps' device), so a wrong tensor is named whatever it lives on."""
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name}: expected a torch.Tensor")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name}: expected dtype torch.float32, got {t.dtype}")
-    want = (B, ch, H, W) if layout == "nchw" else (B, H, W, ch)
-    if tuple(t.shape) != want:
-        raise ValueError(f"{name}: expected shape {want} for layout {layout!r} ({ch} channels), got {tuple(t.shape)}")
+    if t.dtype != dtype:
+        raise TypeError(f"{name}: expected dtype {dtype}, got {t.dtype}")
+    if t.dim() != len(shape) or any(w is not None and w != n for w, n in zip(shape, t.shape)):
+        raise ValueError(f"{name}: expected {want or f'shape {tuple(shape)}'}, got {tuple(t.shape)}")
     if not t.is_contiguous():
-        raise ValueError(f"{name}: must be contiguous in layout {layout!r} (the kernel reads the map where it is)")
+        raise ValueError(f"{name}: must be contiguous{how}")
+    if dev is not None and (not t.is_cuda or t.device != dev):
+        raise RuntimeError(f"{name}: expected a tensor on {dev} (sad_amd has no CPU path)")
     return t
+
+
+def _head_map(t: torch.Tensor, name: str, B: int, ch: int, H: int, W: int, layout: str) -> torch.Tensor:
+    """A head map [B,ch,H,W] (nchw) / [B,H,W,ch] (nhwc): contiguous f32."""
+    want = (B, ch, H, W) if layout == "nchw" else (B, H, W, ch)
+    return _strict(t, name, torch.float32, want, f"shape {want} for layout {layout!r} ({ch} channels)",
+                   f" in layout {layout!r} (the kernel reads the map where it is)")
 
 
 def _head_devices(named) -> torch.device:
@@ -1173,14 +1179,10 @@ def _head_index(index: Optional[torch.Tensor], B: int) -> int:
     """P of index [B,P] int32 (0 without one)."""
     if index is None:
         return 0
-    if not isinstance(index, torch.Tensor):
-        raise TypeError("index: expected a torch.Tensor")
-    if index.dtype != torch.int32:
-        raise TypeError(f"index: expected dtype torch.int32, got {index.dtype}")
-    if index.dim() != 2 or index.shape[0] != B or index.shape[1] < 1:
-        raise ValueError(f"index: expected [B,P] with B = {B} and P >= 1, got {tuple(index.shape)}")
-    if not index.is_contiguous():
-        raise ValueError("index: must be contiguous")
+    want = f"[B,P] with B = {B} and P >= 1"
+    _strict(index, "index", torch.int32, (B, None), want)
+    if index.shape[1] < 1:      # (an empty tensor is contiguous: still judged before contiguity)
+        raise ValueError(f"index: expected {want}, got {tuple(index.shape)}")
     return index.shape[1]
 
 
@@ -1196,24 +1198,44 @@ def _head_grid(first: torch.Tensor, name: str, layout: str) -> Tuple[int, int, i
     return (B, d1, d2, d3) if layout == "nchw" else (B, d3, d1, d2)
 
 
-def _head_outputs(B: int, rows: int, D: int, out: Optional[tuple], dev) -> tuple:
-    """(boxes [B,rows,D], scores [B,rows], labels [B,rows]) of a decode call: ``out`` checked, or new buffers."""
-    if out is None:
-        return (_empty((B, rows, D), dtype=torch.float32, device=dev), _empty((B, rows), dtype=torch.float32, device=dev),
-                _empty((B, rows), dtype=torch.int32, device=dev))
-    boxes, scores, labels = out
-    ok = (tuple(boxes.shape) == (B, rows, D) and tuple(scores.shape) == (B, rows) and tuple(labels.shape) == (B, rows)
-          and boxes.dtype == scores.dtype == torch.float32 and labels.dtype == torch.int32
-          and boxes.is_contiguous() and scores.is_contiguous() and labels.is_contiguous()
-          and boxes.device == scores.device == labels.device == dev)
-    if not ok:
-        raise ValueError(f"out: expected contiguous (boxes [{B},{rows},{D}] f32, scores [{B},{rows}] f32, labels [{B},{rows}] int32) "
-                         "on the device of the maps")
-    return boxes, scores, labels
+def _center_maps(hm: torch.Tensor, reg: torch.Tensor, height: torch.Tensor, dim: torch.Tensor, rot: torch.Tensor,
+                 vel: Optional[torch.Tensor], B: int, C: int, H: int, W: int, layout: str) -> None:
+    """The maps of a centre head against the grid (B, C, H, W) of hm, whose class count the caller has judged; ``vel`` may be
+    ``None``."""
+    _head_map(hm, "hm", B, C, H, W, layout)
+    for t, name, ch in ((reg, "reg", 2), (height, "height", 1), (dim, "dim", 3), (rot, "rot", 2), (vel, "vel", 2)):
+        if t is None and name == "vel":
+            continue
+        if isinstance(t, torch.Tensor) and t.dim() == 4 and _head_grid(t, name, layout)[1] != ch:
+            raise ValueError(f"{name}: expected {ch} channels, got {_head_grid(t, name, layout)[1]}")
+        _head_map(t, name, B, ch, H, W, layout)
 
 
-def _f32(v) -> float:
-    return float(np.float32(v))
+def _anchor_arrays(sizes, z_center, rotations):
+    """``sizes`` [ns,3], ``z_center`` [ns], ``rotations`` [nr] as float32 arrays (what the dense_head modules keep; not judged)."""
+    return (np.asarray(sizes, dtype=np.float32).reshape(-1, 3), np.asarray(z_center, dtype=np.float32).reshape(-1),
+            np.asarray(rotations, dtype=np.float32).reshape(-1))
+
+
+def _anchor_scalars(sizes, z_center, rotations):
+    """The anchor scalars of an operator call, judged -> (sizes, z_center, rotations as float32 arrays, ns, nr)."""
+    sizes_np, zc, rots = _anchor_arrays(sizes, z_center, rotations)
+    ns, nr = sizes_np.shape[0], rots.shape[0]
+    if ns < 1 or nr < 1 or zc.shape[0] != ns:
+        raise ValueError(f"sizes [ns,3], z_center [ns], rotations [nr]: need ns, nr >= 1 and one z_center per size (ns = {ns}, "
+                         f"z_center: {zc.shape[0]}, nr = {nr})")
+    if ns > 16 or nr > 8:
+        raise ValueError(f"sizes / rotations: at most 16 sizes and 8 rotations (got {ns}, {nr})")
+    return sizes_np, zc, rots, ns, nr
+
+
+def _fill_anchors(a, sizes_np: np.ndarray, zc: np.ndarray, rots: np.ndarray, origin, step) -> None:
+    """The anchor fields of an argument block: the scalars of ``_anchor_scalars`` and the grid (``dense_head.anchor_grid``)."""
+    a.ns, a.nr = sizes_np.shape[0], rots.shape[0]
+    a.sizes[:3 * a.ns] = sizes_np.reshape(-1).tolist()
+    a.z_center[:a.ns] = zc.tolist()
+    a.rotations[:a.nr] = rots.tolist()
+    a.x0, a.y0, a.sx, a.sy = _f32(origin[0]), _f32(origin[1]), _f32(step[0]), _f32(step[1])
 
 
 def anchor_decode(cls: torch.Tensor, reg: torch.Tensor, dir: Optional[torch.Tensor] = None, *, sizes, z_center, rotations,
@@ -1227,15 +1249,7 @@ def anchor_decode(cls: torch.Tensor, reg: torch.Tensor, dir: Optional[torch.Tens
     k = (y*W + x)*A + a: ResidualCoder.decode, the direction bin applied when ``dir`` is given, score = sigmoid(max class
     logit).  ``index`` [B,P] int32: only those rows, outputs [B,P,...]; an entry outside [0, K) gives (0..., -inf, -1).
     One launch, no synchronisation, no gradients.  ``out`` = (boxes, scores, labels) to write into."""
-    sizes_np = np.asarray(sizes, dtype=np.float32).reshape(-1, 3)
-    zc = np.asarray(z_center, dtype=np.float32).reshape(-1)
-    rots = np.asarray(rotations, dtype=np.float32).reshape(-1)
-    ns, nr = sizes_np.shape[0], rots.shape[0]
-    if ns < 1 or nr < 1 or zc.shape[0] != ns:
-        raise ValueError(f"sizes [ns,3], z_center [ns], rotations [nr]: need ns, nr >= 1 and one z_center per size (ns = {ns}, "
-                         f"z_center: {zc.shape[0]}, nr = {nr})")
-    if ns > 16 or nr > 8:
-        raise ValueError(f"sizes / rotations: at most 16 sizes and 8 rotations (got {ns}, {nr})")
+    sizes_np, zc, rots, ns, nr = _anchor_scalars(sizes, z_center, rotations)
     A = ns * nr
     B, chc, H, W = _head_grid(cls, "cls", layout)
     if chc < A or chc % A:
@@ -1257,16 +1271,13 @@ def anchor_decode(cls: torch.Tensor, reg: torch.Tensor, dir: Optional[torch.Tens
     P = _head_index(index, B)
     dev = _head_devices((("cls", cls), ("reg", reg), ("dir", dir), ("index", index)))
     rows = P if index is not None else K
-    boxes, scores, labels = _head_outputs(B, rows, 7, out, dev)
+    boxes, scores, labels = _outputs((("boxes", (B, rows, 7), torch.float32), ("scores", (B, rows), torch.float32),
+                                      ("labels", (B, rows), torch.int32)), out, dev, "the maps")
     a = _lib.AnchorDecodeArgs()
     a.struct_size = ctypes.sizeof(_lib.AnchorDecodeArgs)
-    a.cls, a.reg, a.dir = cls.data_ptr(), reg.data_ptr(), dir.data_ptr() if dir is not None else None
-    a.index = index.data_ptr() if index is not None else None
-    a.B, a.H, a.W, a.C, a.nb, a.ns, a.nr, a.layout, a.P = B, H, W, C, nb, ns, nr, _lib.LAYOUTS[layout], P
-    a.sizes[:3 * ns] = sizes_np.reshape(-1).tolist()
-    a.z_center[:ns] = zc.tolist()
-    a.rotations[:nr] = rots.tolist()
-    a.x0, a.y0, a.sx, a.sy = _f32(origin[0]), _f32(origin[1]), _f32(step[0]), _f32(step[1])
+    a.cls, a.reg, a.dir, a.index = cls.data_ptr(), reg.data_ptr(), _ptr(dir), _ptr(index)
+    a.B, a.H, a.W, a.C, a.nb, a.layout, a.P = B, H, W, C, nb, _lib.LAYOUTS[layout], P
+    _fill_anchors(a, sizes_np, zc, rots, origin, step)
     a.dir_offset, a.dir_limit_offset = _f32(dir_offset), _f32(dir_limit_offset)
     a.boxes, a.scores, a.labels = boxes.data_ptr(), scores.data_ptr(), labels.data_ptr()
     with _timed("anchor_decode", f"K{K}R{rows}"):
@@ -1287,27 +1298,18 @@ def center_decode(hm: torch.Tensor, reg: torch.Tensor, height: torch.Tensor, dim
     B, C, H, W = _head_grid(hm, "hm", layout)
     if C < 1:
         raise ValueError("hm: needs at least one class channel")
-    hm = _head_map(hm, "hm", B, C, H, W, layout)
-    maps = []
-    for t, name, ch in ((reg, "reg", 2), (height, "height", 1), (dim, "dim", 3), (rot, "rot", 2), (vel, "vel", 2)):
-        if t is None and name == "vel":
-            maps.append(None)
-            continue
-        if isinstance(t, torch.Tensor) and t.dim() == 4 and _head_grid(t, name, layout)[1] != ch:
-            raise ValueError(f"{name}: expected {ch} channels, got {_head_grid(t, name, layout)[1]}")
-        maps.append(_head_map(t, name, B, ch, H, W, layout))
-    reg, height, dim, rot, vel = maps
+    _center_maps(hm, reg, height, dim, rot, vel, B, C, H, W, layout)
     D = 9 if vel is not None else 7
     K = H * W
     P = _head_index(index, B)
     dev = _head_devices((("hm", hm), ("reg", reg), ("height", height), ("dim", dim), ("rot", rot), ("vel", vel), ("index", index)))
     rows = P if index is not None else K
-    boxes, scores, labels = _head_outputs(B, rows, D, out, dev)
+    boxes, scores, labels = _outputs((("boxes", (B, rows, D), torch.float32), ("scores", (B, rows), torch.float32),
+                                      ("labels", (B, rows), torch.int32)), out, dev, "the maps")
     a = _lib.CenterDecodeArgs()
     a.struct_size = ctypes.sizeof(_lib.CenterDecodeArgs)
     a.hm, a.reg, a.height, a.dim, a.rot = hm.data_ptr(), reg.data_ptr(), height.data_ptr(), dim.data_ptr(), rot.data_ptr()
-    a.vel = vel.data_ptr() if vel is not None else None
-    a.index = index.data_ptr() if index is not None else None
+    a.vel, a.index = _ptr(vel), _ptr(index)
     a.B, a.H, a.W, a.C, a.layout, a.P, a.log_dim, a.peak = B, H, W, C, _lib.LAYOUTS[layout], P, int(bool(log_dim)), int(bool(peak))
     a.lo_x, a.lo_y, a.sx, a.sy = _f32(origin[0]), _f32(origin[1]), _f32(cell[0]), _f32(cell[1])
     a.boxes, a.scores, a.labels = boxes.data_ptr(), scores.data_ptr(), labels.data_ptr()
@@ -1333,18 +1335,6 @@ def _gt_inputs(gt_boxes: torch.Tensor, gt_labels: torch.Tensor, min_d: int = 7) 
     if not gt_boxes.is_contiguous() or not gt_labels.is_contiguous():
         raise ValueError("gt_boxes / gt_labels: must be contiguous")
     return B, G, D, _head_devices((("gt_boxes", gt_boxes), ("gt_labels", gt_labels)))
-
-
-def _target_outputs(spec, out: Optional[tuple], dev, of: str = "gt_boxes") -> tuple:
-    """Buffers of a target call.  ``spec`` = ((name, shape, dtype), ...); ``out`` checked against it, or new buffers."""
-    if out is None:
-        return tuple(_empty(shape, dtype=dt, device=dev) for _, shape, dt in spec)
-    ok = len(out) == len(spec) and all(isinstance(t, torch.Tensor) and tuple(t.shape) == tuple(shape) and t.dtype == dt
-                                       and t.is_contiguous() and t.device == dev for t, (_, shape, dt) in zip(out, spec))
-    if not ok:
-        want = ", ".join(f"{n} {list(shape)} {str(dt).replace('torch.', '')}" for n, shape, dt in spec)
-        raise ValueError(f"out: expected contiguous ({want}) on the device of {of}")
-    return tuple(out)
 
 
 def _per_size(v, ns: int, name: str, dtype) -> np.ndarray:
@@ -1373,15 +1363,7 @@ def anchor_targets(gt_boxes: torch.Tensor, gt_labels: torch.Tensor, *, H: int, W
     when it attains some box's best IoU over the scene; background (-1) below ``neg_thr[s]``, else ignored (-2).  A positive
     gets the class, the index and the residual encoding of its own best box.  Two launches and a memset, no anchor tensor, no
     IoU matrix, no synchronisation, no gradients, bit-identical from call to call.  ``out``: the tuple to write into."""
-    sizes_np = np.asarray(sizes, dtype=np.float32).reshape(-1, 3)
-    zc = np.asarray(z_center, dtype=np.float32).reshape(-1)
-    rots = np.asarray(rotations, dtype=np.float32).reshape(-1)
-    ns, nr = sizes_np.shape[0], rots.shape[0]
-    if ns < 1 or nr < 1 or zc.shape[0] != ns:
-        raise ValueError(f"sizes [ns,3], z_center [ns], rotations [nr]: need ns, nr >= 1 and one z_center per size (ns = {ns}, "
-                         f"z_center: {zc.shape[0]}, nr = {nr})")
-    if ns > 16 or nr > 8:
-        raise ValueError(f"sizes / rotations: at most 16 sizes and 8 rotations (got {ns}, {nr})")
+    sizes_np, zc, rots, ns, nr = _anchor_scalars(sizes, z_center, rotations)
     if not (sizes_np > 0).all():
         raise ValueError("sizes: every anchor extent must be > 0")
     if H < 1 or W < 1:
@@ -1397,29 +1379,22 @@ def anchor_targets(gt_boxes: torch.Tensor, gt_labels: torch.Tensor, *, H: int, W
             ("max_iou", (B, K), torch.float32)]
     if nb:
         spec.append(("dir_target", (B, K), torch.int32))
-    outs = _target_outputs(spec, out, dev)
-    nbytes = lib().sad_anchor_targets_workspace_bytes(B, G)
-    if workspace is None and nbytes:
-        workspace = _empty(nbytes, dtype=torch.uint8, device=dev)
-    if nbytes and (not workspace.is_cuda or workspace.device != dev or not workspace.is_contiguous()
-                   or workspace.numel() * workspace.element_size() < nbytes):
-        raise ValueError(f"workspace: expected at least {nbytes} contiguous bytes on {dev}")
+    outs = _outputs(spec, out, dev, "gt_boxes")
+    nbytes = lib().sad_anchor_targets_workspace_bytes(B, G)     # (0 with G = 0: nothing is matched, no workspace is read)
+    workspace = _workspace(nbytes, workspace, dev, "ops.anchor_targets_workspace") if nbytes else None
     a = _lib.AnchorTargetsArgs()
     a.struct_size = ctypes.sizeof(_lib.AnchorTargetsArgs)
     a.gt_boxes, a.gt_labels = (gt_boxes.data_ptr(), gt_labels.data_ptr()) if G else (None, None)
-    a.B, a.G, a.D, a.H, a.W, a.ns, a.nr, a.nb, a.use_size_class = B, G, D, H, W, ns, nr, nb, int(sc is not None)
-    a.sizes[:3 * ns] = sizes_np.reshape(-1).tolist()
-    a.z_center[:ns] = zc.tolist()
-    a.rotations[:nr] = rots.tolist()
+    a.B, a.G, a.D, a.H, a.W, a.nb, a.use_size_class = B, G, D, H, W, nb, int(sc is not None)
+    _fill_anchors(a, sizes_np, zc, rots, origin, step)
     a.pos_thr[:ns] = pos.tolist()
     a.neg_thr[:ns] = neg.tolist()
     if sc is not None:
         a.size_class[:ns] = sc.tolist()
-    a.x0, a.y0, a.sx, a.sy = _f32(origin[0]), _f32(origin[1]), _f32(step[0]), _f32(step[1])
     a.dir_offset = _f32(dir_offset)
     a.labels, a.match, a.reg_target, a.max_iou = (t.data_ptr() for t in outs[:4])
     a.dir_target = outs[4].data_ptr() if nb else None
-    a.workspace = workspace.data_ptr() if nbytes else None
+    a.workspace = _ptr(workspace)
     with _timed("anchor_targets", f"K{K}G{G}"):
         check(lib().sad_anchor_targets_f32(ctypes.byref(a), _stream()), "sad_anchor_targets_f32")
     return outs
@@ -1449,7 +1424,7 @@ def center_targets(gt_boxes: torch.Tensor, gt_labels: torch.Tensor, *, C: int, H
     na = 10 if vel else 8
     spec = (("heatmap", (B, C, H, W) if layout == "nchw" else (B, H, W, C), torch.float32), ("ind", (B, G), torch.int32),
             ("anno", (B, G, na), torch.float32))
-    heatmap, ind, anno = _target_outputs(spec, out, dev)
+    heatmap, ind, anno = _outputs(spec, out, dev, "gt_boxes")
     a = _lib.CenterTargetsArgs()
     a.struct_size = ctypes.sizeof(_lib.CenterTargetsArgs)
     a.gt_boxes, a.gt_labels = (gt_boxes.data_ptr(), gt_labels.data_ptr()) if G else (None, None)
@@ -1461,30 +1436,6 @@ def center_targets(gt_boxes: torch.Tensor, gt_labels: torch.Tensor, *, C: int, H
     with _timed("center_targets", f"K{H * W}G{G}"):
         check(lib().sad_center_targets_f32(ctypes.byref(a), _stream()), "sad_center_targets_f32")
     return heatmap, ind, anno
-
-
-def _dense_targets(named, dev) -> None:
-    """(name, tensor, shape, dtype) rows of a loss call: contiguous tensors of that shape and dtype on the maps' device."""
-    for name, t, shape, dt in named:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name}: expected a torch.Tensor")
-        if t.dtype != dt:
-            raise TypeError(f"{name}: expected dtype {dt}, got {t.dtype}")
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
-        if not t.is_contiguous():
-            raise ValueError(f"{name}: must be contiguous")
-        if not t.is_cuda or t.device != dev:
-            raise RuntimeError(f"{name}: expected a tensor on {dev} (sad_amd has no CPU path)")
-
-
-def _loss_workspace(nbytes: int, workspace: Optional[torch.Tensor], dev) -> torch.Tensor:
-    if workspace is None:
-        return _empty(nbytes, dtype=torch.uint8, device=dev)
-    if (not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or workspace.device != dev or not workspace.is_contiguous()
-            or workspace.numel() * workspace.element_size() < nbytes):
-        raise ValueError(f"workspace: expected at least {nbytes} contiguous bytes on {dev}")
-    return workspace
 
 
 def _weights(v, n: int, name: str) -> list:
@@ -1545,23 +1496,24 @@ def anchor_head_loss(cls: torch.Tensor, reg: torch.Tensor, dir: Optional[torch.T
     cw, sc = _weights(code_weights, 7, "code_weights"), _weights(scale, 3, "scale")
     K = H * W * A
     dev = _head_devices((("cls", cls), ("reg", reg), ("dir", dir)))
-    _dense_targets([("labels", labels, (B, K), torch.int32), ("reg_target", reg_target, (B, K, 7), torch.float32)]
-                   + ([("dir_target", dir_target, (B, K), torch.int32)] if nb else []), dev)
+    for name, t, shape, dt in ([("labels", labels, (B, K), torch.int32), ("reg_target", reg_target, (B, K, 7), torch.float32)]
+                               + ([("dir_target", dir_target, (B, K), torch.int32)] if nb else [])):
+        _strict(t, name, dt, shape, dev=dev)
     spec = [("loss", (B, 3), torch.float32), ("num_pos", (B,), torch.int32), ("grad_cls", tuple(cls.shape), torch.float32),
             ("grad_reg", tuple(reg.shape), torch.float32)]
     if nb:
         spec.append(("grad_dir", tuple(dir.shape), torch.float32))
     if per_anchor:
         spec.append(("per_anchor", (B, K, 3), torch.float32))
-    outs = _target_outputs(spec, out, dev, "the maps")
+    outs = _outputs(spec, out, dev, "the maps")
     nbytes = lib().sad_anchor_head_loss_workspace_bytes(B, H, W, A)
     if not nbytes:
         raise ValueError(f"anchor_head_loss: unsupported shape (B = {B}, K = {K}: B <= 65535 and B * K < 2^31)")
-    workspace = _loss_workspace(nbytes, workspace, dev)
+    workspace = _workspace(nbytes, workspace, dev, "ops.anchor_head_loss_workspace")
     a = _lib.AnchorHeadLossArgs()
     a.struct_size = ctypes.sizeof(_lib.AnchorHeadLossArgs)
-    a.cls, a.reg, a.dir = cls.data_ptr(), reg.data_ptr(), dir.data_ptr() if nb else None
-    a.labels, a.reg_target, a.dir_target = labels.data_ptr(), reg_target.data_ptr(), dir_target.data_ptr() if nb else None
+    a.cls, a.reg, a.dir = cls.data_ptr(), reg.data_ptr(), _ptr(dir)
+    a.labels, a.reg_target, a.dir_target = labels.data_ptr(), reg_target.data_ptr(), _ptr(dir_target)
     a.B, a.H, a.W, a.A, a.C, a.nb, a.layout = B, H, W, A, C, nb, _lib.LAYOUTS[layout]
     a.sin_diff, a.normalize = int(bool(sin_diff)), int(bool(normalize))
     a.alpha, a.beta = _f32(alpha), _f32(beta)
@@ -1597,11 +1549,7 @@ def center_head_loss(hm: torch.Tensor, reg: torch.Tensor, height: torch.Tensor, 
     B, C, H, W = _head_grid(hm, "hm", layout)
     if C < 1 or C > 64:
         raise ValueError(f"hm: expected 1 .. 64 class channels, got {C}")
-    hm = _head_map(hm, "hm", B, C, H, W, layout)
-    maps = []
-    for t, name, ch in ((reg, "reg", 2), (height, "height", 1), (dim, "dim", 3), (rot, "rot", 2), (vel, "vel", 2)):
-        maps.append(None if t is None and name == "vel" else _head_map(t, name, B, ch, H, W, layout))
-    reg, height, dim, rot, vel = maps
+    _center_maps(hm, reg, height, dim, rot, vel, B, C, H, W, layout)
     na = 10 if vel is not None else 8
     dev = _head_devices((("hm", hm), ("reg", reg), ("height", height), ("dim", dim), ("rot", rot), ("vel", vel)))
     if not isinstance(ind, torch.Tensor) or ind.dim() != 2 or ind.shape[0] != B:
@@ -1609,21 +1557,22 @@ def center_head_loss(hm: torch.Tensor, reg: torch.Tensor, height: torch.Tensor, 
     G = ind.shape[1]
     if G > 1024:
         raise ValueError(f"ind: at most 1024 boxes per scene (got G = {G})")
-    _dense_targets((("heatmap", heatmap, tuple(hm.shape), torch.float32), ("ind", ind, (B, G), torch.int32),
-                    ("anno", anno, (B, G, na), torch.float32)), dev)
+    for name, t, shape, dt in (("heatmap", heatmap, tuple(hm.shape), torch.float32), ("ind", ind, (B, G), torch.int32),
+                               ("anno", anno, (B, G, na), torch.float32)):
+        _strict(t, name, dt, shape, dev=dev)
     cw, sc = _weights(code_weights, na, "code_weights"), _weights(scale, 2, "scale")
     spec = [("loss", (B, 2), torch.float32), ("num_pos", (B, 2), torch.int32), ("grad_hm", tuple(hm.shape), torch.float32)]
     spec += [(f"grad_{n}", tuple(t.shape), torch.float32) for n, t in (("reg", reg), ("height", height), ("dim", dim), ("rot", rot), ("vel", vel))
              if t is not None]
-    outs = _target_outputs(spec, out, dev, "the maps")
+    outs = _outputs(spec, out, dev, "the maps")
     nbytes = lib().sad_center_head_loss_workspace_bytes(B, H, W, G)
     if not nbytes:
         raise ValueError(f"center_head_loss: unsupported shape (B = {B}, H * W = {H * W}: B <= 65535 and B * H * W < 2^31)")
-    workspace = _loss_workspace(nbytes, workspace, dev)
+    workspace = _workspace(nbytes, workspace, dev, "ops.center_head_loss_workspace")
     a = _lib.CenterHeadLossArgs()
     a.struct_size = ctypes.sizeof(_lib.CenterHeadLossArgs)
     a.hm, a.reg, a.height, a.dim, a.rot = hm.data_ptr(), reg.data_ptr(), height.data_ptr(), dim.data_ptr(), rot.data_ptr()
-    a.vel = vel.data_ptr() if vel is not None else None
+    a.vel = _ptr(vel)
     a.heatmap = heatmap.data_ptr()
     a.ind, a.anno = (ind.data_ptr(), anno.data_ptr()) if G else (None, None)
     a.B, a.H, a.W, a.C, a.G, a.layout, a.normalize = B, H, W, C, G, _lib.LAYOUTS[layout], int(bool(normalize))

@@ -257,6 +257,14 @@ def test_wrappers_name_the_wrong_argument(sad):
         ops.anchor_decode(cls, reg, dir_, index=torch.zeros(1, 4, dtype=torch.int64), **kw)
     with pytest.raises(ValueError, match="index: expected \\[B,P\\]"):
         ops.anchor_decode(cls, reg, dir_, index=torch.zeros(2, 4, dtype=torch.int32), **kw)
+    with pytest.raises(ValueError, match="index: must be contiguous"):
+        ops.anchor_decode(cls, reg, dir_, index=torch.zeros(1, 8, dtype=torch.int32)[:, ::2], **kw)
+    with pytest.raises(TypeError, match="reg: expected a torch.Tensor"):
+        ops.anchor_decode(cls, reg.numpy(), dir_, **kw)
+    with pytest.raises(TypeError, match="dir: expected dtype torch.float32"):
+        ops.anchor_decode(cls, reg, dir_.half(), **kw)
+    with pytest.raises(ValueError, match="cls: .*multiple of A"):          # channel count before dtype, cls before reg
+        ops.anchor_decode(torch.zeros(1, 7, H, W).half(), torch.zeros(1, A * 6, H, W), dir_, **kw)
     with pytest.raises(ValueError, match="layout"):
         ops.anchor_decode(cls, reg, dir_, layout="chwn", **kw)
     with pytest.raises(ValueError, match="z_center"):
@@ -275,6 +283,12 @@ def test_wrappers_name_the_wrong_argument(sad):
         ops.center_decode(hm, r2, h1, d3, r2, index=torch.zeros(1, 4), **ckw)
     with pytest.raises(TypeError, match="height: expected dtype"):
         ops.center_decode(hm, r2, h1.half(), d3, r2, **ckw)
+    with pytest.raises(ValueError, match="reg: expected shape"):
+        ops.center_decode(hm, torch.zeros(1, 2, H + 1, W), h1, d3, r2, **ckw)
+    with pytest.raises(ValueError, match="hm: must be contiguous"):
+        ops.center_decode(torch.zeros(1, H, W, 3).permute(0, 3, 1, 2), r2, h1, d3, r2, **ckw)
+    with pytest.raises(ValueError, match="hm: needs at least one class channel"):      # before the other maps
+        ops.center_decode(torch.zeros(1, 0, H, W), r2, h1.half(), d3, r2, **ckw)
 
 
 def test_lazy_exports(sad):

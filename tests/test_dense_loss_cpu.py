@@ -377,10 +377,39 @@ def test_ops_refuse_cpu_tensors_and_bad_shapes(sad):
         ops.anchor_head_loss(cls, reg, None, lab, tgt, beta=0.0)
     with pytest.raises(ValueError, match="together"):
         ops.anchor_head_loss(cls, reg, torch.zeros(1, 4, 2, 2), lab, tgt)
+    with pytest.raises(TypeError, match="cls: expected dtype torch.float32"):
+        ops.anchor_head_loss(cls.double(), reg, None, lab, tgt)
+    with pytest.raises(TypeError, match="reg: expected a torch.Tensor"):
+        ops.anchor_head_loss(cls, None, None, lab, tgt)
+    with pytest.raises(ValueError, match="reg: expected shape"):
+        ops.anchor_head_loss(cls, torch.zeros(1, 14, 2, 3), None, lab, tgt)
+    with pytest.raises(ValueError, match="cls: must be contiguous"):
+        ops.anchor_head_loss(torch.zeros(1, 2, 2, 6).permute(0, 3, 1, 2), reg, None, lab, tgt)
+    with pytest.raises(ValueError, match="cls: 5 channels are not a multiple of A = 2"):
+        ops.anchor_head_loss(torch.zeros(1, 5, 2, 2), reg, None, lab, tgt)
+    with pytest.raises(ValueError, match="dir: 2 channels are not A \\* nb"):
+        ops.anchor_head_loss(cls, reg, torch.zeros(1, 2, 2, 2), lab, tgt, lab)
+    with pytest.raises(ValueError, match="dir: 18 channels are not A \\* nb with 2 <= nb <= 8"):
+        ops.anchor_head_loss(cls, reg, torch.zeros(1, 18, 2, 2), lab, tgt, lab)
+    with pytest.raises(ValueError, match="reg: at most 128 anchors"):         # the limits come before dtypes
+        ops.anchor_head_loss(torch.zeros(1, 129, 1, 1).half(), torch.zeros(1, 129 * 7, 1, 1), None, lab, tgt)
+    with pytest.raises(ValueError, match="cls: at most 64 classes"):
+        ops.anchor_head_loss(torch.zeros(1, 130, 2, 2).half(), reg, None, lab, tgt)
     hm = torch.zeros(1, 3, 2, 2)
     m = [torch.zeros(1, ch, 2, 2) for ch in (2, 1, 3, 2)]
     with pytest.raises(RuntimeError, match="no CPU path"):
         ops.center_head_loss(hm, *m, None, hm, torch.zeros(1, 2, dtype=torch.int32), torch.zeros(1, 2, 8))
+    ind, anno = torch.zeros(1, 2, dtype=torch.int32), torch.zeros(1, 2, 8)
+    with pytest.raises(ValueError, match="dim: expected 3 channels, got 2"):
+        ops.center_head_loss(hm, m[0], m[1], m[0], m[3], None, hm, ind, anno)
+    with pytest.raises(TypeError, match="height: expected dtype torch.float32"):
+        ops.center_head_loss(hm, m[0], m[1].half(), m[2], m[3], None, hm, ind, anno)
+    with pytest.raises(ValueError, match="rot: must be contiguous"):
+        ops.center_head_loss(hm, m[0], m[1], m[2], torch.zeros(1, 2, 2, 2).permute(0, 3, 1, 2), None, hm, ind, anno)
+    with pytest.raises(ValueError, match="vel: expected shape"):
+        ops.center_head_loss(hm, *m, torch.zeros(2, 2, 2, 2), hm, ind, anno)
+    with pytest.raises(ValueError, match="hm: expected 1 .. 64 class channels, got 65"):
+        ops.center_head_loss(torch.zeros(1, 65, 2, 2), m[0].half(), *m[1:], None, hm, ind, anno)
     loss = dense_head.AnchorHeadDecoder([[1, 1, 1]], [0], [0], (0, 0), (1, 1), layout="nhwc").loss(beta=0.2)
     assert isinstance(loss, dense_head.AnchorHeadLoss) and loss.cfg["layout"] == "nhwc" and loss.cfg["beta"] == 0.2
     closs = dense_head.CenterHeadDecoder((0, 0), (1, 1)).loss(scale=(1.0, 0.25))

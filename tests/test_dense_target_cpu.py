@@ -240,6 +240,18 @@ def test_wrappers_name_the_wrong_argument(sad):
         ops.anchor_targets(torch.zeros(1, 3, 6), lab, **kw)
     with pytest.raises(ValueError, match="gt_labels: expected shape"):
         ops.anchor_targets(gt, torch.zeros(1, 4, dtype=torch.int32), **kw)
+    with pytest.raises(TypeError, match="gt_boxes: expected dtype torch.float32"):
+        ops.anchor_targets(gt.double(), lab, **kw)
+    with pytest.raises(TypeError, match="gt_boxes: expected a torch.Tensor"):
+        ops.anchor_targets(gt.numpy(), lab, **kw)
+    with pytest.raises(ValueError, match="gt_boxes / gt_labels: must be contiguous"):
+        ops.anchor_targets(torch.zeros(1, 7, 3).transpose(1, 2), lab, **kw)
+    with pytest.raises(ValueError, match="gt_boxes / gt_labels: must be contiguous"):
+        ops.anchor_targets(gt, torch.zeros(1, 6, dtype=torch.int32)[:, ::2], **kw)
+    with pytest.raises(TypeError, match="gt_labels: expected dtype"):         # both dtypes are judged before any shape
+        ops.anchor_targets(torch.zeros(1, 3, 6), lab.long(), **kw)
+    with pytest.raises(ValueError, match="at most 1024"):                      # G before contiguity
+        ops.anchor_targets(torch.zeros(1, 7, 1025).transpose(1, 2), torch.zeros(1, 1025, dtype=torch.int32), **kw)
     with pytest.raises(ValueError, match="at most 1024"):
         ops.anchor_targets(torch.zeros(1, 1025, 7), torch.zeros(1, 1025, dtype=torch.int32), **kw)
     with pytest.raises(ValueError, match="sizes: every anchor extent"):
@@ -253,6 +265,10 @@ def test_wrappers_name_the_wrong_argument(sad):
         ops.center_targets(gt, lab, **ckw)
     with pytest.raises(ValueError, match="gt_boxes: expected \\[B,G,D\\] with B >= 1 and D >= 9"):
         ops.center_targets(gt, lab, vel=True, **ckw)
+    with pytest.raises(ValueError, match="gt_labels: expected shape"):
+        ops.center_targets(gt, torch.zeros(1, 4, dtype=torch.int32), **ckw)
+    with pytest.raises(TypeError, match="gt_labels: expected dtype torch.int32"):
+        ops.center_targets(gt, lab.short(), **ckw)
     with pytest.raises(ValueError, match="min_overlap"):
         ops.center_targets(gt, lab, min_overlap=1.0, **ckw)
     with pytest.raises(ValueError, match="layout"):

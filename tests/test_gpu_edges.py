@@ -381,6 +381,40 @@ def test_nms_workspace_reuse(orc, sad, dev):
         _nms_all(orc, dev, bx, 0.1, sthr, out=buf)
 
 
+def test_nms_out_buffers_checked(sad, dev):
+    """A caller's ``out`` that a kernel would write past its end is refused before anything is launched: keep / order / count of
+    a 2-byte dtype, keep / order as a ``[:, ::2]`` view of a twice-as-wide tensor (count [1] has no strided form: a view of one
+    element is contiguous), a workspace one byte short (``single_kernel=True`` uses none).  The buffers keep their fill, and
+    the untouched tuple then gives the result of the call without ``out``."""
+    import torch
+    from sad_amd import ops
+    B, K = 1, 4
+    boxes = _t(_boxes(18, B, K, extent=6.0), dev)
+    scores = boxes[..., 7].contiguous()
+    bev, big = ops.nms_bev_buffers(B, K, dev), ops.nms_boxes_buffers(B, K, dev)
+    for name, buf, call, uses_ws in (
+            ("nms_bev", bev, lambda out: ops.nms_bev(boxes, 0.1, 0.0, out=out), True),
+            ("nms_bev single_kernel", bev, lambda out: ops.nms_bev(boxes, 0.1, 0.0, single_kernel=True, out=out), False),
+            ("nms_boxes", big, lambda out: ops.nms_boxes(boxes, scores, None, 0.1, 0.0, out=out), True)):
+        for t in buf[:3]:
+            t.fill_(-7)
+        bad = []
+        for i, t in enumerate(buf[:3]):
+            bad.append((i, torch.zeros(t.shape, dtype=torch.int16, device=dev)))
+            if t.dim() == 2:
+                bad.append((i, torch.zeros((B, 2 * t.shape[1]), dtype=torch.int32, device=dev)[:, ::2]))
+        if uses_ws:
+            assert buf[3].numel() > 1
+            bad.append((3, buf[3][:-1]))
+        for i, t in bad:
+            with pytest.raises(ValueError, match="^(out|workspace): "):
+                call(buf[:i] + (t,) + buf[i + 1:])
+        torch.cuda.synchronize()
+        assert all(bool((t == -7).all()) for t in buf[:3]), f"{name}: a refused call wrote into the buffers"
+        for g, w in zip(call(buf), call(None)):
+            assert torch.equal(g, w), name
+
+
 # ---------------------------------------------------------------- kNN (SPEC.md §4)
 def _lattice(seed, B, n):
     """B scenes of the n^3 integer lattice, each in its own point order (so index order is not spatial order)."""

@@ -73,10 +73,12 @@ __global__ __launch_bounds__(VX_THREADS) void sp_nbr_kernel(int32_t *out_coors, 
     int k[3];
     kk_split(kk, g, k);
     const int32_t *c = out_coors + (size_t)o * 3;
-    const int z = c[0] * g.s[0] - g.p[0] + k[0], y = c[1] * g.s[1] - g.p[1] + k[1], x = c[2] * g.s[2] - g.p[2] + k[2];
+    // 64-bit: o * s reaches G + 2 p - K, which passes 2^31 - 1 on a grid near the cell limit
+    const long long z = (long long)c[0] * g.s[0] - g.p[0] + k[0], y = (long long)c[1] * g.s[1] - g.p[1] + k[1],
+                    x = (long long)c[2] * g.s[2] - g.p[2] + k[2];
     int r = -1;
     if (z >= 0 && z < g.G[0] && y >= 0 && y < g.G[1] && x >= 0 && x < g.G[2]) {
-        const u64 k64 = ((u64)(unsigned)scene_of(out_offsets, B, o) << 32) | (unsigned)((z * g.G[1] + y) * g.G[2] + x);
+        const u64 k64 = ((u64)(unsigned)scene_of(out_offsets, B, o) << 32) | (unsigned)(((int)z * g.G[1] + (int)y) * g.G[2] + (int)x);
         const int slot = hash_find(tkeys, mask, shift, k64);
         if (slot >= 0) r = tvals[slot];
     }
@@ -91,10 +93,13 @@ __device__ __forceinline__ bool cand_site(const int32_t *__restrict__ coors, int
     bool ok = true;
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
-        const int t = coors[(size_t)i * 3 + d] + g.p[d] - k[d];
-        const int q = t / g.s[d];
-        ok = ok && t >= 0 && q * g.s[d] == t && q < g.O[d];
-        o[d] = q;
+        // unsigned: coors + p passes 2^31 - 1 on a grid near the cell limit (it stays below 2^32: p <= 65535)
+        const int x = coors[(size_t)i * 3 + d];
+        const unsigned xp = (unsigned)x + (unsigned)g.p[d];
+        const unsigned t = xp - (unsigned)k[d];
+        const unsigned q = t / (unsigned)g.s[d];
+        ok = ok && x >= 0 && xp >= (unsigned)k[d] && q * (unsigned)g.s[d] == t && q < (unsigned)g.O[d];
+        o[d] = (int)q;
     }
     return ok;
 }

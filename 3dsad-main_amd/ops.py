@@ -781,7 +781,8 @@ def _int3(v, name: str, lo: int):
 
 def sparse_conv_geometry(spatial_shape, kernel, stride=1, padding=0, subm: bool = False):
     """Host arithmetic of SPEC.md §21: -> (spatial_shape, kernel, stride, padding, out_shape), tuples of 3 ints (z,y,x).
-    ``subm`` demands odd kernel sizes and fixes stride 1 and padding K // 2.  Needs no GPU."""
+    ``subm`` demands odd kernel sizes and fixes stride 1 and padding K // 2.  Refuses what the library refuses (sp_geo in
+    csrc/spconv.hip): more than 2^31 - 1 cells in either shape, a stride or padding above 65535.  Needs no GPU."""
     G, _ = _int3(spatial_shape, "spatial_shape", 1)
     K, _ = _int3(kernel, "kernel", 1)
     if max(K) > 3:
@@ -799,9 +800,13 @@ def sparse_conv_geometry(spatial_shape, kernel, stride=1, padding=0, subm: bool 
     else:
         s, _ = _int3(stride, "stride", 1)
         p, _ = _int3(padding, "padding", 0)
+        if max(s) > 65535 or max(p) > 65535:
+            raise ValueError(f"stride {s} / padding {p} above 65535")
     if any(g + 2 * q - k < 0 for g, q, k in zip(G, p, K)):
         raise ValueError(f"kernel {K} does not fit the padded grid {G} + 2 * {p}")
     O = tuple((g + 2 * q - k) // t + 1 for g, q, k, t in zip(G, p, K, s))
+    if O[0] * O[1] * O[2] > 2 ** 31 - 1:
+        raise ValueError(f"out_shape {O} exceeds 2^31 - 1 cells")
     return G, K, s, p, O
 
 

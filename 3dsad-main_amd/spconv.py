@@ -116,7 +116,7 @@ class _SparseConvBase(nn.Module):
                  indice_key: Optional[str] = None):
         super().__init__()
         # (shape checks on fixed sizes; the layer's own geometry is checked here so that a bad layer fails at construction)
-        _, self.kernel_size, self.stride, self.padding, _ = ops.sparse_conv_geometry((1 << 10,) * 3, kernel_size, stride, padding, self.subm)
+        _, self.kernel_size, self.stride, self.padding, _ = ops.sparse_conv_geometry((3, 3, 3), kernel_size, stride, padding, self.subm)
         self.in_channels, self.out_channels = int(in_channels), int(out_channels)
         if not (1 <= self.in_channels <= 256 and 1 <= self.out_channels <= 256):
             raise ValueError(f"channels must be in 1 .. 256, got {in_channels} -> {out_channels}")
@@ -250,7 +250,7 @@ class SparseMaxPool3d(nn.Module):
 
     def __init__(self, kernel_size, stride=None, padding=0, indice_key: Optional[str] = None):
         super().__init__()
-        _, self.kernel_size, self.stride, self.padding, _ = ops.sparse_conv_geometry((1 << 10,) * 3, kernel_size,
+        _, self.kernel_size, self.stride, self.padding, _ = ops.sparse_conv_geometry((3, 3, 3), kernel_size,
                                                                                       kernel_size if stride is None else stride, padding, False)
         self.indice_key = indice_key
 

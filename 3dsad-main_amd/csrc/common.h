@@ -231,6 +231,11 @@ inline void lds_attr_once(std::atomic<uint64_t> &done, const void *fn, int bytes
 
 // x rounded up to a multiple of 16: the alignment of every slice of a workspace (and of LDS images read 16 bytes at a time)
 __host__ __device__ inline size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
+// carves a workspace into slices of that alignment: take() returns the offset of the next slice, o is the offset behind the last
+struct Carve {
+    size_t o = 0;
+    size_t take(size_t bytes) { const size_t at = o; o += al16(bytes); return at; }
+};
 // workgroups of `threads` that cover n items
 inline unsigned blocks_for(unsigned long long n, int threads) { return (unsigned)((n + threads - 1) / threads); }
 

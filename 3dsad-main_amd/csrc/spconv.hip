@@ -1,12 +1,11 @@
 // Sparse 3-D convolution (SPEC.md §21): the rulebook (which input row every kernel offset of every output row reads), the
 // convolution itself and the scatter to a dense tensor.  The upstream reference has no such operator; the semantics are SPEC.md's own.
 //
-// rulebook   the input rows go into the coordinate hash table of vox_hash.h under (scene << 32 | (z*Gy + y)*Gx + x), lowest row by
-//            atomicMin; nbr[o, kk] is then one lookup per (output row, kernel offset).  The strided form finds its output sites with
-//            a SECOND table keyed by output site that keeps the lowest candidate number i*Kvol + kk (atomicMin); a candidate is an
-//            OPENER iff it is that lowest number, openers are counted per 64 candidates by a ballot and numbered by a scan over
-//            the candidates: the §20.2 scheme with candidates in the place of rows.  Nothing read back depends on the order of an
-//            atomic.  `count` ends with out_offsets[B+1] on the device, `fill` numbers the openers and does the lookups.
+// rulebook   the input rows go into a coordinate table of vox_hash.h under (scene << 32 | (z*Gy + y)*Gx + x) with their row;
+//            nbr[o, kk] is then one lookup per (output row, kernel offset).  The strided form finds its output sites with a SECOND
+//            table keyed by output site that takes the candidate numbers i*Kvol + kk, and the first-appearance numbering of
+//            vox_hash.h over the candidates numbers the sites.  Nothing read back depends on the order of an atomic.  `count`
+//            ends with out_offsets[B+1] on the device, `fill` numbers the openers and does the lookups.
 // conv       output-stationary implicit GEMM on v_mfma_f32_32x32x2_f32.  A workgroup (4 waves) owns TR = 64 or 128 output rows and
 //            ALL output channels; every output element lives in one accumulator from the bias to the store, kk ascending and ci
 //            ascending inside, which is SPEC §21.2's fmaf chain bit for bit (no split K, no atomics).  Per kk: the tile's neighbour
@@ -41,27 +40,21 @@ __device__ __forceinline__ void kk_split(int kk, const SpGeo &g, int *k) {
 }
 
 // ---- rulebook ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(VX_THREADS) void sp_init_kernel(u64 *__restrict__ tkeys, int32_t *__restrict__ tvals, unsigned cap) {
-    const unsigned stride = gridDim.x * VX_THREADS;
-    for (unsigned s = blockIdx.x * VX_THREADS + threadIdx.x; s < cap; s += stride) { tkeys[s] = VX_EMPTY; tvals[s] = INT_MAX; }
-}
+__global__ __launch_bounds__(VX_THREADS) void sp_init_kernel(CoordTable t) { t.clear(); }
 
 __global__ __launch_bounds__(VX_THREADS) void sp_insert_kernel(const int32_t *__restrict__ coors, const int32_t *__restrict__ offsets, int Nv, int B,
-                                                               SpGeo g, u64 *tkeys, int32_t *tvals, unsigned mask, int shift) {
+                                                               SpGeo g, CoordTable t) {
     const int i = blockIdx.x * VX_THREADS + threadIdx.x;
     if (i >= Nv) return;
     const int32_t *c = coors + (size_t)i * 3;
     const int key = (c[0] * g.G[1] + c[1]) * g.G[2] + c[2];
-    const u64 k64 = ((u64)(unsigned)scene_of(offsets, B, i) << 32) | (unsigned)key;
-    const int slot = hash_insert(tkeys, mask, shift, k64);
-    if (slot >= 0) hash_min(tvals, slot, i);
+    t.insert_min(((u64)(unsigned)scene_of(offsets, B, i) << 32) | (unsigned)key, i);
 }
 
 // nbr[o, kk] = lowest input row of o's scene at out_coors[o] * s - p + k, or -1.  Rows at and above the true total
 // (out_offsets[B]; a fill with spare capacity) get nbr -1 and coordinates -1.
 __global__ __launch_bounds__(VX_THREADS) void sp_nbr_kernel(int32_t *out_coors, const int32_t *__restrict__ out_offsets, int rows, int B, SpGeo g,
-                                                            const u64 *__restrict__ tkeys, const int32_t *__restrict__ tvals, unsigned mask,
-                                                            int shift, int pad_coors, int32_t *__restrict__ nbr) {
+                                                            CoordTable t, int pad_coors, int32_t *__restrict__ nbr) {
     const long long e = (long long)blockIdx.x * VX_THREADS + threadIdx.x;
     if (e >= (long long)rows * g.Kvol) return;
     const int o = (int)(e / g.Kvol), kk = (int)(e - (long long)o * g.Kvol);
@@ -79,8 +72,8 @@ __global__ __launch_bounds__(VX_THREADS) void sp_nbr_kernel(int32_t *out_coors, 
     int r = -1;
     if (z >= 0 && z < g.G[0] && y >= 0 && y < g.G[1] && x >= 0 && x < g.G[2]) {
         const u64 k64 = ((u64)(unsigned)scene_of(out_offsets, B, o) << 32) | (unsigned)(((int)z * g.G[1] + (int)y) * g.G[2] + (int)x);
-        const int slot = hash_find(tkeys, mask, shift, k64);
-        if (slot >= 0) r = tvals[slot];
+        const int slot = t.find(k64);
+        if (slot >= 0) r = t.lowest(slot);
     }
     nbr[e] = r;
 }
@@ -108,65 +101,49 @@ __device__ __forceinline__ u64 site_key(const int32_t *__restrict__ offsets, int
     return ((u64)(unsigned)scene_of(offsets, B, i) << 32) | (unsigned)((o[0] * g.O[1] + o[1]) * g.O[2] + o[2]);
 }
 
-__global__ __launch_bounds__(VX_THREADS) void sp_cand_insert_kernel(const int32_t *__restrict__ coors, const int32_t *__restrict__ offsets, int NC, int B,
-                                                                    SpGeo g, u64 *tkeys, int32_t *tvals, unsigned mask, int shift) {
-    const long long c = (long long)blockIdx.x * VX_THREADS + threadIdx.x;
-    if (c >= NC) return;
-    int i, o[3];
-    if (!cand_site(coors, (int)c, g, i, o)) return;
-    const int slot = hash_insert(tkeys, mask, shift, site_key(offsets, B, i, o, g));
-    if (slot >= 0) hash_min(tvals, slot, (int)c);
-}
-
-__device__ __forceinline__ bool cand_opener(const int32_t *__restrict__ coors, const int32_t *__restrict__ offsets, long long c, int NC, int B,
-                                            const SpGeo &g, const u64 *__restrict__ tkeys, const int32_t *__restrict__ tvals, unsigned mask, int shift,
-                                            int *o) {
-    if (c >= NC) return false;
-    int i;
-    if (!cand_site(coors, (int)c, g, i, o)) return false;
-    const int slot = hash_find(tkeys, mask, shift, site_key(offsets, B, i, o, g));
-    return slot >= 0 && tvals[slot] == (int)c;
-}
-
-// wavecnt[w] = openers among candidates 64 w .. 64 w + 63
-__global__ __launch_bounds__(VX_THREADS) void sp_flags_kernel(const int32_t *__restrict__ coors, const int32_t *__restrict__ offsets, int NC, int B, SpGeo g,
-                                                              const u64 *__restrict__ tkeys, const int32_t *__restrict__ tvals, unsigned mask, int shift,
-                                                              int32_t *__restrict__ wavecnt) {
-    const long long c = (long long)blockIdx.x * VX_THREADS + threadIdx.x;
-    int o[3];
-    const unsigned long long m = __ballot(cand_opener(coors, offsets, c, NC, B, g, tkeys, tvals, mask, shift, o));
-    if ((threadIdx.x & 63) == 0 && c < NC) wavecnt[c >> 6] = __builtin_popcountll(m);
-}
-
-// wavecnt[nw + 1] -> exclusive prefixes; out_offsets[b] = openers among the candidates of the rows below offsets[b]
-__global__ __launch_bounds__(VX_SCAN_THREADS) void sp_scan_kernel(int32_t *wavecnt, int nw, const int32_t *__restrict__ coors,
-                                                                  const int32_t *__restrict__ offsets, int Nv, int NC, int B, SpGeo g,
-                                                                  const u64 *__restrict__ tkeys, const int32_t *__restrict__ tvals, unsigned mask,
-                                                                  int shift, int32_t *__restrict__ out_offsets) {
-    __shared__ int s_w[VX_SCAN_THREADS / 64 + 1];
-    scan_in_place(wavecnt, nw, s_w);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int b = wave; b <= B; b += VX_SCAN_THREADS / 64) {
-        const long long cs = (long long)min(max(offsets[b], 0), Nv) * g.Kvol;
-        const int w = (int)(cs >> 6);
-        const long long r = ((long long)w << 6) + lane;
-        int o[3];
-        const unsigned long long m = __ballot(r < cs && cand_opener(coors, offsets, r, NC, B, g, tkeys, tvals, mask, shift, o));
-        if (lane == 0) out_offsets[b] = wavecnt[w] + __builtin_popcountll(m);      // (w <= nw: wavecnt[nw] is the total)
+// the candidates of the strided form and the opener of vox_hash.h's numbering over them: a candidate is an opener iff it is
+// the lowest candidate of its output site
+struct CandOpener {
+    using index = long long;
+    const int32_t *coors, *offsets;
+    int n, B;                 // n = NC = Nv * Kvol candidates
+    SpGeo g;
+    CoordTable t;             // keyed by output site
+    // o[3] = the site of c (whenever c names one)
+    __device__ __forceinline__ bool operator()(long long c, int *o) const {
+        if (c >= n) return false;
+        int i;
+        if (!cand_site(coors, (int)c, g, i, o)) return false;
+        const int slot = t.find(site_key(offsets, B, i, o, g));
+        return slot >= 0 && t.lowest(slot) == (int)c;
     }
+    __device__ __forceinline__ bool operator()(long long c) const { int o[3]; return (*this)(c, o); }
+    __device__ __forceinline__ long long first_of(int row) const { return min((long long)max(row, 0) * g.Kvol, (long long)n); }
+};
+
+__global__ __launch_bounds__(VX_THREADS) void sp_cand_insert_kernel(const CandOpener op) {
+    const long long c = (long long)blockIdx.x * VX_THREADS + threadIdx.x;
+    if (c >= op.n) return;
+    int i, o[3];
+    if (!cand_site(op.coors, (int)c, op.g, i, o)) return;
+    op.t.insert_min(site_key(op.offsets, op.B, i, o, op.g), (int)c);
+}
+
+// out_offsets[b] = openers among the candidates of the rows below offsets[b]
+__global__ __launch_bounds__(VX_SCAN_THREADS) void sp_scan_kernel(const CandOpener op, int32_t *wavecnt, int nw, int32_t *__restrict__ out_offsets) {
+    __shared__ int s_w[VX_SCAN_THREADS / 64 + 1];
+    opener_scan(op, op.offsets, op.B, wavecnt, nw, out_offsets, s_w);
 }
 
 // openers write their site at their number (global output row = openers before it), below the capacity
-__global__ __launch_bounds__(VX_THREADS) void sp_number_kernel(const int32_t *__restrict__ coors, const int32_t *__restrict__ offsets, int NC, int B, SpGeo g,
-                                                               const u64 *__restrict__ tkeys, const int32_t *__restrict__ tvals, unsigned mask, int shift,
-                                                               const int32_t *__restrict__ wavepre, int capacity, int32_t *__restrict__ out_coors) {
+__global__ __launch_bounds__(VX_THREADS) void sp_number_kernel(const CandOpener op, const int32_t *__restrict__ wavepre, int capacity,
+                                                               int32_t *__restrict__ out_coors) {
     const long long c = (long long)blockIdx.x * VX_THREADS + threadIdx.x;
-    const int lane = threadIdx.x & 63;
     int o[3];
-    const bool open = cand_opener(coors, offsets, c, NC, B, g, tkeys, tvals, mask, shift, o);
-    const unsigned long long m = __ballot(open);
+    const bool open = op(c, o);
+    const int below = openers_below(open);
     if (!open) return;
-    const int n = wavepre[c >> 6] + __builtin_popcountll(m & ((1ull << lane) - 1ull));
+    const int n = wavepre[c >> 6] + below;
     if (n < 0 || n >= capacity) return;
     out_coors[(size_t)n * 3 + 0] = o[0];
     out_coors[(size_t)n * 3 + 1] = o[1];
@@ -354,10 +331,7 @@ __global__ __launch_bounds__(256) void spconv_kernel(const ConvJob jb) {
 }
 
 // ---- dense ------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(VX_THREADS) void dense_init_kernel(int32_t *__restrict__ cell, unsigned n) {
-    const unsigned stride = gridDim.x * VX_THREADS;
-    for (unsigned s = blockIdx.x * VX_THREADS + threadIdx.x; s < n; s += stride) cell[s] = INT_MAX;
-}
+__global__ __launch_bounds__(VX_THREADS) void dense_init_kernel(int32_t *__restrict__ cell, unsigned n) { grid_fill(cell, n, INT_MAX); }
 
 __global__ __launch_bounds__(VX_THREADS) void dense_owner_kernel(const int32_t *__restrict__ coors, const int32_t *__restrict__ offsets, int No, int B, int Oz,
                                                                  int Oy, int Ox, int32_t *cell) {
@@ -366,7 +340,7 @@ __global__ __launch_bounds__(VX_THREADS) void dense_owner_kernel(const int32_t *
     const int z = coors[(size_t)r * 3], y = coors[(size_t)r * 3 + 1], x = coors[(size_t)r * 3 + 2];
     if (z < 0 || z >= Oz || y < 0 || y >= Oy || x < 0 || x >= Ox) return;
     const size_t at = (((size_t)scene_of(offsets, B, r) * Oz + z) * Oy + y) * Ox + x;
-    if (__hip_atomic_load(&cell[at], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > r) atomicMin(&cell[at], r);
+    keep_min(&cell[at], r);
 }
 
 __global__ __launch_bounds__(VX_THREADS) void dense_write_kernel(const float *__restrict__ feat, const int32_t *__restrict__ cell, int C, unsigned cells,
@@ -425,10 +399,11 @@ int sp_geo(const char *fn, const int *shape, const int *kernel, const int *strid
     return SAD_OK;
 }
 
+// the workspace (NULL: a size query): the input rows by cell; (strided form) the candidates by output site and their per-64 opener counts
 struct SpWs {
-    unsigned cap1, cap2;
-    int shift1, shift2;
-    size_t t1keys, t1vals, t2keys, t2vals, wavecnt, bytes;
+    CoordTable in, sites;
+    int32_t *wavecnt;
+    size_t bytes;
 };
 
 // the distinct output sites of the strided form: at most prod ceil(K_d / s_d) per input row
@@ -446,37 +421,26 @@ int sp_sizes_ok(const char *fn, long long Nv, int B, const SpGeo &g, int subm) {
     return SAD_OK;
 }
 
-SpWs sp_ws(int Nv, const SpGeo &g, int subm) {
-    SpWs w;
-    hash_capacity((unsigned long long)Nv, w.cap1, w.shift1);
-    size_t o = 0;
-    w.t1keys = o;   o += al16((size_t)w.cap1 * 8);
-    w.t1vals = o;   o += al16((size_t)w.cap1 * 4);
-    w.cap2 = 0;
-    w.shift2 = 0;
-    w.t2keys = w.t2vals = w.wavecnt = o;
+SpWs sp_ws(void *ws, int Nv, const SpGeo &g, int subm) {
+    SpWs w = {};
+    sad::Carve c;
+    w.in = CoordTable(ws, c, (unsigned long long)Nv);
     if (!subm) {
-        hash_capacity((unsigned long long)sp_max_sites(Nv, g), w.cap2, w.shift2);
-        w.t2keys = o;   o += al16((size_t)w.cap2 * 8);
-        w.t2vals = o;   o += al16((size_t)w.cap2 * 4);
-        w.wavecnt = o;  o += al16((((size_t)Nv * g.Kvol + 63) / 64 + 2) * 4);
+        w.sites = CoordTable(ws, c, (unsigned long long)sp_max_sites(Nv, g));
+        w.wavecnt = (int32_t *)((uintptr_t)ws + c.take((((size_t)Nv * g.Kvol + 63) / 64 + 2) * 4));
     }
-    w.bytes = o + 16;
+    w.bytes = c.o + 16;
     return w;
 }
 
-inline void launch_table_init(u64 *tkeys, int32_t *tvals, unsigned cap, hipStream_t st) {
-    const unsigned blocks = std::min(blocks_for(cap, VX_THREADS), 16384u);
-    hipLaunchKernelGGL(sp_init_kernel, dim3(blocks ? blocks : 1), dim3(VX_THREADS), 0, st, tkeys, tvals, cap);
+inline void launch_table_init(const CoordTable &t, hipStream_t st) {
+    hipLaunchKernelGGL(sp_init_kernel, dim3(std::min(blocks_for(t.mask + 1ull, VX_THREADS), 16384u)), dim3(VX_THREADS), 0, st, t);
 }
 
-inline void launch_input_table(const int32_t *coors, const int32_t *offsets, int Nv, int B, const SpGeo &g, char *ws, const SpWs &w, hipStream_t st) {
-    u64 *t1keys = (u64 *)(ws + w.t1keys);
-    int32_t *t1vals = (int32_t *)(ws + w.t1vals);
-    launch_table_init(t1keys, t1vals, w.cap1, st);
+inline void launch_input_table(const int32_t *coors, const int32_t *offsets, int Nv, int B, const SpGeo &g, const SpWs &w, hipStream_t st) {
+    launch_table_init(w.in, st);
     if (Nv > 0)
-        hipLaunchKernelGGL(sp_insert_kernel, dim3(blocks_for((unsigned long long)Nv, VX_THREADS)), dim3(VX_THREADS), 0, st, coors, offsets, Nv, B, g,
-                           t1keys, t1vals, w.cap1 - 1, w.shift1);
+        hipLaunchKernelGGL(sp_insert_kernel, dim3(blocks_for((unsigned long long)Nv, VX_THREADS)), dim3(VX_THREADS), 0, st, coors, offsets, Nv, B, g, w.in);
 }
 
 template <int WR, int RS, int NT>
@@ -507,7 +471,7 @@ SAD_API int sad_spconv_workspace_bytes(int Nv, int B, const int *kernel, const i
     const int zero[3] = {0, 0, 0};
     if (int rc = sp_geo("sad_spconv_workspace_bytes", nullptr, kernel, subm ? nullptr : stride, subm ? nullptr : zero, subm, g)) return rc;
     if (int rc = sp_sizes_ok("sad_spconv_workspace_bytes", Nv, B, g, subm)) return rc;
-    *out = sp_ws(Nv, g, subm).bytes;
+    *out = sp_ws(nullptr, Nv, g, subm).bytes;
     return SAD_OK;
 }
 
@@ -519,12 +483,11 @@ SAD_API int sad_spconv_index_subm(const int32_t *coors, const int32_t *offsets, 
     if (int rc = sp_geo("sad_spconv_index_subm", spatial_shape, kernel, nullptr, nullptr, 1, g)) return rc;
     if (int rc = sp_sizes_ok("sad_spconv_index_subm", Nv, B, g, 1)) return rc;
     if (Nv == 0) return SAD_OK;
-    const SpWs w = sp_ws(Nv, g, 1);
-    char *ws = (char *)workspace;
+    const SpWs w = sp_ws(workspace, Nv, g, 1);
     const hipStream_t st = (hipStream_t)stream;
-    launch_input_table(coors, offsets, Nv, B, g, ws, w, st);
+    launch_input_table(coors, offsets, Nv, B, g, w, st);
     hipLaunchKernelGGL(sp_nbr_kernel, dim3(blocks_for((unsigned long long)Nv * g.Kvol, VX_THREADS)), dim3(VX_THREADS), 0, st, (int32_t *)coors, offsets, Nv,
-                       B, g, (const u64 *)(ws + w.t1keys), (const int32_t *)(ws + w.t1vals), w.cap1 - 1, w.shift1, 0, nbr);
+                       B, g, w.in, 0, nbr);
     return sad::check_launch("sad_spconv_index_subm");
 }
 
@@ -535,21 +498,18 @@ SAD_API int sad_spconv_index_count(const int32_t *coors, const int32_t *offsets,
     SpGeo g;
     if (int rc = sp_geo("sad_spconv_index_count", spatial_shape, kernel, stride, padding, 0, g)) return rc;
     if (int rc = sp_sizes_ok("sad_spconv_index_count", Nv, B, g, 0)) return rc;
-    const SpWs w = sp_ws(Nv, g, 0);
-    char *ws = (char *)workspace;
+    const SpWs w = sp_ws(workspace, Nv, g, 0);
     const hipStream_t st = (hipStream_t)stream;
-    u64 *t2keys = (u64 *)(ws + w.t2keys);
-    int32_t *t2vals = (int32_t *)(ws + w.t2vals), *wavecnt = (int32_t *)(ws + w.wavecnt);
     const int NC = Nv * g.Kvol, nw = (NC + 63) / 64;
+    const CandOpener op = {coors, offsets, NC, B, g, w.sites};
     const dim3 gc(blocks_for((unsigned long long)NC, VX_THREADS)), tb(VX_THREADS);
-    launch_input_table(coors, offsets, Nv, B, g, ws, w, st);
-    launch_table_init(t2keys, t2vals, w.cap2, st);
+    launch_input_table(coors, offsets, Nv, B, g, w, st);
+    launch_table_init(w.sites, st);
     if (NC > 0) {
-        hipLaunchKernelGGL(sp_cand_insert_kernel, gc, tb, 0, st, coors, offsets, NC, B, g, t2keys, t2vals, w.cap2 - 1, w.shift2);
-        hipLaunchKernelGGL(sp_flags_kernel, gc, tb, 0, st, coors, offsets, NC, B, g, t2keys, t2vals, w.cap2 - 1, w.shift2, wavecnt);
+        hipLaunchKernelGGL(sp_cand_insert_kernel, gc, tb, 0, st, op);
+        hipLaunchKernelGGL(opener_flags_kernel<CandOpener>, gc, tb, 0, st, op, w.wavecnt);
     }
-    hipLaunchKernelGGL(sp_scan_kernel, dim3(1), dim3(VX_SCAN_THREADS), 0, st, wavecnt, nw, coors, offsets, Nv, NC, B, g, t2keys, t2vals, w.cap2 - 1,
-                       w.shift2, out_offsets);
+    hipLaunchKernelGGL(sp_scan_kernel, dim3(1), dim3(VX_SCAN_THREADS), 0, st, op, w.wavecnt, nw, out_offsets);
     return sad::check_launch("sad_spconv_index_count");
 }
 
@@ -565,16 +525,16 @@ SAD_API int sad_spconv_index_fill(const int32_t *coors, const int32_t *offsets, 
     if (int rc = sp_sizes_ok("sad_spconv_index_fill", Nv, B, g, 0)) return rc;
     if ((long long)capacity * g.Kvol >= (1LL << 31)) return sad::fail(SAD_EUNSUPPORTED, "sad_spconv_index_fill: capacity * Kvol must be below 2^31");
     if (capacity == 0) return SAD_OK;
-    const SpWs w = sp_ws(Nv, g, 0);
-    char *ws = (char *)workspace;
+    const SpWs w = sp_ws(workspace, Nv, g, 0);
     const hipStream_t st = (hipStream_t)stream;
     const int NC = Nv * g.Kvol;
-    if (NC > 0)
-        hipLaunchKernelGGL(sp_number_kernel, dim3(blocks_for((unsigned long long)NC, VX_THREADS)), dim3(VX_THREADS), 0, st, coors, offsets, NC, B, g,
-                           (const u64 *)(ws + w.t2keys), (const int32_t *)(ws + w.t2vals), w.cap2 - 1, w.shift2, (const int32_t *)(ws + w.wavecnt),
-                           capacity, out_coors);
+    if (NC > 0) {
+        const CandOpener op = {coors, offsets, NC, B, g, w.sites};
+        hipLaunchKernelGGL(sp_number_kernel, dim3(blocks_for((unsigned long long)NC, VX_THREADS)), dim3(VX_THREADS), 0, st, op,
+                           (const int32_t *)w.wavecnt, capacity, out_coors);
+    }
     hipLaunchKernelGGL(sp_nbr_kernel, dim3(blocks_for((unsigned long long)capacity * g.Kvol, VX_THREADS)), dim3(VX_THREADS), 0, st, out_coors, out_offsets,
-                       capacity, B, g, (const u64 *)(ws + w.t1keys), (const int32_t *)(ws + w.t1vals), w.cap1 - 1, w.shift1, 1, nbr);
+                       capacity, B, g, w.in, 1, nbr);
     return sad::check_launch("sad_spconv_index_fill");
 }
 

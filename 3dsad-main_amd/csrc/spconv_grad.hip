@@ -28,8 +28,7 @@ constexpr int SG_MAX_C = 256, SG_TR = 64, SG_MAX_TILES = 1024, SG_BIAS_ROWS = 10
 
 // ---- transposed rulebook ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(VX_THREADS) void spt_fill_kernel(int32_t *__restrict__ nbrT, unsigned n, int32_t *__restrict__ collisions) {
-    const unsigned stride = gridDim.x * VX_THREADS;
-    for (unsigned s = blockIdx.x * VX_THREADS + threadIdx.x; s < n; s += stride) nbrT[s] = -1;
+    grid_fill(nbrT, n, -1);
     if (blockIdx.x == 0 && threadIdx.x == 0) *collisions = 0;
 }
 
@@ -39,9 +38,7 @@ __global__ __launch_bounds__(VX_THREADS) void spt_scatter_kernel(const int32_t *
     const int i = nbr[e];
     if (i < 0 || i >= Nv) return;
     const unsigned o = e / (unsigned)Kvol, kk = e - o * (unsigned)Kvol;
-    unsigned *p = nbrT + (size_t)i * Kvol + kk;
-    // (values only go down: a stale value is a larger one, so a thread that sees a lower one can skip the atomic)
-    if (__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > o) atomicMin(p, o);
+    keep_min(nbrT + (size_t)i * Kvol + kk, o);          // (unsigned: the fill's -1 is the largest)
 }
 
 __global__ __launch_bounds__(VX_THREADS) void spt_count_kernel(const int32_t *__restrict__ nbr, unsigned n, int Kvol, int Nv,

@@ -3,15 +3,11 @@
 // are used only where their order cannot show (first row of a key = atomicMin, member counts = atomicAdd, placement inside
 // an UNORDERED member list that is ranked afterwards).
 //
-// voxel numbering (§20.2):
-//   insert   one lane per point: key = (gz*Gy + gy)*Gx + gx, inserted as (scene << 32 | key) into ONE open-addressing table
-//            of >= 2 * total slots (64-bit CAS, linear probing); the lowest row of a key is kept by atomicMin.
-//   flags    a point is an OPENER iff it is the first row of its key; per 64 rows a ballot's popcount.
-//   scan     one workgroup: exclusive scan of the per-64-row counts over ALL rows, then the prefix at every scene start: the
-//            voxel number of an opener is (openers before it) - (openers before its scene), numbers >= V are dropped — the
-//            walk-continues rule of §20.2 needs nothing more.
-//   number   openers write their number, the voxel's (z,y,x) and p2v; follow: the other points copy their opener's number
-//            and every taken point counts into count[b,v].
+// voxel numbering (§20.2): the first-appearance numbering of vox_hash.h over the rows, ALL scenes as one list.
+//   insert   one lane per point: key = (gz*Gy + gy)*Gx + gx goes into the coordinate table as (scene << 32 | key) with the row.
+//   number   the voxel number of an opener is (openers before it) - (openers before its scene); numbers >= V are dropped — the
+//            walk-continues rule of §20.2 needs nothing more.  Openers write their number, the voxel's (z,y,x) and p2v; follow:
+//            the other points copy their opener's number and every taken point counts into count[b,v].
 // member order (§20.3 / §20.4 / §20.5): CSR over the voxels (segment starts = a scan of the counts), members placed with a
 // per-voxel cursor in arrival order, then RANKED: the rank of row i in its voxel is the number of members below i, so
 // sorted[start + rank] = i puts every list in ascending row order whatever the arrival order was (lists are a handful of
@@ -57,16 +53,12 @@ __global__ __launch_bounds__(VX_THREADS) void voxel_coords_kernel(const float *_
 }
 
 // ---- numbering ------------------------------------------------------------------------------------------------
-// grid-stride fill of whatever is passed: the hash table (keys empty, first rows INT_MAX), per-voxel ints cnt / fill (0),
-// coors (-1)
-__global__ __launch_bounds__(VX_THREADS) void voxel_init_kernel(u64 *__restrict__ tkeys, int32_t *__restrict__ tvals, unsigned cap,
-                                                                int32_t *__restrict__ cnt, int32_t *__restrict__ fill,
+// grid-stride fill of whatever is passed: the coordinate table (empty), per-voxel ints cnt / fill (0), coors (-1)
+__global__ __launch_bounds__(VX_THREADS) void voxel_init_kernel(CoordTable t, int32_t *__restrict__ cnt, int32_t *__restrict__ fill,
                                                                 int32_t *__restrict__ coors, unsigned nvox) {
     const unsigned stride = gridDim.x * VX_THREADS;
     const unsigned t0 = blockIdx.x * VX_THREADS + threadIdx.x;
-    if (tkeys) {
-        for (unsigned s = t0; s < cap; s += stride) { tkeys[s] = VX_EMPTY; tvals[s] = INT_MAX; }
-    }
+    if (t.keys) t.clear();
     for (unsigned s = t0; s < nvox; s += stride) {
         if (cnt) cnt[s] = 0;
         if (fill) fill[s] = 0;
@@ -81,8 +73,7 @@ __global__ __launch_bounds__(VX_THREADS) void voxel_init_kernel(u64 *__restrict_
 }
 
 __global__ __launch_bounds__(VX_THREADS) void voxel_insert_kernel(const float *__restrict__ points, const int32_t *__restrict__ offsets,
-                                                                  int total, int B, int C, VoxGrid g, u64 *tkeys, int32_t *tvals,
-                                                                  unsigned mask, int shift, int32_t *__restrict__ pslot) {
+                                                                  int total, int B, int C, VoxGrid g, CoordTable t, int32_t *__restrict__ pslot) {
     const int i = blockIdx.x * VX_THREADS + threadIdx.x;
     if (i >= total) return;
     int gx, gy, gz;
@@ -92,61 +83,46 @@ __global__ __launch_bounds__(VX_THREADS) void voxel_insert_kernel(const float *_
     }
     const int key = (gz * g.G[1] + gy) * g.G[0] + gx;
     const u64 k64 = ((u64)(unsigned)scene_of(offsets, B, i) << 32) | (unsigned)key;
-    const int slot = hash_insert(tkeys, mask, shift, k64);
-    if (slot >= 0) hash_min(tvals, slot, i);
-    pslot[i] = slot;
+    pslot[i] = t.insert_min(k64, i);
 }
 
-__device__ __forceinline__ bool is_opener(const int32_t *__restrict__ pslot, const int32_t *__restrict__ tvals, int i, int total) {
-    if (i >= total) return false;
-    const int s = pslot[i];
-    return s >= 0 && tvals[s] == i;
-}
+// the opener of vox_hash.h's numbering: a point is an opener iff it is the lowest row of its key
+struct VoxOpener {
+    using index = int;
+    const int32_t *pslot;     // [n]: the table slot of every point's key, -1 outside the grid
+    CoordTable t;
+    int n;                    // total points
+    __device__ __forceinline__ int slot_of(int i) const { return i < n ? pslot[i] : -1; }
+    __device__ __forceinline__ bool opens(int slot, int i) const { return slot >= 0 && t.lowest(slot) == i; }   // slot = slot_of(i)
+    __device__ __forceinline__ bool operator()(int i) const { return opens(slot_of(i), i); }
+    __device__ __forceinline__ int first_of(int row) const { return min(max(row, 0), n); }
+};
 
-// wavecnt[w] = openers among rows 64 w .. 64 w + 63
-__global__ __launch_bounds__(VX_THREADS) void voxel_flags_kernel(const int32_t *__restrict__ pslot, const int32_t *__restrict__ tvals, int total,
-                                                                 int32_t *__restrict__ wavecnt) {
-    const int i = blockIdx.x * VX_THREADS + threadIdx.x;
-    const unsigned long long m = __ballot(is_opener(pslot, tvals, i, total));
-    if ((threadIdx.x & 63) == 0 && i < total) wavecnt[i >> 6] = __builtin_popcountll(m);
-}
-
-// wavecnt[nw + 1] -> exclusive prefixes; P[b] = openers in rows below offsets[b] (b = 0 .. B); voxel_num[b] = min(V, openers of b)
-__global__ __launch_bounds__(VX_SCAN_THREADS) void voxel_scan_kernel(int32_t *wavecnt, int nw, const int32_t *__restrict__ pslot,
-                                                                     const int32_t *__restrict__ tvals, const int32_t *__restrict__ offsets,
-                                                                     int total, int B, int V, int32_t *P, int32_t *__restrict__ voxel_num) {
+// P[b] = openers in rows below offsets[b] (b = 0 .. B); voxel_num[b] = min(V, openers of b)
+__global__ __launch_bounds__(VX_SCAN_THREADS) void voxel_scan_kernel(const VoxOpener op, const int32_t *__restrict__ offsets, int B, int32_t *wavecnt,
+                                                                     int nw, int V, int32_t *P, int32_t *__restrict__ voxel_num) {
     __shared__ int s_w[VX_SCAN_THREADS / 64 + 1];
-    scan_in_place(wavecnt, nw, s_w);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int b = wave; b <= B; b += VX_SCAN_THREADS / 64) {
-        const int o = min(max(offsets[b], 0), total);
-        const int w = o >> 6, r = (w << 6) + lane;
-        const unsigned long long m = __ballot(r < o && is_opener(pslot, tvals, r, total));
-        if (lane == 0) P[b] = wavecnt[w] + __builtin_popcountll(m);      // (w <= nw: wavecnt[nw] is the total)
-    }
+    opener_scan(op, offsets, B, wavecnt, nw, P, s_w);
     __syncthreads();
     for (int b = threadIdx.x; b < B; b += VX_SCAN_THREADS) voxel_num[b] = min(max(P[b + 1] - P[b], 0), V);
 }
 
 // openers: voxel number, p2v and the voxel's (z,y,x); invalid points: p2v = -1
-__global__ __launch_bounds__(VX_THREADS) void voxel_number_kernel(const int32_t *__restrict__ pslot, const u64 *__restrict__ tkeys,
-                                                                  const int32_t *__restrict__ tvals, const int32_t *__restrict__ offsets,
-                                                                  const int32_t *__restrict__ wavepre, const int32_t *__restrict__ P, int total,
-                                                                  int B, int V, int Gx, int Gy, int32_t *__restrict__ p2v,
-                                                                  int32_t *__restrict__ coors) {
+__global__ __launch_bounds__(VX_THREADS) void voxel_number_kernel(const VoxOpener op, const int32_t *__restrict__ offsets,
+                                                                  const int32_t *__restrict__ wavepre, const int32_t *__restrict__ P, int B, int V,
+                                                                  int Gx, int Gy, int32_t *__restrict__ p2v, int32_t *__restrict__ coors) {
     const int i = blockIdx.x * VX_THREADS + threadIdx.x;
-    const int lane = threadIdx.x & 63;
-    const int slot = i < total ? pslot[i] : -1;
-    const bool open = slot >= 0 && tvals[slot] == i;
-    const unsigned long long m = __ballot(open);
-    if (i >= total) return;
+    const int slot = op.slot_of(i);                        // (read once: it also tells the rows outside the grid)
+    const bool open = op.opens(slot, i);
+    const int below = openers_below(open);
+    if (i >= op.n) return;
     if (slot < 0) { p2v[i] = -1; return; }
     if (!open) return;
     const int b = scene_of(offsets, B, i);
-    const int vn = wavepre[i >> 6] + __builtin_popcountll(m & ((1ull << lane) - 1ull)) - P[b];
+    const int vn = wavepre[i >> 6] + below - P[b];
     if (vn < 0 || vn >= V) { p2v[i] = -1; return; }       // the voxel cap: this key is dropped, with every later point of it
     p2v[i] = vn;
-    const int key = (int)(unsigned)(tkeys[slot] & 0xFFFFFFFFull);
+    const int key = (int)(unsigned)(op.t.keys[slot] & 0xFFFFFFFFull);
     const int gx = key % Gx, q = key / Gx;
     int32_t *c = coors + ((size_t)b * V + vn) * 3;
     c[0] = q / Gy;
@@ -155,14 +131,13 @@ __global__ __launch_bounds__(VX_THREADS) void voxel_number_kernel(const int32_t 
 }
 
 // the other valid points take their opener's number; every taken point counts
-__global__ __launch_bounds__(VX_THREADS) void voxel_follow_kernel(const int32_t *__restrict__ pslot, const int32_t *__restrict__ tvals,
-                                                                  const int32_t *__restrict__ offsets, int total, int B, int V, int32_t *p2v,
+__global__ __launch_bounds__(VX_THREADS) void voxel_follow_kernel(const VoxOpener op, const int32_t *__restrict__ offsets, int B, int V, int32_t *p2v,
                                                                   int32_t *count) {
-    const int i = blockIdx.x * VX_THREADS + threadIdx.x;
+    const int i = blockIdx.x * VX_THREADS + threadIdx.x, total = op.n;
     if (i >= total) return;
-    const int slot = pslot[i];
+    const int slot = op.pslot[i];
     if (slot < 0) return;
-    const int first = tvals[slot];
+    const int first = op.t.lowest(slot);
     int v;
     if (first == i) v = p2v[i];
     else {
@@ -335,34 +310,30 @@ __global__ __launch_bounds__(VX_THREADS) void voxel_reduce_grad_kernel(const flo
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
-using sad::al16;
 using sad::blocks_for;
 
-// workspace layout (bytes from the base)
+// workspace layout: the coordinate table of `total` keys in workspace `ws` (NULL: a size query), the rest in bytes from the base
 struct VoxWs {
-    unsigned cap;          // hash slots: a power of two >= 2 * total (>= 2)
-    int shift;
-    size_t tkeys, tvals, pslot, wavecnt, P, blocksum, start, fill, cnt, p2v, members, sorted, bytes;
+    CoordTable t;
+    size_t pslot, wavecnt, P, blocksum, start, fill, cnt, p2v, members, sorted, bytes;
 };
 
-VoxWs vox_ws(int total, int B, int V) {
+VoxWs vox_ws(void *ws, int total, int B, int V) {
     VoxWs w;
-    hash_capacity((unsigned long long)total, w.cap, w.shift);
     const size_t nvox = (size_t)B * V, nw = ((size_t)total + 63) / 64;
-    size_t o = 0;
-    w.tkeys = o;    o += al16((size_t)w.cap * 8);
-    w.tvals = o;    o += al16((size_t)w.cap * 4);
-    w.pslot = o;    o += al16((size_t)total * 4);
-    w.wavecnt = o;  o += al16((nw + 1) * 4);
-    w.P = o;        o += al16(((size_t)B + 1) * 4);
-    w.blocksum = o; o += al16((nvox / VX_SCAN_THREADS + 1) * 4);
-    w.start = o;    o += al16(nvox * 4);
-    w.fill = o;     o += al16(nvox * 4);
-    w.cnt = o;      o += al16(nvox * 4);
-    w.p2v = o;      o += al16((size_t)total * 4);
-    w.members = o;  o += al16((size_t)total * 4);
-    w.sorted = o;   o += al16((size_t)total * 4);
-    w.bytes = o + 16;
+    sad::Carve c;
+    w.t = CoordTable(ws, c, (unsigned long long)total);
+    w.pslot = c.take((size_t)total * 4);
+    w.wavecnt = c.take((nw + 1) * 4);
+    w.P = c.take(((size_t)B + 1) * 4);
+    w.blocksum = c.take((nvox / VX_SCAN_THREADS + 1) * 4);
+    w.start = c.take(nvox * 4);
+    w.fill = c.take(nvox * 4);
+    w.cnt = c.take(nvox * 4);
+    w.p2v = c.take((size_t)total * 4);
+    w.members = c.take((size_t)total * 4);
+    w.sorted = c.take((size_t)total * 4);
+    w.bytes = c.o + 16;
     return w;
 }
 
@@ -398,30 +369,30 @@ int vox_grid(const char *fn, const float *voxel_size, const float *point_range, 
     return SAD_OK;
 }
 
-inline void launch_init(u64 *tkeys, int32_t *tvals, unsigned cap, int32_t *cnt, int32_t *fill, int32_t *coors, unsigned nvox, hipStream_t st) {
-    const unsigned long long n = tkeys ? (cap > nvox ? cap : nvox) : nvox;
+// t (keys == NULL: no table) is cleared, cnt / fill / coors (each optional) are filled
+inline void launch_init(const CoordTable &t, int32_t *cnt, int32_t *fill, int32_t *coors, unsigned nvox, hipStream_t st) {
+    const unsigned long long n = std::max<unsigned long long>(t.keys ? t.mask + 1ull : 0ull, nvox);
     const unsigned blocks = (unsigned)std::min<unsigned long long>(blocks_for(n, VX_THREADS), 16384ull);
-    hipLaunchKernelGGL(voxel_init_kernel, dim3(blocks ? blocks : 1), dim3(VX_THREADS), 0, st, tkeys, tvals, cap, cnt, fill, coors, nvox);
+    hipLaunchKernelGGL(voxel_init_kernel, dim3(blocks ? blocks : 1), dim3(VX_THREADS), 0, st, t, cnt, fill, coors, nvox);
 }
 
 // §20.2: p2v[total], coors[B,V,3], count[B,V], voxel_num[B].  `fill` (optional): zeroed for a CSR that follows
 void launch_numbering(const float *points, const int32_t *offsets, int total, int B, int C, const VoxGrid &g, int V, char *ws, const VoxWs &w,
                       int32_t *p2v, int32_t *coors, int32_t *count, int32_t *voxel_num, int32_t *fill, hipStream_t st) {
-    u64 *tkeys = (u64 *)(ws + w.tkeys);
-    int32_t *tvals = (int32_t *)(ws + w.tvals), *pslot = (int32_t *)(ws + w.pslot), *wavecnt = (int32_t *)(ws + w.wavecnt);
-    int32_t *P = (int32_t *)(ws + w.P);
+    int32_t *pslot = (int32_t *)(ws + w.pslot), *wavecnt = (int32_t *)(ws + w.wavecnt), *P = (int32_t *)(ws + w.P);
+    const VoxOpener op = {pslot, w.t, total};
     const unsigned nvox = (unsigned)B * (unsigned)V;
     const int nw = (total + 63) / 64;
     const dim3 gp(blocks_for((unsigned long long)total, VX_THREADS)), tb(VX_THREADS);
-    launch_init(tkeys, tvals, w.cap, count, fill, coors, nvox, st);
+    launch_init(w.t, count, fill, coors, nvox, st);
     if (total > 0) {
-        hipLaunchKernelGGL(voxel_insert_kernel, gp, tb, 0, st, points, offsets, total, B, C, g, tkeys, tvals, w.cap - 1, w.shift, pslot);
-        hipLaunchKernelGGL(voxel_flags_kernel, gp, tb, 0, st, pslot, tvals, total, wavecnt);
+        hipLaunchKernelGGL(voxel_insert_kernel, gp, tb, 0, st, points, offsets, total, B, C, g, w.t, pslot);
+        hipLaunchKernelGGL(opener_flags_kernel<VoxOpener>, gp, tb, 0, st, op, wavecnt);
     }
-    hipLaunchKernelGGL(voxel_scan_kernel, dim3(1), dim3(VX_SCAN_THREADS), 0, st, wavecnt, nw, pslot, tvals, offsets, total, B, V, P, voxel_num);
+    hipLaunchKernelGGL(voxel_scan_kernel, dim3(1), dim3(VX_SCAN_THREADS), 0, st, op, offsets, B, wavecnt, nw, V, P, voxel_num);
     if (total > 0) {
-        hipLaunchKernelGGL(voxel_number_kernel, gp, tb, 0, st, pslot, tkeys, tvals, offsets, wavecnt, P, total, B, V, g.G[0], g.G[1], p2v, coors);
-        hipLaunchKernelGGL(voxel_follow_kernel, gp, tb, 0, st, pslot, tvals, offsets, total, B, V, p2v, count);
+        hipLaunchKernelGGL(voxel_number_kernel, gp, tb, 0, st, op, offsets, wavecnt, P, B, V, g.G[0], g.G[1], p2v, coors);
+        hipLaunchKernelGGL(voxel_follow_kernel, gp, tb, 0, st, op, offsets, B, V, p2v, count);
     }
 }
 
@@ -444,16 +415,16 @@ void launch_csr(const int32_t *p2v, const int32_t *offsets, int total, int B, in
 
 namespace sad {
 
-size_t voxel_ws_bytes(int total, int B, int V) { return vox_ws(total, B, V).bytes; }
+size_t voxel_ws_bytes(int total, int B, int V) { return vox_ws(nullptr, total, B, V).bytes; }
 
 int voxel_sizes_ok(const char *fn, long long total, int B, long long V) { return vox_sizes_ok(fn, total, B, V); }
 
 void voxel_member_lists(const int32_t *p2v, const int32_t *offsets, int total, int B, int V, void *workspace, hipStream_t st,
                         VoxLists &out) {
-    const VoxWs w = vox_ws(total, B, V);
+    const VoxWs w = vox_ws(workspace, total, B, V);
     char *ws = (char *)workspace;
     int32_t *cnt = (int32_t *)(ws + w.cnt);
-    launch_init(nullptr, nullptr, 0, cnt, (int32_t *)(ws + w.fill), nullptr, (unsigned)B * (unsigned)V, st);
+    launch_init(CoordTable{}, cnt, (int32_t *)(ws + w.fill), nullptr, (unsigned)B * (unsigned)V, st);
     if (total > 0)
         hipLaunchKernelGGL(voxel_count_kernel, dim3(blocks_for((unsigned long long)total, VX_THREADS)), dim3(VX_THREADS), 0, st, p2v, offsets,
                            total, B, V, cnt);
@@ -469,7 +440,7 @@ SAD_API int sad_voxel_workspace_bytes(int total_points, int B, int max_voxels, s
     SAD_REQUIRE(out, "sad_voxel_workspace_bytes: NULL out");
     *out = 0;
     if (int rc = vox_sizes_ok("sad_voxel_workspace_bytes", total_points, B, max_voxels)) return rc;
-    *out = vox_ws(total_points, B, max_voxels).bytes;
+    *out = vox_ws(nullptr, total_points, B, max_voxels).bytes;
     return SAD_OK;
 }
 
@@ -497,7 +468,7 @@ SAD_API int sad_voxel_index_f32(const float *points, const int32_t *offsets, int
     SAD_REQUIRE(((uintptr_t)workspace & 15) == 0, "sad_voxel_index_f32: workspace must be 16-byte aligned");
     VoxGrid g;
     if (int rc = vox_grid("sad_voxel_index_f32", voxel_size, point_range, g)) return rc;
-    const VoxWs w = vox_ws(total_points, B, max_voxels);
+    const VoxWs w = vox_ws(workspace, total_points, B, max_voxels);
     launch_numbering(points, offsets, total_points, B, C, g, max_voxels, (char *)workspace, w, point2voxel, coors, count, voxel_num, nullptr,
                      (hipStream_t)stream);
     return sad::check_launch("sad_voxel_index_f32");
@@ -517,7 +488,7 @@ SAD_API int sad_voxelize_f32(const float *points, const int32_t *offsets, int to
         return sad::fail(SAD_EUNSUPPORTED, "sad_voxelize_f32: voxels[B,V,T,C] of %llu floats is too large", nfloats);
     VoxGrid g;
     if (int rc = vox_grid("sad_voxelize_f32", voxel_size, point_range, g)) return rc;
-    const VoxWs w = vox_ws(total_points, B, max_voxels);
+    const VoxWs w = vox_ws(workspace, total_points, B, max_voxels);
     char *ws = (char *)workspace;
     const hipStream_t st = (hipStream_t)stream;
     int32_t *cnt = (int32_t *)(ws + w.cnt), *p2v = (int32_t *)(ws + w.p2v);

@@ -270,17 +270,18 @@ __global__ __launch_bounds__(256) void voxel_encode_kernel(const EncP p) {
     }
 }
 
-inline unsigned long long blocks_of(unsigned long long n, int threads) { return (n + threads - 1) / threads; }
+using sad::blocks_for;
 
 struct EncWs { size_t lists, mean, wimg, bytes; };
 
 EncWs enc_ws(int total, int B, int V, int Cin, int Cout) {
     EncWs w;
-    w.lists = 0;
-    w.mean = sad::voxel_ws_bytes(total, B, V);
-    w.wimg = w.mean + sad::al16((size_t)B * V * 3 * 4);
     const size_t NP = ((size_t)Cout + 31) / 32 * 32, KP = ((size_t)Cin + 7) / 8 * 8;
-    w.bytes = w.wimg + (Cout > 0 ? (NP + NP * KP) * 4 : 0) + 16;
+    sad::Carve c;
+    w.lists = c.take(sad::voxel_ws_bytes(total, B, V));
+    w.mean = c.take((size_t)B * V * 3 * 4);
+    w.wimg = c.take(Cout > 0 ? (NP + NP * KP) * 4 : 0);
+    w.bytes = c.o + 16;
     return w;
 }
 
@@ -319,7 +320,7 @@ void enc_lists(EncP &p, char *ws, const EncWs &w, hipStream_t st) {
     float *mean = (float *)(ws + w.mean);
     p.mean = mean;
     if (p.cc && p.total > 0)
-        hipLaunchKernelGGL(enc_mean_kernel, dim3((unsigned)blocks_of((unsigned long long)p.nvox * 3, VX_THREADS)), dim3(VX_THREADS), 0, st, p.points,
+        hipLaunchKernelGGL(enc_mean_kernel, dim3(blocks_for((unsigned long long)p.nvox * 3, VX_THREADS)), dim3(VX_THREADS), 0, st, p.points,
                            p.C, p.start, p.cnt, p.sorted, p.T, p.total, p.nvox, mean);
 }
 
@@ -346,7 +347,7 @@ SAD_API int sad_voxel_decorate_f32(const float *points, const int32_t *point2vox
     if (total_points == 0) return SAD_OK;
     const hipStream_t st = (hipStream_t)stream;
     enc_lists(p, (char *)workspace, enc_ws(total_points, B, max_voxels, p.Cin, 0), st);
-    hipLaunchKernelGGL(enc_decorate_kernel, dim3((unsigned)blocks_of((unsigned long long)total_points * p.Cin, VX_THREADS)), dim3(VX_THREADS), 0, st,
+    hipLaunchKernelGGL(enc_decorate_kernel, dim3(blocks_for((unsigned long long)total_points * p.Cin, VX_THREADS)), dim3(VX_THREADS), 0, st,
                        p, rows);
     return sad::check_launch("sad_voxel_decorate_f32");
 }
@@ -369,8 +370,9 @@ SAD_API int sad_voxel_encode_f32(const float *points, const int32_t *point2voxel
     p.pooled = pooled; p.arg = arg; p.pointwise = pointwise;
     p.vec_pw = (((uintptr_t)pooled | (uintptr_t)arg | (uintptr_t)pointwise) & 15) == 0;
     const unsigned long long C4 = ((unsigned long long)Cout + 3) / 4;
-    const unsigned long long tile_blocks = blocks_of(blocks_of((unsigned long long)total_points, 32), 4);
-    const unsigned long long zero_blocks = blocks_of((unsigned long long)p.nvox * C4 + (pointwise ? (unsigned long long)total_points * C4 : 0ull), 256);
+    // (each count fits blocks_for's unsigned: nvox < 2^31, total <= 2^30, C4 <= 64; their sum is checked in 64 bits)
+    const unsigned long long tile_blocks = blocks_for(blocks_for((unsigned long long)total_points, 32), 4);
+    const unsigned long long zero_blocks = blocks_for((unsigned long long)p.nvox * C4 + (pointwise ? (unsigned long long)total_points * C4 : 0ull), 256);
     if (tile_blocks + zero_blocks >= (1ull << 31)) return sad::fail(SAD_EUNSUPPORTED, "sad_voxel_encode_f32: too many workgroups");
     p.tile_blocks = (unsigned)tile_blocks;
     const hipStream_t st = (hipStream_t)stream;
@@ -380,7 +382,7 @@ SAD_API int sad_voxel_encode_f32(const float *points, const int32_t *point2voxel
     float *wimg = (float *)(ws + w.wimg);
     p.wimg = wimg;
     const int NP = 32 * p.CT, KP = 8 * p.KG;
-    hipLaunchKernelGGL(enc_pack_kernel, dim3((unsigned)blocks_of((unsigned long long)NP + (unsigned long long)NP * KP, 256)), dim3(256), 0, st, weight,
+    hipLaunchKernelGGL(enc_pack_kernel, dim3(blocks_for((unsigned long long)NP + (unsigned long long)NP * KP, 256)), dim3(256), 0, st, weight,
                        bias, p.Cin, Cout, KP, NP, wimg);
     hipLaunchKernelGGL(voxel_encode_kernel, dim3((unsigned)(tile_blocks + zero_blocks)), dim3(256), 0, st, p);
     return sad::check_launch("sad_voxel_encode_f32");

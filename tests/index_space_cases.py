@@ -342,7 +342,7 @@ def family_rows_voxel(C=4):
 
 
 # ---- probe runs that wrap: the one WHITE-BOX family ------------------------------------------------------------------------
-# A Python model of hash_capacity and hash_slot0 of csrc/vox_hash.h.  If the hash there changes (the multiplier, the key layout
+# A Python model of CoordTable's constructor (capacity, shift) and slot0 of csrc/vox_hash.h.  If the hash there changes (the multiplier, the key layout
 # scene << 32 | cell, the capacity rule), this model must change with it: the coverage assertions below are made on the model.
 HASH_MULT = 0x9E3779B97F4A7C15
 MASK64 = 2 ** 64 - 1

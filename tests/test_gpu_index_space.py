@@ -254,6 +254,46 @@ def test_voxel_limit_grid(sad, dev):
     _check_voxel_case(dev, *ic.family_limit_voxel()[0])
 
 
+# ---- the numbering both share -----------------------------------------------------------------------------------------------
+def test_voxel_and_rulebook_number_alike(sad, dev):
+    """The two users of the first-appearance numbering (csrc/vox_hash.h) on one input: voxel_index over points at cell centres
+    and the strided K = 1, s = 1, p = 0 rulebook over the cells give the same counts, the same coordinates in the same order
+    and the lowest row of every voxel, and each equals its numpy reference.  Scenes of 0, 65, 64 and 129 rows: an empty scene,
+    boundaries off and on a multiple of 64, a last partial wave."""
+    from sad_amd import ops
+    G = (6, 7, 8)                                                            # (z,y,x)
+    sizes = (0, 65, 64, 129)
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    N, B, V = int(off[-1]), len(sizes), int(off[-1])
+    rng = np.random.default_rng(20)
+    cells = np.stack([rng.integers(0, g, N) for g in G], -1).astype(np.int32)
+    cells[128], cells[200] = cells[66], cells[130]                           # duplicates inside a scene, across a wave boundary
+    pts = np.ascontiguousarray(cells[:, ::-1].astype(F) + F(0.5))            # (x,y,z) centres of a unit voxel grid
+    v, r = (1.0, 1.0, 1.0), (0.0, 0.0, 0.0, float(G[2]), float(G[1]), float(G[0]))
+    w_p2v, w_coors, w_count, w_num = voxel_ref.voxel_index(pts, off, v, r, V)
+    w_oc, w_oo, w_nbr = ref.index_vec(cells, off, G, (1, 1, 1), (1, 1, 1), (0, 0, 0))
+    # the input keeps what it is for
+    assert any(w_num[b] < sizes[b] for b in range(B)), "no scene with fewer voxels than rows"
+    assert any(sizes[b] > 0 and off[b] % 64 != 0 for b in range(B)), "no non-empty scene starts off a multiple of 64"
+    assert (w_p2v >= 0).all() and w_nbr.shape == (len(w_oc), 1)
+
+    tp, tc, to = _t(pts, dev), _t(cells, dev), _t(off, dev)
+    g_vox = ops.voxel_index(tp, to, v, r, V)
+    g_sp = ops.sparse_conv_index(tc, to, G, 1, 1, 0, False)
+    for g, x, n in zip(g_vox, (w_p2v, w_coors, w_count, w_num), ("point2voxel", "coors", "count", "voxel_num")):
+        _eq_int(g, x, f"voxel_index.{n}")
+    for g, x, n in zip(g_sp, (w_oc, w_oo, w_nbr), ("out_coors", "out_offsets", "nbr")):
+        _eq_int(g, x, f"sparse_conv_index.{n}")
+    p2v, coors, _, num = (t.cpu().numpy() for t in g_vox)
+    oc, oo, nbr = (t.cpu().numpy() for t in g_sp)
+    assert np.array_equal(num, np.diff(oo)), "voxels per scene != output sites per scene"
+    for b in range(B):
+        assert np.array_equal(coors[b, :num[b]], oc[oo[b]:oo[b + 1]]), f"scene {b}: coordinates or their order differ"
+        rows = np.arange(off[b], off[b + 1])
+        lowest = np.array([rows[p2v[rows] == k].min() for k in range(num[b])], np.int32).reshape(-1)
+        assert np.array_equal(nbr[oo[b]:oo[b + 1], 0], lowest), f"scene {b}: nbr[:, 0] is not the lowest row of each voxel"
+
+
 # ---- modules ----------------------------------------------------------------------------------------------------------------
 def test_sequential_of_sweep_geometries_layer_by_layer(dev, orc):
     import torch

@@ -151,3 +151,54 @@ def test_sparse_conv_geometry_refuses_what_the_library_refuses(sad):
         ops.sparse_conv_geometry((1, 5, 5), 2, 1, 0)
     with pytest.raises(ValueError, match="above 65535"):
         ops.sparse_conv_geometry((1, 5, 5), 2, 65536, 0)
+
+
+# The workspace sizes of the three entry points whose layout is carved from the coordinate table and the numbering arrays, as
+# the library returned them before the table and the carving moved into one place each (read from a build of that commit).
+# Callers allocate by these numbers and the kernels index by the same layout, so a change here is a change of the C-ABI.
+# (total, B, V)
+WS_VOXEL = [
+    ((0, 1, 1), 144),
+    ((1, 1, 1), 208),
+    ((1, 3, 2000), 72176),
+    ((1000, 1, 2000), 64704),
+    ((1000, 3, 2000), 112720),
+    ((65537, 1, 1), 4198576),
+    ((65537, 3, 2000), 4270544),
+]
+# (total, B, V, Cin, Cout)
+WS_ENCODE = [
+    ((0, 1, 1, 4, 0), 176),
+    ((1, 3, 1, 256, 4), 33168),
+    ((1000, 3, 2000, 4, 64), 187040),
+    ((1000, 1, 2000, 64, 0), 88720),
+    ((65537, 1, 2000, 64, 256), 4313104),
+    ((65537, 3, 1, 256, 256), 4461808),
+]
+# (Nv, B, kernel, stride, subm)
+WS_SPCONV = [
+    ((0, 1, (3, 3, 3), None, 1), 48),
+    ((1000, 3, (3, 3, 3), None, 1), 24592),
+    ((65537, 1, (3, 1, 1), None, 1), 3145744),
+    ((0, 1, (3, 3, 3), (2, 2, 2), 0), 96),
+    ((1, 3, (2, 2, 2), (2, 2, 2), 0), 96),
+    ((1000, 3, (3, 3, 3), (2, 2, 2), 0), 222896),
+    ((1000, 1, (3, 3, 3), (1, 1, 1), 0), 812720),
+    ((65537, 3, (3, 1, 1), (1, 1, 1), 0), 9449504),
+    ((65537, 1, (2, 2, 2), (1, 1, 1), 0), 28344352),
+    ((65537, 3, (3, 3, 3), (2, 2, 2), 0), 28422176),
+]
+
+
+def test_workspace_sizes_are_pinned(sad):
+    import ctypes
+    from sad_amd import _lib
+    L = _lib.lib()
+    n = ctypes.c_size_t(0)
+    i3 = lambda t: None if t is None else (ctypes.c_int * 3)(*t)
+    for a, want in WS_VOXEL:
+        assert L.sad_voxel_workspace_bytes(*a, ctypes.byref(n)) == 0 and n.value == want, (a, n.value, want)
+    for a, want in WS_ENCODE:
+        assert L.sad_voxel_encode_workspace_bytes(*a, ctypes.byref(n)) == 0 and n.value == want, (a, n.value, want)
+    for (Nv, B, K, s, subm), want in WS_SPCONV:
+        assert L.sad_spconv_workspace_bytes(Nv, B, i3(K), i3(s), subm, ctypes.byref(n)) == 0 and n.value == want, ((Nv, B, K, s, subm), n.value, want)

@@ -1,30 +1,22 @@
 // Dense head decode (SPEC.md §25): the raw maps of an anchor head / a centre head -> boxes[B,K,D], scores[B,K], labels[B,K],
 // what sad_nms_boxes_f32 takes.  One launch per call, no atomics, every output element stored once.
 //
-// anchor, dense   a workgroup owns a tile of 64 cells x up to 8 anchors: lane = cell (y * W + x), wave + 4 * pass = anchor.
+// anchor, dense   a workgroup owns a tile of 64 cells x up to 8 anchors: lane = cell (y * W + x), wave + 4 * pass = anchor (dense_tile.h).
 //   nchw          channel planes are unit-stride in the cell, so every load of a wave is 256 contiguous bytes.
-//   nhwc          the channels of a cell are contiguous: a pass (64 cells x 4 anchors) is staged through LDS by all 256
-//                 threads walking the floats in memory order (runs of 4 * 7, 4 * nb and 4 * C floats per cell; class
-//                 logits in chunks of 8 classes), and a thread reads its row from LDS.
-//   output        rows k = cell * A + a of a tile are one contiguous span (A <= 8) or one span of 8 rows per cell: the
-//                 thread that decoded a row puts it into an LDS image of that span, and the workgroup stores the image in
-//                 memory order: consecutive lanes store consecutive floats, not seven floats 28 bytes apart.
+//   nhwc          the channels of a cell are contiguous: a pass (64 cells x 4 anchors) is staged through LDS by all 256 threads walking
+//                 the floats in memory order (stage_pass; class logits in chunks of 8 classes), and a thread reads its row from LDS.
+//   output        rows k = cell * A + a of a tile are one contiguous span (A <= 8) or one span of 8 rows per cell: the thread that decoded
+//                 a row puts it into an LDS image, which the workgroup stores in memory order (flush_spans): no stores 28 bytes apart.
 // centre, dense   a workgroup owns 256 consecutive cells, one per thread; the 3 x 3 test reads the neighbours where
 //                 they are (rows above and below are the same 256-byte spans one row away).
 // index           one thread per output row p, 256 consecutive p per workgroup; the row's reads are gathers.
-// The anchor tables (sizes, z centres, rotations) arrive in the kernel arguments and are copied to LDS once per
-// workgroup, since the index path addresses them per lane.
 #include "common.h"
 #include <math.h>
 
 namespace {
 
-#include "prims.h"       // flush_spans, stage_rows
+#include "dense_tile.h"
 
-constexpr int DH_THREADS = 256;
-constexpr int TC = 64;             // cells of an anchor tile
-constexpr int AC = 8;              // anchors of an anchor tile
-constexpr int CCH = 8;             // class logits per staged chunk (nhwc)
 constexpr int MAXD = 9;
 
 struct AncP {
@@ -32,10 +24,9 @@ struct AncP {
     const int32_t *index;
     float *boxes, *scores;
     int32_t *labels;
-    int HW, W, A, C, nb, nr, P, nhwc;
-    int tiles, chunks;
-    float x0, y0, sx, sy, dir_offset, dir_limit, period;
-    float sizes[48], zc[16], rot[8];
+    // (this order keeps the dense kernels' SGPR spills at 42 / 2, nhwc / nchw; others give up to 52: after any change here rerun
+    // tools/kernel_resources.py dense_head)
+    float dir_limit; int HW, C, tiles, nb, chunks; float dir_offset; int P, A; float period; AnchorTab tab; int nhwc;
 };
 
 struct CenP {
@@ -46,11 +37,6 @@ struct CenP {
     int HW, H, W, C, D, P, nhwc, log_dim, peak;
     float lo_x, lo_y, sx, sy;
 };
-
-// element (b, ch, cell) of a map with CH channels
-__device__ __forceinline__ size_t map_at(int nhwc, int b, int ch, int cell, int CH, int HW) {
-    return nhwc ? ((size_t)b * HW + cell) * CH + ch : ((size_t)b * CH + ch) * HW + cell;
-}
 
 // values straight from memory, either layout
 struct AncDirect {
@@ -67,29 +53,24 @@ struct AncStaged {
     const AncP &p;
     float *sreg, *su;
     const float *scene_cls;
-    int cell0, ncell, a0, na;
+    const AnchorTile t;
+    int pass;
     __device__ __forceinline__ float reg(int j) const { return sreg[threadIdx.x * 7 + j]; }
     __device__ __forceinline__ float dir(int d) const { return su[threadIdx.x * (CCH + 1) + d]; }
     __device__ __forceinline__ float cls(int c) const {
         if ((c & (CCH - 1)) == 0) {
             __syncthreads();
-            stage_rows<DH_THREADS, TC, false>(su, CCH + 1, scene_cls, p.C, c, min(CCH, p.C - c), p.A, cell0, ncell, a0, na);
+            stage_pass<false>(t, pass, su, CCH + 1, scene_cls, p.C, c, min(CCH, p.C - c));
             __syncthreads();
         }
         return su[threadIdx.x * (CCH + 1) + (c & (CCH - 1))];
     }
 };
 
-// §25.1: one row.  tab = sizes[48] | z_center[16] | rotations[8]
+// §25.1: one row
 template <class F>
 __device__ __forceinline__ void anchor_row(const AncP &p, const float *tab, int a, int cell, const F &f, float *box, float &score, int &label) {
-    const int s = a / p.nr, r = a - s * p.nr;
-    const int y = cell / p.W, x = cell - y * p.W;
-    const float xa = p.x0 + ((float)x * p.sx);
-    const float ya = p.y0 + ((float)y * p.sy);
-    const float la = tab[3 * s], wa = tab[3 * s + 1], ha = tab[3 * s + 2];
-    const float za = tab[48 + s], ra = tab[64 + r];
-    const float dg = sqrtf((la * la) + (wa * wa));
+    const Anchor an = anchor_of(p.tab, tab, a, cell);
     // every value of the row is fetched before the first is used (logits eight at a time, unrolled): one round trip to memory
     // per row, not one per map and logit
     float t[7], dv[8], cv[CCH];
@@ -99,25 +80,18 @@ __device__ __forceinline__ void anchor_row(const AncP &p, const float *tab, int 
     for (int d = 0; d < 8; ++d) dv[d] = d < p.nb ? f.dir(d) : -INFINITY;
 #pragma unroll
     for (int u = 0; u < CCH; ++u) cv[u] = u < p.C ? f.cls(u) : -INFINITY;
-    box[0] = (t[0] * dg) + xa;
-    box[1] = (t[1] * dg) + ya;
-    box[2] = (t[2] * ha) + za;
-    box[3] = expf(t[3]) * la;
-    box[4] = expf(t[4]) * wa;
-    box[5] = expf(t[5]) * ha;
-    float yaw = t[6] + ra;
+    residual_decode(an, t, box);
     if (p.nb) {
         int bin = 0;
         float best = dv[0];
 #pragma unroll
         for (int d = 1; d < 8; ++d)
             if (dv[d] > best) { best = dv[d]; bin = d; }      // strict: a tie stays with the lowest bin
-        const float v = yaw - p.dir_offset;
+        const float v = box[6] - p.dir_offset;
         const float q = floorf((v / p.period) + p.dir_limit);
         const float rot = v - (q * p.period);
-        yaw = (rot + p.dir_offset) + (p.period * (float)bin);
+        box[6] = (rot + p.dir_offset) + (p.period * (float)bin);
     }
-    box[6] = yaw;
     float m = -INFINITY;
     label = 0;
     for (int c0 = 0;;) {
@@ -132,48 +106,35 @@ __device__ __forceinline__ void anchor_row(const AncP &p, const float *tab, int 
     score = 1.0f / (1.0f + expf(-m));
 }
 
-__device__ __forceinline__ void load_tab(const AncP &p, float *tab) {
-    if (threadIdx.x < 72) tab[threadIdx.x] = threadIdx.x < 48 ? p.sizes[threadIdx.x] : threadIdx.x < 64 ? p.zc[threadIdx.x - 48] : p.rot[threadIdx.x - 64];
-    __syncthreads();
-}
-
 template <bool NHWC>
-__global__ __launch_bounds__(DH_THREADS) void anchor_dense_kernel(const AncP p) {
-    __shared__ float tab[72];
+__global__ __launch_bounds__(DENSE_THREADS) void anchor_dense_kernel(const AncP p) {
+    __shared__ float tab[T_N];
     __shared__ float obox[TC * AC * 7];
     __shared__ float oscore[TC * AC];
     __shared__ int32_t olabel[TC * AC];
-    __shared__ float sreg[NHWC ? DH_THREADS * 7 : 1];
-    __shared__ float su[NHWC ? DH_THREADS * (CCH + 1) : 1];
-    load_tab(p, tab);
-    const int b = blockIdx.y;
-    const int tile = blockIdx.x / p.chunks, chunk = blockIdx.x - tile * p.chunks;
-    const int cell0 = tile * TC, ncell = min(TC, p.HW - cell0);
-    const int a0 = chunk * AC, acn = min(AC, p.A - a0);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int pass = 0; 4 * pass < acn; ++pass) {
-        const int al = 4 * pass + wave;
-        const bool active = lane < ncell && al < acn;
+    __shared__ float sreg[NHWC ? DENSE_THREADS * 7 : 1];
+    __shared__ float su[NHWC ? DENSE_THREADS * (CCH + 1) : 1];
+    load_tab(p.tab, tab);
+    __syncthreads();
+    const AnchorTile t = anchor_tile(p.chunks, p.HW, p.A);
+    for (int pass = 0; 4 * pass < t.acn; ++pass) {
+        const bool active = t.active(pass);
         float box[7], score = 0.0f;
         int label = 0;
         if (NHWC) {
-            const int na = min(4, acn - 4 * pass);
-            const AncStaged f{p, sreg, su, p.cls + (size_t)b * p.HW * p.A * p.C, cell0, ncell, a0 + 4 * pass, na};
+            const AncStaged f{p, sreg, su, p.cls + (size_t)t.b * p.HW * p.A * p.C, t, pass};
             __syncthreads();
-            stage_rows<DH_THREADS, TC, false>(sreg, 7, p.reg + (size_t)b * p.HW * p.A * 7, 7, 0, 7, p.A, cell0, ncell, a0 + 4 * pass,
-                                              na);
-            if (p.nb)
-                stage_rows<DH_THREADS, TC, false>(su, CCH + 1, p.dir + (size_t)b * p.HW * p.A * p.nb, p.nb, 0, p.nb, p.A, cell0, ncell,
-                                                  a0 + 4 * pass, na);
+            stage_pass<false>(t, pass, sreg, 7, p.reg + (size_t)t.b * p.HW * p.A * 7, 7, 0, 7);
+            if (p.nb) stage_pass<false>(t, pass, su, CCH + 1, p.dir + (size_t)t.b * p.HW * p.A * p.nb, p.nb, 0, p.nb);
             __syncthreads();
             // (rows that are not active read stale LDS; their results are dropped below)
-            anchor_row(p, tab, active ? a0 + al : a0, active ? cell0 + lane : cell0, f, box, score, label);
+            anchor_row(p, tab, active ? t.a0 + t.al(pass) : t.a0, active ? t.cell0 + t.lane : t.cell0, f, box, score, label);
         } else if (active) {
-            const AncDirect f{p, b, a0 + al, cell0 + lane};
-            anchor_row(p, tab, a0 + al, cell0 + lane, f, box, score, label);
+            const AncDirect f{p, t.b, t.a0 + t.al(pass), t.cell0 + t.lane};
+            anchor_row(p, tab, t.a0 + t.al(pass), t.cell0 + t.lane, f, box, score, label);
         }
         if (active) {
-            const int slot = lane * acn + al;
+            const int slot = t.slot(pass);
 #pragma unroll
             for (int j = 0; j < 7; ++j) obox[slot * 7 + j] = box[j];
             oscore[slot] = score;
@@ -181,29 +142,29 @@ __global__ __launch_bounds__(DH_THREADS) void anchor_dense_kernel(const AncP p) 
         }
     }
     __syncthreads();
-    const size_t k0 = ((size_t)b * p.HW + cell0) * p.A + a0;
-    flush_spans<DH_THREADS>(obox, p.boxes + k0 * 7, ncell, acn * 7, (size_t)p.A * 7);
-    flush_spans<DH_THREADS>(oscore, p.scores + k0, ncell, acn, (size_t)p.A);
-    flush_spans<DH_THREADS>(olabel, p.labels + k0, ncell, acn, (size_t)p.A);
+    t.store(obox, p.boxes, 7);
+    t.store(oscore, p.scores, 1);
+    t.store(olabel, p.labels, 1);
 }
 
 // the rows of 256 consecutive output positions, decoded by their threads into rows[], go out in memory order
 __device__ __forceinline__ void flush_block(const float *obox, const float *oscore, const int32_t *olabel, float *boxes, float *scores,
                                             int32_t *labels, size_t row0, int n, int D) {
     __syncthreads();
-    flush_spans<DH_THREADS>(obox, boxes + row0 * D, 1, n * D, 0);
-    flush_spans<DH_THREADS>(oscore, scores + row0, 1, n, 0);
-    flush_spans<DH_THREADS>(olabel, labels + row0, 1, n, 0);
+    flush_spans(obox, boxes + row0 * D, 1, n * D, 0);
+    flush_spans(oscore, scores + row0, 1, n, 0);
+    flush_spans(olabel, labels + row0, 1, n, 0);
 }
 
-__global__ __launch_bounds__(DH_THREADS) void anchor_index_kernel(const AncP p) {
-    __shared__ float tab[72];
-    __shared__ float obox[DH_THREADS * 7];
-    __shared__ float oscore[DH_THREADS];
-    __shared__ int32_t olabel[DH_THREADS];
-    load_tab(p, tab);
+__global__ __launch_bounds__(DENSE_THREADS) void anchor_index_kernel(const AncP p) {
+    __shared__ float tab[T_N];
+    __shared__ float obox[DENSE_THREADS * 7];
+    __shared__ float oscore[DENSE_THREADS];
+    __shared__ int32_t olabel[DENSE_THREADS];
+    load_tab(p.tab, tab);
+    __syncthreads();
     const int b = blockIdx.y;
-    const int p0 = blockIdx.x * DH_THREADS, n = min(DH_THREADS, p.P - p0);
+    const int p0 = blockIdx.x * DENSE_THREADS, n = min(DENSE_THREADS, p.P - p0);
     const int t = threadIdx.x;
     if (t < n) {
         const int k = p.index[(size_t)b * p.P + p0 + t];
@@ -268,13 +229,13 @@ __device__ __forceinline__ void center_row(const CenP &p, int b, int cell, float
     score = label < 0 ? 0.0f : 1.0f / (1.0f + expf(-m));
 }
 
-__global__ __launch_bounds__(DH_THREADS) void center_kernel(const CenP p) {
-    __shared__ float obox[DH_THREADS * MAXD];
-    __shared__ float oscore[DH_THREADS];
-    __shared__ int32_t olabel[DH_THREADS];
+__global__ __launch_bounds__(DENSE_THREADS) void center_kernel(const CenP p) {
+    __shared__ float obox[DENSE_THREADS * MAXD];
+    __shared__ float oscore[DENSE_THREADS];
+    __shared__ int32_t olabel[DENSE_THREADS];
     const int b = blockIdx.y;
     const int n_rows = p.index ? p.P : p.HW;
-    const int p0 = blockIdx.x * DH_THREADS, n = min(DH_THREADS, n_rows - p0);
+    const int p0 = blockIdx.x * DENSE_THREADS, n = min(DENSE_THREADS, n_rows - p0);
     const int t = threadIdx.x;
     if (t < n) {
         const int k = p.index ? p.index[(size_t)b * p.P + p0 + t] : p0 + t;
@@ -291,15 +252,13 @@ __global__ __launch_bounds__(DH_THREADS) void center_kernel(const CenP p) {
 }
 
 // the shape rules both operators share: B, H, W, C, layout, index / P; K = H * W * A
-int shape_ok(const char *fn, int B, int H, int W, int C, long long A, int layout, const int32_t *index, int P) {
+int shape_ok(const char *fn, int B, int H, int W, int C, int A, int layout, const int32_t *index, int P) {
     SAD_REQUIRE(layout == SAD_LAYOUT_NCHW || layout == SAD_LAYOUT_NHWC, "%s: layout must be SAD_LAYOUT_NCHW or SAD_LAYOUT_NHWC (got %d)", fn, layout);
     SAD_REQUIRE(B >= 1 && H >= 1 && W >= 1 && C >= 1, "%s: need B, H, W, C >= 1 (got %d, %d, %d, %d)", fn, B, H, W, C);
     SAD_REQUIRE(index == nullptr || P >= 1, "%s: index needs P >= 1 (got %d)", fn, P);
     if (B > 65535) return sad::fail(SAD_EUNSUPPORTED, "%s: B = %d (1 .. 65535 supported)", fn, B);
     if (C > 64) return sad::fail(SAD_EUNSUPPORTED, "%s: C = %d classes (1 .. 64 supported)", fn, C);
-    const long long K = (long long)H * W * A;
-    if ((long long)H * W >= (1LL << 31) || K >= (1LL << 31) || (long long)B * K >= (1LL << 31))
-        return sad::fail(SAD_EUNSUPPORTED, "%s: B * K = %d * %lld rows (B * K < 2^31 supported)", fn, B, K);
+    if (!rows_fit(B, H, W, A)) return sad::fail(SAD_EUNSUPPORTED, "%s: B * K = %d * %lld rows (B * K < 2^31 supported)", fn, B, (long long)H * W * A);
     if (index && (long long)B * P >= (1LL << 31)) return sad::fail(SAD_EUNSUPPORTED, "%s: B * P = %d * %d rows (B * P < 2^31 supported)", fn, B, P);
     return SAD_OK;
 }
@@ -308,46 +267,34 @@ int shape_ok(const char *fn, int B, int H, int W, int C, long long A, int layout
 
 SAD_API int sad_anchor_decode_f32(const sad_anchor_decode_args *a, sad_stream_t stream) {
     const char *fn = "sad_anchor_decode_f32";
-    SAD_REQUIRE(a, "%s: NULL args", fn);
-    SAD_REQUIRE(a->struct_size == sizeof(sad_anchor_decode_args), "%s: struct_size %zu, this library has %zu", fn, a->struct_size,
-                sizeof(sad_anchor_decode_args));
+    if (int rc = args_ok(fn, a)) return rc;
     SAD_REQUIRE(a->cls && a->reg && a->boxes && a->scores && a->labels, "%s: NULL pointer", fn);
     SAD_REQUIRE(a->ns >= 1 && a->nr >= 1, "%s: need ns, nr >= 1 (got %d, %d)", fn, a->ns, a->nr);
     SAD_REQUIRE(a->nb == 0 || a->nb >= 2, "%s: nb must be 0 (no direction map) or 2 .. 8 (got %d)", fn, a->nb);
     SAD_REQUIRE((a->nb == 0) == (a->dir == nullptr), "%s: dir and nb must be given together (nb = %d)", fn, a->nb);
-    if (a->ns > 16 || a->nr > 8 || a->nb > 8)
-        return sad::fail(SAD_EUNSUPPORTED, "%s: ns = %d, nr = %d, nb = %d (ns <= 16, nr <= 8, nb <= 8 supported)", fn, a->ns, a->nr, a->nb);
+    AncP p = {};
+    if (int rc = fill_anchor_tab(fn, a, &p.tab)) return rc;
     const int A = a->ns * a->nr;
     if (int rc = shape_ok(fn, a->B, a->H, a->W, a->C, A, a->layout, a->index, a->P)) return rc;
-    AncP p = {};
     p.cls = a->cls; p.reg = a->reg; p.dir = a->dir; p.index = a->index;
     p.boxes = a->boxes; p.scores = a->scores; p.labels = a->labels;
-    p.HW = a->H * a->W; p.W = a->W; p.A = A; p.C = a->C; p.nb = a->nb; p.nr = a->nr; p.P = a->P;
+    p.HW = a->H * a->W; p.A = A; p.C = a->C; p.nb = a->nb; p.P = a->P;
     p.nhwc = a->layout == SAD_LAYOUT_NHWC;
-    p.x0 = a->x0; p.y0 = a->y0; p.sx = a->sx; p.sy = a->sy;
-    p.dir_offset = a->dir_offset; p.dir_limit = a->dir_limit_offset;
-    p.period = a->nb ? (float)(6.283185307179586476925286766559 / (double)a->nb) : 0.0f;      // in double, rounded once
-    for (int i = 0; i < 3 * a->ns; ++i) p.sizes[i] = a->sizes[i];
-    for (int i = 0; i < a->ns; ++i) p.zc[i] = a->z_center[i];
-    for (int i = 0; i < a->nr; ++i) p.rot[i] = a->rotations[i];
+    p.dir_offset = a->dir_offset; p.dir_limit = a->dir_limit_offset; p.period = dir_period(a->nb);
     const hipStream_t st = (hipStream_t)stream;
     if (a->index) {
-        hipLaunchKernelGGL(anchor_index_kernel, dim3((unsigned)((a->P + DH_THREADS - 1) / DH_THREADS), a->B), dim3(DH_THREADS), 0, st, p);
+        hipLaunchKernelGGL(anchor_index_kernel, dim3((unsigned)((a->P + DENSE_THREADS - 1) / DENSE_THREADS), a->B), dim3(DENSE_THREADS), 0, st, p);
         return sad::check_launch(fn);
     }
-    p.tiles = (p.HW + TC - 1) / TC;
-    p.chunks = (A + AC - 1) / AC;
-    const dim3 grid((unsigned)p.tiles * (unsigned)p.chunks, a->B);       // (tiles * chunks <= K / 8 + ...: far below 2^31)
-    if (p.nhwc) hipLaunchKernelGGL(anchor_dense_kernel<true>, grid, dim3(DH_THREADS), 0, st, p);
-    else hipLaunchKernelGGL(anchor_dense_kernel<false>, grid, dim3(DH_THREADS), 0, st, p);
+    const dim3 grid((unsigned)anchor_grid_of(p.HW, A, &p.tiles, &p.chunks), a->B);
+    if (p.nhwc) hipLaunchKernelGGL(anchor_dense_kernel<true>, grid, dim3(DENSE_THREADS), 0, st, p);
+    else hipLaunchKernelGGL(anchor_dense_kernel<false>, grid, dim3(DENSE_THREADS), 0, st, p);
     return sad::check_launch(fn);
 }
 
 SAD_API int sad_center_decode_f32(const sad_center_decode_args *a, sad_stream_t stream) {
     const char *fn = "sad_center_decode_f32";
-    SAD_REQUIRE(a, "%s: NULL args", fn);
-    SAD_REQUIRE(a->struct_size == sizeof(sad_center_decode_args), "%s: struct_size %zu, this library has %zu", fn, a->struct_size,
-                sizeof(sad_center_decode_args));
+    if (int rc = args_ok(fn, a)) return rc;
     SAD_REQUIRE(a->hm && a->reg && a->height && a->dim && a->rot && a->boxes && a->scores && a->labels, "%s: NULL pointer", fn);
     if (int rc = shape_ok(fn, a->B, a->H, a->W, a->C, 1, a->layout, a->index, a->P)) return rc;
     CenP p = {};
@@ -358,6 +305,6 @@ SAD_API int sad_center_decode_f32(const sad_center_decode_args *a, sad_stream_t 
     p.log_dim = a->log_dim != 0; p.peak = a->peak != 0;
     p.lo_x = a->lo_x; p.lo_y = a->lo_y; p.sx = a->sx; p.sy = a->sy;
     const int rows = a->index ? a->P : p.HW;
-    hipLaunchKernelGGL(center_kernel, dim3((unsigned)((rows + DH_THREADS - 1) / DH_THREADS), a->B), dim3(DH_THREADS), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(center_kernel, dim3((unsigned)((rows + DENSE_THREADS - 1) / DENSE_THREADS), a->B), dim3(DENSE_THREADS), 0, (hipStream_t)stream, p);
     return sad::check_launch(fn);
 }

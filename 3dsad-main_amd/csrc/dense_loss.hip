@@ -1,18 +1,16 @@
 // Dense head losses (SPEC.md §27): the maps of an anchor head / a centre head and the targets of §26 -> the per-scene losses
 // and the gradient with respect to every map, written in the map's own layout.  The training companion of dense_head.hip and
-// dense_target.hip: same K, same k numbering, same channel numbering, same tiles.  No float atomics anywhere: every sum is a
+// dense_target.hip: same K, same k numbering, same channel numbering, same tiles (dense_tile.h).  No float atomics anywhere: every sum is a
 // per-thread sum in ascending order, a butterfly over the wave, four wave sums added in order and, in a last small launch, the
 // workgroups' partial sums added by one wave per scene (lane l takes workgroups l, l + 64, ... ascending, then the butterfly).
 //
 // anchor head     memset(num_pos) | count | main | finish.
 //   count         num_pos[b] = #(labels >= 0): integer atomics, order-independent.
-//   main          a workgroup owns a tile of 64 cells x up to 8 anchors (lane = cell, wave + 4 * pass = anchor, as
-//                 anchor_dense_kernel).  labels / reg_target / dir_target rows of the tile are contiguous spans and come in
-//                 through LDS in memory order (load_spans, the inverse of flush_spans); per_anchor leaves the same way.
+//   main          a workgroup owns an anchor tile (dense_tile.h).  labels / reg_target / dir_target rows of the tile are contiguous
+//                 spans and come in through LDS in memory order (load_spans); per_anchor leaves the same way (flush_spans).
 //     nchw        channel planes are unit-stride in the cell: loads and gradient stores of a wave are 256 contiguous bytes.
-//     nhwc        a pass (64 cells x 4 anchors) is staged through LDS in memory order (stage_rows), the thread that owns a row
-//                 overwrites its values with their gradients, and the image goes back in memory order (stage_rows, OUT): class
-//                 logits in chunks of 8 classes.
+//     nhwc        a pass (64 cells x 4 anchors) is staged through LDS in memory order (stage_pass), the thread that owns a row overwrites
+//                 its values with their gradients, and the image goes back the same way (OUT): class logits in chunks of 8 classes.
 // centre head     memset(num_pos) | count | heat map | boxes | finish.
 //   heat map      a workgroup owns 256 consecutive cells, one per thread, classes ascending; nhwc staged 16 classes at a time.
 //                 It also zero-fills the regression gradients of its cells: the box pass, a later launch, overwrites a few.
@@ -23,14 +21,9 @@
 
 namespace {
 
-#include "prims.h"       // load_spans, flush_spans, stage_rows
+#include "dense_tile.h"
 
-constexpr int DL_THREADS = 256;
-constexpr int TC = 64;             // cells of an anchor tile
-constexpr int AC = 8;              // anchors of an anchor tile
-constexpr int CCH = 8;             // class logits per staged chunk (anchor head, nhwc)
 constexpr int HCH = 16;            // classes per staged chunk (centre head, nhwc)
-constexpr int MAXG = 1024;
 constexpr int CNT = 16;            // elements per thread of the count kernels
 constexpr float CLAMP_LO = 1e-4f;
 
@@ -89,13 +82,13 @@ __device__ __forceinline__ void sigmoid2(float x, float e, float &p, float &pc) 
     pc = x >= 0.0f ? small : big;
 }
 
-__global__ __launch_bounds__(DL_THREADS) void anchor_count_kernel(const int32_t *labels, int K, int32_t *num_pos) {
+__global__ __launch_bounds__(DENSE_THREADS) void anchor_count_kernel(const int32_t *labels, int K, int32_t *num_pos) {
     const int b = blockIdx.y;
     const int32_t *row = labels + (size_t)b * K;
     int v[CNT];
 #pragma unroll
     for (int q = 0; q < CNT; ++q) {                                   // (independent loads, issued together)
-        const long long i = ((long long)blockIdx.x * CNT + q) * DL_THREADS + threadIdx.x;
+        const long long i = ((long long)blockIdx.x * CNT + q) * DENSE_THREADS + threadIdx.x;
         v[q] = i < K ? row[i] : -1;
     }
     int cnt = 0;
@@ -172,29 +165,27 @@ __device__ __forceinline__ float cls_one(const AncL &p, float x, bool t, bool li
     return live ? l * wq : 0.0f;
 }
 
+__device__ __forceinline__ size_t plane_at(int ch, int cell, int HW) { return map_at(0, 0, ch, cell, 0, HW); }      // nchw, from the scene's base
+
 template <bool NHWC>
-__global__ __launch_bounds__(DL_THREADS) void anchor_loss_kernel(const AncL p) {
+__global__ __launch_bounds__(DENSE_THREADS) void anchor_loss_kernel(const AncL p) {
     __shared__ int32_t slab[TC * AC];
     __shared__ int32_t sdirt[TC * AC];
     __shared__ float stgt[TC * AC * 7];
     __shared__ float oper[TC * AC * 3];
-    __shared__ float sreg[NHWC ? DL_THREADS * 7 : 1];
-    __shared__ float su[NHWC ? DL_THREADS * (CCH + 1) : 1];
+    __shared__ float sreg[NHWC ? DENSE_THREADS * 7 : 1];
+    __shared__ float su[NHWC ? DENSE_THREADS * (CCH + 1) : 1];
     __shared__ float red[4];
-    const int b = blockIdx.y;
-    const int tile = blockIdx.x / p.chunks, chunk = blockIdx.x - tile * p.chunks;
-    const int cell0 = tile * TC, ncell = min(TC, p.HW - cell0);
-    const int a0 = chunk * AC, acn = min(AC, p.A - a0);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, tid = threadIdx.x;
+    const AnchorTile tl = anchor_tile(p.chunks, p.HW, p.A);
+    const int b = tl.b, tid = threadIdx.x;
     const size_t HW = (size_t)p.HW;
-    const size_t k0 = ((size_t)b * HW + cell0) * p.A + a0;
-    load_spans<DL_THREADS>(slab, p.labels + k0, ncell, acn, (size_t)p.A);
-    load_spans<DL_THREADS>(stgt, p.tgt + k0 * 7, ncell, acn * 7, (size_t)p.A * 7);
-    if (p.nb) load_spans<DL_THREADS>(sdirt, p.dirt + k0, ncell, acn, (size_t)p.A);
+    tl.load(slab, p.labels, 1);
+    tl.load(stgt, p.tgt, 7);
+    if (p.nb) tl.load(sdirt, p.dirt, 1);
     const int n = p.num_pos[b];
     const float wq0 = norm_weight(p.scale[0], n, p.normalize), wq1 = norm_weight(p.scale[1], n, p.normalize),
                 wq2 = norm_weight(p.scale[2], n, p.normalize);
-    // scene bases of the maps (nhwc: rows of the staged passes; nchw: channel planes)
+    // scene bases of the maps (nhwc: rows of the staged passes; nchw: channel planes, addressed by plane_at)
     const float *scls = p.cls + (size_t)b * HW * p.A * p.C;
     float *gcls = p.gcls + (size_t)b * HW * p.A * p.C;
     const float *sregm = p.reg + (size_t)b * HW * p.A * 7;
@@ -203,12 +194,10 @@ __global__ __launch_bounds__(DL_THREADS) void anchor_loss_kernel(const AncL p) {
     float *gdirm = p.nb ? p.gdir + (size_t)b * HW * p.A * p.nb : nullptr;
     __syncthreads();
     float acc0 = 0.0f, acc1 = 0.0f, acc2 = 0.0f;
-    for (int pass = 0; 4 * pass < acn; ++pass) {
-        const int al = 4 * pass + wave;
-        const bool active = lane < ncell && al < acn;
-        const int slot = active ? lane * acn + al : 0;
-        const int a = a0 + (active ? al : 0), cell = cell0 + (active ? lane : 0);
-        const int pa0 = a0 + 4 * pass, na = min(4, acn - 4 * pass);
+    for (int pass = 0; 4 * pass < tl.acn; ++pass) {
+        const bool active = tl.active(pass);
+        const int slot = active ? tl.slot(pass) : 0;
+        const int a = tl.a0 + (active ? tl.al(pass) : 0), cell = tl.cell0 + (active ? tl.lane : 0);
         const int label = active ? slab[slot] : -2;
         const bool pos = label >= 0;
         // ---- regression
@@ -217,8 +206,8 @@ __global__ __launch_bounds__(DL_THREADS) void anchor_loss_kernel(const AncL p) {
         for (int j = 0; j < 7; ++j) t[j] = stgt[slot * 7 + j];
         if (NHWC) {
             __syncthreads();
-            stage_rows<DL_THREADS, TC, false>(sreg, 7, sregm, 7, 0, 7, p.A, cell0, ncell, pa0, na);
-            if (p.nb) stage_rows<DL_THREADS, TC, false>(su, CCH + 1, sdir, p.nb, 0, p.nb, p.A, cell0, ncell, pa0, na);
+            stage_pass<false>(tl, pass, sreg, 7, sregm, 7, 0, 7);
+            if (p.nb) stage_pass<false>(tl, pass, su, CCH + 1, sdir, p.nb, 0, p.nb);
             __syncthreads();
 #pragma unroll
             for (int j = 0; j < 7; ++j) r[j] = sreg[tid * 7 + j];
@@ -228,11 +217,11 @@ __global__ __launch_bounds__(DL_THREADS) void anchor_loss_kernel(const AncL p) {
         float z[8], x[CCH];
         if (!NHWC) {
 #pragma unroll
-            for (int j = 0; j < 7; ++j) r[j] = sregm[((size_t)a * 7 + j) * HW + cell];
+            for (int j = 0; j < 7; ++j) r[j] = sregm[plane_at(a * 7 + j, cell, p.HW)];
 #pragma unroll
-            for (int d = 0; d < 8; ++d) z[d] = d < p.nb ? sdir[((size_t)a * p.nb + d) * HW + cell] : 0.0f;
+            for (int d = 0; d < 8; ++d) z[d] = d < p.nb ? sdir[plane_at(a * p.nb + d, cell, p.HW)] : 0.0f;
 #pragma unroll
-            for (int u = 0; u < CCH; ++u) x[u] = u < p.C ? scls[((size_t)a * p.C + u) * HW + cell] : 0.0f;
+            for (int u = 0; u < CCH; ++u) x[u] = u < p.C ? scls[plane_at(a * p.C + u, cell, p.HW)] : 0.0f;
         }
         // (positives are a few rows in a thousand: most waves skip the regression and the direction altogether)
         float l1 = 0.0f;
@@ -244,7 +233,7 @@ __global__ __launch_bounds__(DL_THREADS) void anchor_loss_kernel(const AncL p) {
             for (int j = 0; j < 7; ++j) sreg[tid * 7 + j] = g[j];
         } else if (active) {
 #pragma unroll
-            for (int j = 0; j < 7; ++j) gregm[((size_t)a * 7 + j) * HW + cell] = g[j];
+            for (int j = 0; j < 7; ++j) gregm[plane_at(a * 7 + j, cell, p.HW)] = g[j];
         }
         // ---- direction
         float l2 = 0.0f;
@@ -264,13 +253,13 @@ __global__ __launch_bounds__(DL_THREADS) void anchor_loss_kernel(const AncL p) {
             for (int d = 0; d < 8; ++d) {
                 if (d >= p.nb) continue;
                 if (NHWC) su[tid * (CCH + 1) + d] = z[d];
-                else if (active) gdirm[((size_t)a * p.nb + d) * HW + cell] = z[d];
+                else if (active) gdirm[plane_at(a * p.nb + d, cell, p.HW)] = z[d];
             }
         }
         if (NHWC) {
             __syncthreads();
-            stage_rows<DL_THREADS, TC, true>(sreg, 7, gregm, 7, 0, 7, p.A, cell0, ncell, pa0, na);
-            if (p.nb) stage_rows<DL_THREADS, TC, true>(su, CCH + 1, gdirm, p.nb, 0, p.nb, p.A, cell0, ncell, pa0, na);
+            stage_pass<true>(tl, pass, sreg, 7, gregm, 7, 0, 7);
+            if (p.nb) stage_pass<true>(tl, pass, su, CCH + 1, gdirm, p.nb, 0, p.nb);
         }
         // ---- classification, classes ascending
         const bool live = label != -2;
@@ -279,13 +268,13 @@ __global__ __launch_bounds__(DL_THREADS) void anchor_loss_kernel(const AncL p) {
             const int len = min(CCH, p.C - c0);
             if (NHWC) {
                 __syncthreads();
-                stage_rows<DL_THREADS, TC, false>(su, CCH + 1, scls, p.C, c0, len, p.A, cell0, ncell, pa0, na);
+                stage_pass<false>(tl, pass, su, CCH + 1, scls, p.C, c0, len);
                 __syncthreads();
             }
             if (NHWC || c0) {
 #pragma unroll
                 for (int u = 0; u < CCH; ++u)
-                    x[u] = u < len ? (NHWC ? su[tid * (CCH + 1) + u] : scls[((size_t)a * p.C + c0 + u) * HW + cell]) : 0.0f;
+                    x[u] = u < len ? (NHWC ? su[tid * (CCH + 1) + u] : scls[plane_at(a * p.C + c0 + u, cell, p.HW)]) : 0.0f;
             }
 #pragma unroll
             for (int u = 0; u < CCH; ++u) {
@@ -293,11 +282,11 @@ __global__ __launch_bounds__(DL_THREADS) void anchor_loss_kernel(const AncL p) {
                 float gx;
                 l0 = l0 + cls_one(p, x[u], label == c0 + u, live, wq0, gx);
                 if (NHWC) su[tid * (CCH + 1) + u] = gx;
-                else if (active) gcls[((size_t)a * p.C + c0 + u) * HW + cell] = gx;
+                else if (active) gcls[plane_at(a * p.C + c0 + u, cell, p.HW)] = gx;
             }
             if (NHWC) {
                 __syncthreads();
-                stage_rows<DL_THREADS, TC, true>(su, CCH + 1, gcls, p.C, c0, len, p.A, cell0, ncell, pa0, na);
+                stage_pass<true>(tl, pass, su, CCH + 1, gcls, p.C, c0, len);
             }
         }
         if (active) {
@@ -306,7 +295,7 @@ __global__ __launch_bounds__(DL_THREADS) void anchor_loss_kernel(const AncL p) {
         }
     }
     __syncthreads();
-    if (p.per) flush_spans<DL_THREADS>(oper, p.per + k0 * 3, ncell, acn * 3, (size_t)p.A * 3);
+    if (p.per) tl.store(oper, p.per, 3);
     const float s0 = block_sum(acc0, red), s1 = block_sum(acc1, red), s2 = block_sum(acc2, red);
     if (tid == 0) {
         float *o = p.part + ((size_t)b * gridDim.x + blockIdx.x) * 3;
@@ -327,14 +316,14 @@ __global__ __launch_bounds__(64) void finish_kernel(const FinP p) {
     }
 }
 
-__global__ __launch_bounds__(DL_THREADS) void center_count_kernel(const CenL p) {
+__global__ __launch_bounds__(DENSE_THREADS) void center_count_kernel(const CenL p) {
     const int b = blockIdx.y;
     const size_t n = (size_t)p.C * p.HW;
     const float *t = p.heatmap + (size_t)b * n;
     float v[CNT];
 #pragma unroll
     for (int q = 0; q < CNT; ++q) {
-        const size_t i = ((size_t)blockIdx.x * CNT + q) * DL_THREADS + threadIdx.x;
+        const size_t i = ((size_t)blockIdx.x * CNT + q) * DENSE_THREADS + threadIdx.x;
         v[q] = i < n ? t[i] : 0.0f;
     }
     int cnt = 0;
@@ -344,7 +333,7 @@ __global__ __launch_bounds__(DL_THREADS) void center_count_kernel(const CenL p) 
     if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&p.num_pos[2 * b], cnt);
     if (blockIdx.x == 0) {
         int nb = 0;
-        for (int g = threadIdx.x; g < p.G; g += DL_THREADS) {
+        for (int g = threadIdx.x; g < p.G; g += DENSE_THREADS) {
             const int c = p.ind[(size_t)b * p.G + g];
             if (c >= 0 && c < p.HW) ++nb;
         }
@@ -381,7 +370,7 @@ __device__ __forceinline__ float hm_one(float x, float t, float wq, float &g) {
 template <bool OUT, class P>
 __device__ __forceinline__ void stage_cells(float *lds, P *scene, int C, int c0, int len, int cell0, int ncell) {
     const int n = ncell * len;
-    for (int i = threadIdx.x; i < n; i += DL_THREADS) {
+    for (int i = threadIdx.x; i < n; i += DENSE_THREADS) {
         const int cell = i / len, e = i - cell * len;
         P *g = scene + (size_t)(cell0 + cell) * C + c0 + e;
         if constexpr (OUT) *g = lds[cell * (HCH + 1) + e];
@@ -390,12 +379,12 @@ __device__ __forceinline__ void stage_cells(float *lds, P *scene, int C, int c0,
 }
 
 template <bool NHWC>
-__global__ __launch_bounds__(DL_THREADS) void center_hm_kernel(const CenL p) {
-    __shared__ float sx[NHWC ? DL_THREADS * (HCH + 1) : 1];
-    __shared__ float st[NHWC ? DL_THREADS * (HCH + 1) : 1];
+__global__ __launch_bounds__(DENSE_THREADS) void center_hm_kernel(const CenL p) {
+    __shared__ float sx[NHWC ? DENSE_THREADS * (HCH + 1) : 1];
+    __shared__ float st[NHWC ? DENSE_THREADS * (HCH + 1) : 1];
     __shared__ float red[4];
     const int b = blockIdx.y, tid = threadIdx.x;
-    const int cell0 = blockIdx.x * DL_THREADS, ncell = min(DL_THREADS, p.HW - cell0);
+    const int cell0 = blockIdx.x * DENSE_THREADS, ncell = min(DENSE_THREADS, p.HW - cell0);
     const bool active = tid < ncell;
     const size_t HW = (size_t)p.HW, base = (size_t)b * p.C * HW;
     const float wq = norm_weight(p.scale[0], p.num_pos[2 * b], p.normalize);
@@ -433,7 +422,7 @@ __global__ __launch_bounds__(DL_THREADS) void center_hm_kernel(const CenL p) {
         if (!p.gm[m]) continue;
         float *g = p.gm[m] + (size_t)b * CH[m] * HW;
         if (NHWC) {
-            for (int i = tid; i < ncell * CH[m]; i += DL_THREADS) g[(size_t)cell0 * CH[m] + i] = 0.0f;
+            for (int i = tid; i < ncell * CH[m]; i += DENSE_THREADS) g[(size_t)cell0 * CH[m] + i] = 0.0f;
         } else if (active) {
 #pragma unroll
             for (int ch = 0; ch < CH[m]; ++ch) g[(size_t)ch * HW + cell0 + tid] = 0.0f;
@@ -443,14 +432,14 @@ __global__ __launch_bounds__(DL_THREADS) void center_hm_kernel(const CenL p) {
     if (tid == 0) p.part_hm[(size_t)b * p.nwg_hm + blockIdx.x] = s;
 }
 
-__global__ __launch_bounds__(DL_THREADS) void center_reg_kernel(const CenL p) {
+__global__ __launch_bounds__(DENSE_THREADS) void center_reg_kernel(const CenL p) {
     __shared__ int sind[MAXG];
     __shared__ float red[4];
     const int b = blockIdx.y, tid = threadIdx.x;
-    for (int g = tid; g < p.G; g += DL_THREADS) sind[g] = p.ind[(size_t)b * p.G + g];
+    for (int g = tid; g < p.G; g += DENSE_THREADS) sind[g] = p.ind[(size_t)b * p.G + g];
     __syncthreads();
     const float wq = norm_weight(p.scale[1], p.num_pos[2 * b + 1], p.normalize);
-    const int g = blockIdx.x * DL_THREADS + tid;
+    const int g = blockIdx.x * DENSE_THREADS + tid;
     const int cell = g < p.G ? sind[g] : -1;
     float l = 0.0f;
     if (cell >= 0 && cell < p.HW) {
@@ -461,7 +450,7 @@ __global__ __launch_bounds__(DL_THREADS) void center_reg_kernel(const CenL p) {
 #pragma unroll
         for (int j = 0; j < 10; ++j) {
             if (j >= p.na) continue;
-            at[j] = p.nhwc ? ((size_t)b * p.HW + cell) * CH[JM[j]] + JC[j] : ((size_t)b * CH[JM[j]] + JC[j]) * p.HW + cell;
+            at[j] = map_at(p.nhwc, b, JC[j], cell, CH[JM[j]], p.HW);
             pred[j] = p.pm[JM[j]][at[j]];
             const float d = pred[j] - an[j];
             l = l + (fabsf(d) * p.cw[j]) * wq;
@@ -489,32 +478,28 @@ __global__ __launch_bounds__(DL_THREADS) void center_reg_kernel(const CenL p) {
     if (tid == 0) p.part_reg[(size_t)b * p.nwg_reg + blockIdx.x] = s;
 }
 
-int anchor_tiles(int H, int W, int A) { return (int)(((long long)H * W + TC - 1) / TC) * ((A + AC - 1) / AC); }
-
 }  // namespace
 
 SAD_API size_t sad_anchor_head_loss_workspace_bytes(int B, int H, int W, int A) {
     if (B < 1 || B > 65535 || H < 1 || W < 1 || A < 1 || A > 128) return 0;
-    if ((long long)H * W >= (1LL << 31) || (long long)B * ((long long)H * W) * A >= (1LL << 31)) return 0;   // (H * W < 2^62; then < 2^31 * 2^16 * 2^7)
-    return (size_t)B * (size_t)anchor_tiles(H, W, A) * 3 * sizeof(float);
+    if (!rows_fit(B, H, W, A)) return 0;
+    int tiles, chunks;      // (one slot of three partial sums per workgroup of anchor_loss_kernel)
+    return (size_t)B * (size_t)anchor_grid_of(H * W, A, &tiles, &chunks) * 3 * sizeof(float);
 }
 
 SAD_API size_t sad_center_head_loss_workspace_bytes(int B, int H, int W, int G) {
     if (B < 1 || B > 65535 || H < 1 || W < 1 || G < 0 || G > MAXG) return 0;
-    const long long HW = (long long)H * W;                            // (< 2^62)
-    if (HW >= (1LL << 31) || B * HW >= (1LL << 31)) return 0;
-    return (size_t)B * (size_t)((HW + DL_THREADS - 1) / DL_THREADS + (G + DL_THREADS - 1) / DL_THREADS) * sizeof(float);
+    if (!rows_fit(B, H, W, 1)) return 0;
+    const long long HW = (long long)H * W;
+    return (size_t)B * (size_t)((HW + DENSE_THREADS - 1) / DENSE_THREADS + (G + DENSE_THREADS - 1) / DENSE_THREADS) * sizeof(float);
 }
 
 SAD_API int sad_anchor_head_loss_f32(const sad_anchor_head_loss_args *a, sad_stream_t stream) {
     const char *fn = "sad_anchor_head_loss_f32";
-    SAD_REQUIRE(a, "%s: NULL args", fn);
-    SAD_REQUIRE(a->struct_size == sizeof(sad_anchor_head_loss_args), "%s: struct_size %zu, this library has %zu", fn, a->struct_size,
-                sizeof(sad_anchor_head_loss_args));
+    if (int rc = args_ok(fn, a)) return rc;
     SAD_REQUIRE(a->cls && a->reg && a->labels && a->reg_target && a->loss && a->num_pos && a->grad_cls && a->grad_reg && a->workspace,
                 "%s: NULL pointer", fn);
-    SAD_REQUIRE(a->layout == SAD_LAYOUT_NCHW || a->layout == SAD_LAYOUT_NHWC, "%s: layout must be SAD_LAYOUT_NCHW or SAD_LAYOUT_NHWC (got %d)", fn,
-                a->layout);
+    SAD_REQUIRE(a->layout == SAD_LAYOUT_NCHW || a->layout == SAD_LAYOUT_NHWC, "%s: layout must be SAD_LAYOUT_NCHW or SAD_LAYOUT_NHWC (got %d)", fn, a->layout);
     SAD_REQUIRE(a->B >= 1 && a->H >= 1 && a->W >= 1 && a->A >= 1 && a->C >= 1, "%s: need B, H, W, A, C >= 1 (got %d, %d, %d, %d, %d)", fn, a->B,
                 a->H, a->W, a->A, a->C);
     SAD_REQUIRE(a->nb == 0 || a->nb >= 2, "%s: nb must be 0 (no direction loss) or 2 .. 8 (got %d)", fn, a->nb);
@@ -525,28 +510,27 @@ SAD_API int sad_anchor_head_loss_f32(const sad_anchor_head_loss_args *a, sad_str
     if (a->B > 65535) return sad::fail(SAD_EUNSUPPORTED, "%s: B = %d (1 .. 65535 supported)", fn, a->B);
     if (a->C > 64) return sad::fail(SAD_EUNSUPPORTED, "%s: C = %d classes (1 .. 64 supported)", fn, a->C);
     if (a->A > 128 || a->nb > 8) return sad::fail(SAD_EUNSUPPORTED, "%s: A = %d, nb = %d (A <= 128, nb <= 8 supported)", fn, a->A, a->nb);
-    const long long HW = (long long)a->H * a->W;                      // (< 2^62: checked before it is multiplied further)
-    const long long K = HW < (1LL << 31) ? HW * a->A : (1LL << 31);
-    if (K >= (1LL << 31) || (long long)a->B * K >= (1LL << 31))
-        return sad::fail(SAD_EUNSUPPORTED, "%s: B * K = %d * %d * %d * %d rows (B * K < 2^31 supported)", fn, a->B, a->H, a->W, a->A);
+    if (!rows_fit(a->B, a->H, a->W, a->A)) return sad::fail(SAD_EUNSUPPORTED, "%s: B * K = %d * %d * %d * %d rows (B * K < 2^31 supported)", fn, a->B, a->H, a->W, a->A);
+    const int HW = a->H * a->W;
+    const long long K = (long long)HW * a->A;
     AncL p = {};
     p.cls = a->cls; p.reg = a->reg; p.dir = a->dir; p.tgt = a->reg_target; p.labels = a->labels; p.dirt = a->dir_target;
     p.num_pos = a->num_pos; p.gcls = a->grad_cls; p.greg = a->grad_reg; p.gdir = a->grad_dir; p.per = a->per_anchor;
     p.part = (float *)a->workspace;
-    p.HW = (int)HW; p.A = a->A; p.C = a->C; p.nb = a->nb; p.sin_diff = a->sin_diff != 0; p.normalize = a->normalize != 0;
-    p.chunks = (a->A + AC - 1) / AC;
+    p.HW = HW; p.A = a->A; p.C = a->C; p.nb = a->nb; p.sin_diff = a->sin_diff != 0; p.normalize = a->normalize != 0;
     p.alpha = a->alpha; p.oma = 1.0f - a->alpha; p.beta = a->beta;
     for (int j = 0; j < 7; ++j) p.cw[j] = a->code_weights[j];
     for (int i = 0; i < 3; ++i) p.scale[i] = a->scale[i];
     const hipStream_t st = (hipStream_t)stream;
-    const int nwg = anchor_tiles(a->H, a->W, a->A);
+    int tiles;
+    const int nwg = anchor_grid_of(HW, a->A, &tiles, &p.chunks);
     if (hipMemsetAsync(a->num_pos, 0, (size_t)a->B * sizeof(int32_t), st) != hipSuccess) return sad::check_launch(fn);
-    hipLaunchKernelGGL(anchor_count_kernel, dim3((unsigned)((K + CNT * DL_THREADS - 1) / (CNT * DL_THREADS)), a->B), dim3(DL_THREADS), 0, st, a->labels,
+    hipLaunchKernelGGL(anchor_count_kernel, dim3((unsigned)((K + CNT * DENSE_THREADS - 1) / (CNT * DENSE_THREADS)), a->B), dim3(DENSE_THREADS), 0, st, a->labels,
                        (int)K, a->num_pos);
     if (int rc = sad::check_launch(fn)) return rc;
     const dim3 grid((unsigned)nwg, a->B);
-    if (a->layout == SAD_LAYOUT_NHWC) hipLaunchKernelGGL(anchor_loss_kernel<true>, grid, dim3(DL_THREADS), 0, st, p);
-    else hipLaunchKernelGGL(anchor_loss_kernel<false>, grid, dim3(DL_THREADS), 0, st, p);
+    if (a->layout == SAD_LAYOUT_NHWC) hipLaunchKernelGGL(anchor_loss_kernel<true>, grid, dim3(DENSE_THREADS), 0, st, p);
+    else hipLaunchKernelGGL(anchor_loss_kernel<false>, grid, dim3(DENSE_THREADS), 0, st, p);
     if (int rc = sad::check_launch(fn)) return rc;
     FinP f = {};
     for (int i = 0; i < 3; ++i) { f.src[i] = p.part + i; f.n[i] = nwg; f.stride[i] = 3; }
@@ -557,46 +541,42 @@ SAD_API int sad_anchor_head_loss_f32(const sad_anchor_head_loss_args *a, sad_str
 
 SAD_API int sad_center_head_loss_f32(const sad_center_head_loss_args *a, sad_stream_t stream) {
     const char *fn = "sad_center_head_loss_f32";
-    SAD_REQUIRE(a, "%s: NULL args", fn);
-    SAD_REQUIRE(a->struct_size == sizeof(sad_center_head_loss_args), "%s: struct_size %zu, this library has %zu", fn, a->struct_size,
-                sizeof(sad_center_head_loss_args));
+    if (int rc = args_ok(fn, a)) return rc;
     SAD_REQUIRE(a->hm && a->reg && a->height && a->dim && a->rot && a->heatmap && a->loss && a->num_pos && a->grad_hm && a->grad_reg &&
                     a->grad_height && a->grad_dim && a->grad_rot && a->workspace,
                 "%s: NULL pointer", fn);
     SAD_REQUIRE((a->vel == nullptr) == (a->grad_vel == nullptr), "%s: vel and grad_vel must be given together", fn);
-    SAD_REQUIRE(a->layout == SAD_LAYOUT_NCHW || a->layout == SAD_LAYOUT_NHWC, "%s: layout must be SAD_LAYOUT_NCHW or SAD_LAYOUT_NHWC (got %d)", fn,
-                a->layout);
+    SAD_REQUIRE(a->layout == SAD_LAYOUT_NCHW || a->layout == SAD_LAYOUT_NHWC, "%s: layout must be SAD_LAYOUT_NCHW or SAD_LAYOUT_NHWC (got %d)", fn, a->layout);
     SAD_REQUIRE(a->B >= 1 && a->H >= 1 && a->W >= 1 && a->C >= 1 && a->G >= 0, "%s: need B, H, W, C >= 1 and G >= 0 (got %d, %d, %d, %d, %d)", fn,
                 a->B, a->H, a->W, a->C, a->G);
     SAD_REQUIRE(a->G == 0 || (a->ind && a->anno), "%s: NULL pointer (ind, anno)", fn);
     if (a->B > 65535) return sad::fail(SAD_EUNSUPPORTED, "%s: B = %d (1 .. 65535 supported)", fn, a->B);
     if (a->C > 64) return sad::fail(SAD_EUNSUPPORTED, "%s: C = %d classes (1 .. 64 supported)", fn, a->C);
     if (a->G > MAXG) return sad::fail(SAD_EUNSUPPORTED, "%s: G = %d boxes per scene (0 .. 1024 supported)", fn, a->G);
-    const long long HW = (long long)a->H * a->W;
-    if (HW >= (1LL << 31) || (long long)a->B * HW >= (1LL << 31))     // (H * W < 2^62, then B * HW < 2^47)
-        return sad::fail(SAD_EUNSUPPORTED, "%s: B * H * W = %d * %lld cells (B * H * W < 2^31 supported)", fn, a->B, HW);
+    if (!rows_fit(a->B, a->H, a->W, 1)) return sad::fail(SAD_EUNSUPPORTED, "%s: B * H * W = %d * %lld cells (B * H * W < 2^31 supported)", fn, a->B, (long long)a->H * a->W);
+    const int HW = a->H * a->W;
     CenL p = {};
     p.hm = a->hm; p.heatmap = a->heatmap; p.anno = a->anno; p.ind = a->ind; p.num_pos = a->num_pos; p.ghm = a->grad_hm;
     p.pm[0] = a->reg; p.pm[1] = a->height; p.pm[2] = a->dim; p.pm[3] = a->rot; p.pm[4] = a->vel;
     p.gm[0] = a->grad_reg; p.gm[1] = a->grad_height; p.gm[2] = a->grad_dim; p.gm[3] = a->grad_rot; p.gm[4] = a->grad_vel;
-    p.HW = (int)HW; p.C = a->C; p.G = a->G; p.na = a->vel ? 10 : 8; p.nhwc = a->layout == SAD_LAYOUT_NHWC; p.normalize = a->normalize != 0;
-    p.nwg_hm = (int)((HW + DL_THREADS - 1) / DL_THREADS);
-    p.nwg_reg = (a->G + DL_THREADS - 1) / DL_THREADS;
+    p.HW = HW; p.C = a->C; p.G = a->G; p.na = a->vel ? 10 : 8; p.nhwc = a->layout == SAD_LAYOUT_NHWC; p.normalize = a->normalize != 0;
+    p.nwg_hm = (int)(((long long)HW + DENSE_THREADS - 1) / DENSE_THREADS);
+    p.nwg_reg = (a->G + DENSE_THREADS - 1) / DENSE_THREADS;
     p.part_hm = (float *)a->workspace;
     p.part_reg = p.part_hm + (size_t)a->B * p.nwg_hm;
     for (int j = 0; j < 10; ++j) p.cw[j] = a->code_weights[j];
     p.scale[0] = a->scale[0]; p.scale[1] = a->scale[1];
     const hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(a->num_pos, 0, (size_t)a->B * 2 * sizeof(int32_t), st) != hipSuccess) return sad::check_launch(fn);
-    const long long nel = HW * a->C;
-    hipLaunchKernelGGL(center_count_kernel, dim3((unsigned)((nel + CNT * DL_THREADS - 1) / (CNT * DL_THREADS)), a->B), dim3(DL_THREADS), 0, st, p);
+    const long long nel = (long long)HW * a->C;
+    hipLaunchKernelGGL(center_count_kernel, dim3((unsigned)((nel + CNT * DENSE_THREADS - 1) / (CNT * DENSE_THREADS)), a->B), dim3(DENSE_THREADS), 0, st, p);
     if (int rc = sad::check_launch(fn)) return rc;
     const dim3 grid((unsigned)p.nwg_hm, a->B);
-    if (p.nhwc) hipLaunchKernelGGL(center_hm_kernel<true>, grid, dim3(DL_THREADS), 0, st, p);
-    else hipLaunchKernelGGL(center_hm_kernel<false>, grid, dim3(DL_THREADS), 0, st, p);
+    if (p.nhwc) hipLaunchKernelGGL(center_hm_kernel<true>, grid, dim3(DENSE_THREADS), 0, st, p);
+    else hipLaunchKernelGGL(center_hm_kernel<false>, grid, dim3(DENSE_THREADS), 0, st, p);
     if (int rc = sad::check_launch(fn)) return rc;
     if (a->G > 0) {
-        hipLaunchKernelGGL(center_reg_kernel, dim3((unsigned)p.nwg_reg, a->B), dim3(DL_THREADS), 0, st, p);
+        hipLaunchKernelGGL(center_reg_kernel, dim3((unsigned)p.nwg_reg, a->B), dim3(DENSE_THREADS), 0, st, p);
         if (int rc = sad::check_launch(fn)) return rc;
     }
     FinP f = {};

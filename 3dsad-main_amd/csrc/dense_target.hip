@@ -1,9 +1,8 @@
 // Dense head target assignment (SPEC.md §26): ground-truth boxes -> what an anchor head / a centre head is trained
-// against.  The inverse of dense_head.hip: same anchor scalars, same K, same k numbering, same tiles.
+// against.  The inverse of dense_head.hip: same anchor scalars, same K, same k numbering, same tiles (dense_tile.h).
 //
-// anchor targets  two passes over the anchors, neither of which materialises an anchor or a [K,G] IoU matrix.  A workgroup
-//                 owns a tile of 64 cells x up to 8 anchors (lane = cell, wave + 4 * pass = anchor, as anchor_dense_kernel)
-//                 and holds the scene's G <= 1024 nearest-BEV rectangles and labels in LDS (5 words per box).
+// anchor targets  two passes over the anchors, neither of which materialises an anchor or a [K,G] IoU matrix.  A workgroup owns
+//                 an anchor tile (dense_tile.h) and holds the scene's G <= 1024 nearest-BEV rectangles and labels in LDS (5 words per box).
 //   pass 1        best[b,g] = max over the anchors g is eligible for of iou(k,g).  A thread walks the boxes for its anchors
 //                 (the LDS reads are broadcasts); where a box meets a cell of the wave, the wave reduces its 64 IoUs and
 //                 one lane folds the result into the workgroup's value by an LDS atomicMax on the float's bit pattern
@@ -25,19 +24,15 @@
 
 namespace {
 
-#include "prims.h"       // flush_spans
+#include "dense_tile.h"
 
-constexpr int DT_THREADS = 256;
-constexpr int TC = 64;             // cells of an anchor tile
-constexpr int AC = 8;              // anchors of an anchor tile
-constexpr int MAXG = 1024;
 constexpr int MAXRAD = 64;
 constexpr int CT = 16;             // a centre tile is CT x CT cells
 constexpr float PI_F = 3.14159265358979323846f;
 constexpr float PI4_F = 0.78539816339744830962f;
 constexpr float TWO_PI_F = 6.283185307179586476925286766559f;
-// tab = sizes[48] | z_center[16] | rotations[8] | pos_thr[16] | neg_thr[16] | size_class[16] (int bits)
-constexpr int T_ZC = 48, T_ROT = 64, T_POS = 72, T_NEG = 88, T_SC = 104, T_N = 120;
+// tab = the anchor table (dense_tile.h) | pos_thr[16] | neg_thr[16] | size_class[16] (int bits)
+constexpr int T_POS = T_N, T_NEG = T_N + 16, T_SC = T_N + 32, T_END = T_N + 48;
 
 struct TgtP {
     const float *gt;
@@ -45,10 +40,11 @@ struct TgtP {
     int32_t *labels, *match, *dir_target;
     float *reg, *max_iou;
     unsigned *best;
-    int G, D, HW, W, A, nr, nb, use_sc;
+    int G, D, HW, A, nb, use_sc;
     int tiles, chunks;
-    float x0, y0, sx, sy, dir_offset, period;
-    float sizes[48], zc[16], rot[8], pos[16], neg[16];
+    float dir_offset, period;
+    AnchorTab tab;
+    float pos[16], neg[16];
     int32_t sc[16];
 };
 
@@ -85,38 +81,20 @@ __device__ __forceinline__ float rect_iou(const float4 a, const float4 g) {
     return inter / den;
 }
 
-__device__ __forceinline__ void load_tab(const TgtP &p, float *tab) {
+// the anchor table and the per-size entries behind it -> LDS (the caller synchronises)
+__device__ __forceinline__ void load_tabs(const TgtP &p, float *tab) {
+    load_tab(p.tab, tab);
     const int t = threadIdx.x;
-    if (t < T_N)
-        tab[t] = t < T_ZC ? p.sizes[t] : t < T_ROT ? p.zc[t - T_ZC] : t < T_POS ? p.rot[t - T_ROT] : t < T_NEG ? p.pos[t - T_POS]
-                 : t < T_SC ? p.neg[t - T_NEG] : __int_as_float(p.sc[t - T_SC]);
+    if (t >= T_POS && t < T_END) tab[t] = t < T_NEG ? p.pos[t - T_POS] : t < T_SC ? p.neg[t - T_NEG] : __int_as_float(p.sc[t - T_SC]);
 }
 
 // the scene's rectangles and labels -> LDS (the caller synchronises)
 __device__ __forceinline__ void load_gts(const TgtP &p, int b, float4 *grect, int *glab) {
-    for (int g = threadIdx.x; g < p.G; g += DT_THREADS) {
+    for (int g = threadIdx.x; g < p.G; g += DENSE_THREADS) {
         const float *r = p.gt + ((size_t)b * p.G + g) * p.D;
         grect[g] = nearest_rect(r[0], r[1], r[3], r[4], r[6]);
         glab[g] = p.gl[(size_t)b * p.G + g];
     }
-}
-
-struct Anchor {
-    float xa, ya, za, la, wa, ha, ra;
-    int s;
-};
-
-__device__ __forceinline__ Anchor anchor_of(const TgtP &p, const float *tab, int a, int cell) {
-    Anchor an;
-    an.s = a / p.nr;
-    const int r = a - an.s * p.nr;
-    const int y = cell / p.W, x = cell - y * p.W;
-    an.xa = p.x0 + ((float)x * p.sx);
-    an.ya = p.y0 + ((float)y * p.sy);
-    an.la = tab[3 * an.s]; an.wa = tab[3 * an.s + 1]; an.ha = tab[3 * an.s + 2];
-    an.za = tab[T_ZC + an.s];
-    an.ra = tab[T_ROT + r];
-    return an;
 }
 
 __device__ __forceinline__ bool eligible(const TgtP &p, const float *tab, int s, int label) {
@@ -130,7 +108,7 @@ __device__ __forceinline__ bool eligible(const TgtP &p, const float *tab, int s,
 // A box that fails the test has IoU exactly 0 with every anchor of the tile, which is what leaving it out computes: best[]
 // only takes values > 0, and pass 2 falls back to the lowest eligible box when a row met nothing (see anchor_assign_kernel).
 // Bits are walked in ascending g, so ties still go to the lowest g.
-__device__ __forceinline__ void cull_gts(const TgtP &p, const float *tab, const float4 *grect, unsigned *mask, int cell0, int ncell) {
+__device__ __forceinline__ void cull_gts(const AnchorTab &p, int G, const float *tab, const float4 *grect, unsigned *mask, int cell0, int ncell) {
     const int y_first = cell0 / p.W, y_last = (cell0 + ncell - 1) / p.W;
     const int x_first = y_first == y_last ? cell0 - y_first * p.W : 0;
     const int x_last = y_first == y_last ? cell0 + ncell - 1 - y_first * p.W : p.W - 1;
@@ -140,36 +118,32 @@ __device__ __forceinline__ void cull_gts(const TgtP &p, const float *tab, const 
     for (int i = 0; i < 3 * 16; i += 3) half = fmaxf(half, fmaxf(tab[i], tab[i + 1]) * 0.5f);      // (unused sizes are 0)
     const float xlo = fminf(xa, xb) - half, xhi = fmaxf(xa, xb) + half;
     const float ylo = fminf(ya, yb) - half, yhi = fmaxf(ya, yb) + half;
-    for (int w = threadIdx.x; w < MAXG / 32; w += DT_THREADS) mask[w] = 0u;
+    for (int w = threadIdx.x; w < MAXG / 32; w += DENSE_THREADS) mask[w] = 0u;
     __syncthreads();
-    for (int g = threadIdx.x; g < p.G; g += DT_THREADS) {
+    for (int g = threadIdx.x; g < G; g += DENSE_THREADS) {
         const float4 r = grect[g];
         if (r.y >= xlo && r.x <= xhi && r.w >= ylo && r.z <= yhi) atomicOr(&mask[g >> 5], 1u << (g & 31));
     }
     __syncthreads();
 }
 
-__global__ __launch_bounds__(DT_THREADS) void anchor_best_kernel(const TgtP p) {
-    __shared__ float tab[T_N];
+__global__ __launch_bounds__(DENSE_THREADS) void anchor_best_kernel(const TgtP p) {
+    __shared__ float tab[T_END];
     __shared__ float4 grect[MAXG];
     __shared__ int glab[MAXG];
     __shared__ unsigned sbest[MAXG];
     __shared__ unsigned gmask[MAXG / 32];
-    load_tab(p, tab);
-    const int b = blockIdx.y;
-    const int tile = blockIdx.x / p.chunks, chunk = blockIdx.x - tile * p.chunks;
-    const int cell0 = tile * TC, ncell = min(TC, p.HW - cell0);
-    const int a0 = chunk * AC, acn = min(AC, p.A - a0);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    load_tabs(p, tab);
+    const AnchorTile t = anchor_tile(p.chunks, p.HW, p.A);
+    const int b = t.b, lane = t.lane;
     load_gts(p, b, grect, glab);
-    for (int g = threadIdx.x; g < p.G; g += DT_THREADS) sbest[g] = 0u;
+    for (int g = threadIdx.x; g < p.G; g += DENSE_THREADS) sbest[g] = 0u;
     __syncthreads();
-    cull_gts(p, tab, grect, gmask, cell0, ncell);
-    for (int pass = 0; 4 * pass < acn; ++pass) {
-        const int al = 4 * pass + wave;
-        if (al >= acn) continue;                                     // (the whole wave: one anchor per wave)
-        const bool live = lane < ncell;
-        const Anchor an = anchor_of(p, tab, a0 + al, cell0 + (live ? lane : 0));
+    cull_gts(p.tab, p.G, tab, grect, gmask, t.cell0, t.ncell);
+    for (int pass = 0; 4 * pass < t.acn; ++pass) {
+        if (t.al(pass) >= t.acn) continue;                           // (the whole wave: one anchor per wave)
+        const bool live = lane < t.ncell;
+        const Anchor an = anchor_of(p.tab, tab, t.a0 + t.al(pass), t.cell0 + (live ? lane : 0));
         const float4 ar = nearest_rect(an.xa, an.ya, an.la, an.wa, an.ra);
         for (int w32 = 0; w32 * 32 < p.G; ++w32) {
             for (unsigned bits = gmask[w32]; bits; bits &= bits - 1) {       // (LDS broadcast: the same for the whole wave)
@@ -185,12 +159,12 @@ __global__ __launch_bounds__(DT_THREADS) void anchor_best_kernel(const TgtP p) {
         }
     }
     __syncthreads();
-    for (int g = threadIdx.x; g < p.G; g += DT_THREADS)
+    for (int g = threadIdx.x; g < p.G; g += DENSE_THREADS)
         if (sbest[g]) atomicMax(&p.best[(size_t)b * p.G + g], sbest[g]);
 }
 
-__global__ __launch_bounds__(DT_THREADS) void anchor_assign_kernel(const TgtP p) {
-    __shared__ float tab[T_N];
+__global__ __launch_bounds__(DENSE_THREADS) void anchor_assign_kernel(const TgtP p) {
+    __shared__ float tab[T_END];
     __shared__ float4 grect[MAXG];
     __shared__ int glab[MAXG];
     __shared__ float gbest[MAXG];
@@ -201,26 +175,21 @@ __global__ __launch_bounds__(DT_THREADS) void anchor_assign_kernel(const TgtP p)
     __shared__ int32_t odir[TC * AC];
     __shared__ unsigned gmask[MAXG / 32];
     __shared__ int first[16];
-    load_tab(p, tab);
-    const int b = blockIdx.y;
-    const int tile = blockIdx.x / p.chunks, chunk = blockIdx.x - tile * p.chunks;
-    const int cell0 = tile * TC, ncell = min(TC, p.HW - cell0);
-    const int a0 = chunk * AC, acn = min(AC, p.A - a0);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    load_gts(p, b, grect, glab);
-    for (int g = threadIdx.x; g < p.G; g += DT_THREADS) gbest[g] = __uint_as_float(p.best[(size_t)b * p.G + g]);
+    load_tabs(p, tab);
+    const AnchorTile t = anchor_tile(p.chunks, p.HW, p.A);
+    load_gts(p, t.b, grect, glab);
+    for (int g = threadIdx.x; g < p.G; g += DENSE_THREADS) gbest[g] = __uint_as_float(p.best[(size_t)t.b * p.G + g]);
     if (threadIdx.x < 16) first[threadIdx.x] = MAXG;
     __syncthreads();
     // first[s] = the lowest box eligible for size s: j of a row that meets no box (every IoU 0: the lowest eligible g attains it)
-    for (int i = threadIdx.x; i < p.G * 16; i += DT_THREADS) {
+    for (int i = threadIdx.x; i < p.G * 16; i += DENSE_THREADS) {
         const int g = i >> 4, sz = i & 15;
-        if (sz * p.nr < p.A && eligible(p, tab, sz, glab[g])) atomicMin(&first[sz], g);
+        if (sz * p.tab.nr < p.A && eligible(p, tab, sz, glab[g])) atomicMin(&first[sz], g);
     }
-    cull_gts(p, tab, grect, gmask, cell0, ncell);
-    for (int pass = 0; 4 * pass < acn; ++pass) {
-        const int al = 4 * pass + wave;
-        if (lane >= ncell || al >= acn) continue;
-        const Anchor an = anchor_of(p, tab, a0 + al, cell0 + lane);
+    cull_gts(p.tab, p.G, tab, grect, gmask, t.cell0, t.ncell);
+    for (int pass = 0; 4 * pass < t.acn; ++pass) {
+        if (!t.active(pass)) continue;
+        const Anchor an = anchor_of(p.tab, tab, t.a0 + t.al(pass), t.cell0 + t.lane);
         const float4 ar = nearest_rect(an.xa, an.ya, an.la, an.wa, an.ra);
         float m = 0.0f;
         int j = -1;
@@ -237,23 +206,14 @@ __global__ __launch_bounds__(DT_THREADS) void anchor_assign_kernel(const TgtP p)
         }
         if (j < 0 && first[an.s] < MAXG) j = first[an.s];            // every IoU of the row is 0: m = 0 at the lowest eligible box
         const bool positive = forced || (j >= 0 && m >= tab[T_POS + an.s]);
-        float t[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        float res[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         int label, match = -1, bin = -1;
         if (positive) {
-            const float *r = p.gt + ((size_t)b * p.G + j) * p.D;
-            const float gx = r[0], gy = r[1], gz = r[2], gl = r[3], gw = r[4], gh = r[5], gyaw = r[6];
-            const float dg = sqrtf((an.la * an.la) + (an.wa * an.wa));
-            t[0] = (gx - an.xa) / dg;
-            t[1] = (gy - an.ya) / dg;
-            t[2] = (gz - an.za) / an.ha;
-            t[3] = logf(fmaxf(gl, 1e-5f) / an.la);
-            t[4] = logf(fmaxf(gw, 1e-5f) / an.wa);
-            t[5] = logf(fmaxf(gh, 1e-5f) / an.ha);
-            t[6] = gyaw - an.ra;
+            residual_encode(an, p.gt + ((size_t)t.b * p.G + j) * p.D, res);
             label = glab[j];
             match = j;
             if (p.nb) {
-                const float rg = t[6] + an.ra;
+                const float rg = res[6] + an.ra;
                 const float v = rg - p.dir_offset;
                 const float o = v - (floorf(v / TWO_PI_F) * TWO_PI_F);
                 bin = (int)floorf(o / p.period);
@@ -262,21 +222,20 @@ __global__ __launch_bounds__(DT_THREADS) void anchor_assign_kernel(const TgtP p)
         } else {
             label = (j < 0 || m < tab[T_NEG + an.s]) ? -1 : -2;
         }
-        const int slot = lane * acn + al;
+        const int slot = t.slot(pass);
 #pragma unroll
-        for (int q = 0; q < 7; ++q) oreg[slot * 7 + q] = t[q];
+        for (int q = 0; q < 7; ++q) oreg[slot * 7 + q] = res[q];
         omax[slot] = m;
         olabel[slot] = label;
         omatch[slot] = match;
         odir[slot] = bin;
     }
     __syncthreads();
-    const size_t k0 = ((size_t)b * p.HW + cell0) * p.A + a0;
-    flush_spans<DT_THREADS>(oreg, p.reg + k0 * 7, ncell, acn * 7, (size_t)p.A * 7);
-    flush_spans<DT_THREADS>(omax, p.max_iou + k0, ncell, acn, (size_t)p.A);
-    flush_spans<DT_THREADS>(olabel, p.labels + k0, ncell, acn, (size_t)p.A);
-    flush_spans<DT_THREADS>(omatch, p.match + k0, ncell, acn, (size_t)p.A);
-    if (p.nb) flush_spans<DT_THREADS>(odir, p.dir_target + k0, ncell, acn, (size_t)p.A);
+    t.store(oreg, p.reg, 7);
+    t.store(omax, p.max_iou, 1);
+    t.store(olabel, p.labels, 1);
+    t.store(omatch, p.match, 1);
+    if (p.nb) t.store(odir, p.dir_target, 1);
 }
 
 // §26.2: one box.  false: unassigned
@@ -317,7 +276,7 @@ __device__ __forceinline__ bool center_box(const CtrP &p, const float *r, int la
     return true;
 }
 
-__global__ __launch_bounds__(DT_THREADS) void center_map_kernel(const CtrP p) {
+__global__ __launch_bounds__(DENSE_THREADS) void center_map_kernel(const CtrP p) {
     __shared__ int lix[MAXG], liy[MAXG], lrad[MAXG], llab[MAXG];
     __shared__ float lden[MAXG];
     __shared__ int count;
@@ -326,7 +285,7 @@ __global__ __launch_bounds__(DT_THREADS) void center_map_kernel(const CtrP p) {
     const int x0 = tx * CT, y0 = ty * CT;
     if (threadIdx.x == 0) count = 0;
     __syncthreads();
-    for (int g = threadIdx.x; g < p.G; g += DT_THREADS) {
+    for (int g = threadIdx.x; g < p.G; g += DENSE_THREADS) {
         const int label = p.gl[(size_t)b * p.G + g];
         CBox bx;
         if (!center_box(p, p.gt + ((size_t)b * p.G + g) * p.D, label, bx)) continue;
@@ -338,7 +297,7 @@ __global__ __launch_bounds__(DT_THREADS) void center_map_kernel(const CtrP p) {
     const int n = count;
     const int x = x0 + (threadIdx.x & (CT - 1)), y = y0 + (threadIdx.x >> 4);
     if (x >= p.W || y >= p.H) return;
-    const size_t cell = (size_t)y * p.W + x, HW = (size_t)p.H * p.W;
+    const int cell = y * p.W + x, HW = p.H * p.W;
     for (int c = 0; c < p.C; ++c) {
         float v = 0.0f;
         for (int i = 0; i < n; ++i) {
@@ -347,12 +306,12 @@ __global__ __launch_bounds__(DT_THREADS) void center_map_kernel(const CtrP p) {
             if (dx < -rad || dx > rad || dy < -rad || dy > rad) continue;
             v = fmaxf(v, expf(-(float)(dx * dx + dy * dy) / lden[i]));
         }
-        p.hm[p.nhwc ? ((size_t)b * HW + cell) * p.C + c : ((size_t)b * p.C + c) * HW + cell] = v;
+        p.hm[map_at(p.nhwc, b, c, cell, p.C, HW)] = v;
     }
 }
 
-__global__ __launch_bounds__(DT_THREADS) void center_anno_kernel(const CtrP p) {
-    const int g = blockIdx.x * DT_THREADS + threadIdx.x, b = blockIdx.y;
+__global__ __launch_bounds__(DENSE_THREADS) void center_anno_kernel(const CtrP p) {
+    const int g = blockIdx.x * DENSE_THREADS + threadIdx.x, b = blockIdx.y;
     if (g >= p.G) return;
     const size_t row = (size_t)b * p.G + g;
     const float *r = p.gt + row * p.D;
@@ -397,57 +356,42 @@ SAD_API size_t sad_anchor_targets_workspace_bytes(int B, int G) {
 
 SAD_API int sad_anchor_targets_f32(const sad_anchor_targets_args *a, sad_stream_t stream) {
     const char *fn = "sad_anchor_targets_f32";
-    SAD_REQUIRE(a, "%s: NULL args", fn);
-    SAD_REQUIRE(a->struct_size == sizeof(sad_anchor_targets_args), "%s: struct_size %zu, this library has %zu", fn, a->struct_size,
-                sizeof(sad_anchor_targets_args));
+    if (int rc = args_ok(fn, a)) return rc;
     SAD_REQUIRE(a->labels && a->match && a->reg_target && a->max_iou, "%s: NULL pointer", fn);
     SAD_REQUIRE(a->H >= 1 && a->W >= 1, "%s: need H, W >= 1 (got %d, %d)", fn, a->H, a->W);
     SAD_REQUIRE(a->ns >= 1 && a->nr >= 1, "%s: need ns, nr >= 1 (got %d, %d)", fn, a->ns, a->nr);
     SAD_REQUIRE(a->nb == 0 || a->nb >= 2, "%s: nb must be 0 (no direction target) or 2 .. 8 (got %d)", fn, a->nb);
     SAD_REQUIRE((a->nb == 0) == (a->dir_target == nullptr), "%s: dir_target and nb must be given together (nb = %d)", fn, a->nb);
     if (int rc = gt_ok(fn, a->gt_boxes, a->gt_labels, a->B, a->G, a->D)) return rc;
-    if (a->ns > 16 || a->nr > 8 || a->nb > 8)
-        return sad::fail(SAD_EUNSUPPORTED, "%s: ns = %d, nr = %d, nb = %d (ns <= 16, nr <= 8, nb <= 8 supported)", fn, a->ns, a->nr, a->nb);
+    TgtP p = {};
+    if (int rc = fill_anchor_tab(fn, a, &p.tab)) return rc;
     for (int i = 0; i < 3 * a->ns; ++i)
         SAD_REQUIRE(a->sizes[i] > 0.0f, "%s: anchor size %d has a non-positive extent (%g)", fn, i / 3, (double)a->sizes[i]);
     SAD_REQUIRE(a->G == 0 || a->workspace, "%s: NULL workspace (sad_anchor_targets_workspace_bytes(B, G) bytes)", fn);
     const int A = a->ns * a->nr;
-    const long long HW = (long long)a->H * a->W, K = HW * A;
-    if (HW >= (1LL << 31) || K >= (1LL << 31) || (long long)a->B * K >= (1LL << 31))
-        return sad::fail(SAD_EUNSUPPORTED, "%s: B * K = %d * %lld rows (B * K < 2^31 supported)", fn, a->B, K);
-    TgtP p = {};
+    if (!rows_fit(a->B, a->H, a->W, A)) return sad::fail(SAD_EUNSUPPORTED, "%s: B * K = %d * %lld rows (B * K < 2^31 supported)", fn, a->B, (long long)a->H * a->W * A);
     p.gt = a->gt_boxes; p.gl = a->gt_labels;
     p.labels = a->labels; p.match = a->match; p.dir_target = a->dir_target; p.reg = a->reg_target; p.max_iou = a->max_iou;
     p.best = (unsigned *)a->workspace;
-    p.G = a->G; p.D = a->D; p.HW = (int)HW; p.W = a->W; p.A = A; p.nr = a->nr; p.nb = a->nb; p.use_sc = a->use_size_class != 0;
-    p.x0 = a->x0; p.y0 = a->y0; p.sx = a->sx; p.sy = a->sy; p.dir_offset = a->dir_offset;
-    p.period = a->nb ? (float)(6.283185307179586476925286766559 / (double)a->nb) : 0.0f;      // in double, rounded once (§25.1)
-    for (int i = 0; i < 3 * a->ns; ++i) p.sizes[i] = a->sizes[i];
-    for (int i = 0; i < a->ns; ++i) {
-        p.zc[i] = a->z_center[i]; p.pos[i] = a->pos_thr[i]; p.neg[i] = a->neg_thr[i]; p.sc[i] = a->size_class[i];
-    }
-    for (int i = 0; i < a->nr; ++i) p.rot[i] = a->rotations[i];
-    p.tiles = (p.HW + TC - 1) / TC;
-    p.chunks = (A + AC - 1) / AC;
+    p.G = a->G; p.D = a->D; p.HW = a->H * a->W; p.A = A; p.nb = a->nb; p.use_sc = a->use_size_class != 0;
+    p.dir_offset = a->dir_offset; p.period = dir_period(a->nb);
+    for (int i = 0; i < a->ns; ++i) { p.pos[i] = a->pos_thr[i]; p.neg[i] = a->neg_thr[i]; p.sc[i] = a->size_class[i]; }
     const hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)p.tiles * (unsigned)p.chunks, a->B);
+    const dim3 grid((unsigned)anchor_grid_of(p.HW, A, &p.tiles, &p.chunks), a->B);
     if (a->G > 0) {
         if (hipMemsetAsync(a->workspace, 0, sad_anchor_targets_workspace_bytes(a->B, a->G), st) != hipSuccess) return sad::check_launch(fn);
-        hipLaunchKernelGGL(anchor_best_kernel, grid, dim3(DT_THREADS), 0, st, p);
+        hipLaunchKernelGGL(anchor_best_kernel, grid, dim3(DENSE_THREADS), 0, st, p);
         if (int rc = sad::check_launch(fn)) return rc;
     }
-    hipLaunchKernelGGL(anchor_assign_kernel, grid, dim3(DT_THREADS), 0, st, p);
+    hipLaunchKernelGGL(anchor_assign_kernel, grid, dim3(DENSE_THREADS), 0, st, p);
     return sad::check_launch(fn);
 }
 
 SAD_API int sad_center_targets_f32(const sad_center_targets_args *a, sad_stream_t stream) {
     const char *fn = "sad_center_targets_f32";
-    SAD_REQUIRE(a, "%s: NULL args", fn);
-    SAD_REQUIRE(a->struct_size == sizeof(sad_center_targets_args), "%s: struct_size %zu, this library has %zu", fn, a->struct_size,
-                sizeof(sad_center_targets_args));
+    if (int rc = args_ok(fn, a)) return rc;
     SAD_REQUIRE(a->heatmap, "%s: NULL pointer (heatmap)", fn);
-    SAD_REQUIRE(a->layout == SAD_LAYOUT_NCHW || a->layout == SAD_LAYOUT_NHWC, "%s: layout must be SAD_LAYOUT_NCHW or SAD_LAYOUT_NHWC (got %d)", fn,
-                a->layout);
+    SAD_REQUIRE(a->layout == SAD_LAYOUT_NCHW || a->layout == SAD_LAYOUT_NHWC, "%s: layout must be SAD_LAYOUT_NCHW or SAD_LAYOUT_NHWC (got %d)", fn, a->layout);
     SAD_REQUIRE(a->H >= 1 && a->W >= 1 && a->C >= 1, "%s: need H, W, C >= 1 (got %d, %d, %d)", fn, a->H, a->W, a->C);
     if (int rc = gt_ok(fn, a->gt_boxes, a->gt_labels, a->B, a->G, a->D)) return rc;
     SAD_REQUIRE(a->G == 0 || (a->ind && a->anno), "%s: NULL pointer (ind, anno)", fn);
@@ -456,9 +400,7 @@ SAD_API int sad_center_targets_f32(const sad_center_targets_args *a, sad_stream_
     SAD_REQUIRE(a->min_radius >= 0 && a->min_radius <= MAXRAD, "%s: need 0 <= min_radius <= 64 (got %d)", fn, a->min_radius);
     SAD_REQUIRE(!a->vel || a->D >= 9, "%s: vel needs D >= 9 (got %d)", fn, a->D);
     if (a->C > 64) return sad::fail(SAD_EUNSUPPORTED, "%s: C = %d classes (1 .. 64 supported)", fn, a->C);
-    const long long HW = (long long)a->H * a->W;
-    if (HW >= (1LL << 31) || (long long)a->B * HW >= (1LL << 31))
-        return sad::fail(SAD_EUNSUPPORTED, "%s: B * H * W = %d * %lld cells (B * H * W < 2^31 supported)", fn, a->B, HW);
+    if (!rows_fit(a->B, a->H, a->W, 1)) return sad::fail(SAD_EUNSUPPORTED, "%s: B * H * W = %d * %lld cells (B * H * W < 2^31 supported)", fn, a->B, (long long)a->H * a->W);
     CtrP p = {};
     p.gt = a->gt_boxes; p.gl = a->gt_labels; p.hm = a->heatmap; p.ind = a->ind; p.anno = a->anno;
     p.G = a->G; p.D = a->D; p.C = a->C; p.H = a->H; p.W = a->W; p.nhwc = a->layout == SAD_LAYOUT_NHWC;
@@ -467,10 +409,10 @@ SAD_API int sad_center_targets_f32(const sad_center_targets_args *a, sad_stream_
     p.tx = (a->W + CT - 1) / CT;
     const long long tiles = (long long)p.tx * ((a->H + CT - 1) / CT);                           // (<= H * W < 2^31)
     const hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(center_map_kernel, dim3((unsigned)tiles, a->B), dim3(DT_THREADS), 0, st, p);
+    hipLaunchKernelGGL(center_map_kernel, dim3((unsigned)tiles, a->B), dim3(DENSE_THREADS), 0, st, p);
     if (int rc = sad::check_launch(fn)) return rc;
     if (a->G > 0) {
-        hipLaunchKernelGGL(center_anno_kernel, dim3((unsigned)((a->G + DT_THREADS - 1) / DT_THREADS), a->B), dim3(DT_THREADS), 0, st, p);
+        hipLaunchKernelGGL(center_anno_kernel, dim3((unsigned)((a->G + DENSE_THREADS - 1) / DENSE_THREADS), a->B), dim3(DENSE_THREADS), 0, st, p);
         return sad::check_launch(fn);
     }
     return SAD_OK;

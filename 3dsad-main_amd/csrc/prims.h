@@ -1,8 +1,8 @@
 // Device primitives that more than one translation unit needs: the vector types of the MFMA kernels, the cross-lane
-// (DPP / readlane) unsigned maxima of the samplers, the LDS-DMA load with its wait, the float atomic max of the pooled
-// outputs, and the tile-image span copies and the pass staging of the dense head kernels.  Included inside each file's
-// anonymous namespace, like reg_common.h and vox_hash.h (which include it).  ONE definition of each: a helper moves here when
-// a second file needs it; a helper with a single user stays in that file.
+// (DPP / readlane) unsigned maxima of the samplers, the LDS-DMA load with its wait, and the float atomic max of the pooled
+// outputs.  Included inside each file's anonymous namespace, like reg_common.h, vox_hash.h and dense_tile.h (which include it).
+// ONE definition of each: a helper moves here when a second family needs it; a helper with a single user stays in that file,
+// and what only one family shares lives in that family's header (the dense heads' tile-image copies: dense_tile.h).
 #pragma once
 
 typedef unsigned long long u64;
@@ -109,51 +109,4 @@ template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_wai
 // bit patterns read as unsigned integers, and 0 is the neutral element.  A negative value or -0 would win every comparison.
 __device__ __forceinline__ void atomic_max_pos(float *addr, float v) {
     atomicMax(reinterpret_cast<unsigned *>(addr), __builtin_bit_cast(unsigned, v));
-}
-
-// ---- tile image <-> memory ---------------------------------------------------------------------------------------------------
-// The dense head kernels (dense_head.hip, dense_target.hip, dense_loss.hip) move the rows of a tile through an LDS image in
-// memory order: `ncell` spans of `seg` elements, span c at mem[c * stride]; the image holds them back to back.  All THREADS
-// threads of the workgroup call these; consecutive threads touch consecutive elements.  When one chunk of anchors covers the
-// row (seg == stride) the tile is a single run and no index is divided.
-template <int THREADS, class T>
-__device__ __forceinline__ void flush_spans(const T *img, T *dst, int ncell, int seg, size_t stride) {
-    const int n = ncell * seg;
-    if ((size_t)seg == stride) {
-        for (int i = threadIdx.x; i < n; i += THREADS) dst[i] = img[i];
-        return;
-    }
-    for (int i = threadIdx.x; i < n; i += THREADS) {
-        const int c = i / seg;
-        dst[(size_t)c * stride + (i - c * seg)] = img[i];
-    }
-}
-
-template <int THREADS, class T>
-__device__ __forceinline__ void load_spans(T *img, const T *src, int ncell, int seg, size_t stride) {
-    const int n = ncell * seg;
-    if ((size_t)seg == stride) {
-        for (int i = threadIdx.x; i < n; i += THREADS) img[i] = src[i];
-        return;
-    }
-    for (int i = threadIdx.x; i < n; i += THREADS) {
-        const int c = i / seg;
-        img[i] = src[(size_t)c * stride + (i - c * seg)];
-    }
-}
-
-// The channels-last (nhwc) passes of the anchor head (dense_head.hip, dense_loss.hip): rows (al, cell) of a pass <->
-// lds[(al * CELLS + cell) * ld + e], e < len: channels ch0 .. ch0 + len - 1 of anchor a0 + al out of CHA per anchor, CELLS the
-// cells of an anchor tile.  All THREADS threads walk the floats of the pass in memory order; OUT: the image goes back to memory.
-template <int THREADS, int CELLS, bool OUT, class P>
-__device__ __forceinline__ void stage_rows(float *lds, int ld, P *scene, int CHA, int ch0, int len, int A, int cell0, int ncell, int a0,
-                                           int na) {
-    const int n = ncell * na * len;
-    for (int i = threadIdx.x; i < n; i += THREADS) {
-        const int row = i / len, e = i - row * len;
-        const int cell = row / na, al = row - cell * na;
-        P *g = scene + ((size_t)(cell0 + cell) * A + a0 + al) * CHA + ch0 + e;
-        if constexpr (OUT) *g = lds[(al * CELLS + cell) * ld + e];
-        else lds[(al * CELLS + cell) * ld + e] = *g;
-    }
 }

@@ -259,6 +259,8 @@ ANCHOR_SHAPES = {
     "a:1x1:b3":     (1, 1, 3, 3, 2, 3, 4),
     "a:5x7:a1":     (5, 7, 1, 1, 1, 3, 2),
     "a:3x67:a1":    (3, 67, 1, 1, 1, 1, 2),
+    "a:3x67:a9":    (3, 67, 1, 3, 3, 10, 2),       # a partial last chunk behind a full one: 8 + 1 anchors, the last tile 9 cells
+    "a:5x7:a11":    (5, 7, 3, 11, 1, 3, 2),        # 8 + 3 anchors, fewer cells than one tile
 }
 #          name            H   W    B  C  vel    log    peak
 CENTER_SHAPES = {

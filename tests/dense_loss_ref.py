@@ -381,6 +381,8 @@ ANCHOR_SHAPES = {
     "l:9x130:a32": (9, 130, 32, 1, 2),     # 19 tiles x 4 chunks = 76 workgroups per scene: the sum of the partials wraps its 64 lanes
     "l:edges":   (5, 7, 6, 3, 2),
     "l:exact":   (5, 7, 6, 3, 0),
+    "l:3x67:a9": (3, 67, 9, 3, 2),         # a partial last chunk behind a full one: 8 + 1 anchors, the last tile 9 cells
+    "l:5x7:a11": (5, 7, 11, 10, 2),        # 8 + 3 anchors, fewer cells than one tile
 }
 ANCHOR_CASES = list(ANCHOR_SHAPES)
 ANCHOR_KW = dict(alpha=0.25, beta=1.0 / 9.0, code_weights=(1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0), sin_diff=True, scale=(1.0, 2.0, 0.2),

@@ -275,6 +275,8 @@ ANCHOR_SHAPES = {
     "t:5x7:g1024":   (5, 7, 1, 3, 2, 1024, 0, True),
     "t:5x7:g0":      (5, 7, 2, 3, 2, 0, 2, True),
     "t:3x67:any":    (3, 67, 3, 3, 2, 65, 2, False),
+    "t:3x67:a9":     (3, 67, 3, 3, 3, 65, 2, True),     # a partial last chunk behind a full one: 8 + 1 anchors, the last tile 9 cells
+    "t:5x7:a11":     (5, 7, 1, 11, 1, 3, 2, True),      # 8 + 3 anchors, fewer cells than one tile
 }
 
 

@@ -311,11 +311,12 @@ def test_coverage_labels_and_bins(name):
 
 def test_coverage_tiles():
     """What the shapes are for: a partial wave, rows crossing one and two 64-lane boundaries, K no multiple of 256, more than
-    8 anchors (two anchor chunks, the second one partial passes) and fewer than 4."""
+    8 anchors (sixteen full anchor chunks; 9 and 11: a full chunk and a partial one of 1 and of 3 anchors) and fewer than 4."""
     cells = {s[0] * s[1] for s in ref.ANCHOR_SHAPES.values()} | {s[0] * s[1] for s in ref.CENTER_SHAPES.values()}
     assert {1, 35, 201, 1170} <= cells and 67 > 64 and 130 > 128
     assert all(ref.rows_of(n) % 256 for n in ref.ALL_CASES)
-    assert {s[3] * s[4] for s in ref.ANCHOR_SHAPES.values()} == {1, 6, 128}
+    assert {s[3] * s[4] for s in ref.ANCHOR_SHAPES.values()} == {1, 6, 9, 11, 128}
+    assert {(s[0] * s[1], s[3] * s[4]) for s in ref.ANCHOR_SHAPES.values()} >= {(201, 9), (35, 11)}
     assert {s[5] for s in ref.ANCHOR_SHAPES.values()} == {1, 3, 10} and {s[6] for s in ref.ANCHOR_SHAPES.values()} == {0, 2, 4}
     assert {s[2] for s in ref.ANCHOR_SHAPES.values()} == {1, 3}
 

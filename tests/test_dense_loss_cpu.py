@@ -136,7 +136,7 @@ def test_shapes_of_the_cases():
     """Every value of the issue's shape table occurs: H x W, A, C, nb, G; B = 3 everywhere."""
     hw = {s[:2] for s in ref.ANCHOR_SHAPES.values()}
     assert {(1, 1), (5, 7), (3, 67), (9, 130)} <= hw and hw == {s[:2] for s in ref.CENTER_SHAPES.values()}
-    assert {1, 6, 128} <= {s[2] for s in ref.ANCHOR_SHAPES.values()}
+    assert {1, 6, 9, 11, 128} <= {s[2] for s in ref.ANCHOR_SHAPES.values()}      # (9, 11: a full anchor chunk and a partial one)
     assert {1, 3, 64} <= {s[3] for s in ref.ANCHOR_SHAPES.values()} and {1, 3, 64} <= {s[2] for s in ref.CENTER_SHAPES.values()}
     assert {0, 2, 4} <= {s[4] for s in ref.ANCHOR_SHAPES.values()}
     assert {0, 1, 3, 65, 1024} <= {s[3] for s in ref.CENTER_SHAPES.values()}

@@ -36,7 +36,8 @@ def test_coverage_shapes():
     wave) and 1024 (the limit), B = 3 with differing padding."""
     a, c = ref.ANCHOR_SHAPES, ref.CENTER_SHAPES
     assert {s[0] * s[1] for s in a.values()} == {1, 35, 201, 1170} and {s[0] * s[1] for s in c.values()} >= {1, 35, 201, 1170}
-    assert {s[3] * s[4] for s in a.values()} == {1, 6, 128}
+    assert {s[3] * s[4] for s in a.values()} == {1, 6, 9, 11, 128}      # (9, 11: a full anchor chunk and a partial one of 1 and of 3)
+    assert {(s[0] * s[1], s[3] * s[4]) for s in a.values()} >= {(201, 9), (35, 11)}
     assert {s[5] for s in a.values()} == {0, 1, 3, 65, 1024} and {s[4] for s in c.values()} == {0, 1, 3, 65, 1024}
     assert {s[6] for s in a.values()} == {0, 2, 4} and {s[7] for s in a.values()} == {True, False}
     for name in ("t:5x7", "t:9x130", "ct:9x130"):

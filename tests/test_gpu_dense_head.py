@@ -96,7 +96,8 @@ def test_decode_parity_layouts_and_determinism(dev, name):
     _same_bits(_run(c, dev, layout="nhwc"), got, f"{name}: nhwc against nchw")
 
 
-@pytest.mark.parametrize("name", ["a:5x7", "a:3x67:128", "a:9x130", "a:edges", "a:3x67:c10", "c:5x7", "c:9x130:peak", "c:3x67", "c:edges:vel"])
+@pytest.mark.parametrize("name", ["a:5x7", "a:3x67:128", "a:9x130", "a:edges", "a:3x67:c10", "a:3x67:a9", "a:5x7:a11", "c:5x7", "c:9x130:peak", "c:3x67",
+                                  "c:edges:vel"])
 def test_index_rows_are_the_rows_of_the_full_decode(dev, name):
     c = ref.case(name)
     full = _run(c, dev)

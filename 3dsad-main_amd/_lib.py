@@ -148,6 +148,23 @@ class CenterHeadLossArgs(ctypes.Structure):
     ]
 
 
+ROI_CLS_MODES = {"roi_iou": 0, "cls": 1}      # SAD_ROI_CLS_*
+
+
+class RoiTargetsArgs(ctypes.Structure):
+    """``struct sad_roi_targets_args`` (include/sad_amd.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("rois", vp), ("roi_count", vp), ("roi_labels", vp), ("gt_boxes", vp), ("gt_labels", vp),
+        ("B", ctypes.c_int), ("R", ctypes.c_int), ("D", ctypes.c_int), ("G", ctypes.c_int), ("Dg", ctypes.c_int),
+        ("S", ctypes.c_int), ("fg_max", ctypes.c_int), ("cls_mode", ctypes.c_int), ("seed", ctypes.c_uint),
+        ("fg_thr", ctypes.c_float), ("bg_lo", ctypes.c_float), ("hard_ratio", ctypes.c_float), ("reg_fg_thr", ctypes.c_float),
+        ("cls_fg_thr", ctypes.c_float), ("cls_bg_thr", ctypes.c_float),
+        ("index", vp), ("match", vp), ("labels", vp), ("iou", vp), ("cls_target", vp), ("reg_valid", vp),
+        ("rois_s", vp), ("gt_local", vp), ("reg_target", vp), ("workspace", vp),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/sad_amd.h declares
 SIGNATURES = {
     "sad_version": (ctypes.c_int, []),
@@ -253,6 +270,9 @@ SIGNATURES = {
     "sad_anchor_head_loss_f32": (ctypes.c_int, [ctypes.POINTER(AnchorHeadLossArgs), vp]),
     "sad_center_head_loss_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
     "sad_center_head_loss_f32": (ctypes.c_int, [ctypes.POINTER(CenterHeadLossArgs), vp]),
+    "sad_roi_targets_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "sad_roi_targets_f32": (ctypes.c_int, [ctypes.POINTER(RoiTargetsArgs), vp]),
+    "sad_roi_decode_f32": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp]),
 }
 
 _lib = None

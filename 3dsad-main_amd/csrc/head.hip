@@ -101,13 +101,7 @@ SAD_API int sad_decode_boxes_f32(const float *cand, const float *o, int B, int K
 // HBM-bound row copy (algorithmic bytes: n_points * C * 4 read + written per scene); one thread per output row,
 // the source row is a pure integer function of (seed, scene, row), identical to io.fix_size and the oracle.
 namespace {
-__device__ __forceinline__ unsigned mix32(unsigned a) {
-    a ^= a >> 16; a *= 0x85EBCA6Bu; a ^= a >> 13; a *= 0xC2B2AE35u; a ^= a >> 16;
-    return a;
-}
-__device__ __forceinline__ unsigned h17(unsigned seed, unsigned b, unsigned i) {
-    return mix32(seed * 0x9E3779B1u + b * 0x85EBCA77u + i * 0xC2B2AE3Du + 0x27D4EB2Fu);
-}
+#include "prims.h"      // h17, the integer hash (shared with roi_head.hip)
 __global__ __launch_bounds__(256) void subsample_pad_kernel(const float *__restrict__ points, const int32_t *__restrict__ offsets,
                                                             int C, int n_points, unsigned seed, float *__restrict__ out) {
     const int b = blockIdx.y;

@@ -1,6 +1,6 @@
 // Device primitives that more than one translation unit needs: the vector types of the MFMA kernels, the cross-lane
-// (DPP / readlane) unsigned maxima of the samplers, the LDS-DMA load with its wait, and the float atomic max of the pooled
-// outputs.  Included inside each file's anonymous namespace, like reg_common.h, vox_hash.h and dense_tile.h (which include it).
+// (DPP / readlane) unsigned maxima of the samplers, the LDS-DMA load with its wait, the integer hash of SPEC.md §17 and the
+// float atomic max of the pooled outputs.  Included inside each file's anonymous namespace, like reg_common.h, vox_hash.h and dense_tile.h (which include it).
 // ONE definition of each: a helper moves here when a second family needs it; a helper with a single user stays in that file,
 // and what only one family shares lives in that family's header (the dense heads' tile-image copies: dense_tile.h).
 #pragma once
@@ -103,6 +103,17 @@ __device__ __forceinline__ void glds16(const void *gsrc, unsigned lds_dst) {
     // so they keep their order among themselves and relative to the barriers, which is all the rings need)
 }
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N)); }
+
+// ---- the integer hash of SPEC.md §17 ---------------------------------------------------------------------------------------
+// h(seed, b, i): a pure 32-bit integer function, the same in io.fix_size, the oracle, subsample_pad (head.hip) and the RoI
+// sampler (roi_head.hip).
+__device__ __forceinline__ unsigned mix32(unsigned a) {
+    a ^= a >> 16; a *= 0x85EBCA6Bu; a ^= a >> 13; a *= 0xC2B2AE35u; a ^= a >> 16;
+    return a;
+}
+__device__ __forceinline__ unsigned h17(unsigned seed, unsigned b, unsigned i) {
+    return mix32(seed * 0x9E3779B1u + b * 0x85EBCA77u + i * 0xC2B2AE3Du + 0x27D4EB2Fu);
+}
 
 // ---- float atomic max ------------------------------------------------------------------------------------------------------
 // Valid ONLY for values >= +0 (outputs of a ReLU) merged into a buffer that starts at zero: such floats order like their

@@ -1443,6 +1443,101 @@ def center_targets(gt_boxes: torch.Tensor, gt_labels: torch.Tensor, *, C: int, H
     return heatmap, ind, anno
 
 
+ROI_OUTPUTS = ("index", "match", "labels", "iou", "cls_target", "reg_valid", "rois_s", "gt_local", "reg_target")
+
+
+def roi_output_spec(B: int, S: int) -> tuple:
+    """((name, shape, dtype), ...) of ``roi_targets``' outputs, what its ``out=`` tuple is checked against."""
+    i32, f32 = torch.int32, torch.float32
+    return (("index", (B, S), i32), ("match", (B, S), i32), ("labels", (B, S), i32), ("iou", (B, S), f32), ("cls_target", (B, S), f32),
+            ("reg_valid", (B, S), i32), ("rois_s", (B, S, 7), f32), ("gt_local", (B, S, 7), f32), ("reg_target", (B, S, 7), f32))
+
+
+def roi_targets_workspace(B: int, R: int, device) -> torch.Tensor:
+    """The workspace of ``roi_targets(..., workspace=...)`` for a caller that keeps it."""
+    nbytes = lib().sad_roi_targets_workspace_bytes(B, R)
+    if not nbytes:
+        raise ValueError(f"roi_targets_workspace: need 1 <= B <= 65535 and 1 <= R <= 4096 (got {B}, {R})")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def roi_targets(rois: torch.Tensor, roi_count: Optional[torch.Tensor], roi_labels: Optional[torch.Tensor], gt_boxes: torch.Tensor,
+                gt_labels: torch.Tensor, *, S: int, fg_max: int, fg_thr: float, bg_lo: float, hard_ratio: float, reg_fg_thr: float,
+                cls_fg_thr: float, cls_bg_thr: float, cls_mode: str = "roi_iou", seed: int = 0, out: Optional[tuple] = None,
+                workspace: Optional[torch.Tensor] = None) -> tuple:
+    """RoI head proposal sampling and targets (SPEC.md §28.1).  rois [B,R,D>=7] f32 rows (cx,cy,cz,l,w,h,yaw,...), roi_count [B]
+    int32 or ``None`` (the candidates of scene b are its first ``roi_count[b]`` rows; the rows beyond are never read, so the
+    gathered output of ``nms_boxes`` goes in as it is), roi_labels [B,R] int32 or ``None`` (given: a RoI is matched against the
+    boxes of its own class only), gt_boxes [B,G,Dg>=7] / gt_labels [B,G] int32 as in ``anchor_targets`` ->
+    (index [B,S] int32, match, labels, iou [B,S] f32, cls_target [B,S] f32, reg_valid [B,S] int32, rois_s [B,S,7], gt_local
+    [B,S,7], reg_target [B,S,7]).  A candidate's best 3-D IoU m makes it fg (m >= fg_thr), hard (bg_lo <= m < fg_thr) or easy;
+    the first min(fg_max, n_fg, S) slots hold fg candidates without replacement, the others draw from hard (``hard_ratio`` of
+    them) and easy with replacement, all from an integer hash of (seed, scene, row or slot).  ``index`` gathers whatever was
+    pooled per RoI.  Two launches, no IoU matrix, no synchronisation, no gradients, bit-identical from call to call."""
+    if cls_mode not in _lib.ROI_CLS_MODES:
+        raise ValueError(f"cls_mode: expected 'roi_iou' or 'cls', got {cls_mode!r}")
+    _strict(rois, "rois", torch.float32, (None, None, None), "[B,R,D] with B, R >= 1 and D >= 7")
+    B, R, D = rois.shape
+    if B < 1 or R < 1 or D < 7:
+        raise ValueError(f"rois: expected [B,R,D] with B, R >= 1 and D >= 7, got {tuple(rois.shape)}")
+    if R > 4096:
+        raise ValueError(f"rois: at most 4096 RoIs per scene (got R = {R})")
+    if roi_count is not None:
+        _strict(roi_count, "roi_count", torch.int32, (B,))
+    if roi_labels is not None:
+        _strict(roi_labels, "roi_labels", torch.int32, (B, R))
+    S, fg_max = int(S), int(fg_max)
+    if not 1 <= S <= 1024:
+        raise ValueError(f"S: expected 1 .. 1024, got {S}")
+    if fg_max < 0:
+        raise ValueError(f"fg_max: expected >= 0, got {fg_max}")
+    fg_thr, bg_lo, hard_ratio, reg_fg_thr = _f32(fg_thr), _f32(bg_lo), _f32(hard_ratio), _f32(reg_fg_thr)
+    cls_fg_thr, cls_bg_thr = _f32(cls_fg_thr), _f32(cls_bg_thr)
+    if not (0.0 <= bg_lo <= fg_thr and fg_thr > 0.0):
+        raise ValueError(f"fg_thr, bg_lo: need 0 <= bg_lo <= fg_thr and fg_thr > 0 (got {fg_thr}, {bg_lo})")
+    if not cls_bg_thr < cls_fg_thr:
+        raise ValueError(f"cls_fg_thr, cls_bg_thr: need cls_bg_thr < cls_fg_thr (got {cls_fg_thr}, {cls_bg_thr})")
+    if not 0.0 <= hard_ratio <= 1.0:
+        raise ValueError(f"hard_ratio: expected a value in [0, 1], got {hard_ratio}")
+    if reg_fg_thr != reg_fg_thr:
+        raise ValueError("reg_fg_thr: NaN")
+    if isinstance(gt_boxes, torch.Tensor) and gt_boxes.dim() == 3 and gt_boxes.shape[0] != B:
+        raise ValueError(f"gt_boxes: expected {B} scenes like rois, got {gt_boxes.shape[0]}")
+    _, G, Dg, _ = _gt_inputs(gt_boxes, gt_labels)
+    dev = _head_devices((("rois", rois), ("roi_count", roi_count), ("roi_labels", roi_labels), ("gt_boxes", gt_boxes)))
+    outs = _outputs(roi_output_spec(B, S), out, dev, "rois")
+    workspace = _workspace(lib().sad_roi_targets_workspace_bytes(B, R), workspace, dev, "ops.roi_targets_workspace", 4)
+    a = _lib.RoiTargetsArgs()
+    a.struct_size = ctypes.sizeof(_lib.RoiTargetsArgs)
+    a.rois, a.roi_count, a.roi_labels = rois.data_ptr(), _ptr(roi_count), _ptr(roi_labels)
+    a.gt_boxes, a.gt_labels = (gt_boxes.data_ptr(), gt_labels.data_ptr()) if G else (None, None)
+    a.B, a.R, a.D, a.G, a.Dg, a.S, a.fg_max, a.cls_mode = B, R, D, G, Dg, S, fg_max, _lib.ROI_CLS_MODES[cls_mode]
+    a.seed = int(seed) & 0xFFFFFFFF
+    a.fg_thr, a.bg_lo, a.hard_ratio, a.reg_fg_thr, a.cls_fg_thr, a.cls_bg_thr = fg_thr, bg_lo, hard_ratio, reg_fg_thr, cls_fg_thr, cls_bg_thr
+    for n, t in zip(ROI_OUTPUTS, outs):
+        setattr(a, n, t.data_ptr())
+    a.workspace = workspace.data_ptr()
+    with _timed("roi_targets", f"R{R}G{G}S{S}"):
+        check(lib().sad_roi_targets_f32(ctypes.byref(a), _stream()), "sad_roi_targets_f32")
+    return outs
+
+
+def roi_decode(rois: torch.Tensor, reg: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The inverse of ``roi_targets``' residual code (SPEC.md §28.2), what a RoI head runs at inference: rois [B,S,D>=7] f32,
+    reg [B,S,7] f32 -> boxes [B,S,7]: the residuals scaled by the RoI's diagonal and height, rotated out of the RoI's frame and
+    moved to its centre, exp of the size residuals times the RoI's extents, yaw = reg6 + the RoI's.  One launch."""
+    _strict(rois, "rois", torch.float32, (None, None, None), "[B,S,D] with B, S >= 1 and D >= 7")
+    B, S, D = rois.shape
+    if B < 1 or S < 1 or D < 7:
+        raise ValueError(f"rois: expected [B,S,D] with B, S >= 1 and D >= 7, got {tuple(rois.shape)}")
+    _strict(reg, "reg", torch.float32, (B, S, 7))
+    dev = _head_devices((("rois", rois), ("reg", reg)))
+    boxes, = _outputs((("boxes", (B, S, 7), torch.float32),), None if out is None else (out,), dev, "rois")
+    with _timed("roi_decode", f"R{B * S}"):
+        check(lib().sad_roi_decode_f32(rois.data_ptr(), D, reg.data_ptr(), B, S, boxes.data_ptr(), _stream()), "sad_roi_decode_f32")
+    return boxes
+
+
 def _weights(v, n: int, name: str) -> list:
     a = np.ones(n, np.float32) if v is None else np.asarray(v, dtype=np.float32).reshape(-1)
     if a.shape[0] != n:

@@ -736,6 +736,48 @@ typedef struct sad_center_head_loss_args {
 size_t sad_center_head_loss_workspace_bytes(int B, int H, int W, int G);   /* 4*B*(ceil(H*W/256) + ceil(G/256)); 0 outside the limits */
 int sad_center_head_loss_f32(const sad_center_head_loss_args *args, sad_stream_t stream);
 
+/* SPEC.md §28.  RoI head: which of the nms_boxes survivors a second stage trains on, their matched ground truth in the
+ * RoI's frame, and the residual code with its inverse.  Box rows and padded ground truth as in §19 / §26 (a negative
+ * label marks a padding row, 0 <= G <= 1024, G == 0 with NULL pointers).  No gradients.  Outputs are fully written by
+ * the call.  A fixed sequence of launches whose dimensions depend on the shapes only; nothing is read back, nothing
+ * synchronises, no float atomics: two calls are bit-equal.  NaN in an input or |yaw| >= 1e4 is undefined behaviour. */
+#define SAD_ROI_CLS_ROI_IOU 0
+#define SAD_ROI_CLS_CLS 1
+
+/* §28.1 proposal sampling and targets.  rois[B,R,D] (D >= 7); roi_count[B] or NULL (the candidates of scene b are rows
+ * r < clamp(roi_count[b], 0, R), rows beyond are never read); roi_labels[B,R] or NULL (not NULL: a RoI is matched against
+ * the boxes of its own class only).  m(r) = the largest §19.3 3-D IoU over the eligible boxes, j(r) = the lowest box that
+ * attains it (-1 without one).  fg: m >= fg_thr; hard: bg_lo <= m < fg_thr; easy: m < bg_lo.  Of the S slots the first
+ * min(fg_max, n_fg, S) hold the fg candidates with the smallest (h(b, r), r), the others draw with replacement from hard
+ * (floor((S - nf) * hard_ratio) of them, at most n_hard) and easy by h(b, 0x80000000 + i) mod the class count, h = the hash
+ * of sad_subsample_pad_f32 under `seed`.  Per slot: index (the RoI's row), match (j), labels, iou (m), cls_target (1 above
+ * cls_fg_thr, 0 below cls_bg_thr, between them (m - cls_bg_thr) / (cls_fg_thr - cls_bg_thr) or, SAD_ROI_CLS_CLS, -1),
+ * reg_valid (j >= 0 and m > reg_fg_thr), rois_s[.,7], gt_local[.,7] (the box in the RoI's frame, heading in [-pi/2, pi/2])
+ * and reg_target[.,7] (residuals against the RoI's extents); a scene without candidates gives (-1, -1, -1, 0, -1, 0, 0...).
+ * 1 <= B <= 65535, 1 <= R <= 4096, 1 <= S <= 1024 (SAD_EUNSUPPORTED above); need 0 <= bg_lo <= fg_thr, fg_thr > 0,
+ * cls_bg_thr < cls_fg_thr, 0 <= hard_ratio <= 1, fg_max >= 0 (SAD_EINVAL).  workspace: sad_roi_targets_workspace_bytes(B, R)
+ * bytes ((m, j) per RoI), contents irrelevant. */
+typedef struct sad_roi_targets_args {
+    size_t struct_size;   /* = sizeof(sad_roi_targets_args) */
+    const float *rois;
+    const int32_t *roi_count, *roi_labels;
+    const float *gt_boxes;
+    const int32_t *gt_labels;
+    int B, R, D, G, Dg, S, fg_max, cls_mode;
+    unsigned seed;
+    float fg_thr, bg_lo, hard_ratio, reg_fg_thr, cls_fg_thr, cls_bg_thr;
+    int32_t *index, *match, *labels;   /* [B,S] */
+    float *iou, *cls_target;           /* [B,S] */
+    int32_t *reg_valid;                /* [B,S] */
+    float *rois_s, *gt_local, *reg_target; /* [B,S,7] */
+    void *workspace;
+} sad_roi_targets_args;
+size_t sad_roi_targets_workspace_bytes(int B, int R);   /* 8*B*R; 0 outside 1 <= B <= 65535, 1 <= R <= 4096 */
+int sad_roi_targets_f32(const sad_roi_targets_args *args, sad_stream_t stream);
+
+/* §28.2 the inverse of §28.1's code: rois[B,S,D] (D >= 7), reg[B,S,7] -> boxes[B,S,7].  One launch.  B*S < 2^31. */
+int sad_roi_decode_f32(const float *rois, int D, const float *reg, int B, int S, float *boxes, sad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

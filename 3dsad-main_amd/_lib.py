@@ -165,6 +165,17 @@ class RoiTargetsArgs(ctypes.Structure):
     ]
 
 
+class RoiHeadLossArgs(ctypes.Structure):
+    """``struct sad_roi_head_loss_args`` (include/sad_amd.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("rcnn_cls", vp), ("rcnn_reg", vp), ("cls_target", vp), ("reg_valid", vp), ("reg_target", vp), ("rois", vp), ("gt_local", vp),
+        ("B", ctypes.c_int), ("S", ctypes.c_int), ("D", ctypes.c_int), ("normalize", ctypes.c_int),
+        ("beta", ctypes.c_float), ("code_weights", ctypes.c_float * 7), ("scale", ctypes.c_float * 3),
+        ("loss", vp), ("num", vp), ("grad_cls", vp), ("grad_reg", vp), ("grad_corner", vp), ("per_roi", vp),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/sad_amd.h declares
 SIGNATURES = {
     "sad_version": (ctypes.c_int, []),
@@ -273,6 +284,7 @@ SIGNATURES = {
     "sad_roi_targets_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "sad_roi_targets_f32": (ctypes.c_int, [ctypes.POINTER(RoiTargetsArgs), vp]),
     "sad_roi_decode_f32": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp]),
+    "sad_roi_head_loss_f32": (ctypes.c_int, [ctypes.POINTER(RoiHeadLossArgs), vp]),
 }
 
 _lib = None

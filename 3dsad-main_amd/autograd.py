@@ -404,3 +404,26 @@ class CenterHeadLoss(torch.autograd.Function):
         saved = ctx.saved_tensors
         grads = [_scaled(g, grad_loss[:, 0 if i == 0 else 1]) for i, g in enumerate(saved)]
         return (*grads, *([None] if len(grads) == 5 else []), None, None, None, None)
+
+
+class RoIHeadLoss(torch.autograd.Function):
+    """(rcnn_cls, rcnn_reg, cls_target, reg_valid, reg_target, rois | None, gt_local | None, cfg) -> loss [B,3], num [B,2]
+    (SPEC.md §29), differentiable in the two predictions.  The forward is ``ops.roi_head_loss``, which already produced the
+    gradient of every component: the backward returns ``grad_cls · g[:, 0]`` and ``grad_reg · g[:, 1] + grad_corner · g[:, 2]``
+    broadcast per scene (torch multiplies), and ``None`` for the targets.  ``cfg``: the operator's keywords."""
+
+    @staticmethod
+    def forward(ctx, rcnn_cls, rcnn_reg, cls_target, reg_valid, reg_target, rois, gt_local, cfg):
+        outs = ops.roi_head_loss(rcnn_cls, rcnn_reg, cls_target, reg_valid, reg_target, rois, gt_local, **cfg)
+        ctx.save_for_backward(*outs[2:5 if rois is not None else 4])
+        ctx.mark_non_differentiable(outs[1])
+        return outs[0], outs[1]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss, _grad_num):
+        saved = ctx.saved_tensors
+        greg = _scaled(saved[1], grad_loss[:, 1])
+        if len(saved) == 3:
+            greg = greg + _scaled(saved[2], grad_loss[:, 2])
+        return _scaled(saved[0], grad_loss[:, 0]), greg, None, None, None, None, None, None

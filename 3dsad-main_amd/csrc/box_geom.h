@@ -1,5 +1,5 @@
-// Rotated-box geometry of SPEC.md §13, shared by the NMS kernels (nms.hip) and the box operators (boxes.hip):
-// the reproducible sin/cos, the box corners and the Sutherland-Hodgman clipped area.  Binary32, no contraction
+// Rotated-box geometry of SPEC.md §13, shared by the NMS kernels (nms.hip), the box operators (boxes.hip) and the RoI head
+// (roi_head.hip, roi_loss.hip): the reproducible sin/cos, the box corners, the Sutherland-Hodgman clipped area and the RoI's local anchor.  Binary32, no contraction
 // (the library is built with -ffp-contract=off), so the CPU oracle and every kernel agree bit for bit.
 #pragma once
 #include "common.h"
@@ -42,6 +42,17 @@ __device__ __forceinline__ void box_corners(const float *bx, float *cx, float *c
         t = bx[1] + a;
         cy[k] = t + b;
     }
+}
+
+// §28.1 the local anchor of a RoI: clamped extents and the diagonal
+struct RoiAnchor { float la, wa, ha, dg; };
+__device__ __forceinline__ RoiAnchor roi_anchor(const float *roi) {
+    RoiAnchor a;
+    a.la = fmaxf(roi[3], 1e-5f);
+    a.wa = fmaxf(roi[4], 1e-5f);
+    a.ha = fmaxf(roi[5], 1e-5f);
+    a.dg = sqrtf((a.la * a.la) + (a.wa * a.wa));
+    return a;
 }
 
 // area of (polygon a) ∩ (convex quad b); corners counter-clockwise; vertex lists live in LDS

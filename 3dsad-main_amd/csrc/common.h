@@ -324,3 +324,10 @@ __device__ __forceinline__ float d2f(float px, float py, float pz, float cx, flo
     do {                                                      \
         if (!(cond)) return sad::fail(SAD_EINVAL, __VA_ARGS__); \
     } while (0)
+
+// every argument block begins with struct_size: a caller built against another header is refused before a field is read
+template <class T> int args_ok(const char *fn, const T *a) {
+    SAD_REQUIRE(a, "%s: NULL args", fn);
+    SAD_REQUIRE(a->struct_size == sizeof(T), "%s: struct_size %zu, this library has %zu", fn, a->struct_size, sizeof(T));
+    return SAD_OK;
+}

@@ -53,34 +53,7 @@ struct FinP {
     float *loss;
 };
 
-// the sum of a workgroup: butterfly over the wave (every lane ends with the same bits: + is commutative), then the four wave sums
-// in order.  Every thread of the workgroup calls it; `red` has 4 floats.
-__device__ __forceinline__ float block_sum(float v, float *red) {
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v = v + __shfl_xor(v, off);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
-__device__ __forceinline__ int wave_count(int v) {
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-__device__ __forceinline__ float norm_weight(float scale, int n, int normalize) {
-    return normalize ? scale / (float)max(n, 1) : scale;
-}
-
-// §27.1 the sigmoid and its complement
-__device__ __forceinline__ void sigmoid2(float x, float e, float &p, float &pc) {
-    const float den = 1.0f + e;
-    const float big = 1.0f / den, small = e / den;
-    p = x >= 0.0f ? big : small;
-    pc = x >= 0.0f ? small : big;
-}
+// (block_sum, wave_count, norm_weight and sigmoid2: prims.h, shared with roi_loss.hip)
 
 __global__ __launch_bounds__(DENSE_THREADS) void anchor_count_kernel(const int32_t *labels, int K, int32_t *num_pos) {
     const int b = blockIdx.y;

@@ -106,11 +106,7 @@ __device__ __forceinline__ void residual_encode(const Anchor &an, const float *r
 inline float dir_period(int nb) { return nb ? (float)(6.283185307179586476925286766559 / (double)nb) : 0.0f; }
 
 // ---- host checks ---------------------------------------------------------------------------------------------------------------
-template <class T> int args_ok(const char *fn, const T *a) {
-    SAD_REQUIRE(a, "%s: NULL args", fn);
-    SAD_REQUIRE(a->struct_size == sizeof(T), "%s: struct_size %zu, this library has %zu", fn, a->struct_size, sizeof(T));
-    return SAD_OK;
-}
+// (args_ok, the struct_size check of every argument block: common.h)
 // Rows are numbered in int: H * W, K = H * W * A and B * K stay below 2^31 (centre head: A = 1).  B, H, W >= 1 and A <= 128 are checked
 // before: H * W < 2^62 is exact, and a product is multiplied further only once it is known to be below 2^31.  The caller words the refusal.
 inline bool rows_fit(int B, int H, int W, int A) {

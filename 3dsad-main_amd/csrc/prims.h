@@ -1,6 +1,6 @@
 // Device primitives that more than one translation unit needs: the vector types of the MFMA kernels, the cross-lane
-// (DPP / readlane) unsigned maxima of the samplers, the LDS-DMA load with its wait, the integer hash of SPEC.md §17 and the
-// float atomic max of the pooled outputs.  Included inside each file's anonymous namespace, like reg_common.h, vox_hash.h and dense_tile.h (which include it).
+// (DPP / readlane) unsigned maxima of the samplers, the LDS-DMA load with its wait, the integer hash of SPEC.md §17, the
+// float atomic max of the pooled outputs and the sums, counts, normaliser and sigmoid pair of the loss kernels (§27, §29).  Included inside each file's anonymous namespace, like reg_common.h, vox_hash.h and dense_tile.h (which include it).
 // ONE definition of each: a helper moves here when a second family needs it; a helper with a single user stays in that file,
 // and what only one family shares lives in that family's header (the dense heads' tile-image copies: dense_tile.h).
 #pragma once
@@ -120,4 +120,35 @@ __device__ __forceinline__ unsigned h17(unsigned seed, unsigned b, unsigned i) {
 // bit patterns read as unsigned integers, and 0 is the neutral element.  A negative value or -0 would win every comparison.
 __device__ __forceinline__ void atomic_max_pos(float *addr, float v) {
     atomicMax(reinterpret_cast<unsigned *>(addr), __builtin_bit_cast(unsigned, v));
+}
+
+// ---- the loss kernels (dense_loss.hip §27, roi_loss.hip §29) -----------------------------------------------------------------
+// the sum of a workgroup of 256 threads: butterfly over the wave (every lane ends with the same bits: + is commutative), then the
+// four wave sums in order.  Every thread of the workgroup calls it; `red` has 4 floats.
+__device__ __forceinline__ float block_sum(float v, float *red) {
+#pragma unroll
+    for (int off = 32; off; off >>= 1) v = v + __shfl_xor(v, off);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+__device__ __forceinline__ int wave_count(int v) {
+#pragma unroll
+    for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// §27 the weight of a component: scale / (float)max(n, 1), or scale
+__device__ __forceinline__ float norm_weight(float scale, int n, int normalize) {
+    return normalize ? scale / (float)max(n, 1) : scale;
+}
+
+// §27.1 the sigmoid and its complement
+__device__ __forceinline__ void sigmoid2(float x, float e, float &p, float &pc) {
+    const float den = 1.0f + e;
+    const float big = 1.0f / den, small = e / den;
+    p = x >= 0.0f ? big : small;
+    pc = x >= 0.0f ? small : big;
 }

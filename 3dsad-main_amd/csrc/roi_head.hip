@@ -153,16 +153,7 @@ __device__ __forceinline__ float local_heading(float gyaw, float rr) {
     return fminf(fmaxf(o, -HALF_PI_F), HALF_PI_F);
 }
 
-// the local anchor of a RoI: clamped extents and the diagonal
-struct RoiAnchor { float la, wa, ha, dg; };
-__device__ __forceinline__ RoiAnchor roi_anchor(const float *roi) {
-    RoiAnchor a;
-    a.la = fmaxf(roi[3], 1e-5f);
-    a.wa = fmaxf(roi[4], 1e-5f);
-    a.ha = fmaxf(roi[5], 1e-5f);
-    a.dg = sqrtf((a.la * a.la) + (a.wa * a.wa));
-    return a;
-}
+// (roi_anchor, the local anchor of a RoI: box_geom.h, shared with roi_loss.hip)
 
 __global__ __launch_bounds__(P2_THREADS) void roi_sample_kernel(const RoiP p) {
     __shared__ u64 keys[ROI_MAXR];                      // the fg keys, sorted (32 KB)
@@ -309,12 +300,6 @@ __global__ __launch_bounds__(256) void roi_decode_kernel(const float *__restrict
     o[6] = t[6] + roi[6];
 }
 
-template <class T> int roi_args_ok(const char *fn, const T *a) {
-    SAD_REQUIRE(a, "%s: NULL args", fn);
-    SAD_REQUIRE(a->struct_size == sizeof(T), "%s: struct_size %zu, this library has %zu", fn, a->struct_size, sizeof(T));
-    return SAD_OK;
-}
-
 }  // namespace
 
 SAD_API size_t sad_roi_targets_workspace_bytes(int B, int R) {
@@ -324,7 +309,7 @@ SAD_API size_t sad_roi_targets_workspace_bytes(int B, int R) {
 
 SAD_API int sad_roi_targets_f32(const sad_roi_targets_args *a, sad_stream_t stream) {
     const char *fn = "sad_roi_targets_f32";
-    if (int rc = roi_args_ok(fn, a)) return rc;
+    if (int rc = args_ok(fn, a)) return rc;
     SAD_REQUIRE(a->rois && a->index && a->match && a->labels && a->iou && a->cls_target && a->reg_valid && a->rois_s && a->gt_local &&
                     a->reg_target, "%s: NULL pointer", fn);
     SAD_REQUIRE(a->B >= 1 && a->R >= 1 && a->S >= 1 && a->G >= 0, "%s: need B, R, S >= 1 and G >= 0 (got %d, %d, %d, %d)", fn, a->B, a->R,

@@ -1685,6 +1685,68 @@ def center_head_loss(hm: torch.Tensor, reg: torch.Tensor, height: torch.Tensor, 
     return outs
 
 
+def roi_loss_output_spec(B: int, S: int, corner: bool, per_roi: bool) -> tuple:
+    """((name, shape, dtype), ...) of ``roi_head_loss``' outputs, what its ``out=`` tuple is checked against."""
+    f32 = torch.float32
+    spec = [("loss", (B, 3), f32), ("num", (B, 2), torch.int32), ("grad_cls", (B, S), f32), ("grad_reg", (B, S, 7), f32)]
+    if corner:
+        spec.append(("grad_corner", (B, S, 7), f32))
+    if per_roi:
+        spec.append(("per_roi", (B, S, 3), f32))
+    return tuple(spec)
+
+
+def roi_head_loss(rcnn_cls: torch.Tensor, rcnn_reg: torch.Tensor, cls_target: torch.Tensor, reg_valid: torch.Tensor,
+                  reg_target: torch.Tensor, rois: Optional[torch.Tensor] = None, gt_local: Optional[torch.Tensor] = None, *,
+                  beta: float = 1.0 / 9.0, code_weights=None, scale=(1.0, 1.0, 1.0), normalize: bool = True, per_roi: bool = False,
+                  out: Optional[tuple] = None) -> tuple:
+    """RoI head losses with their gradients (SPEC.md §29).  rcnn_cls [B,S] f32 (one logit per RoI), rcnn_reg [B,S,7] f32, and the
+    targets ``roi_targets`` makes, read where they are: cls_target [B,S] f32 (-1: ignored), reg_valid [B,S] int32, reg_target
+    [B,S,7]; with rois [B,S,D>=7] (``rois_s``; only the extents are read) and gt_local [B,S,7] the corner loss is on (both or
+    neither) -> (loss [B,3] = (cls, reg, corner), num [B,2] int32 = (n_cls, n_reg), grad_cls [B,S], grad_reg [B,S,7]
+    [, grad_corner [B,S,7]][, per_roi [B,S,3]]): binary cross-entropy on the soft target over the rows with cls_target >= 0,
+    smooth-L1 over the rows with reg_valid != 0, and the replaced code bases' ``get_corner_loss_lidar`` on the decoded box over
+    the same rows, each scaled by ``scale[i] / max(n, 1)`` per scene (``normalize=False``: by ``scale[i]``).  grad_reg and
+    grad_corner are the gradients of loss[:, 1] and loss[:, 2] with respect to rcnn_reg.  One launch, no workspace, no
+    synchronisation, bit-identical from call to call.  ``out``: the tuple to write into."""
+    _strict(rcnn_cls, "rcnn_cls", torch.float32, (None, None), "[B,S] with 1 <= B <= 65535 and 1 <= S <= 1024")
+    B, S = rcnn_cls.shape
+    if not (1 <= B <= 65535 and 1 <= S <= 1024):
+        raise ValueError(f"rcnn_cls: expected [B,S] with 1 <= B <= 65535 and 1 <= S <= 1024, got {tuple(rcnn_cls.shape)}")
+    _strict(rcnn_reg, "rcnn_reg", torch.float32, (B, S, 7))
+    _strict(cls_target, "cls_target", torch.float32, (B, S))
+    _strict(reg_valid, "reg_valid", torch.int32, (B, S))
+    _strict(reg_target, "reg_target", torch.float32, (B, S, 7))
+    if (rois is None) != (gt_local is None):
+        raise ValueError("rois and gt_local must be given together (the corner component)")
+    corner, D = rois is not None, 0
+    if corner:
+        _strict(rois, "rois", torch.float32, (B, S, None), f"[B,S,D] with B = {B}, S = {S} and D >= 7")
+        D = rois.shape[2]
+        if D < 7:
+            raise ValueError(f"rois: expected [B,S,D] with B = {B}, S = {S} and D >= 7, got {tuple(rois.shape)}")
+        _strict(gt_local, "gt_local", torch.float32, (B, S, 7))
+    beta = _f32(beta)
+    if not beta > 0.0:
+        raise ValueError(f"beta: must be > 0, got {beta}")
+    cw, sc = _weights(code_weights, 7, "code_weights"), _weights(scale, 3, "scale")
+    dev = _head_devices((("rcnn_cls", rcnn_cls), ("rcnn_reg", rcnn_reg), ("cls_target", cls_target), ("reg_valid", reg_valid),
+                         ("reg_target", reg_target), ("rois", rois), ("gt_local", gt_local)))
+    outs = _outputs(roi_loss_output_spec(B, S, corner, bool(per_roi)), out, dev, "rcnn_cls")
+    a = _lib.RoiHeadLossArgs()
+    a.struct_size = ctypes.sizeof(_lib.RoiHeadLossArgs)
+    a.rcnn_cls, a.rcnn_reg, a.cls_target, a.reg_valid, a.reg_target = (t.data_ptr() for t in (rcnn_cls, rcnn_reg, cls_target, reg_valid, reg_target))
+    a.rois, a.gt_local = _ptr(rois), _ptr(gt_local)
+    a.B, a.S, a.D, a.normalize, a.beta = B, S, D, int(bool(normalize)), beta
+    a.code_weights[:], a.scale[:] = cw, sc
+    a.loss, a.num, a.grad_cls, a.grad_reg = (t.data_ptr() for t in outs[:4])
+    a.grad_corner = outs[4].data_ptr() if corner else None
+    a.per_roi = outs[-1].data_ptr() if per_roi else None
+    with _timed("roi_head_loss", f"S{S}"):
+        check(lib().sad_roi_head_loss_f32(ctypes.byref(a), _stream()), "sad_roi_head_loss_f32")
+    return outs
+
+
 # The fused MLP chains (PackedMLP / PackedMLPBf16, grouped_multi, rowscan_multi, the autotuner) live in mlp.py; they belong
 # to this operator surface, so their public names are re-exported here (the same objects).
 from .mlp import (GroupedCall, PackedMLP, PackedMLPBf16, check_workspace, choose_stage_assignment, cont_buffer,  # noqa: E402,F401

@@ -1,7 +1,8 @@
-"""RoI head (SPEC.md §28): which of the ``ops.nms_boxes`` survivors a second stage (PV-RCNN, Voxel R-CNN, Part-A2, PointRCNN)
-trains on, their matched ground truth in the RoI's frame with the residual code, and the decode of that code at inference.
-``ProposalTargetLayer`` holds the sampling configuration only and has no parameters; the pooling and the head's layers are
-the caller's.  No gradients pass through it: its outputs are targets."""
+"""RoI head (SPEC.md §28, §29): which of the ``ops.nms_boxes`` survivors a second stage (PV-RCNN, Voxel R-CNN, Part-A2, PointRCNN)
+trains on, their matched ground truth in the RoI's frame with the residual code, the decode of that code at inference, and
+the loss on those targets.  ``ProposalTargetLayer`` holds the sampling configuration only and has no parameters; the pooling
+and the head's layers are the caller's.  No gradients pass through it: its outputs are targets.  ``RoIHeadLoss`` is the loss
+of the head's two predictions against them, differentiable in the predictions."""
 from collections import namedtuple
 from typing import Optional
 
@@ -53,3 +54,36 @@ class ProposalTargetLayer(nn.Module):
     def decode(self, rois: torch.Tensor, reg: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``ops.roi_decode``: the head's residuals on their RoIs -> boxes [B,S,7]."""
         return ops.roi_decode(rois, reg, out)
+
+    def loss(self, **cfg) -> "RoIHeadLoss":
+        """The loss module on this layer's targets: ``RoIHeadLoss(**cfg)``."""
+        return RoIHeadLoss(**cfg)
+
+
+class RoIHeadLoss(nn.Module):
+    """Losses of a RoI head (``ops.roi_head_loss``, SPEC.md §29): the configuration only, no parameters.  ``cls_weight``,
+    ``reg_weight`` and ``corner_weight`` are the replaced code bases' ``LOSS_WEIGHTS`` (the operator's ``scale``);
+    ``corner=False`` leaves the corner loss out.  ``forward(rcnn_cls, rcnn_reg, targets) -> loss [B,3]`` (classification,
+    regression, corner), each already divided by the scene's own count, differentiable in the two predictions; ``targets`` is the
+    ``RoiTargets`` of ``ProposalTargetLayer``, read where it is.  rcnn_cls may come as [B,S], [B,S,1] or [B*S,1], rcnn_reg as
+    [B,S,7] or [B*S,7]: contiguous views, never copied.  The module keeps ``num`` [B,2] int32 = (n_cls, n_reg) of its LAST call
+    as an attribute (``None`` before the first), for logging."""
+
+    def __init__(self, beta: float = 1.0 / 9.0, code_weights=None, cls_weight: float = 1.0, reg_weight: float = 1.0,
+                 corner_weight: float = 1.0, corner: bool = True, normalize: bool = True):
+        super().__init__()
+        self.cfg = dict(beta=float(beta), code_weights=None if code_weights is None else [float(v) for v in code_weights],
+                        scale=(float(cls_weight), float(reg_weight), float(corner_weight)), normalize=bool(normalize))
+        self.corner = bool(corner)
+        self.num = None
+
+    def forward(self, rcnn_cls: torch.Tensor, rcnn_reg: torch.Tensor, targets: RoiTargets) -> torch.Tensor:
+        from .autograd import RoIHeadLoss as _Fn
+        B, S = targets.cls_target.shape
+        if rcnn_cls.numel() != B * S or rcnn_reg.numel() != B * S * 7 or not rcnn_cls.is_contiguous() or not rcnn_reg.is_contiguous():
+            raise ValueError(f"rcnn_cls / rcnn_reg: expected contiguous predictions for {B} x {S} RoIs ([B,S], [B,S,1] or [B*S,1]; "
+                             f"[B,S,7] or [B*S,7]), got {tuple(rcnn_cls.shape)} and {tuple(rcnn_reg.shape)}")
+        rois, gt_local = (targets.rois_s, targets.gt_local) if self.corner else (None, None)
+        loss, self.num = _Fn.apply(rcnn_cls.view(B, S), rcnn_reg.view(B, S, 7), targets.cls_target, targets.reg_valid,
+                                   targets.reg_target, rois, gt_local, self.cfg)
+        return loss

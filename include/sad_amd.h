@@ -778,6 +778,40 @@ int sad_roi_targets_f32(const sad_roi_targets_args *args, sad_stream_t stream);
 /* §28.2 the inverse of §28.1's code: rois[B,S,D] (D >= 7), reg[B,S,7] -> boxes[B,S,7].  One launch.  B*S < 2^31. */
 int sad_roi_decode_f32(const float *rois, int D, const float *reg, int B, int S, float *boxes, sad_stream_t stream);
 
+/* SPEC.md §29.  RoI head loss on §28.1's targets, read where they are, with the gradient with respect to both predictions:
+ * binary cross-entropy of the logit rcnn_cls against the soft target cls_target over the rows with cls_target >= 0 (-1: the
+ * ignored band and the empty slot), smooth-L1 of rcnn_reg against reg_target and, with rois and gt_local (both or neither),
+ * the corner loss of the decoded box against gt_local in the RoI's frame, both over the rows with reg_valid != 0.
+ * num[B,2] = (n_cls, n_reg); component i is weighted scale[i] / (float)max(n, 1) (n = n_cls for i = 0, n_reg for i = 1, 2)
+ * or, normalize == 0, scale[i]: the normaliser is per scene.  rois[B,S,D] (D >= 7): columns 3..5 are read at row stride D.
+ * grad_corner is given iff the corner component is on (without it loss[.,2] = 0); per_roi[B,S,3] may be NULL.  What
+ * reg_target, gt_local or rois hold in a row with reg_valid == 0 never reaches a result.  One launch, one workgroup per scene,
+ * no workspace, no memset, no atomics; outputs are fully written; nothing is read back, nothing synchronises; two calls are
+ * bit-equal.  |rcnn_reg[.,6]| >= 1e4 is undefined behaviour.  1 <= B <= 65535, 1 <= S <= 1024 (SAD_EUNSUPPORTED above); a
+ * NULL required pointer, a wrong struct_size, a size below 1, D < 7, beta <= 0 or NaN, rois without gt_local or the reverse,
+ * grad_corner given or missing against them: SAD_EINVAL. */
+typedef struct sad_roi_head_loss_args {
+    size_t struct_size;   /* = sizeof(sad_roi_head_loss_args) */
+    const float *rcnn_cls;         /* [B,S] */
+    const float *rcnn_reg;         /* [B,S,7] */
+    const float *cls_target;       /* [B,S] */
+    const int32_t *reg_valid;      /* [B,S] */
+    const float *reg_target;       /* [B,S,7] */
+    const float *rois;             /* [B,S,D] or NULL */
+    const float *gt_local;         /* [B,S,7] or NULL */
+    int B, S, D, normalize;
+    float beta;
+    float code_weights[7];
+    float scale[3];       /* cls, reg, corner */
+    float *loss;          /* [B,3] */
+    int32_t *num;         /* [B,2] */
+    float *grad_cls;      /* [B,S] */
+    float *grad_reg;      /* [B,S,7] */
+    float *grad_corner;   /* [B,S,7] or NULL */
+    float *per_roi;       /* [B,S,3] or NULL */
+} sad_roi_head_loss_args;
+int sad_roi_head_loss_f32(const sad_roi_head_loss_args *args, sad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,7 @@ _LAZY = {
     "AnchorHeadLoss": "dense_head", "CenterHeadLoss": "dense_head",
     "roi_targets": "ops", "roi_targets_workspace": "ops", "roi_decode": "ops", "ProposalTargetLayer": "roi_head",
     "roi_head_loss": "ops", "RoIHeadLoss": "roi_head",
+    "roi_grid_points": "ops", "voxel_query": "ops", "voxel_query_workspace": "ops", "VoxelRoIPool": "voxel_roi_pool",
     "Voxelization": "voxel", "DynamicScatter": "voxel", "PillarFeatureNet": "voxel",
     "sparse_conv_index": "ops", "sparse_conv": "ops", "sparse_to_dense": "ops", "PackedSparseWeight": "ops",
     "sparse_conv_index_transpose": "ops", "sparse_conv_grad_weight": "ops", "sparse_conv_grad_input": "ops",

@@ -176,6 +176,28 @@ class RoiHeadLossArgs(ctypes.Structure):
     ]
 
 
+class RoiGridPointsArgs(ctypes.Structure):
+    """``struct sad_roi_grid_points_args`` (include/sad_amd.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("rois", vp), ("roi_count", vp),
+        ("B", ctypes.c_int), ("R", ctypes.c_int), ("D", ctypes.c_int), ("G", ctypes.c_int),
+        ("pts", vp),
+    ]
+
+
+class VoxelQueryArgs(ctypes.Structure):
+    """``struct sad_voxel_query_args`` (include/sad_amd.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("coors", vp), ("offsets", vp), ("new_xyz", vp),
+        ("Nv", ctypes.c_int), ("B", ctypes.c_int), ("M", ctypes.c_int), ("S", ctypes.c_int),
+        ("spatial_shape", ctypes.c_int * 3), ("max_range", ctypes.c_int * 3),
+        ("voxel_size", ctypes.c_float * 3), ("lo", ctypes.c_float * 3), ("radius", ctypes.c_float),
+        ("idx", vp), ("cnt", vp), ("workspace", vp),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/sad_amd.h declares
 SIGNATURES = {
     "sad_version": (ctypes.c_int, []),
@@ -285,6 +307,9 @@ SIGNATURES = {
     "sad_roi_targets_f32": (ctypes.c_int, [ctypes.POINTER(RoiTargetsArgs), vp]),
     "sad_roi_decode_f32": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp]),
     "sad_roi_head_loss_f32": (ctypes.c_int, [ctypes.POINTER(RoiHeadLossArgs), vp]),
+    "sad_roi_grid_points_f32": (ctypes.c_int, [ctypes.POINTER(RoiGridPointsArgs), vp]),
+    "sad_voxel_query_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "sad_voxel_query_f32": (ctypes.c_int, [ctypes.POINTER(VoxelQueryArgs), vp]),
 }
 
 _lib = None

@@ -40,16 +40,7 @@ __device__ __forceinline__ void kk_split(int kk, const SpGeo &g, int *k) {
 }
 
 // ---- rulebook ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(VX_THREADS) void sp_init_kernel(CoordTable t) { t.clear(); }
-
-__global__ __launch_bounds__(VX_THREADS) void sp_insert_kernel(const int32_t *__restrict__ coors, const int32_t *__restrict__ offsets, int Nv, int B,
-                                                               SpGeo g, CoordTable t) {
-    const int i = blockIdx.x * VX_THREADS + threadIdx.x;
-    if (i >= Nv) return;
-    const int32_t *c = coors + (size_t)i * 3;
-    const int key = (c[0] * g.G[1] + c[1]) * g.G[2] + c[2];
-    t.insert_min(((u64)(unsigned)scene_of(offsets, B, i) << 32) | (unsigned)key, i);
-}
+// (the input table, the rows under (scene << 32 | cell): launch_coord_rows of vox_hash.h)
 
 // nbr[o, kk] = lowest input row of o's scene at out_coors[o] * s - p + k, or -1.  Rows at and above the true total
 // (out_offsets[B]; a fill with spare capacity) get nbr -1 and coordinates -1.
@@ -433,16 +424,6 @@ SpWs sp_ws(void *ws, int Nv, const SpGeo &g, int subm) {
     return w;
 }
 
-inline void launch_table_init(const CoordTable &t, hipStream_t st) {
-    hipLaunchKernelGGL(sp_init_kernel, dim3(std::min(blocks_for(t.mask + 1ull, VX_THREADS), 16384u)), dim3(VX_THREADS), 0, st, t);
-}
-
-inline void launch_input_table(const int32_t *coors, const int32_t *offsets, int Nv, int B, const SpGeo &g, const SpWs &w, hipStream_t st) {
-    launch_table_init(w.in, st);
-    if (Nv > 0)
-        hipLaunchKernelGGL(sp_insert_kernel, dim3(blocks_for((unsigned long long)Nv, VX_THREADS)), dim3(VX_THREADS), 0, st, coors, offsets, Nv, B, g, w.in);
-}
-
 template <int WR, int RS, int NT>
 int launch_conv(const ConvJob &jb, hipStream_t st) {
     constexpr int TR = 32 * WR * RS;
@@ -485,7 +466,7 @@ SAD_API int sad_spconv_index_subm(const int32_t *coors, const int32_t *offsets, 
     if (Nv == 0) return SAD_OK;
     const SpWs w = sp_ws(workspace, Nv, g, 1);
     const hipStream_t st = (hipStream_t)stream;
-    launch_input_table(coors, offsets, Nv, B, g, w, st);
+    launch_coord_rows(coors, offsets, Nv, B, g.G[1], g.G[2], w.in, st);
     hipLaunchKernelGGL(sp_nbr_kernel, dim3(blocks_for((unsigned long long)Nv * g.Kvol, VX_THREADS)), dim3(VX_THREADS), 0, st, (int32_t *)coors, offsets, Nv,
                        B, g, w.in, 0, nbr);
     return sad::check_launch("sad_spconv_index_subm");
@@ -503,8 +484,8 @@ SAD_API int sad_spconv_index_count(const int32_t *coors, const int32_t *offsets,
     const int NC = Nv * g.Kvol, nw = (NC + 63) / 64;
     const CandOpener op = {coors, offsets, NC, B, g, w.sites};
     const dim3 gc(blocks_for((unsigned long long)NC, VX_THREADS)), tb(VX_THREADS);
-    launch_input_table(coors, offsets, Nv, B, g, w, st);
-    launch_table_init(w.sites, st);
+    launch_coord_rows(coors, offsets, Nv, B, g.G[1], g.G[2], w.in, st);
+    launch_coord_clear(w.sites, st);
     if (NC > 0) {
         hipLaunchKernelGGL(sp_cand_insert_kernel, gc, tb, 0, st, op);
         hipLaunchKernelGGL(opener_flags_kernel<CandOpener>, gc, tb, 0, st, op, w.wavecnt);

@@ -12,6 +12,7 @@
 //            bool operator()(e), is e an opener (false for e >= n); index first_of(row), the first element of input row `row`
 //            (offsets[b] goes in; clamped to 0 .. n).
 // scans      exclusive scans over the 1024 threads of a workgroup, and of an int array in place by one workgroup.
+// rows       the table of a sparse tensor's rows (§21): clear + insert, with their launches.
 #pragma once
 #include "prims.h"       // u64
 
@@ -101,6 +102,32 @@ struct CoordTable {
     // the lowest number inserted under the key of `slot` (a table nobody writes any more)
     __device__ __forceinline__ int lowest(int slot) const { return vals[slot]; }
 };
+
+// ---- the table of a sparse tensor's rows (§21) --------------------------------------------------------------------
+// every slot empty; then row i of coors [Nv,3] (z,y,x) goes in under (its scene << 32 | (z * Gy + y) * Gx + x): the lowest row
+// owns a duplicated coordinate.  The rulebook (spconv.hip) and the voxel query (voxel_query.hip) build their input table this way.
+__global__ __launch_bounds__(VX_THREADS) void coord_clear_kernel(CoordTable t) { t.clear(); }
+
+__global__ __launch_bounds__(VX_THREADS) void coord_insert_rows_kernel(const int32_t *__restrict__ coors, const int32_t *__restrict__ offsets, int Nv,
+                                                                       int B, int Gy, int Gx, CoordTable t) {
+    const int i = blockIdx.x * VX_THREADS + threadIdx.x;
+    if (i >= Nv) return;
+    const int32_t *c = coors + (size_t)i * 3;
+    const int key = (c[0] * Gy + c[1]) * Gx + c[2];
+    t.insert_min(((u64)(unsigned)scene_of(offsets, B, i) << 32) | (unsigned)key, i);
+}
+
+inline void launch_coord_clear(const CoordTable &t, hipStream_t st) {
+    const unsigned long long slots = t.mask + 1ull;
+    hipLaunchKernelGGL(coord_clear_kernel, dim3(slots > 16384ull * VX_THREADS ? 16384u : sad::blocks_for(slots, VX_THREADS)), dim3(VX_THREADS), 0, st, t);
+}
+
+inline void launch_coord_rows(const int32_t *coors, const int32_t *offsets, int Nv, int B, int Gy, int Gx, const CoordTable &t, hipStream_t st) {
+    launch_coord_clear(t, st);
+    if (Nv > 0)
+        hipLaunchKernelGGL(coord_insert_rows_kernel, dim3(sad::blocks_for((unsigned long long)Nv, VX_THREADS)), dim3(VX_THREADS), 0, st, coors, offsets, Nv,
+                           B, Gy, Gx, t);
+}
 
 __device__ __forceinline__ int wave_incl_scan(int x, int lane) {
 #pragma unroll

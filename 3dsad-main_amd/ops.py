@@ -1747,6 +1747,88 @@ def roi_head_loss(rcnn_cls: torch.Tensor, rcnn_reg: torch.Tensor, cls_target: to
     return outs
 
 
+def roi_grid_points(rois: torch.Tensor, roi_count: Optional[torch.Tensor], grid_size: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The grid points of every RoI (SPEC.md §30): rois [B,R,D>=7] f32 rows (cx,cy,cz,l,w,h,yaw,...), roi_count [B] int32 or
+    ``None`` (as in ``roi_targets``: the rows beyond it are never read) -> pts [B,R,G^3,3] with G = ``grid_size`` (1 .. 16): point
+    g = (ix*G + iy)*G + iz sits at ((i + 0.5) / G - 0.5) * extent on each axis of the RoI's frame, rotated by its yaw and moved to
+    its centre.  The points of a row beyond ``roi_count`` are NaN, which ``voxel_query`` answers with an empty neighbourhood, so the
+    output of ``nms_boxes`` is pooled with nothing synchronised in between.  One launch."""
+    _strict(rois, "rois", torch.float32, (None, None, None), "[B,R,D] with B, R >= 1 and D >= 7")
+    B, R, D = rois.shape
+    if B < 1 or R < 1 or D < 7:
+        raise ValueError(f"rois: expected [B,R,D] with B, R >= 1 and D >= 7, got {tuple(rois.shape)}")
+    if roi_count is not None:
+        _strict(roi_count, "roi_count", torch.int32, (B,))
+    G = int(grid_size)
+    if not 1 <= G <= 16:
+        raise ValueError(f"grid_size: expected 1 .. 16, got {G}")
+    if B > 65535 or B * R * G ** 3 >= 2 ** 31:
+        raise ValueError(f"rois: B <= 65535 and B * R * G^3 < 2^31 supported (got B = {B}, R = {R}, G = {G})")
+    dev = _head_devices((("rois", rois), ("roi_count", roi_count)))
+    pts, = _outputs((("pts", (B, R, G ** 3, 3), torch.float32),), None if out is None else (out,), dev, "rois")
+    a = _lib.RoiGridPointsArgs()
+    a.struct_size = ctypes.sizeof(_lib.RoiGridPointsArgs)
+    a.rois, a.roi_count, a.pts = rois.data_ptr(), _ptr(roi_count), pts.data_ptr()
+    a.B, a.R, a.D, a.G = B, R, D, G
+    with _timed("roi_grid_points", f"R{B * R}G{G}"):
+        check(lib().sad_roi_grid_points_f32(ctypes.byref(a), _stream()), "sad_roi_grid_points_f32")
+    return pts
+
+
+def voxel_query_workspace(Nv: int, device) -> torch.Tensor:
+    """The workspace of ``voxel_query(..., workspace=...)`` (the coordinate table of ``Nv`` voxels) for a caller that keeps it."""
+    nbytes = lib().sad_voxel_query_workspace_bytes(int(Nv))
+    if not nbytes:
+        raise ValueError(f"voxel_query_workspace: need 0 <= Nv <= 2^30 (got {Nv})")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def voxel_query(coors: torch.Tensor, offsets: torch.Tensor, spatial_shape, voxel_size, point_range, new_xyz: torch.Tensor, *,
+                max_range, radius: float, S: int, out: Optional[tuple] = None, workspace: Optional[torch.Tensor] = None) -> tuple:
+    """The non-empty voxels around every query point, in walk order (SPEC.md §30).  coors [Nv,3] int32 (z,y,x), offsets [B+1] int32
+    and ``spatial_shape`` (Gz,Gy,Gx): a sparse tensor of §21; ``voxel_size`` (vx,vy,vz): the size of a voxel AT THAT SCALE (base
+    size x stride); ``point_range`` (x0,y0,z0,x1,y1,z1), of which the low corner is read; new_xyz [B,M,3] f32 ->
+    (idx [B,M,S] int32, cnt [B,M] int32).  The candidates of a query are the cells within ``max_range`` = (rz,ry,rx) cells of its
+    own, walked dz slowest and dx fastest; one counts if the query's scene holds a voxel there whose centre is closer than
+    ``radius`` (strict).  idx holds the GLOBAL rows (into Nv) of the first S in walk order, padded with the first; cnt =
+    min(accepted, S); a NaN / Inf query, and one with nothing in reach, gives cnt 0 and idx 0: what ``PackedMLP.grouped`` takes as
+    (idx, cnt) with the voxels as one scene.  Three launches, no synchronisation, no gradients, bit-identical from call to call."""
+    vs, pr = _voxel_grid(voxel_size, point_range)
+    G, _ = _int3(spatial_shape, "spatial_shape", 1)
+    if isinstance(max_range, (int, np.integer)):
+        raise ValueError("max_range: 3 ints (rz,ry,rx) expected")
+    rng, _ = _int3(max_range, "max_range", 0)
+    if max(rng) > 8:
+        raise ValueError(f"max_range: entries 0 .. 8 are implemented, got {rng}")
+    S, radius = int(S), _f32(radius)
+    if not 1 <= S <= 128:
+        raise ValueError(f"S: expected 1 .. 128, got {S}")
+    if not radius > 0.0:
+        raise ValueError(f"radius: must be > 0, got {radius}")
+    if G[0] * G[1] * G[2] > 2 ** 31 - 1:
+        raise ValueError(f"spatial_shape {G} exceeds 2^31 - 1 cells")
+    coors, offsets, B = _sparse_coors(coors, offsets)
+    new_xyz = _need(new_xyz, "new_xyz", torch.float32, 3)
+    if new_xyz.shape[0] != B or new_xyz.shape[2] != 3:
+        raise ValueError(f"new_xyz: expected [B,M,3] with B = {B}, got {tuple(new_xyz.shape)}")
+    if new_xyz.device != coors.device:
+        raise ValueError("new_xyz must be on the device of coors")
+    Nv, M, dev = coors.shape[0], new_xyz.shape[1], coors.device
+    if B > 65535 or B * M * S >= 2 ** 31 or Nv > 2 ** 30:
+        raise ValueError(f"voxel_query: B <= 65535, B * M * S < 2^31 and Nv <= 2^30 supported (got B = {B}, M = {M}, S = {S}, Nv = {Nv})")
+    idx, cnt = _outputs((("idx", (B, M, S), torch.int32), ("cnt", (B, M), torch.int32)), out, dev, "coors")
+    workspace = _workspace(lib().sad_voxel_query_workspace_bytes(Nv), workspace, dev, "ops.voxel_query_workspace", 16)
+    a = _lib.VoxelQueryArgs()
+    a.struct_size = ctypes.sizeof(_lib.VoxelQueryArgs)
+    a.coors, a.offsets, a.new_xyz = coors.data_ptr(), offsets.data_ptr(), new_xyz.data_ptr()
+    a.Nv, a.B, a.M, a.S = Nv, B, M, S
+    a.spatial_shape[:], a.max_range[:], a.voxel_size[:], a.lo[:], a.radius = G, rng, list(vs), list(pr)[:3], radius
+    a.idx, a.cnt, a.workspace = idx.data_ptr(), cnt.data_ptr(), workspace.data_ptr()
+    with _timed("voxel_query", f"n{Nv}m{B * M}s{S}"):
+        check(lib().sad_voxel_query_f32(ctypes.byref(a), _stream()), "sad_voxel_query_f32")
+    return idx, cnt
+
+
 # The fused MLP chains (PackedMLP / PackedMLPBf16, grouped_multi, rowscan_multi, the autotuner) live in mlp.py; they belong
 # to this operator surface, so their public names are re-exported here (the same objects).
 from .mlp import (GroupedCall, PackedMLP, PackedMLPBf16, check_workspace, choose_stage_assignment, cont_buffer,  # noqa: E402,F401

@@ -812,6 +812,51 @@ typedef struct sad_roi_head_loss_args {
 } sad_roi_head_loss_args;
 int sad_roi_head_loss_f32(const sad_roi_head_loss_args *args, sad_stream_t stream);
 
+/* SPEC.md §30.  Voxel RoI pooling, the index side: the grid points of the RoIs and the ordered voxel neighbourhood of every query
+ * point at one backbone scale.  No gradients.  Outputs are fully written by the call.  A fixed sequence of launches whose dimensions
+ * depend on the shapes only; nothing is read back, nothing synchronises, no atomics on an output: two calls are bit-equal. */
+
+/* rois[B,R,D] (D >= 7, rows (cx,cy,cz,l,w,h,yaw,...)), roi_count[B] or NULL (as §28.1: rows r >= clamp(roi_count[b], 0, R) are never
+ * read) -> pts[B,R,G^3,3]: grid point g = (ix*G + iy)*G + iz at ((i + 0.5) / G - 0.5) * extent per axis in the RoI's frame, rotated
+ * and moved as in §28.2; quiet NaN for the rows beyond roi_count (an empty query of sad_voxel_query_f32).  One launch.
+ * 1 <= G <= 16, B <= 65535, B*R*G^3 < 2^31 (SAD_EUNSUPPORTED above); a NULL required pointer, a wrong struct_size, a size below 1,
+ * D < 7: SAD_EINVAL. */
+typedef struct sad_roi_grid_points_args {
+    size_t struct_size;   /* = sizeof(sad_roi_grid_points_args) */
+    const float *rois;
+    const int32_t *roi_count;
+    int B, R, D, G;
+    float *pts;
+} sad_roi_grid_points_args;
+int sad_roi_grid_points_f32(const sad_roi_grid_points_args *args, sad_stream_t stream);
+
+/* coors[Nv,3] (z,y,x) / offsets[B+1] / spatial_shape (Gz,Gy,Gx): a §21 sparse tensor; voxel_size (vx,vy,vz): that scale's; lo
+ * (x0,y0,z0): the low corner of the point range; new_xyz[B,M,3] -> idx[B,M,S] (global rows in [0,Nv)), cnt[B,M].  The cell of a
+ * query is §20.1's; its candidates are the cells within max_range (rz,ry,rx) of it, walked dz slowest, dx fastest, ascending; a
+ * candidate counts if it is inside the grid, the query's scene holds a voxel there (the lowest row of a duplicated coordinate) and
+ * d2(voxel centre (§24), query) < radius^2, strict.  The first S fill idx in walk order, the rest repeat the first; cnt =
+ * min(accepted, S); a query whose cell is not finite or beyond 2^30 (NaN, Inf) is empty: cnt 0, idx 0.  Nv == 0 and M == 0 are valid
+ * (coors / new_xyz, idx, cnt may then be NULL).  workspace: sad_voxel_query_workspace_bytes(Nv) bytes (the coordinate table: a power of two >= 2 Nv
+ * slots, 8 + 4 bytes each), 16-byte aligned, contents irrelevant.  Three launches.
+ * 0 <= max_range <= 8, 1 <= S <= 128, B <= 65535, B*M*S < 2^31, Nv <= 2^30, Gz*Gy*Gx <= 2^31 - 1 (SAD_EUNSUPPORTED above); a NULL
+ * required pointer, a wrong struct_size, B or S below 1, a negative size or range, voxel_size <= 0, radius <= 0 or NaN: SAD_EINVAL. */
+typedef struct sad_voxel_query_args {
+    size_t struct_size;   /* = sizeof(sad_voxel_query_args) */
+    const int32_t *coors, *offsets;
+    const float *new_xyz;
+    int Nv, B, M, S;
+    int spatial_shape[3]; /* (Gz,Gy,Gx) */
+    int max_range[3];     /* (rz,ry,rx) */
+    float voxel_size[3];  /* (vx,vy,vz) */
+    float lo[3];          /* (x0,y0,z0) */
+    float radius;
+    int32_t *idx;         /* [B,M,S] */
+    int32_t *cnt;         /* [B,M] */
+    void *workspace;
+} sad_voxel_query_args;
+size_t sad_voxel_query_workspace_bytes(int Nv);   /* 0 outside 0 <= Nv <= 2^30 */
+int sad_voxel_query_f32(const sad_voxel_query_args *args, sad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -198,6 +198,33 @@ class VoxelQueryArgs(ctypes.Structure):
     ]
 
 
+POINT_CLS_LOSSES = {"bce": 0, "focal": 1}      # SAD_POINT_CLS_*
+
+
+class PointTargetsArgs(ctypes.Structure):
+    """``struct sad_point_targets_args`` (include/sad_amd.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("xyz", vp), ("cand", vp), ("gt_boxes", vp), ("gt_labels", vp),
+        ("B", ctypes.c_int), ("M", ctypes.c_int), ("G", ctypes.c_int), ("D", ctypes.c_int), ("C", ctypes.c_int),
+        ("anchors", ctypes.c_float * 48), ("size_anchor", ctypes.c_float * 3),
+        ("shift_max", ctypes.c_float), ("extra_width", ctypes.c_float),
+        ("labels", vp), ("match", vp), ("centerness", vp), ("shift_target", vp), ("size_target", vp), ("reg_target", vp),
+    ]
+
+
+class PointHeadLossArgs(ctypes.Structure):
+    """``struct sad_point_head_loss_args`` (include/sad_amd.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("o", vp), ("c", vp), ("labels", vp), ("centerness", vp), ("reg_target", vp), ("shift_target", vp), ("size_target", vp),
+        ("B", ctypes.c_int), ("M", ctypes.c_int), ("C", ctypes.c_int), ("cls_loss", ctypes.c_int), ("normalize", ctypes.c_int),
+        ("alpha", ctypes.c_float), ("beta", ctypes.c_float), ("shift_max", ctypes.c_float),
+        ("code_weights", ctypes.c_float * 7), ("scale", ctypes.c_float * 4),
+        ("loss", vp), ("num_pos", vp), ("grad_o", vp), ("grad_c", vp), ("per_point", vp), ("workspace", vp),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/sad_amd.h declares
 SIGNATURES = {
     "sad_version": (ctypes.c_int, []),
@@ -310,6 +337,9 @@ SIGNATURES = {
     "sad_roi_grid_points_f32": (ctypes.c_int, [ctypes.POINTER(RoiGridPointsArgs), vp]),
     "sad_voxel_query_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int]),
     "sad_voxel_query_f32": (ctypes.c_int, [ctypes.POINTER(VoxelQueryArgs), vp]),
+    "sad_point_targets_f32": (ctypes.c_int, [ctypes.POINTER(PointTargetsArgs), vp]),
+    "sad_point_head_loss_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "sad_point_head_loss_f32": (ctypes.c_int, [ctypes.POINTER(PointHeadLossArgs), vp]),
 }
 
 _lib = None

@@ -427,3 +427,30 @@ class RoIHeadLoss(torch.autograd.Function):
         if len(saved) == 3:
             greg = greg + _scaled(saved[2], grad_loss[:, 2])
         return _scaled(saved[0], grad_loss[:, 0]), greg, None, None, None, None, None, None
+
+
+class PointHeadLoss(torch.autograd.Function):
+    """(o, c | None, labels, centerness | None, reg_target, shift_target | None, size_target | None, cfg) -> loss [B,4], num_pos [B]
+    (SPEC.md §31.2), differentiable in o and c.  The forward is ``ops.point_head_loss``, which already produced the gradient of
+    every component: grad_o holds d loss[:, 0] in its first C columns and d loss[:, 1] in the last 7, grad_c d loss[:, 2] in
+    columns 0..2 and d loss[:, 3] in 3..5, so the backward scales them per scene and per component (torch multiplies) and
+    returns ``None`` for the targets.  ``cfg``: the operator's keywords."""
+
+    @staticmethod
+    def forward(ctx, o, c, labels, centerness, reg_target, shift_target, size_target, cfg):
+        outs = ops.point_head_loss(o, c, labels, centerness, reg_target, shift_target, size_target, **cfg)
+        ctx.save_for_backward(*outs[2:4 if c is not None else 3])
+        ctx.mark_non_differentiable(outs[1])
+        return outs[0], outs[1]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss, _grad_num):
+        saved = ctx.saved_tensors
+        C = saved[0].shape[2] - 7
+        w = torch.cat([grad_loss[:, 0:1].expand(-1, C), grad_loss[:, 1:2].expand(-1, 7)], 1)                # [B,C+7]
+        go = saved[0] * w.unsqueeze(1)
+        gc = None
+        if len(saved) == 2:
+            gc = saved[1] * torch.cat([grad_loss[:, 2:3].expand(-1, 3), grad_loss[:, 3:4].expand(-1, 3)], 1).unsqueeze(1)
+        return go, gc, None, None, None, None, None, None

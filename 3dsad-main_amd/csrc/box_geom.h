@@ -44,6 +44,17 @@ __device__ __forceinline__ void box_corners(const float *bx, float *cx, float *c
     }
 }
 
+// §19.1 inside(p, box, e) on the box's constants: centre, half extents of the enlarged box, cos, sin (boxes.hip, point_head.hip)
+__device__ __forceinline__ bool inside(float px, float py, float pz, float cx, float cy, float cz, float hl, float hw,
+                                       float hh, float c, float s) {
+    const float dx = px - cx, dy = py - cy, dz = pz - cz;
+    const float a = dx * c, b = dy * s;
+    const float lx = a + b;
+    const float a2 = dy * c, b2 = dx * s;
+    const float ly = a2 - b2;
+    return fabsf(dz) <= hh && fabsf(lx) < hl && fabsf(ly) < hw;
+}
+
 // §28.1 the local anchor of a RoI: clamped extents and the diagonal
 struct RoiAnchor { float la, wa, ha, dg; };
 __device__ __forceinline__ RoiAnchor roi_anchor(const float *roi) {

@@ -50,15 +50,7 @@ __device__ __forceinline__ BoxK box_consts(const float *bx, float e) {
     return k;
 }
 
-__device__ __forceinline__ bool inside(float px, float py, float pz, float cx, float cy, float cz, float hl, float hw,
-                                       float hh, float c, float s) {
-    const float dx = px - cx, dy = py - cy, dz = pz - cz;
-    const float a = dx * c, b = dy * s;
-    const float lx = a + b;
-    const float a2 = dy * c, b2 = dx * s;
-    const float ly = a2 - b2;
-    return fabsf(dz) <= hh && fabsf(lx) < hl && fabsf(ly) < hw;
-}
+// (inside, the predicate itself: box_geom.h, shared with point_head.hip)
 
 // ---- pairwise IoU -------------------------------------------------------------------------------------------
 // grid (ceil(Kb / IOU_TB), ceil(Ka / IOU_TA), B); mode 0 = BEV (§13 iou_bev), 1 = 3-D (§19.3)

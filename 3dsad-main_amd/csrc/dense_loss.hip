@@ -22,9 +22,9 @@
 namespace {
 
 #include "dense_tile.h"
+#include "loss_sums.h"
 
 constexpr int HCH = 16;            // classes per staged chunk (centre head, nhwc)
-constexpr int CNT = 16;            // elements per thread of the count kernels
 constexpr float CLAMP_LO = 1e-4f;
 
 struct AncL {
@@ -47,33 +47,7 @@ struct CenL {
     float cw[10], scale[2];
 };
 
-struct FinP {
-    const float *src[3];
-    int n[3], stride[3], ncomp;
-    float *loss;
-};
-
-// (block_sum, wave_count, norm_weight and sigmoid2: prims.h, shared with roi_loss.hip)
-
-__global__ __launch_bounds__(DENSE_THREADS) void anchor_count_kernel(const int32_t *labels, int K, int32_t *num_pos) {
-    const int b = blockIdx.y;
-    const int32_t *row = labels + (size_t)b * K;
-    int v[CNT];
-#pragma unroll
-    for (int q = 0; q < CNT; ++q) {                                   // (independent loads, issued together)
-        const long long i = ((long long)blockIdx.x * CNT + q) * DENSE_THREADS + threadIdx.x;
-        v[q] = i < K ? row[i] : -1;
-    }
-    int cnt = 0;
-#pragma unroll
-    for (int q = 0; q < CNT; ++q) cnt += v[q] >= 0;
-    __shared__ int wsum[4];
-    cnt = wave_count(cnt);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    // one atomic per workgroup: positives are spread over the rows, and an atomic per wave queues thousands on B addresses
-    if (threadIdx.x == 0 && wsum[0] + wsum[1] + wsum[2] + wsum[3]) atomicAdd(&num_pos[b], wsum[0] + wsum[1] + wsum[2] + wsum[3]);
-}
+// (block_sum, wave_count, norm_weight, sigmoid2, focal_one and smooth_l1: prims.h; FinP, count_pos_kernel and finish_kernel: loss_sums.h)
 
 // §27.1 regression of one row: r = predictions, t = targets -> term sum (j ascending from +0) and gradients
 __device__ __forceinline__ float reg_row(const AncL &p, const float *r, const float *t, bool pos, float wq, float *g) {
@@ -90,10 +64,8 @@ __device__ __forceinline__ float reg_row(const AncL &p, const float *r, const fl
         } else {
             d = (r[j] - t[j]) * p.cw[j];
         }
-        const float a = fabsf(d);
-        const bool quad = a < p.beta;
-        const float lj = quad ? ((0.5f * a) * a) / p.beta : a - (0.5f * p.beta);
-        const float sg = quad ? d / p.beta : (float)((d > 0.0f) - (d < 0.0f));
+        float sg;
+        const float lj = smooth_l1(d, p.beta, sg);
         float gj = (sg * p.cw[j]) * wq;
         if (j == 6 && p.sin_diff) gj = gj * extra;
         l = l + (pos ? lj * wq : 0.0f);
@@ -125,17 +97,7 @@ __device__ __forceinline__ float dir_row(const AncL &p, float *z, bool pos, int 
 
 // §27.1 classification of one logit -> term (value) and gradient (g)
 __device__ __forceinline__ float cls_one(const AncL &p, float x, bool t, bool live, float wq, float &g) {
-    const float e = expf(-fabsf(x));
-    float pr, pc;
-    sigmoid2(x, e, pr, pc);
-    const float bce = (fmaxf(x, 0.0f) - (t ? x : 0.0f)) + log1pf(e);
-    const float pt = t ? pc : pr;
-    const float aw = t ? p.alpha : p.oma;
-    const float l = (aw * (pt * pt)) * bce;
-    const float gt = ((-p.alpha) * (pc * pc)) * (((2.0f * pr) * bce) + pc);
-    const float gf = (p.oma * (pr * pr)) * (((2.0f * pc) * bce) + pr);
-    g = live ? (t ? gt : gf) * wq : 0.0f;
-    return live ? l * wq : 0.0f;
+    return focal_one(p.alpha, p.oma, x, t, live, wq, g);
 }
 
 __device__ __forceinline__ size_t plane_at(int ch, int cell, int HW) { return map_at(0, 0, ch, cell, 0, HW); }      // nchw, from the scene's base
@@ -273,19 +235,6 @@ __global__ __launch_bounds__(DENSE_THREADS) void anchor_loss_kernel(const AncL p
     if (tid == 0) {
         float *o = p.part + ((size_t)b * gridDim.x + blockIdx.x) * 3;
         o[0] = s0; o[1] = s1; o[2] = s2;
-    }
-}
-
-// one wave per scene: loss[b, i] = the partial sums of component i, lane l adding workgroups l, l + 64, ... in ascending order
-__global__ __launch_bounds__(64) void finish_kernel(const FinP p) {
-    const int b = blockIdx.x, lane = threadIdx.x;
-    for (int i = 0; i < p.ncomp; ++i) {
-        const float *src = p.src[i] + (size_t)b * p.n[i] * p.stride[i];
-        float v = 0.0f;
-        for (int w = lane; w < p.n[i]; w += 64) v = v + src[(size_t)w * p.stride[i]];
-#pragma unroll
-        for (int off = 32; off; off >>= 1) v = v + __shfl_xor(v, off);
-        if (lane == 0) p.loss[(size_t)b * p.ncomp + i] = v;
     }
 }
 
@@ -498,7 +447,7 @@ SAD_API int sad_anchor_head_loss_f32(const sad_anchor_head_loss_args *a, sad_str
     int tiles;
     const int nwg = anchor_grid_of(HW, a->A, &tiles, &p.chunks);
     if (hipMemsetAsync(a->num_pos, 0, (size_t)a->B * sizeof(int32_t), st) != hipSuccess) return sad::check_launch(fn);
-    hipLaunchKernelGGL(anchor_count_kernel, dim3((unsigned)((K + CNT * DENSE_THREADS - 1) / (CNT * DENSE_THREADS)), a->B), dim3(DENSE_THREADS), 0, st, a->labels,
+    hipLaunchKernelGGL(count_pos_kernel, dim3((unsigned)((K + CNT * DENSE_THREADS - 1) / (CNT * DENSE_THREADS)), a->B), dim3(DENSE_THREADS), 0, st, a->labels,
                        (int)K, a->num_pos);
     if (int rc = sad::check_launch(fn)) return rc;
     const dim3 grid((unsigned)nwg, a->B);

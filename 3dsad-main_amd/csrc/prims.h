@@ -1,6 +1,6 @@
 // Device primitives that more than one translation unit needs: the vector types of the MFMA kernels, the cross-lane
 // (DPP / readlane) unsigned maxima of the samplers, the LDS-DMA load with its wait, the integer hash of SPEC.md §17, the
-// float atomic max of the pooled outputs and the sums, counts, normaliser and sigmoid pair of the loss kernels (§27, §29).  Included inside each file's anonymous namespace, like reg_common.h, vox_hash.h and dense_tile.h (which include it).
+// float atomic max of the pooled outputs and the sums, counts, normaliser, sigmoid pair and per-element losses of the loss kernels (§27, §29, §31).  Included inside each file's anonymous namespace, like reg_common.h, vox_hash.h and dense_tile.h (which include it).
 // ONE definition of each: a helper moves here when a second family needs it; a helper with a single user stays in that file,
 // and what only one family shares lives in that family's header (the dense heads' tile-image copies: dense_tile.h).
 #pragma once
@@ -122,7 +122,7 @@ __device__ __forceinline__ void atomic_max_pos(float *addr, float v) {
     atomicMax(reinterpret_cast<unsigned *>(addr), __builtin_bit_cast(unsigned, v));
 }
 
-// ---- the loss kernels (dense_loss.hip §27, roi_loss.hip §29) -----------------------------------------------------------------
+// ---- the loss kernels (dense_loss.hip §27, roi_loss.hip §29, point_head.hip §31) ------------------------------------------------
 // the sum of a workgroup of 256 threads: butterfly over the wave (every lane ends with the same bits: + is commutative), then the
 // four wave sums in order.  Every thread of the workgroup calls it; `red` has 4 floats.
 __device__ __forceinline__ float block_sum(float v, float *red) {
@@ -151,4 +151,37 @@ __device__ __forceinline__ void sigmoid2(float x, float e, float &p, float &pc) 
     const float big = 1.0f / den, small = e / den;
     p = x >= 0.0f ? big : small;
     pc = x >= 0.0f ? small : big;
+}
+
+// §27.1 sigmoid focal classification (gamma = 2) of one logit against a hard target -> term (value) and gradient (g)
+__device__ __forceinline__ float focal_one(float alpha, float oma, float x, bool t, bool live, float wq, float &g) {
+    const float e = expf(-fabsf(x));
+    float pr, pc;
+    sigmoid2(x, e, pr, pc);
+    const float bce = (fmaxf(x, 0.0f) - (t ? x : 0.0f)) + log1pf(e);
+    const float pt = t ? pc : pr;
+    const float aw = t ? alpha : oma;
+    const float l = (aw * (pt * pt)) * bce;
+    const float gt = ((-alpha) * (pc * pc)) * (((2.0f * pr) * bce) + pc);
+    const float gf = (oma * (pr * pr)) * (((2.0f * pc) * bce) + pr);
+    g = live ? (t ? gt : gf) * wq : 0.0f;
+    return live ? l * wq : 0.0f;
+}
+
+// §29 binary cross-entropy of one logit against a soft target -> term (value) and gradient (g)
+__device__ __forceinline__ float bce_one(float x, float t, bool live, float wq, float &g) {
+    const float e = expf(-fabsf(x));
+    float pr, pc;
+    sigmoid2(x, e, pr, pc);
+    const float bce = (fmaxf(x, 0.0f) - (x * t)) + log1pf(e);
+    g = live ? (pr - t) * wq : 0.0f;
+    return live ? bce * wq : 0.0f;
+}
+
+// §27.1 smooth-L1 of one weighted difference d -> the term (value) and its derivative with respect to d (sg)
+__device__ __forceinline__ float smooth_l1(float d, float beta, float &sg) {
+    const float a = fabsf(d);
+    const bool quad = a < beta;
+    sg = quad ? d / beta : (float)((d > 0.0f) - (d < 0.0f));
+    return quad ? ((0.5f * a) * a) / beta : a - (0.5f * beta);
 }

@@ -39,10 +39,8 @@ __device__ __forceinline__ float reg_row(const RoiL &p, const float *r, const fl
 #pragma unroll
     for (int j = 0; j < 7; ++j) {
         const float d = (r[j] - t[j]) * p.cw[j];
-        const float a = fabsf(d);
-        const bool quad = a < p.beta;
-        const float lj = quad ? ((0.5f * a) * a) / p.beta : a - (0.5f * p.beta);
-        const float sg = quad ? d / p.beta : (float)((d > 0.0f) - (d < 0.0f));
+        float sg;
+        const float lj = smooth_l1(d, p.beta, sg);
         g[j] = (sg * p.cw[j]) * wq;
         l = l + lj;
     }
@@ -132,13 +130,9 @@ __global__ __launch_bounds__(RL_THREADS) void roi_loss_kernel(const RoiL p) {
             const int slot = i0 + tid;
             // ---- classification
             const float x = p.cls[row0 + slot], t = s_ct[slot];
-            const bool live = t >= 0.0f;
-            const float e = expf(-fabsf(x));
-            float pr, pc;
-            sigmoid2(x, e, pr, pc);
-            const float bce = (fmaxf(x, 0.0f) - (x * t)) + log1pf(e);
-            const float l0 = live ? bce * wq0 : 0.0f;
-            p.gcls[row0 + slot] = live ? (pr - t) * wq0 : 0.0f;
+            float gx;
+            const float l0 = bce_one(x, t, t >= 0.0f, wq0, gx);
+            p.gcls[row0 + slot] = gx;
             // ---- regression and corners: valid rows only, results selected
             float l1 = 0.0f, l2 = 0.0f, g[7], gc[7];
 #pragma unroll

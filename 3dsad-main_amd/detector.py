@@ -300,6 +300,14 @@ class SADDetector(nn.Module):
                 and all(mlp.preferred_geometry == 2 and mlp.out_channels % 16 == 0 for mlp in self.cluster_branches)
                 and self.cluster_agg.takes_pooled(B * self.cfg.n_cand, self.cluster_agg.out_channels))
 
+    def head_targets(self, trace: dict, gt_boxes: torch.Tensor, gt_labels: torch.Tensor):
+        """What ``trace["cluster"]["c"]`` and ``["head"]`` of a ``forward(points, trace=trace)`` are trained against (SPEC.md §31.1):
+        the ``PointTargets`` of the first K SA3 points and their shifted candidates, for ``point_head.PointHeadLoss``."""
+        from .point_head import PointTargetAssigner
+        K = self.cfg.n_cand
+        xyz = trace[f"sa{len(self.cfg.stages)}"]["new_xyz"][:, :K].contiguous()
+        return PointTargetAssigner.from_config(self.cfg)(xyz, trace["cluster"]["cand"], gt_boxes, gt_labels)
+
     def forward(self, points: torch.Tensor, trace: Optional[dict] = None,
                 input_ready: bool = False, ready=None) -> torch.Tensor:
         """points [B,N,3+in_feat] f32 on the GPU -> boxes [B,K,9].

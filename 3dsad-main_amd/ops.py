@@ -1747,6 +1747,149 @@ def roi_head_loss(rcnn_cls: torch.Tensor, rcnn_reg: torch.Tensor, cls_target: to
     return outs
 
 
+POINT_OUTPUTS = ("labels", "match", "centerness", "shift_target", "size_target", "reg_target")
+
+
+def point_output_spec(B: int, M: int) -> tuple:
+    """((name, shape, dtype), ...) of ``point_targets``' outputs, what its ``out=`` tuple is checked against."""
+    i32, f32 = torch.int32, torch.float32
+    return (("labels", (B, M), i32), ("match", (B, M), i32), ("centerness", (B, M), f32), ("shift_target", (B, M, 3), f32),
+            ("size_target", (B, M, 3), f32), ("reg_target", (B, M, 7), f32))
+
+
+def _point_rows(t: torch.Tensor, name: str, what: str = "B * M < 2^31") -> Tuple[int, int]:
+    """(B, M) of a point-major tensor [B,M,...] whose dtype and rank were judged already."""
+    B, M = t.shape[:2]
+    if not (1 <= B <= 65535 and M >= 1 and B * M < 2 ** 31):
+        raise ValueError(f"{name}: expected 1 <= B <= 65535, M >= 1 and {what}, got {tuple(t.shape)}")
+    return B, M
+
+
+def point_targets(xyz: torch.Tensor, cand: Optional[torch.Tensor], gt_boxes: torch.Tensor, gt_labels: torch.Tensor, *, anchors,
+                  size_anchor, shift_max: float, extra_width: float = 0.2, out: Optional[tuple] = None) -> tuple:
+    """Point head target assignment (SPEC.md §31.1).  xyz [B,M,3] f32: the origin points (the detector: the first K SA3 points);
+    cand [B,M,3] f32 or ``None`` (= xyz): where the head predicts from (§8 step 2's shifted candidates); gt_boxes [B,G,D>=7] f32,
+    gt_labels [B,G] int32 (outside [0, C): padding; so is a box with a non-positive extent), G <= 1024; anchors [C,3]: §9's class
+    anchors; size_anchor [3]: §8's ``anchor_car`` -> (labels [B,M] int32, match [B,M] int32, centerness [B,M], shift_target
+    [B,M,3], size_target [B,M,3], reg_target [B,M,7]).  A point is assigned by its ORIGIN (3DSSD's rule): the lowest box that
+    contains xyz gives the class and the index; a point in no box but within ``extra_width`` of one is ignored (-2), any other
+    is background (-1).  centerness and reg_target (centre - cand, clamp(log(size / anchors[class]), +-2), yaw) are taken at
+    cand; shift_target = clamp(centre - xyz, +-shift_max) and size_target invert §8 steps 2 and 3.  One launch, no workspace,
+    no synchronisation, no gradients, bit-identical from call to call.  ``out``: the tuple to write into."""
+    _strict(xyz, "xyz", torch.float32, (None, None, 3), "[B,M,3]")
+    B, M = _point_rows(xyz, "xyz")
+    if cand is not None:
+        _strict(cand, "cand", torch.float32, (B, M, 3))
+    an = np.asarray(anchors, dtype=np.float32)
+    if an.ndim != 2 or an.shape[1] != 3 or not 1 <= an.shape[0] <= 16:
+        raise ValueError(f"anchors: expected [C,3] with 1 <= C <= 16, got {an.shape}")
+    sa = np.asarray(size_anchor, dtype=np.float32).reshape(-1)
+    if sa.shape[0] != 3:
+        raise ValueError(f"size_anchor: expected 3 values, got {sa.shape[0]}")
+    if not (an > 0).all() or not (sa > 0).all():
+        raise ValueError("anchors / size_anchor: every extent must be > 0")
+    if not (float(shift_max) >= 0.0 and float(extra_width) >= 0.0):
+        raise ValueError(f"shift_max, extra_width: need >= 0 (got {shift_max}, {extra_width})")
+    C = an.shape[0]
+    Bg, G, D, dev = _gt_inputs(gt_boxes, gt_labels)
+    if Bg != B:
+        raise ValueError(f"gt_boxes: expected B = {B} scenes, got {Bg}")
+    if _head_devices((("xyz", xyz), ("cand", cand))) != dev:
+        raise ValueError("xyz / cand: must be on the device of gt_boxes")
+    outs = _outputs(point_output_spec(B, M), out, dev, "xyz")
+    a = _lib.PointTargetsArgs()
+    a.struct_size = ctypes.sizeof(_lib.PointTargetsArgs)
+    a.xyz, a.cand = xyz.data_ptr(), _ptr(cand)
+    a.gt_boxes, a.gt_labels = (gt_boxes.data_ptr(), gt_labels.data_ptr()) if G else (None, None)
+    a.B, a.M, a.G, a.D, a.C = B, M, G, D, C
+    a.anchors[:3 * C] = an.reshape(-1).tolist()
+    a.size_anchor[:] = sa.tolist()
+    a.shift_max, a.extra_width = _f32(shift_max), _f32(extra_width)
+    a.labels, a.match, a.centerness, a.shift_target, a.size_target, a.reg_target = (t.data_ptr() for t in outs)
+    with _timed("point_targets", f"M{M}G{G}"):
+        check(lib().sad_point_targets_f32(ctypes.byref(a), _stream()), "sad_point_targets_f32")
+    return outs
+
+
+def point_loss_output_spec(B: int, M: int, C: int, with_c: bool, per_point: bool) -> tuple:
+    """((name, shape, dtype), ...) of ``point_head_loss``' outputs, what its ``out=`` tuple is checked against."""
+    f32 = torch.float32
+    spec = [("loss", (B, 4), f32), ("num_pos", (B,), torch.int32), ("grad_o", (B, M, C + 7), f32)]
+    if with_c:
+        spec.append(("grad_c", (B, M, 6), f32))
+    if per_point:
+        spec.append(("per_point", (B, M, 4), f32))
+    return tuple(spec)
+
+
+def point_head_loss_workspace(B: int, M: int, device) -> torch.Tensor:
+    """The workspace of ``point_head_loss(..., workspace=...)`` for a caller that keeps it."""
+    nbytes = lib().sad_point_head_loss_workspace_bytes(B, M)
+    if not nbytes:
+        raise ValueError(f"point_head_loss_workspace: unsupported shape B = {B}, M = {M}")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def point_head_loss(o: torch.Tensor, c: Optional[torch.Tensor], labels: torch.Tensor, centerness: Optional[torch.Tensor],
+                    reg_target: torch.Tensor, shift_target: Optional[torch.Tensor] = None, size_target: Optional[torch.Tensor] = None, *,
+                    cls_loss: str = "bce", alpha: float = 0.25, beta: float = 1.0 / 9.0, code_weights=None,
+                    shift_max: Optional[float] = None, scale=(1.0, 1.0, 1.0, 1.0), normalize: bool = True, per_point: bool = False,
+                    workspace: Optional[torch.Tensor] = None, out: Optional[tuple] = None) -> tuple:
+    """Point head losses with their gradients (SPEC.md §31.2).  o [B,M,C+7] f32 (the head's rows: C class logits, then §9's box
+    code), c [B,M,6] f32 or ``None`` (the cluster layer's rows: shift, size), and the targets ``point_targets`` makes, read where
+    they are: labels [B,M] int32, centerness [B,M] or ``None``, reg_target [B,M,7], shift_target / size_target [B,M,3] or
+    ``None`` -> (loss [B,4] = (cls, reg, shift, size), num_pos [B] int32, grad_o [B,M,C+7][, grad_c [B,M,6]][, per_point
+    [B,M,4]]).  Classification over the rows that are not ignored: ``"bce"``, binary cross-entropy against the centre-ness at
+    the label's channel (3DSSD), or ``"focal"``, the sigmoid focal loss of ``anchor_head_loss``; smooth-L1 with the
+    sine-difference yaw of the box code (sizes clamped to +-2 as the decode does), of clamp(c[0:3], +-shift_max) and of
+    clamp(c[3:6], +-1) over the positives; each scaled by ``scale[i] / max(num_pos[b], 1)`` per scene (``normalize=False``: by
+    ``scale[i]``).  The shift / size components are on iff c and their target are given.  grad_o holds d loss[:, 0] in its
+    first C columns and d loss[:, 1] in the last 7; grad_c d loss[:, 2] in columns 0..2 and d loss[:, 3] in 3..5.  Two small
+    launches around one pass over the rows, no synchronisation, bit-identical from call to call.  ``out``: the tuple to write into."""
+    _strict(o, "o", torch.float32, (None, None, None), "[B,M,C+7] with 1 <= C <= 16")
+    B, M = _point_rows(o, "o")
+    C = o.shape[2] - 7
+    if not 1 <= C <= 16:
+        raise ValueError(f"o: expected [B,M,C+7] with 1 <= C <= 16, got {tuple(o.shape)}")
+    if cls_loss not in _lib.POINT_CLS_LOSSES:
+        raise ValueError(f"cls_loss: expected 'bce' or 'focal', got {cls_loss!r}")
+    if c is None and (shift_target is not None or size_target is not None):
+        raise ValueError("shift_target / size_target need c (the cluster layer's rows)")
+    if c is not None and shift_target is None and size_target is None:
+        raise ValueError("c needs shift_target or size_target (without either it has no loss)")
+    for name, t, shape, dt in (("c", c, (B, M, 6), torch.float32), ("labels", labels, (B, M), torch.int32),
+                               ("centerness", centerness, (B, M), torch.float32), ("reg_target", reg_target, (B, M, 7), torch.float32),
+                               ("shift_target", shift_target, (B, M, 3), torch.float32), ("size_target", size_target, (B, M, 3), torch.float32)):
+        if t is not None or name in ("labels", "reg_target"):
+            _strict(t, name, dt, shape)
+    beta = _f32(beta)
+    if not beta > 0.0:
+        raise ValueError(f"beta: must be > 0, got {beta}")
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError(f"alpha: expected a value in [0, 1], got {alpha}")
+    if shift_target is not None and not (shift_max is not None and float(shift_max) >= 0.0):
+        raise ValueError(f"shift_max: the shift component needs shift_max >= 0 (got {shift_max})")
+    cw, sc = _weights(code_weights, 7, "code_weights"), _weights(scale, 4, "scale")
+    dev = _head_devices((("o", o), ("c", c), ("labels", labels), ("centerness", centerness), ("reg_target", reg_target),
+                         ("shift_target", shift_target), ("size_target", size_target)))
+    outs = _outputs(point_loss_output_spec(B, M, C, c is not None, bool(per_point)), out, dev, "o")
+    workspace = _workspace(lib().sad_point_head_loss_workspace_bytes(B, M), workspace, dev, "ops.point_head_loss_workspace")
+    a = _lib.PointHeadLossArgs()
+    a.struct_size = ctypes.sizeof(_lib.PointHeadLossArgs)
+    a.o, a.c, a.labels, a.centerness, a.reg_target = o.data_ptr(), _ptr(c), labels.data_ptr(), _ptr(centerness), reg_target.data_ptr()
+    a.shift_target, a.size_target = _ptr(shift_target), _ptr(size_target)
+    a.B, a.M, a.C, a.cls_loss, a.normalize = B, M, C, _lib.POINT_CLS_LOSSES[cls_loss], int(bool(normalize))
+    a.alpha, a.beta, a.shift_max = _f32(alpha), beta, _f32(0.0 if shift_max is None else shift_max)
+    a.code_weights[:], a.scale[:] = cw, sc
+    a.loss, a.num_pos, a.grad_o = (t.data_ptr() for t in outs[:3])
+    a.grad_c = outs[3].data_ptr() if c is not None else None
+    a.per_point = outs[-1].data_ptr() if per_point else None
+    a.workspace = workspace.data_ptr()
+    with _timed("point_head_loss", f"M{M}C{C}"):
+        check(lib().sad_point_head_loss_f32(ctypes.byref(a), _stream()), "sad_point_head_loss_f32")
+    return outs
+
+
 def roi_grid_points(rois: torch.Tensor, roi_count: Optional[torch.Tensor], grid_size: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The grid points of every RoI (SPEC.md §30): rois [B,R,D>=7] f32 rows (cx,cy,cz,l,w,h,yaw,...), roi_count [B] int32 or
     ``None`` (as in ``roi_targets``: the rows beyond it are never read) -> pts [B,R,G^3,3] with G = ``grid_size`` (1 .. 16): point

@@ -857,6 +857,75 @@ typedef struct sad_voxel_query_args {
 size_t sad_voxel_query_workspace_bytes(int Nv);   /* 0 outside 0 <= Nv <= 2^30 */
 int sad_voxel_query_f32(const sad_voxel_query_args *args, sad_stream_t stream);
 
+/* SPEC.md §31.  Point head: what the size-adaptive cluster layer (§8, c[B,M,6]) and the box / class head (§9, o[B,M,C+7]) are
+ * trained against, and the loss on top with its gradients.  Rows are point-major, M points per scene (the detector: M = K).
+ * Padded ground truth as in §26 (a label outside [0, C) or a non-positive extent marks a padding row, 0 <= G <= 1024, G == 0
+ * with NULL pointers).  Outputs are fully written by the call.  A fixed sequence of memsets and launches whose dimensions
+ * depend on the shapes only; nothing is read back, nothing synchronises, no float atomics: two calls are bit-equal.  NaN in an
+ * input or |yaw| >= 1e4 is undefined behaviour.  1 <= B <= 65535, 1 <= C <= 16, B*M < 2^31 (SAD_EUNSUPPORTED above). */
+
+/* §31.1 targets.  A point is assigned by its origin xyz[B,M,3]: match = the lowest g with §19.1 inside(xyz, box_g, 0), labels =
+ * that box's class; inside no box but inside some box enlarged by extra_width: labels -2 (ignored); else -1 (background).
+ * cand[B,M,3] (NULL: xyz) is where the head predicts from: centerness (the cube root of the product of min/max of the
+ * distances to the two faces per axis, in the box's frame; 0 outside the box) and reg_target[.,7] (centre - cand,
+ * clamp(log(size / anchors[class]), +-2), yaw: §9's code inverted) are taken there; shift_target[.,3] =
+ * clamp(centre - xyz, +-shift_max) and size_target[.,3] = min(sqrt(max(2 size / size_anchor - 1, 0)) - 1, 1) invert §8 steps 2
+ * and 3.  Non-positive rows: match -1, centerness 0, zero targets.  One launch, no workspace, no atomics.  A NULL required
+ * pointer, a wrong struct_size, a size below 1, D < 7, an anchor <= 0, shift_max < 0 or extra_width < 0: SAD_EINVAL. */
+typedef struct sad_point_targets_args {
+    size_t struct_size;   /* = sizeof(sad_point_targets_args) */
+    const float *xyz;              /* [B,M,3] */
+    const float *cand;             /* [B,M,3] or NULL */
+    const float *gt_boxes;         /* [B,G,D] */
+    const int32_t *gt_labels;      /* [B,G] */
+    int B, M, G, D, C;
+    float anchors[48];    /* [C,3] */
+    float size_anchor[3];
+    float shift_max, extra_width;
+    int32_t *labels, *match;       /* [B,M] */
+    float *centerness;             /* [B,M] */
+    float *shift_target, *size_target; /* [B,M,3] */
+    float *reg_target;             /* [B,M,7] */
+} sad_point_targets_args;
+int sad_point_targets_f32(const sad_point_targets_args *args, sad_stream_t stream);
+
+/* §31.2 loss on §31.1's targets, read where they are, with the gradient with respect to o and c.  Component i of scene b is
+ * weighted scale[i] / (float)max(num_pos[b], 1) (normalize != 0) or scale[i]; num_pos[b] = #(labels >= 0).  Classification
+ * over the rows with labels != -2 and every class channel: SAD_POINT_CLS_BCE, §29's binary cross-entropy against the soft
+ * target centerness (NULL: 1) at the label's channel of a positive row and 0 elsewhere, or SAD_POINT_CLS_FOCAL, §27.1's sigmoid
+ * focal loss on the hard target.  Box regression over the positives: §27.1's smooth-L1 with the sine-difference yaw of
+ * o[C .. C+6] (columns 3..5 clamped to +-2 first; the gradient passes where -2 <= x <= 2) against reg_target.  Shift / size
+ * (present iff c and shift_target / size_target are given): smooth-L1 of clamp(c[0:3], +-shift_max) / clamp(c[3:6], +-1) over
+ * the positives, same gradient rule.  loss[B,4] = (cls, reg, shift, size); grad_o[B,M,C+7]: d loss[.,0] in the first C
+ * columns, d loss[.,1] in the last 7; grad_c[B,M,6] (given iff c is): d loss[.,2] in columns 0..2, d loss[.,3] in 3..5;
+ * per_point[B,M,4] may be NULL.  workspace: sad_point_head_loss_workspace_bytes(B, M) bytes (the workgroups' partial sums),
+ * contents irrelevant.  A NULL required pointer, a wrong struct_size, a size below 1, beta <= 0 or NaN, alpha outside [0, 1],
+ * another cls_loss code, c without a target or a target without c, grad_c given or missing against c: SAD_EINVAL. */
+#define SAD_POINT_CLS_BCE 0
+#define SAD_POINT_CLS_FOCAL 1
+typedef struct sad_point_head_loss_args {
+    size_t struct_size;   /* = sizeof(sad_point_head_loss_args) */
+    const float *o;                /* [B,M,C+7] */
+    const float *c;                /* [B,M,6] or NULL */
+    const int32_t *labels;         /* [B,M] */
+    const float *centerness;       /* [B,M] or NULL */
+    const float *reg_target;       /* [B,M,7] */
+    const float *shift_target;     /* [B,M,3] or NULL */
+    const float *size_target;      /* [B,M,3] or NULL */
+    int B, M, C, cls_loss, normalize;
+    float alpha, beta, shift_max;
+    float code_weights[7];
+    float scale[4];       /* cls, reg, shift, size */
+    float *loss;          /* [B,4] */
+    int32_t *num_pos;     /* [B] */
+    float *grad_o;        /* [B,M,C+7] */
+    float *grad_c;        /* [B,M,6] or NULL */
+    float *per_point;     /* [B,M,4] or NULL */
+    void *workspace;
+} sad_point_head_loss_args;
+size_t sad_point_head_loss_workspace_bytes(int B, int M);   /* 16*B*ceil(M/256); 0 outside the limits */
+int sad_point_head_loss_f32(const sad_point_head_loss_args *args, sad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

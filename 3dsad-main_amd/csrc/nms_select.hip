@@ -8,14 +8,17 @@
 //           compaction: everything above the threshold key plus the LOWEST-INDEX ties at it.  Also initialises keep / order.
 //   rank   (256 selected boxes per workgroup): exact counting rank by (key desc, index asc) with the n packed
 //           (key, ~index) words staged through LDS; writes rank2idx, corners, areas, labels in rank order.
-//   mask   (one wave per ranked box): the upper triangle of the n x n suppression matrix, row stride ceil(P/64) words.
-//   walk   (one workgroup per scene): the chunked scalar chain of nms_walk_kernel on wave 0; the words a chunk's kept rows
-//           suppress in later chunks are or-ed into LDS by all four waves (thread k owns word k: no atomics).
+//   mask   (one wave per ranked box): nms_core.h's mask kernel on this file's layout, row stride ceil(P/64) words, labels on.
+//   walk   (one workgroup per scene): chunk_decide (nms_core.h) on wave 0; the words a chunk's kept rows suppress in later
+//           chunks are or-ed into LDS by all four waves (thread k owns word k: no atomics).
+// The pair test, the chain of a chunk, the mask kernel and the workspace view are nms_core.h's, shared with nms.hip.  Here:
+// the selection, the ranking of the selected boxes, the nms_boxes workspace law and the four-wave walk with its post cap.
 #include "box_geom.h"
 
 namespace {
 
-#include "prims.h"       // u64
+#include "prims.h"       // u64, readlane_u64
+#include "nms_core.h"
 
 constexpr int NMSX_MAXP = 16384;
 constexpr int NMSX_MAXW = NMSX_MAXP / 64;        // 256 removed-words per scene, held in LDS by the walk
@@ -30,34 +33,34 @@ __device__ __forceinline__ int lanes_below(u64 ballot) {      // set bits of `ba
     return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ballot, 0u));
 }
 
-struct NmsxWs {           // per-scene slices of the workspace (8-byte items first; the scene stride is a multiple of 16)
-    int *hdr;             // [16]: n, n_above, take, threshold key
-    u64 *sel;             // [P]   selected boxes, unranked: key << 32 | ~index
-    u64 *mask;            // [P][W] row p, word k: bit l = box of rank 64k + l is suppressed by rank p (words k >= p / 64 only)
-    float *cx, *cy;       // [P][4]
-    int *rank2idx;        // [P]
-    int *label;           // [P]
-    float *area;          // [P]
+// per scene (8-byte items first; the scene stride is a multiple of 16): hdr [16] ints, sel [P], mask [P][W], cx, cy [P][4],
+// rank2idx, label, area [P], with W = ceil(P / 64)
+struct NmsxLayout {
+    struct View : NmsWs {
+        int *hdr;         // [16]: n, n_above, take, threshold key (n = hdr)
+        u64 *sel;         // [P]   selected boxes, unranked: key << 32 | ~index
+    };
+    static constexpr bool LABELS = true;
+    __host__ __device__ static size_t scene_bytes(int P) {
+        const size_t W = (size_t)(P + 63) / 64;
+        const size_t b = 64 + (size_t)P * 8 + (size_t)P * W * 8 + (size_t)P * 16 * 2 + (size_t)P * 4 * 3;
+        return sad::al16(b);
+    }
+    __device__ __forceinline__ static View view(void *base, int scene, int P) {
+        unsigned char *q = (unsigned char *)base + (size_t)scene * scene_bytes(P);
+        View w;
+        w.W = (P + 63) >> 6;
+        w.n = w.hdr = (int *)q; q += 64;
+        w.sel = (u64 *)q; q += (size_t)P * 8;
+        w.mask = (u64 *)q; q += (size_t)P * w.W * 8;
+        w.cx = (float *)q; q += (size_t)P * 16;
+        w.cy = (float *)q; q += (size_t)P * 16;
+        w.rank2idx = (int *)q; q += (size_t)P * 4;
+        w.label = (int *)q; q += (size_t)P * 4;
+        w.area = (float *)q;
+        return w;
+    }
 };
-__host__ __device__ inline size_t nmsx_ws_scene_bytes(int P) {
-    const size_t W = (size_t)(P + 63) / 64;
-    const size_t b = 64 + (size_t)P * 8 + (size_t)P * W * 8 + (size_t)P * 16 * 2 + (size_t)P * 4 * 3;
-    return sad::al16(b);
-}
-__device__ __forceinline__ NmsxWs nmsx_ws(void *base, int scene, int P) {
-    unsigned char *q = (unsigned char *)base + (size_t)scene * nmsx_ws_scene_bytes(P);
-    const size_t W = (size_t)(P + 63) / 64;
-    NmsxWs w;
-    w.hdr = (int *)q; q += 64;
-    w.sel = (u64 *)q; q += (size_t)P * 8;
-    w.mask = (u64 *)q; q += (size_t)P * W * 8;
-    w.cx = (float *)q; q += (size_t)P * 16;
-    w.cy = (float *)q; q += (size_t)P * 16;
-    w.rank2idx = (int *)q; q += (size_t)P * 4;
-    w.label = (int *)q; q += (size_t)P * 4;
-    w.area = (float *)q;
-    return w;
-}
 
 // ---- select ---------------------------------------------------------------------------------------------------------
 // T_k = max(P-th largest key of the scene, key(score_thr)).  n_above = #(key > T_k) <= P - 1 and the selection is those
@@ -75,7 +78,7 @@ __global__ __launch_bounds__(THREADS) void nmsx_select_kernel(const float *__res
     const unsigned uK = (unsigned)K;
     const float *sc = scores + (size_t)blockIdx.x * K;
     int32_t *kp = keep + (size_t)blockIdx.x * K, *od = order + (size_t)blockIdx.x * Pout;
-    const NmsxWs w = nmsx_ws(wsbase, blockIdx.x, P);
+    const auto w = NmsxLayout::view(wsbase, blockIdx.x, P);
 
     for (unsigned i = tid; i < uK; i += THREADS) kp[i] = 0;
     for (int i = tid; i < Pout; i += THREADS) od[i] = -1;
@@ -180,8 +183,8 @@ __global__ __launch_bounds__(256) void nmsx_rank_kernel(const float *__restrict_
                                                         int K, int P, void *__restrict__ wsbase) {
     __shared__ u64 s_c[NMSX_RANK_TILE];
     const int tid = threadIdx.x;
-    const NmsxWs w = nmsx_ws(wsbase, blockIdx.y, P);
-    const int n = w.hdr[0];
+    const auto w = NmsxLayout::view(wsbase, blockIdx.y, P);
+    const int n = w.n[0];
     const int j = blockIdx.x * 256 + tid;
     if (blockIdx.x * 256 >= n) return;                           // surplus workgroup (uniform)
     const bool have = j < n;
@@ -209,47 +212,9 @@ __global__ __launch_bounds__(256) void nmsx_rank_kernel(const float *__restrict_
     }
 }
 
-// ---- mask -----------------------------------------------------------------------------------------------------------
-// Row p gets its words k = p / 64 .. ceil(n / 64) - 1 (the diagonal word onwards).  The words below the diagonal word are
-// NOT stored: the walk never reads them.
-constexpr int NMSX_ROWS_PER_WG = 16;
-__global__ __launch_bounds__(256) void nmsx_mask_kernel(int P, float iou_thr, int has_labels, void *__restrict__ wsbase) {
-    __shared__ float s_poly[4 * 10 * 256];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const NmsxWs w = nmsx_ws(wsbase, blockIdx.y, P);
-    const int n = w.hdr[0];
-    if (blockIdx.x * NMSX_ROWS_PER_WG >= n) return;              // surplus workgroup (uniform)
-    const int W = (P + 63) >> 6, nch = (n + 63) >> 6;
-    for (int rr = wave; rr < NMSX_ROWS_PER_WG; rr += 4) {
-        const int p = blockIdx.x * NMSX_ROWS_PER_WG + rr;
-        if (p >= n) continue;                                    // wave-uniform
-        float pcx[4], pcy[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { pcx[k] = w.cx[p * 4 + k]; pcy[k] = w.cy[p * 4 + k]; }
-        const float pa = w.area[p];
-        const int pl = w.label[p];
-        for (int k = p >> 6; k < nch; ++k) {
-            const int q = 64 * k + lane;
-            bool sup = false;
-            if (q > p && q < n && !(has_labels && w.label[q] != pl)) {    // another class: decided without clipping
-                float qcx[4], qcy[4];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) { qcx[c] = w.cx[q * 4 + c]; qcy[c] = w.cy[q * 4 + c]; }
-                const float inter = poly_clip_area<256>(pcx, pcy, qcx, qcy, s_poly + tid);
-                float den = pa + w.area[q];
-                den = den - inter;
-                const float iou = den > 0.0f ? inter / den : 0.0f;
-                sup = iou > iou_thr;
-            }
-            const u64 word = __ballot(sup);
-            if (lane == 0) w.mask[(size_t)p * W + k] = word;
-        }
-    }
-}
-
 // ---- walk -----------------------------------------------------------------------------------------------------------
-// Greedy walk, 64 ranks (one chunk) at a time.  Wave 0 decides a chunk exactly as nms_walk_kernel does (scalar chain over
-// the chunk's own words), cuts it at post_max and writes keep / order (positions nk + prefix < min(n, post_max) <= Pout).
+// Greedy walk, 64 ranks (one chunk) at a time.  Wave 0 decides a chunk with chunk_decide (the scalar chain over the chunk's
+// own words), cuts it at post_max and writes keep / order (positions nk + prefix < min(n, post_max) <= Pout).
 // Then thread t or-s the words k = c + 1 + t of the chunk's kept rows into s_rem[k]: coalesced along a row, sixteen
 // independent loads in flight, and a one-wave loop over the rows' later words (a dependent-latency chain at n = 16 384) is gone.
 __global__ __launch_bounds__(256) void nmsx_walk_kernel(int K, int P, int Pout, int post_max, int32_t *__restrict__ keep,
@@ -258,10 +223,10 @@ __global__ __launch_bounds__(256) void nmsx_walk_kernel(int K, int P, int Pout, 
     __shared__ u64 s_rem[NMSX_MAXW];
     __shared__ u64 s_kept;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const NmsxWs w = nmsx_ws(wsbase, blockIdx.x, P);
+    const auto w = NmsxLayout::view(wsbase, blockIdx.x, P);
     int32_t *kp = keep + (size_t)blockIdx.x * K, *od = order + (size_t)blockIdx.x * Pout;
-    const int n = __builtin_amdgcn_readfirstlane(w.hdr[0]);
-    const int W = (P + 63) >> 6, nch = (n + 63) >> 6;            // nch <= W <= NMSX_MAXW
+    const int n = __builtin_amdgcn_readfirstlane(w.n[0]);
+    const int W = w.W, nch = (n + 63) >> 6;                      // nch <= W <= NMSX_MAXW
     s_rem[tid] = 0ull;
     __syncthreads();
     int nk = 0;
@@ -271,28 +236,7 @@ __global__ __launch_bounds__(256) void nmsx_walk_kernel(int K, int P, int Pout, 
             const bool have = p < n;
             const u64 own = have ? w.mask[(size_t)p * W + c] : 0ull;       // suppressed by p inside its chunk
             const int idx = have ? w.rank2idx[p] : 0;
-            const int left = n - 64 * c;
-            const u64 valid = left >= 64 ? ~0ull : ((1ull << left) - 1ull);
-            const u64 remw = s_rem[c];
-            const u64 rem_lo = (u64)(unsigned)__builtin_amdgcn_readfirstlane((int)(remw & 0xFFFFFFFFull));
-            const u64 rem_hi = (u64)(unsigned)__builtin_amdgcn_readfirstlane((int)(remw >> 32));
-            u64 alive = valid & ~(rem_lo | (rem_hi << 32));
-            u64 kept = 0ull;
-            const u64 nz = __ballot(own != 0ull);
-            const unsigned own_lo = (unsigned)own, own_hi = (unsigned)(own >> 32);
-            while (true) {
-                const u64 cand = alive & nz;
-                if (cand == 0ull) {
-                    kept |= alive;
-                    break;
-                }
-                const int i = __builtin_amdgcn_readfirstlane(__builtin_ctzll(cand));
-                const u64 upto = (2ull << i) - 1ull;                           // ranks 0 .. i of the chunk
-                kept |= alive & upto;
-                const u64 r = (u64)(unsigned)__builtin_amdgcn_readlane((int)own_lo, i) |
-                              ((u64)(unsigned)__builtin_amdgcn_readlane((int)own_hi, i) << 32);
-                alive &= ~(r | upto);
-            }
+            u64 kept = chunk_decide(own, n, c, s_rem[c]);
             // post cap: the first post_max - nk kept boxes of the chunk (nk < post_max here)
             const int before = __builtin_popcountll(kept & ((1ull << lane) - 1ull));
             const bool mine = ((kept >> lane) & 1ull) && before < post_max - nk;
@@ -338,7 +282,7 @@ SAD_API size_t sad_nms_boxes_workspace_bytes(int B, int K, int pre_max) {
     if (B < 1 || B > 65535 || K < 1 || pre_max < 1 || (long long)B * K >= (1ll << 31)) return 0;
     const int P = nmsx_P(K, pre_max);
     if (P > NMSX_MAXP) return 0;
-    return (size_t)B * nmsx_ws_scene_bytes(P);
+    return (size_t)B * NmsxLayout::scene_bytes(P);
 }
 
 SAD_API int sad_nms_boxes_f32(const float *boxes, int D, const float *scores, const int32_t *labels, int B, int K,
@@ -360,7 +304,7 @@ SAD_API int sad_nms_boxes_f32(const float *boxes, int D, const float *scores, co
     else
         hipLaunchKernelGGL((nmsx_select_kernel<1024>), dim3(B), dim3(1024), 0, st, scores, K, P, Pout, score_thr, keep, order, workspace);
     hipLaunchKernelGGL(nmsx_rank_kernel, dim3((P + 255) / 256, B), dim3(256), 0, st, boxes, D, labels, K, P, workspace);
-    hipLaunchKernelGGL(nmsx_mask_kernel, dim3((P + NMSX_ROWS_PER_WG - 1) / NMSX_ROWS_PER_WG, B), dim3(256), 0, st, P, iou_thr,
+    hipLaunchKernelGGL(nms_mask_kernel<NmsxLayout>, dim3((P + NMS_ROWS_PER_WG - 1) / NMS_ROWS_PER_WG, B), dim3(256), 0, st, P, iou_thr,
                        labels ? 1 : 0, workspace);
     hipLaunchKernelGGL(nmsx_walk_kernel, dim3(B), dim3(256), 0, st, K, P, Pout, post_max, keep, order, count, workspace);
     return sad::check_launch("sad_nms_boxes_f32");

@@ -2,7 +2,8 @@
 // (DPP / readlane) unsigned maxima of the samplers, the LDS-DMA load with its wait, the integer hash of SPEC.md §17, the
 // float atomic max of the pooled outputs and the sums, counts, normaliser, sigmoid pair and per-element losses of the loss kernels (§27, §29, §31).  Included inside each file's anonymous namespace, like reg_common.h, vox_hash.h and dense_tile.h (which include it).
 // ONE definition of each: a helper moves here when a second family needs it; a helper with a single user stays in that file,
-// and what only one family shares lives in that family's header (the dense heads' tile-image copies: dense_tile.h).
+// and what only one family shares lives in that family's header (the dense heads' tile-image copies: dense_tile.h; the NMS
+// pair test, ranking, chunk chain, workspace view and mask kernel: nms_core.h).
 #pragma once
 
 typedef unsigned long long u64;

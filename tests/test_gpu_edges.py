@@ -381,6 +381,35 @@ def test_nms_workspace_reuse(orc, sad, dev):
         _nms_all(orc, dev, bx, 0.1, sthr, out=buf)
 
 
+def _boxes_few_candidates(B=2, K=200, n1=70):
+    """Crowded scenes; in scene 1 only ``n1`` scattered boxes reach score 0.1: ceil(n/64) = 2 < ceil(K/64) = 4, last chunk partial."""
+    bx = _boxes(19, B, K, extent=2.0 * np.sqrt(K))
+    rng = np.random.default_rng(20)
+    low = np.ones(K, bool)
+    low[rng.permutation(K)[:n1]] = False
+    bx[1, :, 7] = np.where(low, np.float32(0.09) * bx[1, :, 7], np.float32(0.1) + np.float32(0.9) * bx[1, :, 7])
+    return bx
+
+
+def test_nms_workspace_unwritten_words(orc, sad, dev):
+    """The three-kernel nms_bev on a workspace whose every byte is 0xFF, twice on the same buffers: the mask kernel stores only
+    the words k = p/64 .. ceil(n/64) - 1 of row p, so whatever the walk reads must have been written in this call.  Exact against
+    the oracle; both scenes keep strictly between 0 and n boxes."""
+    from sad_amd import ops
+    B, K, thr, sthr = 2, 200, 0.1, 0.1
+    bx = _boxes_few_candidates(B, K)
+    n = (bx[..., 7] >= np.float32(sthr)).sum(1)
+    assert n[1] == 70 and 128 < n[0] < K
+    want = orc.nms_bev(bx, thr, sthr)
+    assert (want[2] > 0).all() and (want[2] < n).all()
+    buf = ops.nms_bev_buffers(B, K, dev)
+    buf[3].fill_(0xFF)
+    for call in (1, 2):
+        got = ops.nms_bev(_t(bx, dev), thr, sthr, out=buf)
+        for name, g, w in zip(("keep", "order", "count"), got, want):
+            np.testing.assert_array_equal(g.cpu().numpy(), w, err_msg=f"{name}, call {call}")
+
+
 def test_nms_out_buffers_checked(sad, dev):
     """A caller's ``out`` that a kernel would write past its end is refused before anything is launched: keep / order / count of
     a 2-byte dtype, keep / order as a ``[:, ::2]`` view of a twice-as-wide tensor (count [1] has no strided form: a view of one

@@ -2,7 +2,7 @@
 (a) B = 32, K = 512, crowded and sparse scenes: nms_boxes next to the three-kernel nms_bev on the same rows (the old path
     is the yardstick), the two alternated over several rounds; (b) B = 32, K = 70 400, pre_max 1000 and 4096.
 Under `rocprofv3 --kernel-trace --stats -- python tools/nms_boxes_time.py --split` only (b) runs, a few calls per shape:
-the per-stage split is the trace's nmsx_select / nmsx_rank / nmsx_mask / nmsx_walk rows.  Any error ends the process."""
+the per-stage split is the trace's nmsx_select / nmsx_rank / nms_mask_kernel<NmsxLayout> / nmsx_walk rows.  Any error ends the process."""
 import argparse
 import os
 import sys

@@ -225,6 +225,28 @@ class PointHeadLossArgs(ctypes.Structure):
     ]
 
 
+GRAD_FEAT, GRAD_XYZ, GRAD_NEW_XYZ, GRAD_PARAMS = 1, 2, 4, 8      # SAD_GRAD_*
+
+
+class MlpGradArgs(ctypes.Structure):
+    """``struct sad_mlp_grad_args`` (include/sad_amd.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("xyz", vp), ("new_xyz", vp), ("feat", vp), ("idx", vp), ("cnt", vp),
+        ("ld_feat", ctypes.c_int),
+        ("B", ctypes.c_int), ("N", ctypes.c_int), ("M", ctypes.c_int), ("S", ctypes.c_int), ("C", ctypes.c_int),
+        ("L", ctypes.c_int), ("dims", ctypes.c_int * (MAX_LAYERS + 1)),
+        ("W", vp * MAX_LAYERS), ("b", vp * MAX_LAYERS),
+        ("relu_mask", ctypes.c_int), ("skip_empty", ctypes.c_int),
+        ("pooled", vp), ("ld_pooled", ctypes.c_int), ("pooled_off", ctypes.c_int),
+        ("grad_out", vp), ("ld_grad", ctypes.c_int), ("col_off", ctypes.c_int),
+        ("need", ctypes.c_int),
+        ("grad_feat", vp), ("grad_xyz", vp), ("grad_new_xyz", vp),
+        ("grad_W", vp * MAX_LAYERS), ("grad_b", vp * MAX_LAYERS),
+        ("workspace", vp), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/sad_amd.h declares
 SIGNATURES = {
     "sad_version": (ctypes.c_int, []),
@@ -340,6 +362,9 @@ SIGNATURES = {
     "sad_point_targets_f32": (ctypes.c_int, [ctypes.POINTER(PointTargetsArgs), vp]),
     "sad_point_head_loss_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "sad_point_head_loss_f32": (ctypes.c_int, [ctypes.POINTER(PointHeadLossArgs), vp]),
+    "sad_mlp_grad_workspace_bytes": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_size_t),
+                                                                          ctypes.POINTER(ctypes.c_size_t)]),
+    "sad_mlp_grad_f32": (ctypes.c_int, [ctypes.POINTER(MlpGradArgs), vp]),
 }
 
 _lib = None

@@ -4,7 +4,9 @@
 ``sparse_to_dense`` §21.4, ``sparse_max_pool`` §22.2) as ``torch.autograd.Function``s whose forward
 AND backward are this package's HIP kernels (float32 only): the classic unfused
 ``group -> shared MLP (any torch layers) -> max over nsample`` stack becomes trainable without a
-PyTorch-side scatter.  The fused inference kernels (``PackedMLP.grouped``) have no backward.
+PyTorch-side scatter.  The fused chains have a backward of their own (SPEC.md §32): ``GroupedMLP`` / ``MLPRows`` run
+``PackedMLP.grouped`` / ``.rows`` forward, keep the inputs and the output only, and recompute the activations in
+``ops.grouped_mlp_grad`` / ``ops.mlp_rows_grad``.
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -454,3 +456,62 @@ class PointHeadLoss(torch.autograd.Function):
         if len(saved) == 2:
             gc = saved[1] * torch.cat([grad_loss[:, 2:3].expand(-1, 3), grad_loss[:, 3:4].expand(-1, 3)], 1).unsqueeze(1)
         return go, gc, None, None, None, None, None, None
+
+
+def _layers_of(params):
+    """(W_1 .. W_L, b_1 .. b_L) -> [(W_l, b_l)]."""
+    L = len(params) // 2
+    return [(params[l], params[L + l]) for l in range(L)]
+
+
+class GroupedMLP(torch.autograd.Function):
+    """The fused grouped chain + max-pool (SPEC.md §6) with the backward of §32.  ``apply(packed, skip_empty, xyz [B,N,3],
+    feat_pm [B,N,C] | None, new_xyz [B,M,3], idx [B,M,S], cnt [B,M] | None, W_1 .. W_L, b_1 .. b_L) -> pooled [B,M,C_L]``:
+    ``packed`` is the ``PackedMLP`` of exactly these layers (the forward is its ``grouped``, unchanged), the unpacked tensors are
+    what the backward reads and what receives the gradients.  Saved: the inputs and the output.  ``skip_empty``: groups with
+    ``cnt == 0`` give no gradient (a caller that overwrites their output).  ``mismatch`` of the last backward (a 1-element int32
+    GPU tensor, 0 when the recompute met every pooled value) is left in ``GroupedMLP.last_mismatch``."""
+    last_mismatch = None
+
+    @staticmethod
+    def forward(ctx, packed, skip_empty, xyz, feat_pm, new_xyz, idx, cnt, *params):
+        if len(params) != 2 * packed.L:
+            raise ValueError("GroupedMLP: expected the chain's L weights followed by its L biases")
+        out = packed.grouped(xyz, feat_pm, new_xyz, idx, cnt=cnt)
+        ctx.save_for_backward(xyz, feat_pm, new_xyz, idx, cnt, out, *params)
+        ctx.skip_empty = bool(skip_empty)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        xyz, feat_pm, new_xyz, idx, cnt, out, *params = ctx.saved_tensors
+        want = ctx.needs_input_grad
+        need = [n for n, w in (("xyz", want[2]), ("feat", want[3]), ("new_xyz", want[4]), ("params", any(want[7:]))) if w]
+        gf, gx, gn, gW, gb, GroupedMLP.last_mismatch = ops.grouped_mlp_grad(
+            xyz, feat_pm, new_xyz, idx, cnt, _layers_of(params), out, grad_out, skip_empty=ctx.skip_empty, need=need)
+        gp = [g if w else None for g, w in zip((gW or []) + (gb or []), want[7:])] if gW is not None else [None] * len(params)
+        return (None, None, gx, gf, gn, None, None, *gp)
+
+
+class MLPRows(torch.autograd.Function):
+    """The fused plain-row chain with the backward of §32: ``apply(packed, x [..., C_0], W_1 .. W_L, b_1 .. b_L) -> [..., C_L]``
+    (``packed``: the ``PackedMLP`` of these layers, its ``relu_mask`` included).  Saved: the inputs."""
+
+    @staticmethod
+    def forward(ctx, packed, x, *params):
+        if len(params) != 2 * packed.L:
+            raise ValueError("MLPRows: expected the chain's L weights followed by its L biases")
+        ctx.save_for_backward(x, *params)
+        ctx.relu_mask = packed.relu_mask
+        return packed.rows(x)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        x, *params = ctx.saved_tensors
+        want = ctx.needs_input_grad
+        need = [n for n, w in (("feat", want[1]), ("params", any(want[2:]))) if w]
+        gx, gW, gb = ops.mlp_rows_grad(x, _layers_of(params), grad_out, relu_mask=ctx.relu_mask, need=need)
+        gp = [g if w else None for g, w in zip((gW or []) + (gb or []), want[2:])] if gW is not None else [None] * len(params)
+        return (None, gx, *gp)

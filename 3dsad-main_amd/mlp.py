@@ -7,6 +7,8 @@ chain, who prepares its pooling buffer, what a recorded step plan (plan.py) must
 merged dispatch, ``_PackedChain`` holds what the two classes share; each class keeps its kernel choice and tuning policy.
 The switches (``AUTOTUNE``, ``LAUNCH_LOG``, ``RERUN_LOG``, ``MERGE_BF16``, ``SPLIT_POOL``) stay in ``ops.py``, where callers
 assign them, and are read as ``ops.NAME`` at call time.  ``ops.py`` re-exports the public names of this module.
+The backward of the chains (``grouped_mlp_grad`` / ``mlp_rows_grad``, SPEC.md §32) closes the module: one validated C-ABI call
+each, on the unpacked layers.
 """
 import ctypes
 import os
@@ -792,6 +794,224 @@ class PackedMLPBf16(_PackedChain):
 def mlp_chain(x: torch.Tensor, layers, relu_mask: Optional[int] = None) -> torch.Tensor:
     """One-shot convenience: pack ``layers`` and apply them to rows x [..., C]."""
     return PackedMLP(layers, False, x.device, relu_mask).rows(x)
+
+
+# ---- backward of the chains (SPEC.md §32, csrc/mlp_grad.hip) -------------------------------------------------------------
+NEED_BITS = {"feat": _lib.GRAD_FEAT, "xyz": _lib.GRAD_XYZ, "new_xyz": _lib.GRAD_NEW_XYZ, "params": _lib.GRAD_PARAMS}
+GRAD_WS_BUDGET: int = 1 << 30      # bytes of workspace a call allocates at most when it is given none (it then works in chunks)
+
+
+def _need_mask(need, allowed: int, default: int) -> int:
+    if need is None:
+        return default
+    if isinstance(need, str):
+        need = (need,)
+    m = 0
+    for n in need:
+        if n not in NEED_BITS:
+            raise ValueError(f"need: unknown gradient '{n}' (one of {sorted(NEED_BITS)})")
+        m |= NEED_BITS[n]
+    if m == 0 or m & ~allowed:
+        raise ValueError("need: empty, or asks for a gradient this call does not have")
+    return m
+
+
+def _grad_layers(layers) -> Tuple[list, list, list]:
+    """Unpacked layers [(W [C_l, C_{l-1}], b [C_l])] checked -> (Ws, bs, dims)."""
+    if not 1 <= len(layers) <= _lib.MAX_LAYERS:
+        raise ValueError(f"1..{_lib.MAX_LAYERS} layers supported")
+    Ws, bs = [], []
+    for l, (w, b) in enumerate(layers):
+        if not isinstance(w, torch.Tensor) or not isinstance(b, torch.Tensor):
+            raise TypeError("layers: expected (W, b) pairs of tensors")
+        w = ops._strict(w.detach(), f"W[{l}]", torch.float32, (None, None))
+        b = ops._strict(b.detach(), f"b[{l}]", torch.float32, (None,))
+        if b.shape[0] != w.shape[0] or (Ws and w.shape[1] != Ws[-1].shape[0]) or min(w.shape) < 1:
+            raise ValueError("layer shapes do not chain")
+        Ws.append(w)
+        bs.append(b)
+    return Ws, bs, [Ws[0].shape[1]] + [w.shape[0] for w in Ws]
+
+
+def _grad_rows_check(t: torch.Tensor, name: str, rows_shape: tuple, width: int, col_off: int) -> None:
+    """A gradient / pooled tensor [*rows_shape, ld] that is read as rows of ``width`` columns from ``col_off``: float32 and wide
+    enough (judged before any device)."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        raise TypeError(f"{name}: expected a float32 tensor")
+    if t.dim() != len(rows_shape) + 1 or tuple(t.shape[:-1]) != tuple(rows_shape):
+        raise ValueError(f"{name}: expected shape {list(rows_shape)} + [ld], got {list(t.shape)}")
+    if col_off < 0 or col_off + width > t.shape[-1]:
+        raise ValueError(f"{name}: col_off + C_L = {col_off + width} exceeds its width {t.shape[-1]}")
+
+
+def _grad_rows_read(t: torch.Tensor, name: str) -> torch.Tensor:
+    """Rows at one stride with unit column stride are read where they lie, anything else through a packed copy."""
+    uniform = t.stride(-1) == 1 and t.stride(-2) >= t.shape[-1] and all(t.stride(i) == t.stride(i + 1) * t.shape[i + 1]
+                                                                          for i in range(t.dim() - 2))
+    if not uniform:
+        ops._unrecordable(f"{name}: strided copy")
+        t = t.contiguous()
+    return t
+
+
+def _grad_on_gpu(named) -> None:
+    for name, t in named:
+        if t is not None:
+            if not t.is_cuda:
+                raise RuntimeError(f"{name}: expected a GPU tensor (sad_amd has no CPU path)")
+            ops._on_current_device(t, name)
+
+
+def mlp_grad_workspace_bytes(B: int, M: int, S: int, dims: Sequence[int], grouped: bool = True, has_cnt: bool = True) -> Tuple[int, int]:
+    """(minimum, no-chunking size) in bytes of the workspace of ``grouped_mlp_grad`` (``grouped``) / ``mlp_rows_grad`` (B = 1, M = rows)."""
+    lo, hi = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    check(lib().sad_mlp_grad_workspace_bytes(int(B), int(M), int(S), int(grouped), int(has_cnt), len(dims) - 1,
+                                             (ctypes.c_int * len(dims))(*[int(d) for d in dims]), ctypes.byref(lo), ctypes.byref(hi)),
+          "sad_mlp_grad_workspace_bytes")
+    return lo.value, hi.value
+
+
+def _grad_budget(sizes, workspace, budget) -> int:
+    """Bytes to allocate when no workspace is given: the no-chunking size, capped by the budget, which may not be below the minimum."""
+    lo, hi = sizes
+    cap = GRAD_WS_BUDGET if budget is None else int(budget)
+    if workspace is None and cap < lo:
+        raise ValueError(f"workspace budget of {cap} bytes is below the minimum of {lo} (mlp_grad_workspace_bytes)")
+    return min(hi, cap)
+
+
+def _grad_call(a, Ws, bs, dims, need: int, spec, out, workspace, nbytes: int, lo: int, dev, maker: str):
+    """Fills the layer / output / workspace fields of ``a`` -> ({name: output tensor}, workspace)."""
+    L = len(Ws)
+    a.struct_size = ctypes.sizeof(_lib.MlpGradArgs)
+    a.L, a.need = L, need
+    for i, d in enumerate(dims):
+        a.dims[i] = d
+    for l in range(L):
+        a.W[l], a.b[l] = Ws[l].data_ptr(), bs[l].data_ptr()
+    if need & _lib.GRAD_PARAMS:
+        spec = list(spec) + [(f"grad_W{l}", tuple(Ws[l].shape), torch.float32) for l in range(L)] \
+            + [(f"grad_b{l}", tuple(bs[l].shape), torch.float32) for l in range(L)]
+    outs = dict(zip([n for n, _, _ in spec], ops._outputs(spec, out, dev, maker)))
+    workspace = ops._workspace(nbytes if workspace is None else lo, workspace, dev, "mlp_grad_workspace_bytes", align=16)
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    if need & _lib.GRAD_PARAMS:
+        for l in range(L):
+            a.grad_W[l], a.grad_b[l] = outs[f"grad_W{l}"].data_ptr(), outs[f"grad_b{l}"].data_ptr()
+    return outs, workspace
+
+
+def _param_lists(outs: dict, L: int, need: int):
+    if not need & _lib.GRAD_PARAMS:
+        return None, None
+    return [outs[f"grad_W{l}"] for l in range(L)], [outs[f"grad_b{l}"] for l in range(L)]
+
+
+def grouped_mlp_grad(xyz: torch.Tensor, feat_pm: Optional[torch.Tensor], new_xyz: torch.Tensor, idx: torch.Tensor,
+                     cnt: Optional[torch.Tensor], layers, pooled: torch.Tensor, grad_out: torch.Tensor, col_off: int = 0,
+                     pooled_off: int = 0, skip_empty: bool = False, need=None, out: Optional[tuple] = None,
+                     workspace: Optional[torch.Tensor] = None, budget_bytes: Optional[int] = None):
+    """Backward of ``PackedMLP.grouped`` (SPEC.md §32).  Inputs as the forward's, ``layers`` = the UNPACKED [(W_l, b_l)] GPU tensors,
+    ``pooled`` [B,M,ldp] the forward's output (columns pooled_off .. + C_L), ``grad_out`` [B,M,ld] read at columns col_off .. + C_L.
+    ``need``: names out of ("feat", "xyz", "new_xyz", "params"), default all that exist; ``out``: the buffers to write, in the order
+    (grad_feat, grad_xyz, grad_new_xyz, grad_W..., grad_b...) restricted to what is needed.  ``workspace``: at least the minimum of
+    ``mlp_grad_workspace_bytes``; else one of at most ``budget_bytes`` (default ``GRAD_WS_BUDGET``) is allocated and the groups
+    are processed in chunks.  -> (grad_feat [B,N,C], grad_xyz [B,N,3], grad_new_xyz [B,M,3], [grad_W], [grad_b], mismatch) with
+    None for what was not asked; ``mismatch`` is a 1-element int32 GPU tensor (a view of the workspace: reading it synchronises,
+    the call does not): 0 whenever ``pooled`` is the forward's.  Shapes and dtypes are judged before devices."""
+    xyz = ops._strict(xyz, "xyz", torch.float32, (None, None, 3), "[B,N,3]")
+    B, N, _ = xyz.shape
+    idx = ops._strict(idx, "idx", torch.int32, (B, None, None), "[B,M,S]")
+    _, M, S = idx.shape
+    new_xyz = ops._strict(new_xyz, "new_xyz", torch.float32, (B, M, 3), "[B,M,3]")
+    if min(B, N, M) < 1:
+        raise ValueError("B, N and M must be >= 1")
+    if not 1 <= S <= 64:
+        raise ValueError(f"S = {S}: the grouped chain takes 1 .. 64 samples")
+    Ws, bs, dims = _grad_layers(layers)
+    C = 0
+    if feat_pm is not None:
+        if not isinstance(feat_pm, torch.Tensor) or feat_pm.dtype != torch.float32:
+            raise TypeError("feat_pm: expected a float32 tensor")
+        if feat_pm.dim() != 3 or feat_pm.shape[0] != B or feat_pm.shape[1] != N or feat_pm.shape[2] < 1:
+            raise ValueError("feat_pm: expected [B,N,C]")
+        C = feat_pm.shape[2]
+    if dims[0] != C + 3:
+        raise ValueError(f"MLP expects {dims[0] - 3} feature channels, got {C}")
+    if cnt is not None:
+        cnt = ops._strict(cnt, "cnt", torch.int32, (B, M), "[B,M]")
+    elif skip_empty:
+        raise ValueError("skip_empty needs cnt")
+    _grad_rows_check(pooled, "pooled", (B, M), dims[-1], pooled_off)
+    _grad_rows_check(grad_out, "grad_out", (B, M), dims[-1], col_off)
+    allowed = _lib.GRAD_XYZ | _lib.GRAD_NEW_XYZ | _lib.GRAD_PARAMS | (_lib.GRAD_FEAT if C else 0)
+    need = _need_mask(need, allowed, allowed)
+    sizes = mlp_grad_workspace_bytes(B, M, S, dims, True, cnt is not None)
+    nbytes = _grad_budget(sizes, workspace, budget_bytes)
+    _grad_on_gpu([("xyz", xyz), ("new_xyz", new_xyz), ("idx", idx), ("cnt", cnt), ("feat_pm", feat_pm), ("pooled", pooled), ("grad_out", grad_out)]
+                 + [(f"W[{l}]", w) for l, w in enumerate(Ws)] + [(f"b[{l}]", b) for l, b in enumerate(bs)])
+    a = _lib.MlpGradArgs()
+    if feat_pm is not None:
+        if feat_pm.stride(2) != 1 or feat_pm.stride(0) != N * feat_pm.stride(1) or feat_pm.stride(1) < C:
+            ops._unrecordable("feat_pm: strided copy")
+            feat_pm = feat_pm.contiguous()
+        a.feat, a.ld_feat = feat_pm.data_ptr(), feat_pm.stride(1)
+    pooled, grad_out = _grad_rows_read(pooled, "pooled"), _grad_rows_read(grad_out, "grad_out")
+    spec = [(n, s, torch.float32) for n, s, bit in (("grad_feat", (B, N, C), _lib.GRAD_FEAT), ("grad_xyz", (B, N, 3), _lib.GRAD_XYZ),
+                                                    ("grad_new_xyz", (B, M, 3), _lib.GRAD_NEW_XYZ)) if need & bit]
+    a.xyz, a.new_xyz, a.idx, a.cnt = xyz.data_ptr(), new_xyz.data_ptr(), idx.data_ptr(), ops._ptr(cnt)
+    a.B, a.N, a.M, a.S, a.C = B, N, M, S, C
+    a.relu_mask, a.skip_empty = (1 << len(Ws)) - 1, int(bool(skip_empty))
+    a.pooled, a.ld_pooled, a.pooled_off = pooled.data_ptr(), pooled.stride(-2), int(pooled_off)
+    a.grad_out, a.ld_grad, a.col_off = grad_out.data_ptr(), grad_out.stride(-2), int(col_off)
+    outs, workspace = _grad_call(a, Ws, bs, dims, need, spec, out, workspace, nbytes, sizes[0], xyz.device, "grouped_mlp_grad")
+    a.grad_feat, a.grad_xyz, a.grad_new_xyz = ops._ptr(outs.get("grad_feat")), ops._ptr(outs.get("grad_xyz")), ops._ptr(outs.get("grad_new_xyz"))
+    with ops._timed("mlp_grad", f"g{B * M}s{S}"):
+        check(lib().sad_mlp_grad_f32(ctypes.byref(a), ops._stream()), "sad_mlp_grad_f32")
+    return (outs.get("grad_feat"), outs.get("grad_xyz"), outs.get("grad_new_xyz")) + _param_lists(outs, len(Ws), need) \
+        + (workspace[:4].view(torch.int32),)
+
+
+def mlp_rows_grad(x: torch.Tensor, layers, grad_out: torch.Tensor, relu_mask: Optional[int] = None, col_off: int = 0, need=None,
+                  out: Optional[tuple] = None, workspace: Optional[torch.Tensor] = None, budget_bytes: Optional[int] = None):
+    """Backward of ``PackedMLP.rows`` (SPEC.md §32): x [..., C_0] (unit last-dim stride), ``layers`` unpacked, ``relu_mask`` bit l = ReLU
+    after layer l (default: all), ``grad_out`` [..., ld] read at columns col_off .. + C_L.  ``need`` out of ("feat", "params"):
+    "feat" is the gradient of x.  ``out`` / ``workspace`` / ``budget_bytes`` as for ``grouped_mlp_grad`` (grad_x as [rows, C_0]).
+    -> (grad_x [..., C_0], [grad_W], [grad_b]), None for what was not asked."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+        raise TypeError("x: expected a float32 tensor")
+    Ws, bs, dims = _grad_layers(layers)
+    L = len(Ws)
+    if x.dim() < 1 or x.shape[-1] != dims[0]:
+        raise ValueError(f"MLP expects {dims[0]} channels, got x of shape {list(x.shape)}")
+    R = x.numel() // dims[0]
+    if R < 1:
+        raise ValueError("x: at least one row")
+    relu_mask = (1 << L) - 1 if relu_mask is None else int(relu_mask)
+    if relu_mask & ~((1 << L) - 1):
+        raise ValueError("relu_mask: a bit beyond the last layer")
+    _grad_rows_check(grad_out, "grad_out", tuple(x.shape[:-1]), dims[-1], col_off)
+    allowed = _lib.GRAD_FEAT | _lib.GRAD_PARAMS
+    need = _need_mask(need, allowed, allowed)
+    sizes = mlp_grad_workspace_bytes(1, R, 1, dims, False, False)
+    nbytes = _grad_budget(sizes, workspace, budget_bytes)
+    _grad_on_gpu([("x", x), ("grad_out", grad_out)] + [(f"W[{l}]", w) for l, w in enumerate(Ws)] + [(f"b[{l}]", b) for l, b in enumerate(bs)])
+    x2 = _grad_rows_read(x if x.dim() > 1 else x.unsqueeze(0), "x")
+    x2 = x2.view(-1, dims[0]) if x2.dim() != 2 else x2
+    g2 = _grad_rows_read(grad_out if grad_out.dim() > 1 else grad_out.unsqueeze(0), "grad_out")
+    g2 = g2.view(-1, g2.shape[-1]) if g2.dim() != 2 else g2
+    spec = [("grad_feat", (R, dims[0]), torch.float32)] if need & _lib.GRAD_FEAT else []
+    a = _lib.MlpGradArgs()
+    a.feat, a.ld_feat = x2.data_ptr(), x2.stride(0)
+    a.B, a.N, a.M, a.S, a.C = 1, 0, R, 1, dims[0]
+    a.relu_mask = relu_mask
+    a.grad_out, a.ld_grad, a.col_off = g2.data_ptr(), g2.stride(0), int(col_off)
+    outs, workspace = _grad_call(a, Ws, bs, dims, need, spec, out, workspace, nbytes, sizes[0], x.device, "mlp_rows_grad")
+    a.grad_feat = ops._ptr(outs.get("grad_feat"))
+    with ops._timed("mlp_grad", f"r{R}"):
+        check(lib().sad_mlp_grad_f32(ctypes.byref(a), ops._stream()), "sad_mlp_grad_f32")
+    gx = outs.get("grad_feat")
+    return (gx.view(tuple(x.shape)) if gx is not None else None,) + _param_lists(outs, L, need)
 
 
 # Last, because ops.py closes with a re-export of the names above: whichever of the two modules is imported first, the other

@@ -1975,4 +1975,4 @@ def voxel_query(coors: torch.Tensor, offsets: torch.Tensor, spatial_shape, voxel
 # The fused MLP chains (PackedMLP / PackedMLPBf16, grouped_multi, rowscan_multi, the autotuner) live in mlp.py; they belong
 # to this operator surface, so their public names are re-exported here (the same objects).
 from .mlp import (GroupedCall, PackedMLP, PackedMLPBf16, check_workspace, choose_stage_assignment, cont_buffer,  # noqa: E402,F401
-                  grouped_multi, mlp_chain, rowscan_multi, workspace_status)
+                  grouped_mlp_grad, grouped_multi, mlp_chain, mlp_grad_workspace_bytes, mlp_rows_grad, rowscan_multi, workspace_status)

@@ -175,6 +175,65 @@ class SAModuleMSG(nn.Module):
         return new_xyz, out_pm.transpose(1, 2).contiguous()
 
 
+class SAModuleMSGTrain(nn.Module):
+    """The trainable counterpart of ``SAModuleMSG`` (f32): built from the same ``SAStage`` and weights dict, same ``forward_pm`` /
+    ``forward`` surface.  Sampling and the ball query run under ``no_grad``; every branch is a ``SharedMLP`` (fused forward, the
+    backward of SPEC.md §32), so is the aggregation layer.  Without gradients the branches write into slices of one zeroed buffer
+    and the result equals ``SAModuleMSG``'s on the ``export()``ed weights bit for bit; with gradients each branch returns its
+    own pooled tensor (what its backward keeps) and the slices are concatenated.  Parameters are created with
+    ``requires_grad=False``: ``module.requires_grad_(True)`` selects training."""
+
+    def __init__(self, in_channels: int, stage: SAStage, device, weights: Optional[dict] = None, seed: int = 0, name: str = "sa"):
+        super().__init__()
+        from .shared_mlp import SharedMLP
+        self.stage = stage
+        self.in_channels = in_channels
+        if weights is None:
+            rng = np.random.default_rng(seed)
+            weights = {f"b{i}": make_mlp_weights([in_channels + 3] + list(m), rng) for i, m in enumerate(stage.mlps)}
+            if stage.agg:
+                weights["agg"] = make_mlp_weights([sum(m[-1] for m in stage.mlps), stage.agg], rng)
+        self.branches = nn.ModuleList([SharedMLP([in_channels + 3] + list(m), True, layers=weights[f"b{i}"], name=f"{name}.b{i}")
+                                       for i, m in enumerate(stage.mlps)])
+        self.cat_channels = sum(m[-1] for m in stage.mlps)
+        self.agg = SharedMLP([self.cat_channels, stage.agg], False, layers=weights["agg"], name=f"{name}.agg") if stage.agg else None
+        self.out_channels = stage.agg if stage.agg else self.cat_channels
+        self.to(torch.device(device))
+
+    def forward_pm(self, xyz: torch.Tensor, feat_pm: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """feat_pm [B,N,C] point-major -> (new_xyz [B,M,3], new_feat_pm [B,M,C'])."""
+        st = self.stage
+        with torch.no_grad():
+            new_xyz = ops.gather_xyz(xyz, ops.fps(xyz, st.npoint))
+            idxs, cnts = ops.ball_query_multi(st.radii, st.nsamples, xyz, new_xyz, None, return_counts=True)
+        train = torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters())
+                                             or (feat_pm is not None and feat_pm.requires_grad) or xyz.requires_grad)
+        if train:
+            outs = [mlp.grouped(xyz, feat_pm, new_xyz, idx, cnt) for mlp, idx, cnt in zip(self.branches, idxs, cnts)]
+            cat = outs[0] if len(outs) == 1 else torch.cat(outs, 2)
+        else:
+            with torch.no_grad():
+                cat = torch.zeros((new_xyz.shape[0], new_xyz.shape[1], self.cat_channels), dtype=torch.float32, device=xyz.device)
+                off = 0
+                for mlp, idx, cnt in zip(self.branches, idxs, cnts):
+                    mlp.packed().grouped(xyz, feat_pm, new_xyz, idx, out=cat, col_off=off, cnt=cnt)
+                    off += mlp.out_channels
+        return new_xyz, (cat if self.agg is None else self.agg.rows(cat))
+
+    def forward(self, xyz: torch.Tensor, features: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Drop-in surface: features [B,C,N] channel-major -> (new_xyz, new_features [B,C',M])."""
+        feat_pm = features.transpose(1, 2).contiguous() if features is not None else None
+        new_xyz, out_pm = self.forward_pm(xyz, feat_pm)
+        return new_xyz, out_pm.transpose(1, 2).contiguous()
+
+    def export(self) -> dict:
+        """The weights dict ``SAModuleMSG`` takes: {"b<i>": [(W, b), ...], "agg": [(W, b)]} as numpy arrays."""
+        w = {f"b{i}": mlp.export() for i, mlp in enumerate(self.branches)}
+        if self.agg is not None:
+            w["agg"] = self.agg.export()
+        return w
+
+
 class SAModule(SAModuleMSG):
     """Single-radius set abstraction = the one-branch case (BASELINE.json configs[0])."""
 

@@ -10,7 +10,8 @@ centres are §24's formula evaluated by framework elementwise operations (a mult
 own), not by a kernel of this package.
 
 Inference (no gradient asked for) runs the fused ``PackedMLP.grouped`` per scale into one zeroed buffer.  Training runs the same
-rows through ``autograd.GroupPoints``, the module's layers as framework matrix products, and ``autograd.MaxPoolS``.  One set of
+rows through ``autograd.GroupPoints``, the module's layers as framework matrix products, and ``autograd.MaxPoolS`` - or, with
+``fused_grad=True``, through the fused chain and its own backward (SPEC.md §32).  One set of
 weights (BatchNorm folded in, as everywhere here) serves both; the packed chain is rebuilt when a weight changes, as the sparse
 convolution layers rebuild theirs.  Parameters are created with ``requires_grad=False``, like those layers:
 ``module.requires_grad_(True)``, or features that require grad, select the training path.
@@ -25,6 +26,7 @@ import torch
 from torch import nn
 
 from . import autograd, ops
+from .shared_mlp import grouped_chain, packed_for
 from .spconv import SparseTensor
 
 
@@ -35,10 +37,14 @@ class VoxelRoIPool(nn.Module):
     (x0,y0,z0,x1,y1,z1) is the detector's.  ``weight[k]`` / ``bias[k]`` hold scale k's layers ([C_out,C_in] each, the first over
     [relative xyz (3) | features (C)]), ReLU after every layer.
 
+    ``fused_grad``: the training path of a scale is the fused chain with the backward of SPEC.md §32 (``SharedMLP``'s path: the
+    forward is the inference kernel, nothing but inputs and output is kept) instead of the unfused composition.
+
     forward(rois [B,R,D>=7], roi_count [B] int32 | None, tensors) -> pooled [B,R,G^3,sum C_out]."""
 
-    def __init__(self, grid_size: int, scales: Sequence[dict], point_range: Sequence[float]):
+    def __init__(self, grid_size: int, scales: Sequence[dict], point_range: Sequence[float], fused_grad: bool = False):
         super().__init__()
+        self.fused_grad = bool(fused_grad)
         self.grid_size = int(grid_size)
         if not 1 <= self.grid_size <= 16:
             raise ValueError(f"grid_size: expected 1 .. 16, got {grid_size}")
@@ -75,11 +81,7 @@ class VoxelRoIPool(nn.Module):
 
     def packed(self, k: int) -> "ops.PackedMLP":
         """Scale k's layers as the fused chain reads them; repacked when a parameter was replaced or written."""
-        params = list(self.weight[k]) + list(self.bias[k])
-        key = tuple((p.data_ptr(), p._version) for p in params)
-        if self._packed[k] is None or self._packed[k][0] != key:
-            layers = [(w.data, b.data) for w, b in zip(self.weight[k], self.bias[k])]
-            self._packed[k] = (key, ops.PackedMLP(layers, True, params[0].device, name=f"voxel_roi_pool{k}"))
+        self._packed[k] = packed_for(self._packed[k], self.weight[k], self.bias[k], True, name=f"voxel_roi_pool{k}")
         return self._packed[k][1]
 
     def centres(self, k: int, coors: torch.Tensor) -> torch.Tensor:
@@ -118,7 +120,11 @@ class VoxelRoIPool(nn.Module):
                 idx, cnt = idx.view(1, B * M, s["nsample"]), cnt.view(1, B * M)
                 xyz = self.centres(k, t.coors).unsqueeze(0)
                 empty = cnt.view(B * M, 1) == 0
-            if train:
+            if train and self.fused_grad:
+                # the fused chain forward, its own backward (SPEC.md §32); empty groups (NaN coordinates among them) give no gradient
+                rows = grouped_chain(self.packed(k), self.weight[k], self.bias[k], xyz, t.feat.unsqueeze(0), new_xyz, idx, cnt, skip_empty=True)
+                cols.append(rows[0].masked_fill(empty, 0.0))
+            elif train:
                 cols.append(self._train_rows(k, t.feat, xyz, new_xyz, idx).masked_fill(empty, 0.0))
             else:
                 with torch.no_grad():

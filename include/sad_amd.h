@@ -926,6 +926,57 @@ typedef struct sad_point_head_loss_args {
 size_t sad_point_head_loss_workspace_bytes(int B, int M);   /* 16*B*ceil(M/256); 0 outside the limits */
 int sad_point_head_loss_f32(const sad_point_head_loss_args *args, sad_stream_t stream);
 
+/* SPEC.md §32 (backward of the MLP chains; additions of ABI 4 as well).  One entry serves both forms: idx != NULL is the grouped
+ * chain + max-pool of §6, idx == NULL plain rows.  The activations are recomputed (§6 is bit-reproducible), so the call needs the
+ * forward's inputs, its pooled output (grouped form) and the UNPACKED layers W[l] [dims[l+1], dims[l]] row-major, b[l] [dims[l+1]].
+ * grouped: xyz[B,N,3], feat[B,N,C] at row stride ld_feat (NULL iff C == 0), new_xyz[B,M,3], idx[B,M,S], cnt[B,M] or NULL (every
+ *   slot is a row), dims[0] = C + 3, relu_mask = all layers; pooled / grad_out: row g = b M + m at g * ld + offset, C_L wide.
+ *   skip_empty != 0: groups with cnt == 0 contribute to no gradient (their coordinates may be NaN).
+ * plain rows: B = 1, M = R rows, x[R, dims[0]] in feat at row stride ld_feat, C = dims[0], any relu_mask (bit l = ReLU after
+ *   layer l, counted from 0), grad_out[R, C_L] likewise; grad_x[R, dims[0]] contiguous goes to grad_feat.
+ * need: SAD_GRAD_FEAT | SAD_GRAD_XYZ | SAD_GRAD_NEW_XYZ | SAD_GRAD_PARAMS; what is not asked for is neither computed nor
+ *   written, and its pointer may be NULL.  grad_feat[B,N,C], grad_xyz[B,N,3], grad_new_xyz[B,M,3], grad_W[l], grad_b[l] are
+ *   OVERWRITTEN.  binary32 sums whose order is not specified (float atomics): two calls may differ in the last bits.
+ * workspace: 16-byte aligned, workspace_bytes >= *min_bytes of sad_mlp_grad_workspace_bytes; the groups (rows) are processed in
+ *   chunks that fit, *full_bytes holds all of them at once.  Its first int32 is `mismatch` after the call: the (group, channel)
+ *   pairs whose pooled value no recomputed row attains; 0 whenever pooled came from sad_mlp_chain_f32 with the same layers.
+ * 1 <= L <= SAD_MAX_LAYERS, S <= 64, B * M * S < 2^29 (SAD_EUNSUPPORTED above), every width 1 .. 65536. */
+#define SAD_GRAD_FEAT 1
+#define SAD_GRAD_XYZ 2
+#define SAD_GRAD_NEW_XYZ 4
+#define SAD_GRAD_PARAMS 8
+typedef struct sad_mlp_grad_args {
+    size_t struct_size;   /* = sizeof(sad_mlp_grad_args) */
+    const float *xyz;              /* [B,N,3] (grouped) */
+    const float *new_xyz;          /* [B,M,3] (grouped) */
+    const float *feat;             /* [B,N,C] or NULL; plain rows: x */
+    const int32_t *idx;            /* [B,M,S]; NULL = plain rows */
+    const int32_t *cnt;            /* [B,M] or NULL */
+    int ld_feat;
+    int B, N, M, S, C;
+    int L;
+    int dims[SAD_MAX_LAYERS + 1];
+    const float *W[SAD_MAX_LAYERS];
+    const float *b[SAD_MAX_LAYERS];
+    int relu_mask;
+    int skip_empty;
+    const float *pooled;           /* grouped: the forward's output */
+    int ld_pooled, pooled_off;
+    const float *grad_out;
+    int ld_grad, col_off;
+    int need;
+    float *grad_feat;              /* plain rows: grad_x */
+    float *grad_xyz;
+    float *grad_new_xyz;
+    float *grad_W[SAD_MAX_LAYERS];
+    float *grad_b[SAD_MAX_LAYERS];
+    void *workspace;
+    size_t workspace_bytes;
+} sad_mlp_grad_args;
+int sad_mlp_grad_workspace_bytes(int B, int M, int S, int grouped, int has_cnt, int L, const int *dims, size_t *min_bytes,
+                                 size_t *full_bytes);
+int sad_mlp_grad_f32(const sad_mlp_grad_args *args, sad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

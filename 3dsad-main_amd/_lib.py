@@ -334,6 +334,8 @@ SIGNATURES = {
     "sad_candidates_f32": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_float, ctypes.c_float, ctypes.c_float, c_f32p,
                                          vp, vp, vp]),
+    "sad_candidates_grad_f32": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, vp, vp]),
+    "sad_prefix_rows_grad_f32": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
     "sad_nms_bev_f32": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float,
                                       vp, vp, vp, vp]),
     "sad_nms_bev_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),

@@ -515,3 +515,41 @@ class MLPRows(torch.autograd.Function):
         gx, gW, gb = ops.mlp_rows_grad(x, _layers_of(params), grad_out, relu_mask=ctx.relu_mask, need=need)
         gp = [g if w else None for g, w in zip((gW or []) + (gb or []), want[2:])] if gW is not None else [None] * len(params)
         return (None, gx, *gp)
+
+
+class Candidates(torch.autograd.Function):
+    """§8 steps 2-4 with the backward of §33.1: ``apply(xyz3 [B,M3,3], c [B,K,6], K, shift_max, r_min, r_max, anchor) -> (cand
+    [B,K,3], radius [B,K])``.  The forward is ``ops.candidates``; ``radius`` is not differentiable (it feeds an index decision);
+    the backward returns ``ops.candidates_grad`` for c.  No gradient with respect to xyz3 is offered: SA3's centroids are
+    sampled input points."""
+
+    @staticmethod
+    def forward(ctx, xyz3, c, K, shift_max, r_min, r_max, anchor):
+        cand, radius = ops.candidates(xyz3, c, K, shift_max, r_min, r_max, anchor)
+        ctx.save_for_backward(c)
+        ctx.shift_max = shift_max
+        ctx.mark_non_differentiable(radius)
+        return cand, radius
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_cand, _grad_radius):
+        (c,) = ctx.saved_tensors
+        return None, ops.candidates_grad(c, grad_cand.contiguous(), ctx.shift_max), None, None, None, None, None
+
+
+class PrefixRows(torch.autograd.Function):
+    """``apply(x [B,M,C] f32, K) -> x[:, :K]`` packed (``ops.prefix_rows``, one library launch) with the backward of §33.2
+    (``ops.prefix_rows_grad``: the padded gradient in one launch, no zero fill).  ``K == M``: the identity, no copy."""
+
+    @staticmethod
+    def forward(ctx, x, K):
+        ctx.M = x.shape[1]
+        return x if K == ctx.M else ops.prefix_rows(_f32(x, "x", 3), K)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        if grad_out.shape[1] == ctx.M:
+            return grad_out, None
+        return ops.prefix_rows_grad(grad_out.contiguous(), ctx.M), None

@@ -1,4 +1,4 @@
-// Candidate centres + adaptive radius (SPEC.md §8 steps 2-4) and box decode (SPEC.md §9).
+// Candidate centres + adaptive radius (SPEC.md §8 steps 2-4), their backward (SPEC.md §33) and box decode (SPEC.md §9).
 // No reference source exists (/root/reference/README.md:1-2).  Tiny element-wise kernels.
 #include "common.h"
 
@@ -43,6 +43,24 @@ __global__ __launch_bounds__(256) void candidates_kernel(const float *__restrict
     radius[(size_t)b * K + i] = r;
 }
 
+// SPEC.md §33.1: the backward of §8 step 2 with respect to c.  A selection (the clamp passes the gradient on its closed
+// interval, a NaN c fails both comparisons), never a multiplication; the size columns feed an index decision only: +0.
+__global__ __launch_bounds__(256) void candidates_grad_kernel(const float *__restrict__ c, const float *__restrict__ grad_cand,
+                                                              int K, float shift_max, float *__restrict__ grad_c) {
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= K) return;
+    const float *ci = c + ((size_t)b * K + i) * 6;
+    const float *g = grad_cand + ((size_t)b * K + i) * 3;
+    float *o = grad_c + ((size_t)b * K + i) * 6;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const float sh = ci[d];
+        o[d] = (sh >= -shift_max && sh <= shift_max) ? g[d] : 0.0f;
+        o[3 + d] = 0.0f;
+    }
+}
+
 __global__ __launch_bounds__(256) void decode_kernel(const float *__restrict__ cand,
                                                      const float *__restrict__ o, int total, F9 anchors,
                                                      float *__restrict__ boxes) {
@@ -83,6 +101,18 @@ SAD_API int sad_candidates_f32(const float *xyz3, const float *c, int B, int M3,
     hipLaunchKernelGGL(candidates_kernel, grid, dim3(256), 0, (hipStream_t)stream, xyz3, c, M3, K,
                        shift_max, r_min, r_max, a, cand, radius);
     return sad::check_launch("sad_candidates_f32");
+}
+
+SAD_API int sad_candidates_grad_f32(const float *c, const float *grad_cand, int B, int K, float shift_max, float *grad_c,
+                                    sad_stream_t stream) {
+    SAD_REQUIRE(c && grad_cand && grad_c, "sad_candidates_grad_f32: NULL pointer");
+    SAD_REQUIRE(B >= 1 && K >= 1, "sad_candidates_grad_f32: need B >= 1 and K >= 1 (B=%d K=%d)", B, K);
+    SAD_REQUIRE(shift_max >= 0.0f, "sad_candidates_grad_f32: shift_max must be >= 0 and not NaN");
+    if (B > 65535 || (long long)B * K >= (1LL << 31))
+        return sad::fail(SAD_EUNSUPPORTED, "sad_candidates_grad_f32: B <= 65535 and B * K < 2^31 supported (B=%d K=%d)", B, K);
+    dim3 grid((K + 255) / 256, B);
+    hipLaunchKernelGGL(candidates_grad_kernel, grid, dim3(256), 0, (hipStream_t)stream, c, grad_cand, K, shift_max, grad_c);
+    return sad::check_launch("sad_candidates_grad_f32");
 }
 
 SAD_API int sad_decode_boxes_f32(const float *cand, const float *o, int B, int K, const float *anchors,
@@ -175,4 +205,43 @@ SAD_API int sad_copy_rows_u32(const void *src, long long src_stride_words, void 
         hipLaunchKernelGGL(copy_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const unsigned *>(src),
                            src_stride_words, reinterpret_cast<unsigned *>(dst), dst_stride_words, total, (unsigned)row_words);
     return sad::check_launch("sad_copy_rows_u32");
+}
+
+// ---- SPEC.md §33.2: the backward of ops.prefix_rows ------------------------------------------------------------
+// out[b, :K] = g[b], out[b, K:] = +0: every word of out written exactly once (no fill in front), words handled as the row
+// copy above handles them (16-byte chunks when both scene lengths allow).
+namespace {
+template <typename W>
+__global__ __launch_bounds__(256) void prefix_rows_grad_kernel(const W *__restrict__ g, long long in_scene, W *__restrict__ out,
+                                                               long long out_scene, long long total) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long b = i / out_scene;
+        const long long w = i - b * out_scene;
+        W v{};
+        if (w < in_scene) v = g[b * in_scene + w];
+        out[i] = v;
+    }
+}
+}  // namespace
+
+SAD_API int sad_prefix_rows_grad_f32(const float *g, int B, int K, int M, int C, float *out, sad_stream_t stream) {
+    SAD_REQUIRE(g && out, "sad_prefix_rows_grad_f32: NULL pointer");
+    SAD_REQUIRE(B >= 1 && C >= 1 && K >= 1 && K <= M, "sad_prefix_rows_grad_f32: need B >= 1, C >= 1 and 1 <= K <= M (B=%d K=%d M=%d C=%d)",
+                B, K, M, C);
+    SAD_REQUIRE(((uintptr_t)g & 3) == 0 && ((uintptr_t)out & 3) == 0, "sad_prefix_rows_grad_f32: pointers must be 4-byte aligned");
+    const long long in_scene = (long long)K * C, out_scene = (long long)M * C;
+    if (out_scene > (1LL << 40) / B)
+        return sad::fail(SAD_EUNSUPPORTED, "sad_prefix_rows_grad_f32: B * M * C <= 2^40 supported (B=%d M=%d C=%d)", B, M, C);
+    const bool v4 = in_scene % 4 == 0 && out_scene % 4 == 0 && (((uintptr_t)g | (uintptr_t)out) & 15) == 0;
+    const long long total = v4 ? B * (out_scene / 4) : B * out_scene;
+    long long blocks = (total + 255) / 256;
+    const long long cap = (long long)sad::device_cus() * 16;
+    if (blocks > cap) blocks = cap;
+    if (v4)
+        hipLaunchKernelGGL(prefix_rows_grad_kernel<uint4>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                           reinterpret_cast<const uint4 *>(g), in_scene / 4, reinterpret_cast<uint4 *>(out), out_scene / 4, total);
+    else
+        hipLaunchKernelGGL(prefix_rows_grad_kernel<unsigned>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                           reinterpret_cast<const unsigned *>(g), in_scene, reinterpret_cast<unsigned *>(out), out_scene, total);
+    return sad::check_launch("sad_prefix_rows_grad_f32");
 }

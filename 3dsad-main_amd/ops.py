@@ -1890,6 +1890,86 @@ def point_head_loss(o: torch.Tensor, c: Optional[torch.Tensor], labels: torch.Te
     return outs
 
 
+def candidates_grad_output_spec(B: int, K: int) -> tuple:
+    """((name, shape, dtype),) of ``candidates_grad``'s output, what its ``out=`` is checked against."""
+    return (("grad_c", (B, K, 6), torch.float32),)
+
+
+def prefix_rows_grad_output_spec(B: int, M: int, C: int) -> tuple:
+    """((name, shape, dtype),) of ``prefix_rows_grad``'s output, what its ``out=`` is checked against."""
+    return (("out", (B, M, C), torch.float32),)
+
+
+def _shift_max(shift_max) -> float:
+    """§8 step 2's clamp bound as the float32 the kernels get: >= 0, not NaN."""
+    if not float(shift_max) >= 0.0:
+        raise ValueError(f"shift_max: need >= 0 (got {shift_max})")
+    return _f32(shift_max)
+
+
+def candidates(xyz3: torch.Tensor, c: torch.Tensor, K: int, shift_max: float, r_min: float, r_max: float, anchor,
+               out: Optional[tuple] = None) -> tuple:
+    """Candidate centres and adaptive radius (SPEC.md §8 steps 2-4).  xyz3 [B,M3,3] f32 (SA3's centroids), c [B,K,6] f32 (the
+    candidate layer's rows: shift, size), 1 <= K <= M3, anchor [3] (§8's ``anchor_car``) -> (cand [B,K,3] = xyz3[:, :K] +
+    clamp(c[..., 0:3], +-shift_max), radius [B,K]).  One launch.  ``out``: the tuple to write into."""
+    _strict(xyz3, "xyz3", torch.float32, (None, None, 3), "[B,M3,3]")
+    B, M3 = _point_rows(xyz3, "xyz3")
+    K = int(K)
+    if not 1 <= K <= M3:
+        raise ValueError(f"K: expected 1 <= K <= M3 = {M3}, got {K}")
+    _strict(c, "c", torch.float32, (B, K, 6))
+    sm = _shift_max(shift_max)
+    an = np.asarray(anchor, dtype=np.float32).reshape(-1)
+    if an.shape[0] != 3:
+        raise ValueError(f"anchor: expected 3 values, got {an.shape[0]}")
+    dev = _head_devices((("xyz3", xyz3), ("c", c)))
+    if xyz3.device != c.device:
+        raise ValueError("c: must be on the device of xyz3")
+    cand, radius = _outputs((("cand", (B, K, 3), torch.float32), ("radius", (B, K), torch.float32)), out, dev, "xyz3")
+    with _timed("candidates", f"K{K}"):
+        check(lib().sad_candidates_f32(xyz3.data_ptr(), c.data_ptr(), B, M3, K, sm, _f32(r_min), _f32(r_max),
+                                       (ctypes.c_float * 3)(*an.tolist()), cand.data_ptr(), radius.data_ptr(), _stream()),
+              "sad_candidates_f32")
+    return cand, radius
+
+
+def candidates_grad(c: torch.Tensor, grad_cand: torch.Tensor, shift_max: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The backward of ``candidates`` with respect to c (SPEC.md §33.1).  c [B,K,6] f32, grad_cand [B,K,3] f32 -> grad_c [B,K,6]:
+    column d < 3 is grad_cand's where -shift_max <= c[..., d] <= shift_max (bounds included, §31.2's convention; a selection, so a
+    NaN c gives +0), else +0; columns 3..5 are +0: the size columns reach the forward only through the radius of an index
+    decision and are trained by ``size_target`` alone.  One launch, every element written, bit-identical from call to call.
+    ``out``: the tensor to write into."""
+    _strict(c, "c", torch.float32, (None, None, 6), "[B,K,6]")
+    B, K = _point_rows(c, "c", "B * K < 2^31")
+    _strict(grad_cand, "grad_cand", torch.float32, (B, K, 3))
+    sm = _shift_max(shift_max)
+    dev = _head_devices((("c", c), ("grad_cand", grad_cand)))
+    if c.device != grad_cand.device:
+        raise ValueError("grad_cand: must be on the device of c")
+    (grad_c,) = _outputs(candidates_grad_output_spec(B, K), None if out is None else (out,), dev, "c")
+    with _timed("candidates_grad", f"K{K}"):
+        check(lib().sad_candidates_grad_f32(c.data_ptr(), grad_cand.data_ptr(), B, K, sm, grad_c.data_ptr(), _stream()),
+              "sad_candidates_grad_f32")
+    return grad_c
+
+
+def prefix_rows_grad(g: torch.Tensor, M: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The backward of ``prefix_rows`` (SPEC.md §33.2).  g [B,K,C] f32, M >= K -> [B,M,C]: rows < K of every scene are g's, rows
+    K .. M-1 are +0.  One launch writes every element exactly once (no zero fill in front).  ``out``: the tensor to write into."""
+    _strict(g, "g", torch.float32, (None, None, None), "[B,K,C] with B, K, C >= 1")
+    B, K, C = g.shape
+    if min(B, K, C) < 1:
+        raise ValueError(f"g: expected [B,K,C] with B, K, C >= 1, got {tuple(g.shape)}")
+    M = int(M)
+    if M < K:
+        raise ValueError(f"M: expected M >= K = {K}, got {M}")
+    dev = _head_devices((("g", g),))
+    (res,) = _outputs(prefix_rows_grad_output_spec(B, M, C), None if out is None else (out,), dev, "g")
+    with _timed("prefix_rows_grad", f"K{K}M{M}"):
+        check(lib().sad_prefix_rows_grad_f32(g.data_ptr(), B, K, M, C, res.data_ptr(), _stream()), "sad_prefix_rows_grad_f32")
+    return res
+
+
 def roi_grid_points(rois: torch.Tensor, roi_count: Optional[torch.Tensor], grid_size: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The grid points of every RoI (SPEC.md §30): rois [B,R,D>=7] f32 rows (cx,cy,cz,l,w,h,yaw,...), roi_count [B] int32 or
     ``None`` (as in ``roi_targets``: the rows beyond it are never read) -> pts [B,R,G^3,3] with G = ``grid_size`` (1 .. 16): point

@@ -200,11 +200,14 @@ class SAModuleMSGTrain(nn.Module):
         self.out_channels = stage.agg if stage.agg else self.cat_channels
         self.to(torch.device(device))
 
-    def forward_pm(self, xyz: torch.Tensor, feat_pm: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
-        """feat_pm [B,N,C] point-major -> (new_xyz [B,M,3], new_feat_pm [B,M,C'])."""
+    def forward_pm(self, xyz: torch.Tensor, feat_pm: Optional[torch.Tensor], new_xyz: Optional[torch.Tensor] = None
+                   ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """feat_pm [B,N,C] point-major -> (new_xyz [B,M,3], new_feat_pm [B,M,C']).  ``new_xyz``: centroids the caller has sampled
+        already (the detector's nested prefix, ``SADDetector._sample_stage``) instead of this stage's own fps + gather."""
         st = self.stage
         with torch.no_grad():
-            new_xyz = ops.gather_xyz(xyz, ops.fps(xyz, st.npoint))
+            if new_xyz is None:
+                new_xyz = ops.gather_xyz(xyz, ops.fps(xyz, st.npoint))
             idxs, cnts = ops.ball_query_multi(st.radii, st.nsamples, xyz, new_xyz, None, return_counts=True)
         train = torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters())
                                              or (feat_pm is not None and feat_pm.requires_grad) or xyz.requires_grad)

@@ -547,6 +547,15 @@ int sad_mlp_chain_multi_bf16(const sad_mlp_bf16_args *const *args, int n, sad_st
 int sad_candidates_f32(const float *xyz3, const float *c, int B, int M3, int K, float shift_max,
                        float r_min, float r_max, const float *anchor, float *cand, float *radius,
                        sad_stream_t stream);
+/* SPEC.md §33.1: the backward of sad_candidates_f32 with respect to c.  c[B,K,6], grad_cand[B,K,3] -> grad_c[B,K,6]:
+ * grad_c[.., d] = grad_cand[.., d] where -shift_max <= c[.., d] <= shift_max (bounds included; a selection, a NaN c gives +0),
+ * else +0; grad_c[.., 3 + d] = +0 (the size columns feed the radius of an index decision only).  One launch, every element
+ * written, no workspace, bit-equal from call to call.  shift_max negative or NaN: SAD_EINVAL; B > 65535: SAD_EUNSUPPORTED. */
+int sad_candidates_grad_f32(const float *c, const float *grad_cand, int B, int K, float shift_max, float *grad_c,
+                            sad_stream_t stream);
+/* SPEC.md §33.2: the backward of a packed prefix copy (rows [0, K) of every scene).  g[B,K,C] -> out[B,M,C]: rows < K are g's,
+ * rows K .. M-1 are +0; one launch, every element of out written exactly once.  1 <= K <= M. */
+int sad_prefix_rows_grad_f32(const float *g, int B, int K, int M, int C, float *out, sad_stream_t stream);
 /* SPEC.md §9.  cand[B,K,3], o[B,K,10] -> boxes[B,K,9]; anchors[9] host (3 classes x lwh). */
 int sad_decode_boxes_f32(const float *cand, const float *o, int B, int K, const float *anchors,
                          float *boxes, sad_stream_t stream);

@@ -40,7 +40,7 @@ _LAZY = {
     "sparse_max_pool": "ops", "sparse_max_pool_grad": "ops", "SparseMaxPool3d": "spconv", "SparseInverseConv3d": "spconv",
     "SparseTensor": "spconv", "SubMConv3d": "spconv", "SparseConv3d": "spconv", "SparseSequential": "spconv",
     "SAModuleMSG": "sa_module", "SAModule": "sa_module", "sa_module": "sa_module", "SAModuleMSGTrain": "sa_module",
-    "SharedMLP": "shared_mlp", "grouped_mlp_grad": "mlp", "mlp_rows_grad": "mlp",
+    "SharedMLP": "shared_mlp", "BranchGroup": "shared_mlp", "grouped_mlp_grad": "mlp", "mlp_rows_grad": "mlp",
     "candidates": "ops", "candidates_grad": "ops", "prefix_rows_grad": "ops", "SADDetectorTrain": "detector_train",
     "SADDetector": "detector", "IngestPipeline": "pipeline",
     "shard_range": "dist", "all_gather_boxes": "dist", "run_sharded": "dist",

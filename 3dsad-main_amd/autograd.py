@@ -12,43 +12,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import ops
-from ._lib import check, lib
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _f32(t, name, ndim):
-    if not t.is_cuda or t.dtype != torch.float32 or t.dim() != ndim:
-        raise TypeError(f"{name}: expected a GPU float32 tensor with {ndim} dims (sad_amd has no CPU path)")
-    return t.contiguous()
-
-
-def group_points_grad(grad_out: torch.Tensor, idx: torch.Tensor, N: int, point_major: bool = False,
-                      via_point_major: bool = True) -> torch.Tensor:
-    """grad_out [B,C,M,S] (or [B,C,M] with idx [B,M]) -> grad_feat [B,C,N] (scatter-add), or
-    [B,N,C] with ``point_major=True``.  By default the sum is formed point-major (contiguous float
-    atomics, ~10x faster) and transposed at the end; ``via_point_major=False`` uses the direct
-    channel-major scatter."""
-    if grad_out.dim() == 3:
-        grad_out, idx = grad_out.unsqueeze(-1), idx.unsqueeze(-1)
-    grad_out = _f32(grad_out, "grad_out", 4)
-    if idx.dtype != torch.int32 or not idx.is_cuda:
-        raise TypeError("idx: expected a GPU int32 tensor")
-    idx = idx.contiguous()
-    B, C, M, S = grad_out.shape
-    if tuple(idx.shape) != (B, M, S):
-        raise ValueError("idx must be [B,M,S]")
-    if point_major or via_point_major:
-        g = torch.zeros((B, N, C), dtype=torch.float32, device=grad_out.device)
-        check(lib().sad_group_points_grad_pm_f32(grad_out.data_ptr(), idx.data_ptr(), B, C, N, M, S, g.data_ptr(),
-                                                 _stream()), "sad_group_points_grad_pm_f32")
-        return g if point_major else g.transpose(1, 2).contiguous()
-    g = torch.zeros((B, C, N), dtype=torch.float32, device=grad_out.device)
-    check(lib().sad_group_points_grad_f32(grad_out.data_ptr(), idx.data_ptr(), B, C, N, M, S, g.data_ptr(),
-                                          _stream()), "sad_group_points_grad_f32")
-    return g
+from .ops import group_points_grad, max_pool_s_with_arg, three_interpolate_grad  # noqa: F401  (the backward operators live in ops)
 
 
 class GroupPoints(torch.autograd.Function):
@@ -58,7 +22,7 @@ class GroupPoints(torch.autograd.Function):
     def forward(ctx, features, idx):
         ctx.save_for_backward(idx)
         ctx.N = features.shape[2]
-        return ops.group_points(_f32(features, "features", 3), idx)
+        return ops.group_points(features, idx)
 
     @staticmethod
     def backward(ctx, grad_out):
@@ -73,23 +37,12 @@ class GatherPoints(torch.autograd.Function):
     def forward(ctx, features, idx):
         ctx.save_for_backward(idx)
         ctx.N = features.shape[2]
-        return ops.gather_points(_f32(features, "features", 3), idx)
+        return ops.gather_points(features, idx)
 
     @staticmethod
     def backward(ctx, grad_out):
         (idx,) = ctx.saved_tensors
         return group_points_grad(grad_out, idx, ctx.N), None
-
-
-def max_pool_s_with_arg(x: torch.Tensor):
-    """x [B,C,M,S] -> (out [B,C,M], arg [B,C,M] int32); ties -> lowest s."""
-    x = _f32(x, "x", 4)
-    B, C, M, S = x.shape
-    out = torch.empty((B, C, M), dtype=torch.float32, device=x.device)
-    arg = torch.empty((B, C, M), dtype=torch.int32, device=x.device)
-    check(lib().sad_max_pool_s_f32(x.data_ptr(), B, C, M, S, out.data_ptr(), arg.data_ptr(), _stream()),
-          "sad_max_pool_s_f32")
-    return out, arg
 
 
 class MaxPoolS(torch.autograd.Function):
@@ -105,34 +58,7 @@ class MaxPoolS(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         (arg,) = ctx.saved_tensors
-        grad_out = _f32(grad_out, "grad_out", 3)
-        B, C, M = grad_out.shape
-        gx = torch.empty((B, C, M, ctx.S), dtype=torch.float32, device=grad_out.device)
-        check(lib().sad_max_pool_s_grad_f32(grad_out.data_ptr(), arg.data_ptr(), B, C, M, ctx.S, gx.data_ptr(),
-                                            _stream()), "sad_max_pool_s_grad_f32")
-        return gx
-
-
-def three_interpolate_grad(grad_out: torch.Tensor, idx: torch.Tensor, w: torch.Tensor, m: int,
-                           point_major: bool = False) -> torch.Tensor:
-    """SPEC.md §18: grad_out [B,C,n] (or [B,n,C] with ``point_major=True``), idx / w [B,n,3] -> grad_feat [B,C,m] (or [B,m,C]):
-    ``grad_feat[.., idx_k] += w_k * grad_out``.  The sum is formed point-major (contiguous float atomics) and transposed at the
-    end for the channel-major layout.  idx and w get no gradient."""
-    grad_out = _f32(grad_out, "grad_out", 3)
-    if idx.dtype != torch.int32 or not idx.is_cuda:
-        raise TypeError("idx: expected a GPU int32 tensor")
-    w = _f32(w, "w", 3)
-    idx = idx.contiguous()
-    if point_major:
-        B, n, C = grad_out.shape
-    else:
-        B, C, n = grad_out.shape
-    if tuple(idx.shape) != (B, n, 3) or tuple(w.shape) != (B, n, 3):
-        raise ValueError("idx and w must be [B,n,3]")
-    g = torch.zeros((B, m, C), dtype=torch.float32, device=grad_out.device)
-    check(lib().sad_three_interpolate_grad_f32(grad_out.data_ptr(), idx.data_ptr(), w.data_ptr(), B, C, n, m, int(bool(point_major)),
-                                               g.data_ptr(), _stream()), "sad_three_interpolate_grad_f32")
-    return g if point_major else g.transpose(1, 2).contiguous()
+        return ops.max_pool_s_grad(grad_out, arg, ctx.S)
 
 
 class ThreeInterpolate(torch.autograd.Function):
@@ -144,7 +70,7 @@ class ThreeInterpolate(torch.autograd.Function):
         ctx.save_for_backward(idx, w)
         ctx.point_major = bool(point_major)
         ctx.m = features.shape[1] if point_major else features.shape[2]
-        return ops.three_interpolate(_f32(features, "features", 3), idx, w, point_major=point_major)
+        return ops.three_interpolate(features, idx, w, point_major=point_major)
 
     @staticmethod
     def backward(ctx, grad_out):
@@ -158,7 +84,6 @@ class VoxelReduce(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, feat, point2voxel, offsets, max_voxels, mode="mean"):
-        feat = _f32(feat, "feat", 2)
         ctx.mode = mode
         aux = None
         if mode == "max":
@@ -174,7 +99,7 @@ class VoxelReduce(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         saved = ctx.saved_tensors
-        g = ops.voxel_reduce_grad(_f32(grad_out, "grad_out", 3), saved[0], saved[1], ctx.mode, saved[2] if ctx.has_aux else None)
+        g = ops.voxel_reduce_grad(grad_out, saved[0], saved[1], ctx.mode, saved[2] if ctx.has_aux else None)
         return g, None, None, None, None
 
 
@@ -187,7 +112,6 @@ class VoxelEncode(torch.autograd.Function):
     @staticmethod
     def forward(ctx, points, point2voxel, offsets, max_voxels, weight, bias, coors, voxel_size, point_range, cluster_center, voxel_center,
                 relu, vox_feat, max_points, return_pointwise):
-        points = _f32(points, "points", 2)
         res = ops.voxel_encode(points, point2voxel, offsets, max_voxels, weight, bias, coors, voxel_size, point_range, cluster_center,
                                voxel_center, relu, vox_feat, max_points, return_arg=True, return_pointwise=return_pointwise)
         pooled, arg = res[0], res[1]
@@ -207,7 +131,7 @@ class VoxelEncode(torch.autograd.Function):
         vox_feat = rest.pop(0) if ctx.has[1] else None
         pointwise = rest.pop(0) if ctx.has[2] else None
         total, C = points.shape
-        gp = _f32(grad_pooled, "grad_pooled", 3)
+        gp = grad_pooled
         if relu:
             gp = torch.where(pooled > 0, gp, torch.zeros_like(gp))      # y of the arg row IS the pooled value
         g = ops.voxel_reduce_grad(gp, p2v, offsets, "max", arg)
@@ -241,14 +165,20 @@ def voxel_encode(points, point2voxel, offsets, max_voxels, weight, bias, coors=N
                              voxel_center, relu, vox_feat, max_points, return_pointwise)
 
 
-def _transposed(transposed, nbr, Nv):
-    """-> (nbrT, collisions as a Python int) from what ``SparseConv`` was given: None (built here, one synchronisation), a
-    callable that returns the pair (a layer's cache) or the pair itself."""
+def _transposed(transposed, nbr, Nv, op: str, section: str):
+    """-> nbrT of a backward of ``op`` (SPEC.md ``section``) from what its Function was given: None (built here, one
+    synchronisation), a callable that returns the pair (nbrT, collisions) (a layer's cache) or the pair itself.  A transposed
+    rulebook with collisions has no gradient: ``ValueError``."""
     if transposed is None:
         nbrT, col = ops.sparse_conv_index_transpose(nbr, Nv)
-        return nbrT, int(col.item())
-    nbrT, col = transposed() if callable(transposed) else transposed
-    return nbrT, int(col)
+        col = col.item()
+    else:
+        nbrT, col = transposed() if callable(transposed) else transposed
+    if int(col):
+        raise ValueError(f"{op} backward: the rulebook maps {int(col)} (output row, offset) pairs onto input rows that a "
+                         "lower row already holds: the input has a duplicate coordinate inside a scene (submanifold form), "
+                         f"for which no gradient with respect to feat is defined (SPEC.md {section})")
+    return nbrT
 
 
 class SparseConv(torch.autograd.Function):
@@ -263,8 +193,8 @@ class SparseConv(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, feat, weight, bias, residual, nbr, relu=False, transposed=None, packed=None, packed_t=None):
-        feat = _f32(feat, "feat", 2)
-        weight = _f32(weight, "weight", 3)
+        if not feat.is_cuda:                       # (the type this Function has always raised; the operators raise RuntimeError)
+            raise TypeError("feat: expected a GPU float32 tensor (sad_amd has no CPU path)")
         if packed is None:
             out = ops.sparse_conv(feat, nbr, weight, bias, residual, relu)
         else:
@@ -278,16 +208,10 @@ class SparseConv(torch.autograd.Function):
     def backward(ctx, grad_out):
         feat, weight, nbr, out = ctx.saved_tensors
         need = ctx.needs_input_grad
-        g = _f32(grad_out, "grad_out", 2)
-        if ctx.relu:
-            g = g * (out > 0)                      # exact: g or 0
+        g = grad_out * (out > 0) if ctx.relu else grad_out      # exact: g or 0
         grad_feat = grad_w = grad_b = None
         if need[0]:
-            nbrT, collisions = _transposed(ctx.transposed, nbr, feat.shape[0])
-            if collisions:
-                raise ValueError(f"sparse_conv backward: the rulebook maps {collisions} (output row, offset) pairs onto input rows that a "
-                                 "lower row already holds: the input has a duplicate coordinate inside a scene (submanifold form), "
-                                 "for which no gradient with respect to feat is defined (SPEC.md §21.4)")
+            nbrT = _transposed(ctx.transposed, nbr, feat.shape[0], "sparse_conv", "§21.4")
             grad_feat = ops.sparse_conv_grad_input(g, nbrT, ctx.packed_t() if ctx.packed_t is not None else weight)
         if need[1] or need[2]:
             grad_w, grad_b = ops.sparse_conv_grad_weight(feat, nbr, g, bias=need[2], weight=need[1])   # (a frozen weight: no GEMM)
@@ -302,7 +226,6 @@ class SparseMaxPool(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, feat, nbr, transposed=None):
-        feat = _f32(feat, "feat", 2)
         out, arg = ops.sparse_max_pool(feat, nbr)
         ctx.Nv, ctx.transposed = feat.shape[0], transposed
         ctx.save_for_backward(arg, nbr)
@@ -314,12 +237,8 @@ class SparseMaxPool(torch.autograd.Function):
         arg, nbr = ctx.saved_tensors
         if not ctx.needs_input_grad[0]:
             return None, None, None
-        nbrT, collisions = _transposed(ctx.transposed, nbr, ctx.Nv)
-        if collisions:
-            raise ValueError(f"sparse_max_pool backward: the rulebook maps {collisions} (output row, offset) pairs onto input rows that a "
-                             "lower row already holds: the input has a duplicate coordinate inside a scene (submanifold form), "
-                             "for which no gradient with respect to feat is defined (SPEC.md §22.2)")
-        return ops.sparse_max_pool_grad(_f32(grad_out, "grad_out", 2), arg, nbrT, ctx.Nv), None, None
+        nbrT = _transposed(ctx.transposed, nbr, ctx.Nv, "sparse_max_pool", "§22.2")
+        return ops.sparse_max_pool_grad(grad_out, arg, nbrT, ctx.Nv), None, None
 
 
 class SparseToDense(torch.autograd.Function):
@@ -332,7 +251,7 @@ class SparseToDense(torch.autograd.Function):
     def forward(ctx, feat, out_coors, out_offsets, out_shape):
         ctx.save_for_backward(out_coors, out_offsets)
         ctx.out_shape = tuple(int(v) for v in out_shape)
-        return ops.sparse_to_dense(_f32(feat, "feat", 2), out_coors, out_offsets, out_shape)
+        return ops.sparse_to_dense(feat, out_coors, out_offsets, out_shape)
 
     @staticmethod
     @once_differentiable
@@ -364,104 +283,87 @@ max_pool_s = MaxPoolS.apply
 three_interpolate = ThreeInterpolate.apply
 
 
-def _scaled(grad: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
-    """grad [B,...] times w [B], broadcast per scene."""
-    return grad * w.view(-1, *([1] * (grad.dim() - 1)))
+def _scale_saved(saved, grad_loss: torch.Tensor, table) -> dict:
+    """The backward of a loss whose forward already produced the gradient of every component: saved [g_0, g_1, ...] (each
+    [B,...]), grad_loss [B,n] and ``table[i]`` = (input that g_i is a gradient of, columns of grad_loss that scale g_i per scene)
+    -> {input: gradient}.  Columns: an int (the whole tensor), or ((width, column), ...) = blocks along the last axis of g_i, one
+    width ``None`` = what the others leave.  Two saved tensors of one input are summed in the order of the table.  Every element
+    is one float32 multiply (and that add).  A ``saved`` shorter than the table: the optional last gradient is absent."""
+    grads = {}
+    for g, (slot, cols) in zip(saved, table):
+        if isinstance(cols, int):
+            w = grad_loss[:, cols].view(-1, *([1] * (g.dim() - 1)))
+        else:
+            rest = g.shape[-1] - sum(n for n, _ in cols if n is not None)
+            w = torch.cat([grad_loss[:, c:c + 1].expand(-1, rest if n is None else n) for n, c in cols], 1)
+            w = w.view(-1, *([1] * (g.dim() - 2)), g.shape[-1])
+        grads[slot] = g * w if slot not in grads else grads[slot] + g * w
+    return grads
 
 
-class AnchorHeadLoss(torch.autograd.Function):
-    """(cls, reg, dir | None, labels, reg_target, dir_target | None, cfg) -> loss [B,3] (SPEC.md §27.1), differentiable in the maps.
-    The forward is ``ops.anchor_head_loss``, which already produced d loss[b, i] / d map for every component i: the backward
-    multiplies the saved gradients by ``grad_loss[:, i]`` per scene (a torch multiply).  ``cfg``: the operator's keywords."""
+class _HeadLoss(torch.autograd.Function):
+    """``apply(*inputs, cfg) -> (loss [B,n], counts)``, differentiable in the predictions.  The forward is ``op(*inputs, **cfg)``
+    (``cfg``: the operator's keywords), which returns (loss, counts, one gradient per row of ``table``, ...): the gradients are
+    saved, without the last when input ``optional`` is ``None``, the counts are not differentiable, and the backward is
+    ``_scale_saved`` (torch multiplies), ``None`` for every other input.  A subclass declares ``op``, ``table`` and ``optional``
+    (``forward`` / ``backward`` are class methods to read them)."""
+    op = table = optional = None
 
-    @staticmethod
-    def forward(ctx, cls, reg, dir, labels, reg_target, dir_target, cfg):
-        outs = ops.anchor_head_loss(cls, reg, dir, labels, reg_target, dir_target, **cfg)
-        ctx.save_for_backward(*outs[2:5 if dir is not None else 4])
+    @classmethod
+    def forward(cls, ctx, *args):
+        outs = cls.op(*args[:-1], **args[-1])
+        ctx.save_for_backward(*outs[2:2 + len(cls.table) - (args[cls.optional] is None)])
         ctx.mark_non_differentiable(outs[1])
+        ctx.n_args = len(args)
         return outs[0], outs[1]
 
-    @staticmethod
+    @classmethod
     @once_differentiable
-    def backward(ctx, grad_loss, _grad_num_pos):
-        saved = ctx.saved_tensors
-        grads = [_scaled(g, grad_loss[:, i]) for i, g in enumerate(saved)]
-        return grads[0], grads[1], grads[2] if len(grads) == 3 else None, None, None, None, None
+    def backward(cls, ctx, grad_loss, _grad_counts):
+        grads = _scale_saved(ctx.saved_tensors, grad_loss, cls.table)
+        return tuple(grads.get(i) for i in range(ctx.n_args))
 
 
-class CenterHeadLoss(torch.autograd.Function):
-    """(hm, reg, height, dim, rot, vel | None, heatmap, ind, anno, cfg) -> loss [B,2] (SPEC.md §27.2), differentiable in the maps:
-    grad_hm scales with ``grad_loss[:, 0]``, the regression gradients with ``grad_loss[:, 1]``."""
-
-    @staticmethod
-    def forward(ctx, hm, reg, height, dim, rot, vel, heatmap, ind, anno, cfg):
-        outs = ops.center_head_loss(hm, reg, height, dim, rot, vel, heatmap, ind, anno, **cfg)
-        ctx.save_for_backward(*outs[2:])
-        ctx.mark_non_differentiable(outs[1])
-        return outs[0], outs[1]
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_loss, _grad_num_pos):
-        saved = ctx.saved_tensors
-        grads = [_scaled(g, grad_loss[:, 0 if i == 0 else 1]) for i, g in enumerate(saved)]
-        return (*grads, *([None] if len(grads) == 5 else []), None, None, None, None)
+class AnchorHeadLoss(_HeadLoss):
+    """(cls, reg, dir | None, labels, reg_target, dir_target | None, cfg) -> loss [B,3], num_pos [B] (SPEC.md §27.1), differentiable
+    in the maps: the gradient of map i scales with ``grad_loss[:, i]``."""
+    op, optional = ops.anchor_head_loss, 2
+    table = ((0, 0), (1, 1), (2, 2))
 
 
-class RoIHeadLoss(torch.autograd.Function):
+class CenterHeadLoss(_HeadLoss):
+    """(hm, reg, height, dim, rot, vel | None, heatmap, ind, anno, cfg) -> loss [B,2], num_pos [B,2] (SPEC.md §27.2), differentiable
+    in the maps: grad_hm scales with ``grad_loss[:, 0]``, the regression gradients with ``grad_loss[:, 1]``."""
+    op, optional = ops.center_head_loss, 5
+    table = ((0, 0), (1, 1), (2, 1), (3, 1), (4, 1), (5, 1))
+
+
+class RoIHeadLoss(_HeadLoss):
     """(rcnn_cls, rcnn_reg, cls_target, reg_valid, reg_target, rois | None, gt_local | None, cfg) -> loss [B,3], num [B,2]
-    (SPEC.md §29), differentiable in the two predictions.  The forward is ``ops.roi_head_loss``, which already produced the
-    gradient of every component: the backward returns ``grad_cls · g[:, 0]`` and ``grad_reg · g[:, 1] + grad_corner · g[:, 2]``
-    broadcast per scene (torch multiplies), and ``None`` for the targets.  ``cfg``: the operator's keywords."""
-
-    @staticmethod
-    def forward(ctx, rcnn_cls, rcnn_reg, cls_target, reg_valid, reg_target, rois, gt_local, cfg):
-        outs = ops.roi_head_loss(rcnn_cls, rcnn_reg, cls_target, reg_valid, reg_target, rois, gt_local, **cfg)
-        ctx.save_for_backward(*outs[2:5 if rois is not None else 4])
-        ctx.mark_non_differentiable(outs[1])
-        return outs[0], outs[1]
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_loss, _grad_num):
-        saved = ctx.saved_tensors
-        greg = _scaled(saved[1], grad_loss[:, 1])
-        if len(saved) == 3:
-            greg = greg + _scaled(saved[2], grad_loss[:, 2])
-        return _scaled(saved[0], grad_loss[:, 0]), greg, None, None, None, None, None, None
+    (SPEC.md §29), differentiable in the two predictions: ``grad_cls · g[:, 0]`` and ``grad_reg · g[:, 1] + grad_corner · g[:, 2]``
+    (the corner term with ``rois``)."""
+    op, optional = ops.roi_head_loss, 5
+    table = ((0, 0), (1, 1), (1, 2))
 
 
-class PointHeadLoss(torch.autograd.Function):
+class PointHeadLoss(_HeadLoss):
     """(o, c | None, labels, centerness | None, reg_target, shift_target | None, size_target | None, cfg) -> loss [B,4], num_pos [B]
-    (SPEC.md §31.2), differentiable in o and c.  The forward is ``ops.point_head_loss``, which already produced the gradient of
-    every component: grad_o holds d loss[:, 0] in its first C columns and d loss[:, 1] in the last 7, grad_c d loss[:, 2] in
-    columns 0..2 and d loss[:, 3] in 3..5, so the backward scales them per scene and per component (torch multiplies) and
-    returns ``None`` for the targets.  ``cfg``: the operator's keywords."""
-
-    @staticmethod
-    def forward(ctx, o, c, labels, centerness, reg_target, shift_target, size_target, cfg):
-        outs = ops.point_head_loss(o, c, labels, centerness, reg_target, shift_target, size_target, **cfg)
-        ctx.save_for_backward(*outs[2:4 if c is not None else 3])
-        ctx.mark_non_differentiable(outs[1])
-        return outs[0], outs[1]
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_loss, _grad_num):
-        saved = ctx.saved_tensors
-        C = saved[0].shape[2] - 7
-        w = torch.cat([grad_loss[:, 0:1].expand(-1, C), grad_loss[:, 1:2].expand(-1, 7)], 1)                # [B,C+7]
-        go = saved[0] * w.unsqueeze(1)
-        gc = None
-        if len(saved) == 2:
-            gc = saved[1] * torch.cat([grad_loss[:, 2:3].expand(-1, 3), grad_loss[:, 3:4].expand(-1, 3)], 1).unsqueeze(1)
-        return go, gc, None, None, None, None, None, None
+    (SPEC.md §31.2), differentiable in o and c: grad_o holds d loss[:, 0] in its first C columns and d loss[:, 1] in the last 7,
+    grad_c d loss[:, 2] in columns 0..2 and d loss[:, 3] in 3..5."""
+    op, optional = ops.point_head_loss, 1
+    table = ((0, ((None, 0), (7, 1))), (1, ((3, 2), (3, 3))))
 
 
 def _layers_of(params):
     """(W_1 .. W_L, b_1 .. b_L) -> [(W_l, b_l)]."""
     L = len(params) // 2
     return [(params[l], params[L + l]) for l in range(L)]
+
+
+def _param_grads(gW, gb, want) -> list:
+    """grad_W [L] and grad_b [L] of a chain's backward (both ``None`` when no parameter asked) -> the gradients of ``*params``
+    (W_1 .. W_L, b_1 .. b_L), ``None`` where ``want`` (their ``needs_input_grad``) is false."""
+    return [g if w else None for g, w in zip(gW + gb, want)] if gW is not None else [None] * len(want)
 
 
 class GroupedMLP(torch.autograd.Function):
@@ -490,8 +392,7 @@ class GroupedMLP(torch.autograd.Function):
         need = [n for n, w in (("xyz", want[2]), ("feat", want[3]), ("new_xyz", want[4]), ("params", any(want[7:]))) if w]
         gf, gx, gn, gW, gb, GroupedMLP.last_mismatch = ops.grouped_mlp_grad(
             xyz, feat_pm, new_xyz, idx, cnt, _layers_of(params), out, grad_out, skip_empty=ctx.skip_empty, need=need)
-        gp = [g if w else None for g, w in zip((gW or []) + (gb or []), want[7:])] if gW is not None else [None] * len(params)
-        return (None, None, gx, gf, gn, None, None, *gp)
+        return (None, None, gx, gf, gn, None, None, *_param_grads(gW, gb, want[7:]))
 
 
 class MLPRows(torch.autograd.Function):
@@ -513,8 +414,7 @@ class MLPRows(torch.autograd.Function):
         want = ctx.needs_input_grad
         need = [n for n, w in (("feat", want[1]), ("params", any(want[2:]))) if w]
         gx, gW, gb = ops.mlp_rows_grad(x, _layers_of(params), grad_out, relu_mask=ctx.relu_mask, need=need)
-        gp = [g if w else None for g, w in zip((gW or []) + (gb or []), want[2:])] if gW is not None else [None] * len(params)
-        return (None, gx, *gp)
+        return (None, gx, *_param_grads(gW, gb, want[2:]))
 
 
 class Candidates(torch.autograd.Function):
@@ -545,7 +445,7 @@ class PrefixRows(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, K):
         ctx.M = x.shape[1]
-        return x if K == ctx.M else ops.prefix_rows(_f32(x, "x", 3), K)
+        return x if K == ctx.M else ops.prefix_rows(x.contiguous(), K)
 
     @staticmethod
     @once_differentiable

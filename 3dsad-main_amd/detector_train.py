@@ -19,7 +19,7 @@ from ._lib import check, lib
 from .config import DetectorConfig
 from .point_head import PointTargetAssigner, PointTargets
 from .sa_module import SAModuleMSGTrain
-from .shared_mlp import SharedMLP
+from .shared_mlp import BranchGroup, SharedMLP
 from .synth import make_weights
 
 # o [B,K,C_cls+7] (the head's rows), c [B,K,6] (the candidate layer's rows), cand [B,K,3], xyz_k [B,K,3] (the first K SA3
@@ -49,10 +49,10 @@ class SADDetectorTrain(nn.Module):
         self.stages = nn.ModuleList(stages)
         self.cand = SharedMLP([c] + list(cfg.cand_mlp), False, relu_mask=(1 << (len(cfg.cand_mlp) - 1)) - 1,
                               layers=weights["cand"], name="cand")
-        self.cluster_branches = nn.ModuleList([SharedMLP([c + 3] + list(m), True, layers=weights[f"cluster.b{i}"], name=f"cluster.b{i}")
-                                               for i, m in enumerate(cfg.cluster_mlps)])
-        self.cluster_cat = sum(m[-1] for m in cfg.cluster_mlps)
-        self.cluster_agg = SharedMLP([self.cluster_cat, cfg.cluster_agg], False, layers=weights["cluster.agg"], name="cluster.agg")
+        self.cluster_branches = BranchGroup(SharedMLP([c + 3] + list(m), True, layers=weights[f"cluster.b{i}"], name=f"cluster.b{i}")
+                                            for i, m in enumerate(cfg.cluster_mlps))
+        self.cluster_agg = SharedMLP([self.cluster_branches.cat_channels, cfg.cluster_agg], False, layers=weights["cluster.agg"],
+                                     name="cluster.agg")
         self.head = SharedMLP([cfg.cluster_agg] + list(cfg.head_mlp), False, relu_mask=(1 << (len(cfg.head_mlp) - 1)) - 1,
                               layers=weights["head"], name="head")
         self.assigner = PointTargetAssigner.from_config(cfg)
@@ -60,17 +60,13 @@ class SADDetectorTrain(nn.Module):
         self._anchors = (ctypes.c_float * 9)(*[v for a in cfg.anchors for v in a])
         self.to(torch.device(device))
 
-    def _trains(self, *tensors) -> bool:
-        return torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters())
-                                            or any(t is not None and t.requires_grad for t in tensors))
-
     def cluster_head(self, xyz3: torch.Tensor, feat3: torch.Tensor) -> TrainOutput:
         """SPEC.md §8 and §9 on SA3's output: xyz3 [B,M3,3], feat3 [B,M3,C3] -> ``TrainOutput``.  Gradients reach the parameters
         of ``cand``, the cluster branches, ``cluster_agg`` and ``head``, and feat3 (the branches' gathered rows plus the padded
         prefix behind the candidate MLP); ``cand`` receives gradient only from the branches' relative coordinates, and passes it
         to c[..., 0:3] where the shift was not clamped (§33.1)."""
         cfg = self.cfg
-        B, M3, K = xyz3.shape[0], xyz3.shape[1], cfg.n_cand
+        M3, K = xyz3.shape[1], cfg.n_cand
         with torch.no_grad():
             xyz_k = xyz3 if K == M3 else ops.prefix_rows(xyz3, K)
         c = self.cand.rows(autograd.PrefixRows.apply(feat3, K))                                    # [B,K,6]
@@ -78,16 +74,7 @@ class SADDetectorTrain(nn.Module):
         with torch.no_grad():
             idxs, cnts = ops.ball_query_multi(cfg.cluster_scales, cfg.cluster_nsamples, xyz3, cand.detach(), radius,
                                               return_counts=True)
-        if self._trains(feat3, cand):
-            outs = [mlp.grouped(xyz3, feat3, cand, idx, cnt) for mlp, idx, cnt in zip(self.cluster_branches, idxs, cnts)]
-            cat = outs[0] if len(outs) == 1 else torch.cat(outs, 2)
-        else:
-            with torch.no_grad():
-                cat = torch.zeros((B, K, self.cluster_cat), dtype=torch.float32, device=xyz3.device)
-                off = 0
-                for mlp, idx, cnt in zip(self.cluster_branches, idxs, cnts):
-                    mlp.packed().grouped(xyz3, feat3, cand, idx, out=cat, col_off=off, cnt=cnt)
-                    off += mlp.out_channels
+        cat = self.cluster_branches(xyz3, feat3, cand, idxs, cnts)
         o = self.head.rows(self.cluster_agg.rows(cat))                                             # [B,K,C_cls+7]
         return TrainOutput(o, c, cand, xyz_k, radius, feat3)
 

@@ -293,6 +293,53 @@ def group_points(features: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def group_points_grad(grad_out: torch.Tensor, idx: torch.Tensor, N: int, point_major: bool = False,
+                      via_point_major: bool = True) -> torch.Tensor:
+    """Backward of ``group_points`` / ``gather_points`` (SPEC.md §16): grad_out [B,C,M,S] f32 (or [B,C,M] with idx [B,M]) ->
+    grad_feat [B,C,N] (scatter-add), or [B,N,C] with ``point_major=True``.  By default the sum is formed point-major (contiguous
+    float atomics, ~10x faster) and transposed at the end; ``via_point_major=False`` uses the direct channel-major scatter."""
+    if isinstance(grad_out, torch.Tensor) and grad_out.dim() == 3 and isinstance(idx, torch.Tensor):
+        grad_out, idx = grad_out.unsqueeze(-1), idx.unsqueeze(-1)
+    grad_out = _need(grad_out, "grad_out", torch.float32, 4)
+    idx = _need(idx, "idx", torch.int32, 3)
+    B, C, M, S = grad_out.shape
+    if tuple(idx.shape) != (B, M, S):
+        raise ValueError("idx must be [B,M,S]")
+    pm = bool(point_major or via_point_major)
+    _unrecordable("group_points_grad: zero fill")
+    g = torch.zeros((B, N, C) if pm else (B, C, N), dtype=torch.float32, device=grad_out.device)      # the kernels add (float atomics)
+    name = "sad_group_points_grad_pm_f32" if pm else "sad_group_points_grad_f32"
+    with _timed("group_points_grad", f"C{C}N{N}M{M}S{S}" + ("pm" if pm else "cm")):
+        check(getattr(lib(), name)(grad_out.data_ptr(), idx.data_ptr(), B, C, N, M, S, g.data_ptr(), _stream()), name)
+    return g.transpose(1, 2).contiguous() if pm and not point_major else g
+
+
+def max_pool_s_with_arg(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """x [B,C,M,S] f32 -> (out [B,C,M], arg [B,C,M] int32): the maximum over S and its position, ties -> lowest s (SPEC.md §16)."""
+    x = _need(x, "x", torch.float32, 4)
+    B, C, M, S = x.shape
+    out = _empty((B, C, M), dtype=torch.float32, device=x.device)
+    arg = _empty((B, C, M), dtype=torch.int32, device=x.device)
+    with _timed("max_pool_s", f"C{C}M{M}S{S}"):
+        check(lib().sad_max_pool_s_f32(x.data_ptr(), B, C, M, S, out.data_ptr(), arg.data_ptr(), _stream()), "sad_max_pool_s_f32")
+    return out, arg
+
+
+def max_pool_s_grad(grad_out: torch.Tensor, arg: torch.Tensor, S: int) -> torch.Tensor:
+    """Backward of ``max_pool_s_with_arg``: grad_out [B,C,M] f32, arg [B,C,M] int32 -> grad_x [B,C,M,S], grad_out in the arg-max
+    slot and 0 elsewhere (every element written: no zero fill)."""
+    grad_out = _need(grad_out, "grad_out", torch.float32, 3)
+    arg = _need(arg, "arg", torch.int32, 3)
+    B, C, M = grad_out.shape
+    if tuple(arg.shape) != (B, C, M):
+        raise ValueError("arg must have the shape of grad_out")
+    gx = _empty((B, C, M, int(S)), dtype=torch.float32, device=grad_out.device)
+    with _timed("max_pool_s_grad", f"C{C}M{M}S{S}"):
+        check(lib().sad_max_pool_s_grad_f32(grad_out.data_ptr(), arg.data_ptr(), B, C, M, int(S), gx.data_ptr(), _stream()),
+              "sad_max_pool_s_grad_f32")
+    return gx
+
+
 def subsample_pad(points: torch.Tensor, offsets: torch.Tensor, n_points: int, seed: int = 0,
                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Ragged scenes -> a fixed point count on the GPU (SPEC.md §17; the step before the path).
@@ -435,6 +482,25 @@ def three_interpolate(feat: torch.Tensor, idx: torch.Tensor, w: torch.Tensor, po
         check(lib().sad_three_interpolate_f32(feat.data_ptr(), idx.data_ptr(), w.data_ptr(), B, C, m, n, int(bool(point_major)),
                                               out.data_ptr(), ld, int(col_off), _stream()), "sad_three_interpolate_f32")
     return out
+
+
+def three_interpolate_grad(grad_out: torch.Tensor, idx: torch.Tensor, w: torch.Tensor, m: int,
+                           point_major: bool = False) -> torch.Tensor:
+    """Backward of ``three_interpolate`` (SPEC.md §18): grad_out [B,C,n] (or [B,n,C] with ``point_major=True``), idx / w [B,n,3] ->
+    grad_feat [B,C,m] (or [B,m,C]): ``grad_feat[.., idx_k] += w_k * grad_out``.  The sum is formed point-major (contiguous float
+    atomics) and transposed at the end for the channel-major layout.  idx and w get no gradient."""
+    grad_out = _need(grad_out, "grad_out", torch.float32, 3)
+    idx = _need(idx, "idx", torch.int32, 3)
+    w = _need(w, "w", torch.float32, 3)
+    (B, n, C) = grad_out.shape if point_major else (grad_out.shape[0], grad_out.shape[2], grad_out.shape[1])
+    if tuple(idx.shape) != (B, n, 3) or tuple(w.shape) != (B, n, 3):
+        raise ValueError("idx and w must be [B,n,3]")
+    _unrecordable("three_interpolate_grad: zero fill")
+    g = torch.zeros((B, int(m), C), dtype=torch.float32, device=grad_out.device)      # the kernel adds (float atomics)
+    with _timed("three_interpolate_grad", f"C{C}" + ("pm" if point_major else "cm")):
+        check(lib().sad_three_interpolate_grad_f32(grad_out.data_ptr(), idx.data_ptr(), w.data_ptr(), B, C, n, int(m), int(bool(point_major)),
+                                                   g.data_ptr(), _stream()), "sad_three_interpolate_grad_f32")
+    return g if point_major else g.transpose(1, 2).contiguous()
 
 
 def _boxes(t: torch.Tensor, name: str, batched: bool = True) -> torch.Tensor:

@@ -22,7 +22,35 @@ from .config import SAStage
 from .synth import make_mlp_weights
 
 
-class SAModuleMSG(nn.Module):
+def stage_weights(in_channels: int, stage: SAStage, seed: int = 0) -> dict:
+    """The default weights of a stage: {"b<i>": [(W,b),...], "agg": [(W,b)]}, seeded Kaiming-uniform, the branches drawn in
+    order and the aggregation layer last."""
+    rng = np.random.default_rng(seed)
+    weights = {f"b{i}": make_mlp_weights([in_channels + 3] + list(m), rng) for i, m in enumerate(stage.mlps)}
+    if stage.agg:
+        weights["agg"] = make_mlp_weights([sum(m[-1] for m in stage.mlps), stage.agg], rng)
+    return weights
+
+
+class _Stage(nn.Module):
+    """What the inference and the trainable form of a stage share: the channel counts and the channel-major drop-in surface
+    over the subclass's ``forward_pm``."""
+
+    def __init__(self, in_channels: int, stage: SAStage):
+        super().__init__()
+        self.stage = stage
+        self.in_channels = in_channels
+        self.cat_channels = sum(m[-1] for m in stage.mlps)
+        self.out_channels = stage.agg if stage.agg else self.cat_channels
+
+    def forward(self, xyz: torch.Tensor, features: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Drop-in surface: features [B,C,N] channel-major -> (new_xyz, new_features [B,C',M])."""
+        feat_pm = features.transpose(1, 2).contiguous() if features is not None else None
+        new_xyz, out_pm = self.forward_pm(xyz, feat_pm)
+        return new_xyz, out_pm.transpose(1, 2).contiguous()
+
+
+class SAModuleMSG(_Stage):
     """Multi-scale-grouping set abstraction.  ``weights`` = {"b<i>": [(W,b),...], "agg": [(W,b)]}
     as numpy arrays (BatchNorm folded); seeded Kaiming-uniform weights are drawn when omitted."""
 
@@ -30,26 +58,18 @@ class SAModuleMSG(nn.Module):
                  seed: int = 0, name: str = "sa", dtype: str = "f32"):
         """``dtype``: "f32" (SPEC.md §6, bit-exact fmaf chains) or "bf16" (SPEC.md §14: bf16 MFMA
         MLPs, float32 accumulation, bf16 stage outputs; index operators unchanged)."""
-        super().__init__()
+        super().__init__(in_channels, stage)
         if dtype not in ("f32", "bf16"):
             raise ValueError("dtype must be 'f32' or 'bf16'")
         self.dtype = dtype
         mlp_cls = ops.PackedMLP if dtype == "f32" else ops.PackedMLPBf16
-        self.stage = stage
-        self.in_channels = in_channels
         self.device = torch.device(device)
         if weights is None:
-            rng = np.random.default_rng(seed)
-            weights = {f"b{i}": make_mlp_weights([in_channels + 3] + list(m), rng)
-                       for i, m in enumerate(stage.mlps)}
-            if stage.agg:
-                weights["agg"] = make_mlp_weights([sum(m[-1] for m in stage.mlps), stage.agg], rng)
+            weights = stage_weights(in_channels, stage, seed)
         self.branches = [mlp_cls(weights[f"b{i}"], True, self.device, name=f"{name}.b{i}")
                          for i in range(len(stage.mlps))]
-        self.cat_channels = sum(m[-1] for m in stage.mlps)
         self.agg = (mlp_cls(weights["agg"], False, self.device, name=f"{name}.agg")
                     if stage.agg else None)
-        self.out_channels = stage.agg if stage.agg else self.cat_channels
 
     def sample(self, xyz: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """fps + gather: (fps_idx [B,M], new_xyz [B,M,3]).  Depends on coordinates only."""
@@ -167,37 +187,22 @@ class SAModuleMSG(nn.Module):
         _, new_xyz = self.sample(xyz)
         return new_xyz, self.group_and_pool(xyz, feat_pm, new_xyz)
 
-    def forward(self, xyz: torch.Tensor, features: Optional[torch.Tensor]
-                ) -> Tuple[torch.Tensor, torch.Tensor]:
-        """Drop-in surface: features [B,C,N] channel-major -> (new_xyz, new_features [B,C',M])."""
-        feat_pm = features.transpose(1, 2).contiguous() if features is not None else None
-        new_xyz, out_pm = self.forward_pm(xyz, feat_pm)
-        return new_xyz, out_pm.transpose(1, 2).contiguous()
 
-
-class SAModuleMSGTrain(nn.Module):
+class SAModuleMSGTrain(_Stage):
     """The trainable counterpart of ``SAModuleMSG`` (f32): built from the same ``SAStage`` and weights dict, same ``forward_pm`` /
-    ``forward`` surface.  Sampling and the ball query run under ``no_grad``; every branch is a ``SharedMLP`` (fused forward, the
-    backward of SPEC.md §32), so is the aggregation layer.  Without gradients the branches write into slices of one zeroed buffer
-    and the result equals ``SAModuleMSG``'s on the ``export()``ed weights bit for bit; with gradients each branch returns its
-    own pooled tensor (what its backward keeps) and the slices are concatenated.  Parameters are created with
+    ``forward`` surface.  Sampling and the ball query run under ``no_grad``; the branches are a ``shared_mlp.BranchGroup`` of
+    ``SharedMLP``s (fused forward, the backward of SPEC.md §32), the aggregation layer is a ``SharedMLP``.  Without gradients
+    the result equals ``SAModuleMSG``'s on the ``export()``ed weights bit for bit.  Parameters are created with
     ``requires_grad=False``: ``module.requires_grad_(True)`` selects training."""
 
     def __init__(self, in_channels: int, stage: SAStage, device, weights: Optional[dict] = None, seed: int = 0, name: str = "sa"):
-        super().__init__()
-        from .shared_mlp import SharedMLP
-        self.stage = stage
-        self.in_channels = in_channels
+        super().__init__(in_channels, stage)
+        from .shared_mlp import BranchGroup, SharedMLP
         if weights is None:
-            rng = np.random.default_rng(seed)
-            weights = {f"b{i}": make_mlp_weights([in_channels + 3] + list(m), rng) for i, m in enumerate(stage.mlps)}
-            if stage.agg:
-                weights["agg"] = make_mlp_weights([sum(m[-1] for m in stage.mlps), stage.agg], rng)
-        self.branches = nn.ModuleList([SharedMLP([in_channels + 3] + list(m), True, layers=weights[f"b{i}"], name=f"{name}.b{i}")
-                                       for i, m in enumerate(stage.mlps)])
-        self.cat_channels = sum(m[-1] for m in stage.mlps)
+            weights = stage_weights(in_channels, stage, seed)
+        self.branches = BranchGroup(SharedMLP([in_channels + 3] + list(m), True, layers=weights[f"b{i}"], name=f"{name}.b{i}")
+                                    for i, m in enumerate(stage.mlps))
         self.agg = SharedMLP([self.cat_channels, stage.agg], False, layers=weights["agg"], name=f"{name}.agg") if stage.agg else None
-        self.out_channels = stage.agg if stage.agg else self.cat_channels
         self.to(torch.device(device))
 
     def forward_pm(self, xyz: torch.Tensor, feat_pm: Optional[torch.Tensor], new_xyz: Optional[torch.Tensor] = None
@@ -209,25 +214,8 @@ class SAModuleMSGTrain(nn.Module):
             if new_xyz is None:
                 new_xyz = ops.gather_xyz(xyz, ops.fps(xyz, st.npoint))
             idxs, cnts = ops.ball_query_multi(st.radii, st.nsamples, xyz, new_xyz, None, return_counts=True)
-        train = torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters())
-                                             or (feat_pm is not None and feat_pm.requires_grad) or xyz.requires_grad)
-        if train:
-            outs = [mlp.grouped(xyz, feat_pm, new_xyz, idx, cnt) for mlp, idx, cnt in zip(self.branches, idxs, cnts)]
-            cat = outs[0] if len(outs) == 1 else torch.cat(outs, 2)
-        else:
-            with torch.no_grad():
-                cat = torch.zeros((new_xyz.shape[0], new_xyz.shape[1], self.cat_channels), dtype=torch.float32, device=xyz.device)
-                off = 0
-                for mlp, idx, cnt in zip(self.branches, idxs, cnts):
-                    mlp.packed().grouped(xyz, feat_pm, new_xyz, idx, out=cat, col_off=off, cnt=cnt)
-                    off += mlp.out_channels
+        cat = self.branches(xyz, feat_pm, new_xyz, idxs, cnts)
         return new_xyz, (cat if self.agg is None else self.agg.rows(cat))
-
-    def forward(self, xyz: torch.Tensor, features: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
-        """Drop-in surface: features [B,C,N] channel-major -> (new_xyz, new_features [B,C',M])."""
-        feat_pm = features.transpose(1, 2).contiguous() if features is not None else None
-        new_xyz, out_pm = self.forward_pm(xyz, feat_pm)
-        return new_xyz, out_pm.transpose(1, 2).contiguous()
 
     def export(self) -> dict:
         """The weights dict ``SAModuleMSG`` takes: {"b<i>": [(W, b), ...], "agg": [(W, b)]} as numpy arrays."""

@@ -22,15 +22,18 @@ def packed_for(cache, weights, biases, first_has_xyz: bool, relu_mask: Optional[
     return cache
 
 
-def _wants_grad(tensors) -> bool:
-    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+def wants_grad(*tensors, module: Optional[nn.Module] = None) -> bool:
+    """Does this call train?  Gradient mode is on and a tensor (``None`` entries are skipped) or a parameter of ``module``
+    requires grad: the one test every layer here puts in front of its choice between the fused call and its autograd form."""
+    return torch.is_grad_enabled() and (any(t is not None and t.requires_grad for t in tensors)
+                                        or (module is not None and any(p.requires_grad for p in module.parameters())))
 
 
 def grouped_chain(packed, weights, biases, xyz, feat_pm, new_xyz, idx, cnt=None, skip_empty: bool = False) -> torch.Tensor:
     """``packed.grouped`` of the chain whose unpacked parameters are ``weights`` / ``biases``: the fused call under ``no_grad`` or
     when nothing requires grad, else ``autograd.GroupedMLP``.  -> pooled [B,M,C_L]."""
     params = list(weights) + list(biases)
-    if not _wants_grad(params + [feat_pm, xyz, new_xyz]):
+    if not wants_grad(*params, feat_pm, xyz, new_xyz):
         with torch.no_grad():
             return packed.grouped(xyz, feat_pm, new_xyz, idx, cnt=cnt)
     return autograd.GroupedMLP.apply(packed, skip_empty, xyz, feat_pm, new_xyz, idx, cnt, *params)
@@ -79,7 +82,7 @@ class SharedMLP(nn.Module):
     def rows(self, x: torch.Tensor) -> torch.Tensor:
         """Plain rows x [..., C_0] -> [..., C_L] (``PackedMLP.rows``), differentiable in the parameters and ``x``."""
         params = list(self.weight) + list(self.bias)
-        if not _wants_grad(params + [x]):
+        if not wants_grad(*params, x):
             with torch.no_grad():
                 return self.packed().rows(x)
         return autograd.MLPRows.apply(self.packed(), x, *params)
@@ -90,3 +93,27 @@ class SharedMLP(nn.Module):
 
     def extra_repr(self) -> str:
         return f"dims={self.dims}, first_has_xyz={self.first_has_xyz}, relu_mask={self.relu_mask}"
+
+
+class BranchGroup(nn.ModuleList):
+    """The branches of a multi-radius layer: ``SharedMLP``s that pool the same (xyz, feat_pm, new_xyz), each over the ball query
+    of its own radius, into one [B,M,``cat_channels``] tensor.  Without gradients the branches write into slices of one zeroed
+    buffer, as the inference modules do; with gradients each branch returns its own pooled tensor (what its backward keeps) and
+    the tensors are concatenated (one branch: its tensor, no copy).  The two forms are equal bit for bit."""
+
+    def __init__(self, mlps):
+        super().__init__(mlps)
+        self.cat_channels = sum(mlp.out_channels for mlp in self)
+
+    def forward(self, xyz: torch.Tensor, feat_pm: Optional[torch.Tensor], new_xyz: torch.Tensor, idxs, cnts) -> torch.Tensor:
+        """``idxs`` / ``cnts``: one idx [B,M,S_b] and one cnt [B,M] per branch (``ops.ball_query_multi``) -> [B,M,sum C_b]."""
+        if wants_grad(xyz, feat_pm, new_xyz, module=self):
+            outs = [mlp.grouped(xyz, feat_pm, new_xyz, idx, cnt) for mlp, idx, cnt in zip(self, idxs, cnts)]
+            return outs[0] if len(outs) == 1 else torch.cat(outs, 2)
+        with torch.no_grad():
+            cat = torch.zeros((new_xyz.shape[0], new_xyz.shape[1], self.cat_channels), dtype=torch.float32, device=xyz.device)
+            off = 0
+            for mlp, idx, cnt in zip(self, idxs, cnts):
+                mlp.packed().grouped(xyz, feat_pm, new_xyz, idx, out=cat, col_off=off, cnt=cnt)
+                off += mlp.out_channels
+        return cat

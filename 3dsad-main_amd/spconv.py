@@ -21,6 +21,7 @@ import torch
 from torch import nn
 
 from . import autograd, ops
+from .shared_mlp import wants_grad
 
 
 class SparseTensor:
@@ -67,7 +68,7 @@ class SparseTensor:
 
     def dense(self) -> torch.Tensor:
         """-> [B,C,Gz,Gy,Gx], zero where no voxel is (§21.3); differentiable with respect to ``feat`` (§21.4)."""
-        if torch.is_grad_enabled() and self.feat.requires_grad:
+        if wants_grad(self.feat):
             return autograd.sparse_to_dense(self.feat, self.coors, self.offsets, self.spatial_shape)
         return ops.sparse_to_dense(self.feat, self.coors, self.offsets, self.spatial_shape)
 
@@ -159,7 +160,7 @@ class _SparseConvBase(nn.Module):
     def forward(self, x: SparseTensor, residual: Optional[torch.Tensor] = None) -> SparseTensor:
         if x.feat.shape[1] != self.in_channels:
             raise ValueError(f"{self.in_channels} input channels expected, got {x.feat.shape[1]}")
-        train = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x.feat, self.weight, self.bias, residual))
+        train = wants_grad(x.feat, self.weight, self.bias, residual)
         with torch.no_grad():
             out_coors, out_offsets, nbr, out_shape = self.rulebook(x)
             if not train:
@@ -228,7 +229,7 @@ class SparseInverseConv3d(_SparseConvBase):
         if x.feat.shape[1] != self.in_channels:
             raise ValueError(f"{self.in_channels} input channels expected, got {x.feat.shape[1]}")
         in_coors, in_offsets, in_shape, nbr = self.rulebook(x)
-        train = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x.feat, self.weight, self.bias, residual))
+        train = wants_grad(x.feat, self.weight, self.bias, residual)
         with torch.no_grad():
             nbrT, collisions = _transposed(x, self.indice_key, nbr, in_coors.shape[0])
             if not train:
@@ -261,7 +262,7 @@ class SparseMaxPool3d(nn.Module):
         return _transposed(x, self.indice_key, nbr, x.feat.shape[0])
 
     def forward(self, x: SparseTensor) -> SparseTensor:
-        train = torch.is_grad_enabled() and x.feat.requires_grad
+        train = wants_grad(x.feat)
         with torch.no_grad():
             out_coors, out_offsets, nbr, out_shape = self.rulebook(x)
             if not train:

@@ -26,7 +26,7 @@ import torch
 from torch import nn
 
 from . import autograd, ops
-from .shared_mlp import grouped_chain, packed_for
+from .shared_mlp import grouped_chain, packed_for, wants_grad
 from .spconv import SparseTensor
 
 
@@ -98,7 +98,7 @@ class VoxelRoIPool(nn.Module):
         for k, (t, s) in enumerate(zip(tensors, self.scales)):
             if t.feat.shape[1] != s["in_channels"]:
                 raise ValueError(f"tensors[{k}]: {s['in_channels']} feature channels expected, got {t.feat.shape[1]}")
-        train = torch.is_grad_enabled() and (any(t.feat.requires_grad for t in tensors) or any(p.requires_grad for p in self.parameters()))
+        train = wants_grad(*(t.feat for t in tensors), module=self)
         with torch.no_grad():
             pts = ops.roi_grid_points(rois, roi_count, self.grid_size)
         B, R, P, _ = pts.shape

@@ -58,24 +58,33 @@ def three_nn_lexsort(unknown, known):
     return dist, idx
 
 
+def in_range(idx, m):
+    """[B,n,3] bool: the slots whose index names a known point; §18: any other slot reads a zero feature and gets no gradient."""
+    return (idx >= 0) & (idx < m)
+
+
 def three_interpolate_pm(feat_pm, idx, w):
-    """feat [B,m,C], idx / w [B,n,3] -> [B,n,C]: (w0*f0 + w1*f1) + w2*f2, every operation rounded."""
+    """feat [B,m,C], idx / w [B,n,3] -> [B,n,C]: (w0*f0 + w1*f1) + w2*f2, every operation rounded; a slot whose index lies
+    outside [0, m) reads a zero feature (its product w * 0 is still formed)."""
     out = np.empty((idx.shape[0], idx.shape[1], feat_pm.shape[2]), F)
+    ok = in_range(idx, feat_pm.shape[1])
     for b in range(idx.shape[0]):
-        f = [feat_pm[b][idx[b, :, k]] for k in range(3)]
+        f = [np.where(ok[b, :, k:k + 1], feat_pm[b][np.where(ok[b, :, k], idx[b, :, k], 0)], F(0)) for k in range(3)]
         ww = [w[b, :, k:k + 1] for k in range(3)]
         out[b] = (ww[0] * f[0] + ww[1] * f[1]) + ww[2] * f[2]
     return out
 
 
 def three_interpolate_grad_pm(grad_pm, idx, w, m):
-    """binary64 sum of the terms w_k * grad (and of their magnitudes): ([B,m,C], [B,m,C])."""
+    """binary64 sum of the terms w_k * grad (and of their magnitudes) over the slots whose index lies in [0, m):
+    ([B,m,C], [B,m,C])."""
     B, n, C = grad_pm.shape
     ref = np.zeros((B, m, C), np.float64)
     mag = np.zeros((B, m, C), np.float64)
+    ok = in_range(idx, m)
     for b in range(B):
         for k in range(3):
-            t = w[b, :, k:k + 1].astype(np.float64) * grad_pm[b].astype(np.float64)
-            np.add.at(ref[b], idx[b, :, k], t)
-            np.add.at(mag[b], idx[b, :, k], np.abs(t))
+            t = (w[b, :, k:k + 1].astype(np.float64) * grad_pm[b].astype(np.float64))[ok[b, :, k]]
+            np.add.at(ref[b], idx[b, ok[b, :, k], k], t)
+            np.add.at(mag[b], idx[b, ok[b, :, k], k], np.abs(t))
     return ref, mag

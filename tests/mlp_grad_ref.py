@@ -25,9 +25,13 @@ def make_layers(rng, dims, lattice):
 
 
 def make_counts(rng, B, M, S, mode):
-    """cnt [B,M] int32: "mixed" holds 0, 1, S and values between in one call, scene 1 is less populated than scene 0."""
+    """cnt [B,M] int32: "mixed" holds 0, 1, S and values between in one call, scene 1 is less populated than scene 0; "ones" /
+    "zeros": every count 1 / 0 (rows far below the slots; nothing but empty groups); None: no counts."""
     if mode is None:
         return None
+    if mode in ("ones", "zeros"):
+        return np.full((B, M), int(mode == "ones"), np.int32)
+    assert mode == "mixed", mode
     cnt = rng.integers(0, S + 1, (B, M))
     flat = cnt.reshape(-1)
     flat[0::7] = 0
@@ -208,3 +212,79 @@ def rows_case(R, lattice, seed=0):
     rng = np.random.default_rng([seed, R, int(lattice)])
     x = (rng.integers(-2, 3, (R, ROWS_DIMS[0])) if lattice else rng.standard_normal((R, ROWS_DIMS[0]))).astype(np.float32)
     return x, make_layers(rng, ROWS_DIMS, lattice), make_grad(rng, (R, ROWS_DIMS[-1]), lattice)
+
+
+# The contract edges and tile boundaries (tests/test_gpu_mlp_grad_edges.py), seeded apart from GROUPED_CASES so that neither
+# table moves the other's inputs.  The GEMM tile is 128 channels x 64 rows x 32 k and a wave owns 32 channels: C_0 = 32 / 64 / 65,
+# widths 1 / 32 / 128 / 129 / 257 (one logit, exact wave and block multiples, one channel into the next block, three blocks), K and
+# the weight gradient's J at 64 / 65; chunks of exactly 64 and 128 rows; 100 rows in 6400 slots; nothing but empty groups;
+# more than three chunks of the minimum workspace with and without counts (without: row = g S + s at a chunk base g0 > 0).
+EDGE_CASES = {
+    "w1_C29_S16_mixed": dict(B=1, N=40, M=9, S=16, C=29, widths=[32, 1], cnt_mode="mixed", skip=False),
+    "w128_C61_S16_mixed": dict(B=1, N=40, M=9, S=16, C=61, widths=[128, 32], cnt_mode="mixed", skip=False),
+    "w129_C62_S16_mixed": dict(B=1, N=40, M=9, S=16, C=62, widths=[129, 64, 65], cnt_mode="mixed", skip=False),
+    "w257_C5_S16_mixed": dict(B=1, N=40, M=9, S=16, C=5, widths=[257, 10], cnt_mode="mixed", skip=False),
+    "rows64_M4_S16_nocnt": dict(B=1, N=40, M=4, S=16, C=5, widths=[33, 10], cnt_mode=None, skip=False),
+    "rows128_M2_S64_nocnt": dict(B=1, N=40, M=2, S=64, C=5, widths=[33, 10], cnt_mode=None, skip=False),
+    "sparse_M100_S64_ones": dict(B=1, N=40, M=100, S=64, C=5, widths=[33, 10], cnt_mode="ones", skip=False),
+    "empty_M100_S64_zeros_skip": dict(B=1, N=40, M=100, S=64, C=5, widths=[33, 10], cnt_mode="zeros", skip=True),
+    "chunks_M100_S16_nocnt_B2": dict(B=2, N=60, M=100, S=16, C=5, widths=[33, 10], cnt_mode=None, skip=False),
+    "chunks_M100_S16_mixed_B2": dict(B=2, N=60, M=100, S=16, C=5, widths=[33, 10], cnt_mode="mixed", skip=False),
+}
+EDGE_ROWS_DIMS = {"64_257_1": [64, 257, 1], "65_128_32": [65, 128, 32]}
+EDGE_ROWS_MASKS = {"all": 3, "none": 0}
+EDGE_ROWS_R = (64, 128)
+
+
+def edge_case(name, lattice, seed=0):
+    """-> (inputs dict, layers, grad_out [B,M,C_L]) of a named edge case (every coordinate finite; a test that wants NaN
+    coordinates in skipped groups writes them itself)."""
+    c = EDGE_CASES[name]
+    rng = np.random.default_rng([seed, sorted(EDGE_CASES).index(name), int(lattice), 1])
+    xyz, feat, new_xyz, idx, cnt = make_grouped(rng, c["B"], c["N"], c["M"], c["S"], c["C"], c["cnt_mode"], lattice)
+    layers = make_layers(rng, [3 + c["C"]] + c["widths"], lattice)
+    grad_out = make_grad(rng, (c["B"], c["M"], c["widths"][-1]), lattice)
+    return dict(xyz=xyz, feat=feat, new_xyz=new_xyz, idx=idx, cnt=cnt, skip_empty=c["skip"]), layers, grad_out
+
+
+def edge_rows_case(R, dims_name, lattice, seed=0):
+    dims = EDGE_ROWS_DIMS[dims_name]
+    rng = np.random.default_rng([seed, R, int(lattice), sorted(EDGE_ROWS_DIMS).index(dims_name), 1])
+    x = (rng.integers(-2, 3, (R, dims[0])) if lattice else rng.standard_normal((R, dims[0]))).astype(np.float32)
+    return x, make_layers(rng, dims, lattice), make_grad(rng, (R, dims[-1]), lattice)
+
+
+LATTICE_UNIT = 2.0 ** -6     # every lattice input is a multiple of it (coordinates: k / 64; everything else: integers)
+
+
+def order_free(res):
+    """True when every sum of a lattice case is exact in float32 in ANY order: all terms are multiples of LATTICE_UNIT and
+    the sum of their magnitudes (``A``) stays below 2^24 units, so no partial sum of any grouping needs more than 24 bits."""
+    worst = 0.0
+    for v in res["A"].values():
+        for a in (v if isinstance(v, list) else [v]):
+            worst = max(worst, float(np.max(a, initial=0.0)))
+    return worst / LATTICE_UNIT < 2.0 ** 24, worst
+
+
+def corrupt_pairs(cnt, grad_out, k_live, k_dead):
+    """(group, channel) pairs whose pooled value a test overwrites: ``k_live`` in groups with cnt > 0 (``cnt`` None: any group)
+    and ``k_dead`` in groups with cnt == 0, dealt in turn to the scenes and spread from the first to the last such group of
+    each, at channels where grad_out is not 0 -> [(b, m, o)], no pair twice."""
+    B, M, CL = grad_out.shape
+    pairs = []
+    for k, want in ((k_live, np.ones((B, M), bool) if cnt is None else cnt > 0), (k_dead, None if cnt is None else cnt == 0)):
+        per = -(-k // B)
+        for i in range(k):
+            b, groups = i % B, np.nonzero(want[i % B])[0]
+            m = int(groups[(i // B) * (len(groups) - 1) // max(1, per - 1)])
+            o = next(o % CL for o in range(7 * i, 7 * i + CL) if grad_out[b, m, o % CL] != 0 and (b, m, o % CL) not in pairs)
+            pairs.append((b, m, o))
+    return pairs
+
+
+def zero_pairs(grad_out, pairs):
+    g = grad_out.copy()
+    for b, m, o in pairs:
+        g[b, m, o] = 0
+    return g

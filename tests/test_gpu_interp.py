@@ -133,3 +133,51 @@ def test_fp_module_bit_exact(orc, sad, dev, B, n, m, C1, C2, mlp):
     got = mod(_t(unk, dev), _t(kn, dev), _t(sk.transpose(0, 2, 1), dev) if C1 else None,
               _t(kf.transpose(0, 2, 1), dev)).cpu().numpy()
     np.testing.assert_array_equal(got, want.transpose(0, 2, 1))
+
+
+def _edge_inputs(B, n, m, C, seed):
+    """Slots outside [0, m) (-1, m, 2^31 - 1; about a third, some points with all three), weights and gradient entries that are
+    exactly 0, and one known point (0) that no valid slot names."""
+    rng = np.random.default_rng(seed)
+    feat_pm = rng.standard_normal((B, m, C)).astype(np.float32)
+    idx = rng.integers(1, m, (B, n, 3)).astype(np.int32)
+    bad = rng.random((B, n, 3)) < 0.3
+    bad[:, ::9] = True
+    idx[bad] = rng.choice(np.array([-1, m, 2 ** 31 - 1], np.int32), int(bad.sum()))
+    w = rng.random((B, n, 3), dtype=np.float32)
+    w[rng.random((B, n, 3)) < 0.2] = 0.0
+    g_pm = rng.standard_normal((B, n, C)).astype(np.float32)
+    g_pm[rng.random((B, n, C)) < 0.2] = 0.0
+    ok = ref.in_range(idx, m)
+    assert not ok.all(2).all() and ok.any() and (w[~ok] != 0).any() and (w[ok] == 0).any() and {-1, m, 2 ** 31 - 1} <= set(idx[~ok].tolist())
+    return feat_pm, idx, w, g_pm
+
+
+@pytest.mark.parametrize("C", [4, 5, 64, 65])                   # point-major: 16-byte chunks (C % 4 == 0) / one channel per thread
+@pytest.mark.parametrize("n", [63, 64, 65])                     # around the 64-point tile of the channel-major gradient
+def test_three_interpolate_out_of_range_slots(sad, dev, n, C):
+    """An index outside [0, m) reads a zero feature and receives no gradient (interp.hip's ``(unsigned)j >= m`` branches), the
+    gradient skips g == 0 and w * g == 0: forward bit-equal to the reference, gradient within the rule of
+    test_three_interpolate_grad of the float64 sum without those slots, exactly 0 for known points no valid slot names."""
+    from sad_amd import ops
+    B, m = 2, 5
+    feat_pm, idx, w, g_pm = _edge_inputs(B, n, m, C, 100 * n + C)
+    want = ref.three_interpolate_pm(feat_pm, idx, w)
+    ti, tw = _t(idx, dev), _t(w, dev)
+    np.testing.assert_array_equal(ops.three_interpolate(_t(feat_pm, dev), ti, tw, point_major=True).cpu().numpy(), want)
+    np.testing.assert_array_equal(ops.three_interpolate(_t(feat_pm.transpose(0, 2, 1), dev), ti, tw).cpu().numpy(), want.transpose(0, 2, 1))
+    if C % 4 == 0:                                               # the same width through the one-channel form: a slice at an odd column
+        out = _t(np.full((B, n, C + 3), np.nan, np.float32), dev)
+        ops.three_interpolate(_t(feat_pm, dev), ti, tw, point_major=True, out=out, col_off=1)
+        np.testing.assert_array_equal(out[..., 1:1 + C].cpu().numpy(), want)
+    gwant, mag = ref.three_interpolate_grad_pm(g_pm, idx, w, m)
+    tol = 1e-5 * mag + 1e-30
+    named = np.zeros((B, m), bool)
+    for b in range(B):
+        named[b, idx[b][ref.in_range(idx[b], m)]] = True
+    assert not named[:, 0].any() and named[:, 1:].all()
+    got_pm = ops.three_interpolate_grad(_t(g_pm, dev), ti, tw, m, point_major=True).cpu().numpy()
+    got_cm = ops.three_interpolate_grad(_t(g_pm.transpose(0, 2, 1), dev), ti, tw, m).cpu().numpy().transpose(0, 2, 1)
+    for name, got in (("point-major", got_pm), ("channel-major", got_cm)):
+        assert np.all(np.abs(got - gwant) <= tol), name
+        assert (got[~named] == 0).all(), f"{name}: gradient at a known point that no valid slot names"

@@ -54,6 +54,31 @@ def test_reference_weights_follow_the_spec_order():
     np.testing.assert_array_equal(w[0, 1], np.array([1, 0, 0], np.float32))
 
 
+def test_reference_out_of_range_slots_read_a_zero_feature():
+    """A slot outside [0, m) is a slot that names an extra known point whose features are 0 (forward: the same bits; gradient:
+    the same sums on the m real points); in range the reference is the plain gather it was."""
+    rng = np.random.default_rng(3)
+    B, n, m, C = 2, 65, 5, 5
+    feat = rng.standard_normal((B, m, C)).astype(np.float32)
+    idx = rng.integers(0, m, (B, n, 3)).astype(np.int32)
+    w = rng.random((B, n, 3), dtype=np.float32)
+    g = rng.standard_normal((B, n, C)).astype(np.float32)
+    plain = np.stack([(w[b, :, 0:1] * feat[b][idx[b, :, 0]] + w[b, :, 1:2] * feat[b][idx[b, :, 1]]) + w[b, :, 2:3] * feat[b][idx[b, :, 2]]
+                      for b in range(B)])
+    np.testing.assert_array_equal(ref.three_interpolate_pm(feat, idx, w), plain)
+    bad = idx.copy()
+    sel = rng.random(idx.shape) < 0.3
+    bad[sel] = rng.choice(np.array([-1, m, 2 ** 31 - 1, -2 ** 31], np.int32), int(sel.sum()))
+    assert not ref.in_range(bad, m)[sel].any() and ref.in_range(bad, m)[~sel].all()
+    ext = np.concatenate([feat, np.zeros((B, 1, C), np.float32)], 1)
+    to_ext = np.where(sel, m, idx).astype(np.int32)
+    np.testing.assert_array_equal(ref.three_interpolate_pm(feat, bad, w), ref.three_interpolate_pm(ext, to_ext, w))
+    got, mag = ref.three_interpolate_grad_pm(g, bad, w, m)
+    want, wmag = ref.three_interpolate_grad_pm(g, to_ext, w, m + 1)
+    np.testing.assert_array_equal(got, want[:, :m])
+    np.testing.assert_array_equal(mag, wmag[:, :m])
+
+
 def test_host_side_argument_errors(sad):
     from sad_amd import _lib
     L = _lib.lib()

@@ -86,6 +86,67 @@ def test_rows_reference_matches_torch_autograd_and_lattice_is_exact(orc, R, mask
     _compare(ref.rows_ref(orc, x, layers, m, grad_out, dtype=np.float32)["val"], r64["val"])
 
 
+@pytest.mark.parametrize("name", sorted(ref.EDGE_CASES))
+def test_edge_reference_matches_torch_autograd_and_lattice_is_exact(orc, name):
+    """The same two checks for every case of EDGE_CASES (tests/test_gpu_mlp_grad_edges.py asserts equality on them), and the
+    stronger form of the second: the sums are exact in float32 in any order, which is what the kernels' atomics need."""
+    inp, layers, grad_out = ref.edge_case(name, lattice=True)
+    r64 = ref.grouped_ref(orc, layers=layers, grad_out=grad_out, **inp)
+    c = ref.EDGE_CASES[name]
+    slots = c["B"] * c["M"] * c["S"]
+    want_rows = {None: slots, "ones": c["B"] * c["M"], "zeros": 0}.get(c["cnt_mode"])
+    assert r64["rows"] == want_rows if want_rows is not None else 0 < r64["rows"] < slots
+    _compare(r64["val"], _torch_grouped(inp, layers, grad_out))
+    r32 = ref.grouped_ref(orc, layers=layers, grad_out=grad_out, dtype=np.float32, **inp)
+    _compare(r32["val"], r64["val"])
+    ok, worst = ref.order_free(r64)
+    assert ok, f"{name}: sum of magnitudes {worst} reaches 2^24 lattice units"
+    if inp["cnt"] is not None and not inp["skip_empty"]:
+        dense = ref.grouped_ref(orc, layers=layers, grad_out=grad_out, **dict(inp, cnt=None))
+        _compare(dense["val"], r64["val"])
+    if c["cnt_mode"] == "zeros":                                                     # nothing but empty groups: every gradient is 0
+        for v in r64["val"].values():
+            assert all((a == 0).all() for a in (v if isinstance(v, list) else [v]))
+
+
+def test_grouped_reference_with_masked_pairs_is_autograd_of_a_masked_output(orc):
+    """What the counter test of the GPU file compares against: zeroing grad_out at chosen (group, channel) pairs is the gradient
+    of an output from which those pairs were removed, so a pair that route gives no row contributes to no gradient."""
+    inp, layers, grad_out = ref.grouped_case("L3_C5_S33_skip_B2", lattice=True)
+    pairs = ref.corrupt_pairs(inp["cnt"], grad_out, 12, 4)
+    masked = ref.zero_pairs(grad_out, pairs)
+    assert sum(inp["cnt"][b, m] == 0 for b, m, _ in pairs) >= 3 and {b for b, _, _ in pairs} == {0, 1}
+    assert all(grad_out[b, m, o] != 0 for b, m, o in pairs) and (masked != grad_out).sum() == len(pairs)
+    r = ref.grouped_ref(orc, layers=layers, grad_out=masked, **inp)
+    _compare(r["val"], _torch_grouped(inp, layers, masked))
+    full = ref.grouped_ref(orc, layers=layers, grad_out=grad_out, **inp)
+    assert any((a != b).any() for a, b in zip(r["val"]["grad_W"], full["val"]["grad_W"])), "the live pairs chosen carry no gradient"
+    assert ref.order_free(r)[0]
+
+
+@pytest.mark.parametrize("mask", sorted(ref.EDGE_ROWS_MASKS))
+@pytest.mark.parametrize("dims", sorted(ref.EDGE_ROWS_DIMS))
+@pytest.mark.parametrize("R", ref.EDGE_ROWS_R)
+def test_edge_rows_reference_matches_torch_autograd_and_lattice_is_exact(orc, R, dims, mask):
+    x, layers, grad_out = ref.edge_rows_case(R, dims, lattice=True)
+    m = ref.EDGE_ROWS_MASKS[mask]
+    r64 = ref.rows_ref(orc, x, layers, m, grad_out)
+    t = lambda a: torch.from_numpy(np.asarray(a, np.float64))
+    xt = t(x).requires_grad_()
+    Ws, bs = [t(w).requires_grad_() for w, _ in layers], [t(b).requires_grad_() for _, b in layers]
+    y = xt
+    for l, (w, b) in enumerate(zip(Ws, bs)):
+        y = y @ w.t() + b
+        if (m >> l) & 1:
+            y = torch.relu(y)
+    assert (y.detach().numpy() == r64["out"]).all()
+    (y * t(grad_out)).sum().backward()
+    _compare(r64["val"], {"grad_x": xt.grad.numpy(), "grad_W": [w.grad.numpy() for w in Ws], "grad_b": [b.grad.numpy() for b in bs]})
+    _compare(ref.rows_ref(orc, x, layers, m, grad_out, dtype=np.float32)["val"], r64["val"])
+    ok, worst = ref.order_free(r64)
+    assert ok, f"R = {R}, {dims}: sum of magnitudes {worst} reaches 2^24 lattice units"
+
+
 def _cpu_call(**over):
     """Arguments of a well-formed grouped call on CPU tensors (refused as such at the very end), with overrides."""
     B, N, M, S, C = 1, 8, 4, 2, 2

@@ -6,7 +6,8 @@ arithmetic, so the kernels are compared with ``==``.  ``cluster_ref`` is the flo
 indices: head rows, cluster.agg rows, one ``grouped_ref`` per branch, the summed grad_new_xyz, ``candidates_grad``, the candidate
 MLP's rows, the padded prefix plus the branches' grad_feat.  Beside every value runs its absolute companion ``A`` and the number
 of roundings ``n`` on the longest path (mlp_grad_ref's bound): a stage that takes a computed gradient adds that gradient's n to
-its own, a sum of k computed terms has the terms' n added up plus k - 1."""
+its own, a sum of k computed terms has the terms' n added up plus k - 1.  ``stack_ref`` carries the gradient at SA3's output on
+through the SA stages (§7) the same way; both walk a multi-radius layer with ``_cat_backward``."""
 import numpy as np
 
 import mlp_grad_ref as ref
@@ -86,6 +87,46 @@ def _pooled(orc, inp, layers):
     return ref.grouped_ref(orc, layers=layers, grad_out=z, **inp)["pooled"]
 
 
+def _put(grads, name, r, layers, extra_n=0):
+    """The parameter gradients of a chain result ``r`` (``rows_chain`` / ``grouped_ref``) as (val, A, n) entries of ``grads``."""
+    for l in range(len(layers)):
+        grads[f"{name}.W{l}"] = (r["val"]["grad_W"][l], r["A"]["grad_W"][l], r["depth"]["grad_W"][l] + extra_n)
+        grads[f"{name}.b{l}"] = (r["val"]["grad_b"][l], r["A"]["grad_b"][l], r["depth"]["grad_b"][l] + extra_n)
+
+
+def _cat_forward(orc, branch, blayers, agg_layers):
+    """The forward of a multi-radius layer: the branches' pooled rows side by side -> (cat [B*M, sum C_b], the aggregation
+    layer's output [B*M, C'])."""
+    B, M = branch[0]["idx"].shape[:2]
+    cat = np.concatenate([_pooled(orc, inp, layers) for inp, layers in zip(branch, blayers)], 2).reshape(B * M, -1)
+    return cat, rows_chain(orc, cat, agg_layers, 1, np.zeros((B * M, agg_layers[-1][0].shape[0])))["out"]
+
+
+def _cat_backward(orc, grads, name, branch, blayers, cat, agg_layers, g, gA, n_in):
+    """The backward of a multi-radius layer (branches -> cat -> aggregation layer with ReLU) from the gradient (g, gA, n_in) at
+    the aggregation layer's output: ``rows_chain`` on the aggregation layer, one ``grouped_ref`` per branch with its column
+    slice of grad_x as grad_out, the branches' input gradients summed.  Writes "<name>.agg.*" and "<name>.b<k>.*" into ``grads``
+    -> {"grad_feat" (where the branches have input features), "grad_new_xyz": (val, A, n)}; n: every branch's depth plus the
+    aggregation's grad_x depth, plus nb - 1 for the sum."""
+    B, M = branch[0]["idx"].shape[:2]
+    agg = rows_chain(orc, cat, agg_layers, 1, g, gA, n_in)
+    _put(grads, f"{name}.agg", agg, agg_layers)
+    n_a = agg["depth"]["grad_x"]
+    keys = ("grad_feat", "grad_new_xyz") if branch[0]["feat"] is not None else ("grad_new_xyz",)
+    tot = {k: [0.0, 0.0, len(branch) - 1] for k in keys}
+    off = 0
+    for k, (inp, layers) in enumerate(zip(branch, blayers)):
+        co = layers[-1][0].shape[0]
+        go = agg["val"]["grad_x"][:, off:off + co].reshape(B, M, co)
+        goA = agg["A"]["grad_x"][:, off:off + co].reshape(B, M, co)
+        r = ref.grouped_ref(orc, layers=layers, grad_out=go, grad_out_A=goA, **inp)
+        _put(grads, f"{name}.b{k}", r, layers, n_a)
+        for key, t in tot.items():
+            t[0], t[1], t[2] = t[0] + r["val"][key], t[1] + r["A"][key], t[2] + r["depth"][key] + n_a
+        off += co
+    return {k: tuple(t) for k, t in tot.items()}
+
+
 def cluster_ref(orc, xyz3, feat3, weights, K, shift_max, idxs, cnts, w_o, w_c, c=None):
     """The cluster section (§8 + §9) forward and backward of ``(o * w_o).sum() + (c * w_c).sum()`` on the indices ``idxs`` /
     ``cnts`` (one [B,K,S] / [B,K] pair per branch).  ``orc``: the oracle (its §6 bits decide every ReLU, arg-max and clamp) or
@@ -102,38 +143,17 @@ def cluster_ref(orc, xyz3, feat3, weights, K, shift_max, idxs, cnts, w_o, w_c, c
     c_use = c_own if c is None else c
     cand = step2(xyz3[:, :K], c_use, shift_max, np.float32 if c_use.dtype == np.float32 else np.float64).astype(np.float32)
     branch = [dict(xyz=xyz3, feat=feat3, new_xyz=cand, idx=i, cnt=n, skip_empty=False) for i, n in zip(idxs, cnts)]
-    cat = np.concatenate([_pooled(orc, inp, weights[f"cluster.b{k}"]) for k, inp in enumerate(branch)], 2).reshape(B * K, -1)
-    agg_out = rows_chain(orc, cat, weights["cluster.agg"], 1, np.zeros((B * K, weights["cluster.agg"][-1][0].shape[0])))["out"]
+    blayers = [weights[f"cluster.b{k}"] for k in range(nb)]
+    cat, agg_out = _cat_forward(orc, branch, blayers, weights["cluster.agg"])
     # ---- backward
     grads = {}
-
-    def put(name, r, layers):
-        for l in range(len(layers)):
-            grads[f"{name}.W{l}"] = (r["val"]["grad_W"][l], r["A"]["grad_W"][l], r["depth"]["grad_W"][l])
-            grads[f"{name}.b{l}"] = (r["val"]["grad_b"][l], r["A"]["grad_b"][l], r["depth"]["grad_b"][l])
-
     Co = weights["head"][-1][0].shape[0]
     head = rows_chain(orc, agg_out, weights["head"], mask(weights["head"]), np.asarray(w_o).reshape(B * K, Co))
-    put("head", head, weights["head"])
-    agg = rows_chain(orc, cat, weights["cluster.agg"], 1, head["val"]["grad_x"], head["A"]["grad_x"], head["depth"]["grad_x"])
-    put("cluster.agg", agg, weights["cluster.agg"])
-    n_a = agg["depth"]["grad_x"]
-    gf, gfA, gf_n = 0.0, 0.0, 0
-    gn, gnA, gn_n = 0.0, 0.0, 0
-    off = 0
-    for k, inp in enumerate(branch):
-        layers = weights[f"cluster.b{k}"]
-        co = layers[-1][0].shape[0]
-        go = agg["val"]["grad_x"][:, off:off + co].reshape(B, K, co)
-        goA = agg["A"]["grad_x"][:, off:off + co].reshape(B, K, co)
-        r = ref.grouped_ref(orc, layers=layers, grad_out=go, grad_out_A=goA, **inp)
-        for l in range(len(layers)):
-            grads[f"cluster.b{k}.W{l}"] = (r["val"]["grad_W"][l], r["A"]["grad_W"][l], r["depth"]["grad_W"][l] + n_a)
-            grads[f"cluster.b{k}.b{l}"] = (r["val"]["grad_b"][l], r["A"]["grad_b"][l], r["depth"]["grad_b"][l] + n_a)
-        gf, gfA, gf_n = gf + r["val"]["grad_feat"], gfA + r["A"]["grad_feat"], gf_n + r["depth"]["grad_feat"] + n_a
-        gn, gnA, gn_n = gn + r["val"]["grad_new_xyz"], gnA + r["A"]["grad_new_xyz"], gn_n + r["depth"]["grad_new_xyz"] + n_a
-        off += co
-    gn_n += nb - 1
+    _put(grads, "head", head, weights["head"])
+    tot = _cat_backward(orc, grads, "cluster", branch, blayers, cat, weights["cluster.agg"], head["val"]["grad_x"], head["A"]["grad_x"],
+                        head["depth"]["grad_x"])
+    gf, gfA, gf_n = tot["grad_feat"]
+    gn, gnA, gn_n = tot["grad_new_xyz"]
     grads["cand_xyz"] = (gn, gnA, gn_n)
     # candidates_grad (a selection on c) plus the direct gradient of (c * w_c).sum()
     wc = np.asarray(w_c, np.float64).reshape(B, K, 6)
@@ -142,12 +162,52 @@ def cluster_ref(orc, xyz3, feat3, weights, K, shift_max, idxs, cnts, w_o, w_c, c
     gc_n = gn_n + 1
     grads["c"] = (gc, gcA, gc_n)
     cm = rows_chain(orc, xk, weights["cand"], mask(weights["cand"]), gc.reshape(B * K, 6), gcA.reshape(B * K, 6), gc_n)
-    put("cand", cm, weights["cand"])
+    _put(grads, "cand", cm, weights["cand"])
     pad = prefix_rows_grad_ref(cm["val"]["grad_x"].reshape(B, K, C3), M3)
     padA = prefix_rows_grad_ref(cm["A"]["grad_x"].reshape(B, K, C3), M3)
-    grads["feat3"] = (gf + pad, gfA + padA, gf_n + cm["depth"]["grad_x"] + nb)
+    grads["feat3"] = (gf + pad, gfA + padA, gf_n + cm["depth"]["grad_x"] + 1)
     o = head["out"].reshape(B, K, Co)
     return {"c": c_own, "cand": cand, "o": o, "grads": grads}
+
+
+def _stage_branches(st):
+    return [dict(xyz=st["xyz"], feat=st["feat"], new_xyz=st["new_xyz"], idx=i, cnt=n, skip_empty=False) for i, n in zip(st["idxs"], st["cnts"])]
+
+
+def stage_forward(orc, st, weights, s):
+    """The forward of SA stage ``s`` (1-based; SPEC.md §7) on a stage dict (see ``stack_ref``) -> (cat [B*M, sum C_b], out
+    [B,M,C']): the oracle's §6 bits, or float64 activations with ``orc`` None."""
+    nb = len(st["idxs"])
+    cat, out = _cat_forward(orc, _stage_branches(st), [weights[f"sa{s}.b{k}"] for k in range(nb)], weights[f"sa{s}.agg"])
+    return cat, out.reshape(st["new_xyz"].shape[:2] + (-1,))
+
+
+def stack_ref(orc, stages, weights, grad_feat_last):
+    """The SA stages' backward (§7 composed with §32) below a given gradient at the last stage's output.  ``stages``: first stage
+    first, dicts of float32 arrays xyz [B,N,3], feat [B,N,C] | None, new_xyz [B,M,3] and one idx [B,M,S] / cnt [B,M] per branch
+    in idxs / cnts: the bits and indices the module used (a stage's feat is the stage below's output).  ``weights``: the
+    ``export()`` dict.  ``grad_feat_last``: (val, A, n) as ``cluster_ref`` returns for "feat3".  Walks from the last stage to the
+    first: the aggregation layer's rows on the incoming gradient, each branch on its column slice of grad_x, the branches'
+    grad_feat summed (a stage output's gradient is the sum over its consumers) and handed to the stage below.
+    -> {"grads": {"sa<s>.b<k>.W<l>" / ".b<l>", "sa<s>.agg.W0" / ".b0", "feat<s>" (the gradient at stage s's INPUT features,
+    where it has any): (val, A, n)}, "out<s>": the reference's own forward of stage s's output}."""
+    res = {"grads": {}}
+    cats = []
+    for s, st in enumerate(stages, 1):
+        cat, res[f"out{s}"] = stage_forward(orc, st, weights, s)
+        cats.append(cat)
+    g, gA, n = grad_feat_last
+    for s in range(len(stages), 0, -1):
+        st = stages[s - 1]
+        B, M = st["new_xyz"].shape[:2]
+        nb = len(st["idxs"])
+        tot = _cat_backward(orc, res["grads"], f"sa{s}", _stage_branches(st), [weights[f"sa{s}.b{k}"] for k in range(nb)], cats[s - 1],
+                            weights[f"sa{s}.agg"], np.asarray(g).reshape(B * M, -1), np.asarray(gA).reshape(B * M, -1), n)
+        if st["feat"] is None:
+            assert s == 1, "only the first stage can be without input features"
+            break
+        res["grads"][f"feat{s}"] = g, gA, n = tot["grad_feat"]
+    return res
 
 
 def check(name, got, entry, extra_n=0):
@@ -196,6 +256,41 @@ def small_inputs(cfg, B=2, seed=0):
     xyz3 = (rng.uniform(-1.0, 1.0, (B, M3, 3)) * np.array([2.0, 2.0, 0.5])).astype(np.float32)
     feat3 = np.abs(rng.standard_normal((B, M3, C3))).astype(np.float32)          # (a stage output: behind a ReLU)
     return xyz3, feat3
+
+
+def small_points(cfg, B=2, seed=0):
+    """points [B, n_points, 3 + in_feat] of the small detector: coordinates drawn as ``small_inputs`` draws xyz3 (a slab of
+    4 x 4 x 1), the feature columns standard normal."""
+    rng = np.random.default_rng([seed, 34])
+    xyz = rng.uniform(-1.0, 1.0, (B, cfg.n_points, 3)) * np.array([2.0, 2.0, 0.5])
+    return np.concatenate([xyz, rng.standard_normal((B, cfg.n_points, cfg.in_feat))], 2).astype(np.float32)
+
+
+def stack_chains(cfg):
+    """The names of the SA stages' chains, as ``param_names`` takes them."""
+    return [f"sa{s}.{ch}" for s, st in enumerate(cfg.stages, 1) for ch in [f"b{k}" for k in range(len(st.mlps))] + ["agg"]]
+
+
+def stack_populations(orc, stages, weights, cfg):
+    """What a test of the SA stack must hold, asserted: in every stage no empty group (a centroid is one of the points) and, in
+    at least one branch, both a partly filled group (0 < cnt < S) and a full one (cnt == S); in every layer of every chain at
+    least one ReLU off and one on.  -> a line that says how many of each."""
+    said = []
+    for s, (st, cs) in enumerate(zip(stages, cfg.stages), 1):
+        assert all((n >= 1).all() for n in st["cnts"]), f"sa{s}: an empty group"
+        part = [int(((n > 0) & (n < S)).sum()) for n, S in zip(st["cnts"], cs.nsamples)]
+        full = [int((n == S).sum()) for n, S in zip(st["cnts"], cs.nsamples)]
+        assert any(p and f for p, f in zip(part, full)), f"sa{s}: no branch holds a partly filled and a full group ({part}, {full})"
+        relu = []
+        for k, inp in enumerate(_stage_branches(st)):
+            layers = weights[f"sa{s}.b{k}"]
+            z = np.zeros(inp["idx"].shape[:2] + (layers[-1][0].shape[0],), np.float32)
+            relu += ref.grouped_ref(orc, layers=layers, grad_out=z, **inp)["relu_on"]
+        out = stage_forward(orc, st, weights, s)[1]
+        relu.append((int((out > 0).sum()), out.size))
+        assert all(0 < on < size for on, size in relu), f"sa{s}: a layer whose ReLUs are all on or all off ({relu})"
+        said.append(f"sa{s}: partly filled {part}, full {full}, ReLU on {[f'{on}/{size}' for on, size in relu]}")
+    return "; ".join(said)
 
 
 def ball_counts(xyz3, cand, radius, scale, S):

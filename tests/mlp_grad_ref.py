@@ -100,7 +100,7 @@ def grouped_ref(orc, xyz, feat, new_xyz, idx, cnt, layers, grad_out, skip_empty=
     """``orc`` None: float64 activations (what a float64 evaluation of the unfused composition decides on).  ``grad_out_A``: the
     absolute companion of a ``grad_out`` that is itself a computed gradient (a stage composed with the next), else |grad_out|.
     -> dict: pooled (the reference's own forward), mismatch-free by construction; val / A: {grad_feat, grad_xyz, grad_new_xyz,
-    grad_W, grad_b}; depth: {name: n}; rows: the number of rows that exist."""
+    grad_W, grad_b}; depth: {name: n}; rows: the number of rows that exist; relu_on: per layer (activations > 0, activations)."""
     B, N, _ = xyz.shape
     _, M, S = idx.shape
     C = 0 if feat is None else feat.shape[2]
@@ -148,7 +148,8 @@ def grouped_ref(orc, xyz, feat, new_xyz, idx, cnt, layers, grad_out, skip_empty=
     depth = {"grad_W": [R + sum(widths[l + 1:]) + L for l in range(L)], "grad_feat": R + sum(widths) + L}
     depth["grad_b"] = depth["grad_W"]
     depth["grad_xyz"] = depth["grad_new_xyz"] = depth["grad_feat"]
-    return {"pooled": pooled.reshape(B, M, CL), "val": val, "A": A, "depth": depth, "rows": R}
+    return {"pooled": pooled.reshape(B, M, CL), "val": val, "A": A, "depth": depth, "rows": R,
+            "relu_on": [(int((x > 0).sum()), x.size) for x in xs[1:]]}
 
 
 def rows_ref(orc, x, layers, relu_mask, grad_out, dtype=np.float64):

@@ -1,7 +1,8 @@
 """The candidate layer's backward without a GPU (SPEC.md §33): the numpy reference of tests/detector_train_ref.py against a float64
 central difference of §8 step 2 and by enumeration at the clamp's edges; the refusals of ``ops.candidates`` /
 ``ops.candidates_grad`` / ``ops.prefix_rows_grad`` and of their C entry points that are decided before any device; the composed
-float64 reference of the cluster section exercised against itself."""
+float64 reference of the cluster section exercised against itself, and the whole composition (``stack_ref`` below ``cluster_ref``)
+against torch autograd in float64."""
 import numpy as np
 import pytest
 
@@ -164,10 +165,11 @@ def test_out_checks(sad):
             ops._outputs(spec, (good, good), cpu, "c")
 
 
-def _small_section(orc, seed=0):
+def _small_section(orc, seed=0, inputs=None):
+    """``inputs``: (xyz3, feat3) to put in place of ``small_inputs`` (the SA stack's own output)."""
     cfg = dref.small_config()
     w = dref.small_weights(cfg, seed)
-    xyz3, feat3 = dref.small_inputs(cfg, 2, seed)
+    xyz3, feat3 = dref.small_inputs(cfg, 2, seed) if inputs is None else inputs
     B, K = 2, cfg.n_cand
     L = len(w["cand"])
     xk = np.ascontiguousarray(feat3[:, :K]).reshape(B * K, -1)
@@ -244,3 +246,140 @@ def test_composed_reference_against_itself():
     print(f"directional derivative through cand: analytic {ana:.6f}, central difference {num:.6f}, A {scale:.3f}")
     assert ana != 0
     assert abs(num - ana) <= 0.1 * abs(ana) + 2.0 ** -24 * scale / h
+
+
+def _small_stack(orc, act):
+    """The three SA stages of ``small_config`` on ``small_points`` as ``stack_ref`` takes them: centroids from the oracle's FPS for
+    stage 1 and the prefix of the stage before after that (what the detector takes), indices from the brute force
+    ``ball_counts`` at the stage's constant radii, features from the reference's own forward on ``act`` (the oracle: §6's bits;
+    ``None``: float64 activations, rounded to float32 where a chain hands over to the next, as every chain's input is).
+    -> (cfg, weights, stage dicts)."""
+    cfg = dref.small_config()
+    w = dref.small_weights(cfg)
+    pts = dref.small_points(cfg)
+    xyz, feat = np.ascontiguousarray(pts[..., :3]), np.ascontiguousarray(pts[..., 3:])
+    stages = []
+    for s, st in enumerate(cfg.stages, 1):
+        new_xyz = orc.gather_xyz(xyz, orc.fps(xyz, st.npoint)) if s == 1 else np.ascontiguousarray(xyz[:, :st.npoint])
+        pairs = [dref.ball_counts(xyz, new_xyz, np.full(new_xyz.shape[:2], r, np.float32), 1.0, S) for r, S in zip(st.radii, st.nsamples)]
+        stages.append(dict(xyz=xyz, feat=feat, new_xyz=new_xyz, idxs=[p[0] for p in pairs], cnts=[p[1] for p in pairs]))
+        xyz, feat = new_xyz, dref.stage_forward(act, stages[-1], w, s)[1].astype(np.float32)
+    return cfg, w, stages, (xyz, feat)
+
+
+def test_small_stack_holds_every_population(orc):
+    """The shared small SA stack on the oracle's bits: (192, 4) points in a slab of 4 x 4 x 1; in every stage no empty group, a
+    partly filled and a full group in one branch at least, and in every layer of every chain ReLUs both on and off (what the
+    GPU tests assert again on the module's own counts and bits)."""
+    cfg, w, stages, _ = _small_stack(orc, orc)
+    assert stages[0]["xyz"].shape == (2, 192, 3) and stages[0]["feat"].shape == (2, 192, 1)
+    assert [st["new_xyz"].shape[1] for st in stages] == [96, 64, 40]
+    for a, b in zip(stages[:-1], stages[1:]):
+        assert b["xyz"] is a["new_xyz"] and np.array_equal(b["new_xyz"], a["new_xyz"][:, :b["new_xyz"].shape[1]])
+    print(dref.stack_populations(orc, stages, w, cfg))
+
+
+def _ste32(x):
+    """x rounded to float32, with the identity as its derivative: a chain's input is a float32 tensor."""
+    return x + (x.detach().float().double() - x.detach())
+
+
+def _t_chain(x, layers, relu_mask):
+    import torch
+    for l, (W, b) in enumerate(layers):
+        x = x @ W.T + b
+        if (relu_mask >> l) & 1:
+            x = torch.relu(x)
+    return x
+
+
+def _t_grouped(xyz, feat, new_xyz, idx, cnt, layers):
+    """The unfused grouped chain in torch float64: index gather, relative coordinates, linear + ReLU layers, max over the slots
+    that exist (slots < max(cnt, 1)).  xyz: numpy; feat [B,N,C] | None and new_xyz [B,M,3]: float64 tensors."""
+    import torch
+    B, M, S = idx.shape
+    bb, mm, ss = np.nonzero(np.arange(S)[None, None, :] < np.clip(cnt, 1, S)[..., None])
+    src = idx[bb, mm, ss]
+    x0 = torch.from_numpy(xyz.astype(np.float64))[bb, src] - new_xyz[bb, mm]
+    if feat is not None:
+        x0 = torch.cat([x0, feat[bb, src]], 1)
+    y = _t_chain(_ste32(x0), layers, (1 << len(layers)) - 1)
+    slots = torch.full((B * M, S, y.shape[1]), -np.inf, dtype=torch.float64)
+    slots = slots.index_put((torch.from_numpy(bb * M + mm), torch.from_numpy(ss)), y)
+    return slots.max(1).values.reshape(B, M, -1)
+
+
+def _torch_gradients(cfg, w, stages, xyz3, idxs, cnts, w_o, w_c):
+    """d ((o * w_o).sum() + (c * w_c).sum()) by torch autograd in float64 on the unfused composition, on the fixed indices of
+    ``stages`` (SA) and ``idxs`` / ``cnts`` (cluster) -> {name: array} under the names of ``stack_ref`` / ``cluster_ref``."""
+    import torch
+    tw = {n: [(torch.tensor(W, dtype=torch.float64, requires_grad=True), torch.tensor(b, dtype=torch.float64, requires_grad=True))
+              for W, b in layers] for n, layers in w.items()}
+    kept = {}
+    feat = torch.tensor(stages[0]["feat"], dtype=torch.float64, requires_grad=True)
+    kept["feat1"] = feat
+    for s, st in enumerate(stages, 1):
+        new_xyz = torch.from_numpy(st["new_xyz"].astype(np.float64))
+        cat = torch.cat([_t_grouped(st["xyz"], feat, new_xyz, i, n, tw[f"sa{s}.b{k}"]) for k, (i, n) in enumerate(zip(st["idxs"], st["cnts"]))], 2)
+        feat = _t_chain(_ste32(cat), tw[f"sa{s}.agg"], 1)
+        feat.retain_grad()
+        kept[f"feat{s + 1}" if s < len(stages) else "cluster.feat3"] = feat
+    K, sm = cfg.n_cand, cfg.shift_max
+    mask = lambda layers: (1 << (len(layers) - 1)) - 1
+    c = _t_chain(_ste32(feat[:, :K]), tw["cand"], mask(tw["cand"]))
+    cand = _ste32(torch.from_numpy(xyz3[:, :K].astype(np.float64)) + torch.clamp(c[..., :3], -sm, sm))
+    for name, t in (("c", c), ("cand_xyz", cand)):
+        t.retain_grad()
+        kept[name] = t
+    cat = torch.cat([_t_grouped(xyz3, feat, cand, i, n, tw[f"cluster.b{k}"]) for k, (i, n) in enumerate(zip(idxs, cnts))], 2)
+    o = _t_chain(_ste32(_t_chain(_ste32(cat), tw["cluster.agg"], 1)), tw["head"], mask(tw["head"]))
+    ((o * torch.from_numpy(w_o)).sum() + (c * torch.from_numpy(w_c)).sum()).backward()
+    got = {n: t.grad.numpy() for n, t in kept.items()}
+    for n, layers in tw.items():
+        for l, (W, b) in enumerate(layers):
+            got[f"{n}.W{l}"], got[f"{n}.b{l}"] = W.grad.numpy(), b.grad.numpy()
+    return got, o.detach().numpy()
+
+
+def test_stack_reference_against_autograd(orc):
+    """``stack_ref`` below ``cluster_ref`` with float64 activations (``orc=None``; the oracle only samples stage 1's centroids)
+    against torch autograd in float64 on the unfused composition on the same fixed indices: every parameter of every chain, the
+    gradient at every stage's input features, at c and at cand agree within 1e-10 A (float64 sums in another order; a lost
+    consumer, a wrong column slice or a wrong ReLU decision is of the order of A), A >= |val| everywhere, the depths grow from
+    the last stage to the first, and doubling both loss weights doubles every value exactly.  This checks the reference, not
+    the library."""
+    cfg, w, stages, (xyz3, feat3) = _small_stack(orc, None)
+    print(dref.stack_populations(None, stages, w, cfg))
+    _, _, _, _, c, cand, radius, idxs, cnts = _small_section(None, inputs=(xyz3, feat3))
+    B, K = 2, cfg.n_cand
+    rng = np.random.default_rng(6)
+    w_o = rng.standard_normal((B, K, cfg.head_mlp[-1]))
+    w_c = rng.standard_normal((B, K, 6))
+
+    def reference(scale):
+        cl = dref.cluster_ref(None, xyz3, feat3, w, K, cfg.shift_max, idxs, cnts, scale * w_o, scale * w_c)
+        st = dref.stack_ref(None, stages, w, cl["grads"]["feat3"])
+        grads = {("cluster.feat3" if n == "feat3" else n): e for n, e in cl["grads"].items()}
+        assert not set(grads) & set(st["grads"])
+        grads.update(st["grads"])
+        return cl, st, grads
+    cl, st, grads = reference(1.0)
+    assert np.array_equal(st["out3"].astype(np.float32), feat3)       # (the indices are fixed: that _small_section placed its candidates in float32 decides nothing)
+    names = dref.param_names(w) + dref.param_names(w, dref.stack_chains(cfg)) + ["feat1", "feat2", "feat3", "cluster.feat3", "c", "cand_xyz"]
+    assert sorted(names) == sorted(grads) and len(names) == len(set(names))
+    got, o = _torch_gradients(cfg, w, stages, xyz3, idxs, cnts, w_o, w_c)
+    assert np.abs(o - cl["o"]).max() <= 1e-12 * np.abs(o).max()
+    worst = 0.0
+    for name in names:
+        val, A, n = grads[name]
+        assert got[name].shape == np.shape(val) == np.shape(A), name
+        assert (A >= np.abs(val) * (1 - 1e-12)).all() and (A > 0).any(), name
+        err = np.abs(got[name] - val)
+        assert (err <= 1e-10 * A).all(), f"{name}: {int((err > 1e-10 * A).sum())} elements differ from autograd, worst {np.max(err / np.maximum(A, 1e-300)):.3e} A"
+        worst = max(worst, float(np.max(err[A > 0] / A[A > 0])))
+    print(f"worst |reference - autograd| / A over {len(names)} entries: {worst:.3e}")
+    depth = [grads[f"sa{s}.agg.W0"][2] for s in (3, 2, 1)]
+    assert grads["cluster.feat3"][2] < depth[0] < depth[1] < depth[2], depth
+    _, _, twice = reference(2.0)
+    for name, (val, A, n) in grads.items():
+        assert np.array_equal(2 * np.asarray(val), twice[name][0]) and np.array_equal(2 * np.asarray(A), twice[name][1]) and n == twice[name][2], name

@@ -265,6 +265,46 @@ def test_sa_module_train(sad, dev, orc):
     ref.check_close("grad_feat", _np(ft.grad), gf, gfA, 2 * depth + 1)
 
 
+def test_stage_without_input_features(sad, dev, orc):
+    """The same stage on coordinates alone (``in_channels = 0``, ``feat_pm=None``, a leaf xyz that does not require grad) through
+    the module class: the no_grad forward equals SAModuleMSG's on the exported weights; every parameter gradient lies within
+    the composed bound (``detector_train_ref.stack_ref`` on the one stage: C = 0 in ``grouped_ref``, no grad_feat to hand on)."""
+    import torch
+    import detector_train_ref as dref
+    from sad_amd import ops
+    from sad_amd.config import SAStage
+    from sad_amd.sa_module import SAModuleMSG, SAModuleMSGTrain
+    st = SAStage(24, (0.6, 1.2), (8, 16), ((16, 16), (16, 33)), 20)
+    B, N = 2, 96
+    rng = np.random.default_rng(6)
+    xyz = rng.uniform(-1.5, 1.5, (B, N, 3)).astype(np.float32)
+    m = SAModuleMSGTrain(0, st, dev, seed=4)
+    assert m.branches[0].dims[0] == 3
+    xt = _t(xyz, dev)
+    with torch.no_grad():
+        new_xyz, plain = m.forward_pm(xt, None)
+        want_xyz, want = SAModuleMSG(0, st, dev, weights=m.export()).forward_pm(xt, None)
+        idxs, cnts = ops.ball_query_multi(st.radii, st.nsamples, xt, new_xyz, None, return_counts=True)
+    assert torch.equal(new_xyz, want_xyz) and torch.equal(plain, want)
+    assert any(((c > 0) & (c < S)).any() and (c == S).any() for c, S in zip(cnts, st.nsamples)), "partly filled and full groups are both needed"
+    m.requires_grad_(True)
+    assert xt.is_leaf and not xt.requires_grad
+    _, out = m.forward_pm(xt, None)
+    assert out.requires_grad and torch.equal(out.detach(), plain)
+    gw = rng.standard_normal(tuple(out.shape)).astype(np.float32)
+    (out * _t(gw, dev)).sum().backward()
+    assert xt.grad is None
+    w = {f"sa1.{k}": v for k, v in m.export().items()}
+    stage = dict(xyz=xyz, feat=None, new_xyz=_np(new_xyz), idxs=[_np(i) for i in idxs], cnts=[_np(c) for c in cnts])
+    res = dref.stack_ref(orc, [stage], w, (gw.astype(np.float64), np.abs(gw).astype(np.float64), 0))
+    assert np.array_equal(res["out1"], _np(plain)), "the reference's forward is not the module's output"
+    assert "feat1" not in res["grads"] and len(res["grads"]) == 10
+    for name, chain in [("b0", m.branches[0]), ("b1", m.branches[1]), ("agg", m.agg)]:
+        for l in range(len(chain.weight)):
+            dref.check(f"{name} grad_W[{l}]", _np(chain.weight[l].grad), res["grads"][f"sa1.{name}.W{l}"])
+            dref.check(f"{name} grad_b[{l}]", _np(chain.bias[l].grad), res["grads"][f"sa1.{name}.b{l}"])
+
+
 def test_voxel_roi_pool_fused_grad(sad, dev):
     """VoxelRoIPool(fused_grad=True): its forward equals the inference path; at one small shape (2 scales, G = 2, a few hundred
     voxels, RoIs beyond roi_count and an empty scene) the parameter and feature gradients of BOTH training paths lie within the

@@ -28,7 +28,9 @@ __device__ __forceinline__ void sincos_r(float th, float &s_out, float &c_out) {
     c_out = q == 0 ? C : (q == 1 ? -S : (q == 2 ? -C : S));
 }
 
-__device__ __forceinline__ void box_corners(const float *bx, float *cx, float *cy) {
+// §13 local corners: the four corner offsets of a box from its own centre, counter-clockwise.  The centre is not added: a pair
+// is clipped in the frame of its second box (poly_clip_area), so the IoU does not depend on where the scene lies.
+__device__ __forceinline__ void box_corners(const float *bx, float *ox, float *oy) {
     float s, c;
     sincos_r(bx[6], s, c);
     const float hl = 0.5f * bx[3], hw = 0.5f * bx[4];
@@ -36,11 +38,9 @@ __device__ __forceinline__ void box_corners(const float *bx, float *cx, float *c
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         float a = c * dx[k], b = s * dy[k];
-        float t = bx[0] + a;
-        cx[k] = t - b;
+        ox[k] = a - b;
         a = s * dx[k]; b = c * dy[k];
-        t = bx[1] + a;
-        cy[k] = t + b;
+        oy[k] = a + b;
     }
 }
 
@@ -66,10 +66,11 @@ __device__ __forceinline__ RoiAnchor roi_anchor(const float *roi) {
     return a;
 }
 
-// area of (polygon a) ∩ (convex quad b); corners counter-clockwise; vertex lists live in LDS
+// area of (box a) ∩ (box b) in b's frame: a's vertices are (ddx, ddy) + its local corners, with (ddx, ddy) = a.centre - b.centre
+// (one rounding each, by the caller), b's vertices are its local corners; counter-clockwise; vertex lists live in LDS
 // scratch vertex lists: element v of list L lives at sc[(L*10 + v) * STRIDE] (thread-interleaved LDS)
 template <int STRIDE>
-__device__ float poly_clip_area(const float *ax, const float *ay, const float *bxs, const float *bys,
+__device__ float poly_clip_area(const float *ax, const float *ay, float ddx, float ddy, const float *bxs, const float *bys,
                                 float *sc) {
     // two vertex lists, A = lists 0/1 (x/y), B = lists 2/3; a pass reads one and writes the other (round 5: the copy back
     // and the integer modulo of the neighbour index are gone — same floating-point operations, same order, same results)
@@ -77,7 +78,7 @@ __device__ float poly_clip_area(const float *ax, const float *ay, const float *b
 #define vy(L, i) sc[((L) * 20 + 10 + (i)) * STRIDE]
     int n = 4;
     int cur = 0;
-    for (int i = 0; i < 4; ++i) { vx(0, i) = ax[i]; vy(0, i) = ay[i]; }
+    for (int i = 0; i < 4; ++i) { vx(0, i) = ddx + ax[i]; vy(0, i) = ddy + ay[i]; }
     for (int e = 0; e < 4 && n > 0; ++e) {
         const float q0x = bxs[e], q0y = bys[e], q1x = bxs[(e + 1) & 3], q1y = bys[(e + 1) & 3];
         const float ex = q1x - q0x, ey = q1y - q0y;

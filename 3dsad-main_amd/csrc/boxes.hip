@@ -2,7 +2,7 @@
 // operators a detector's users reach for after NMS.  Geometry (sincos_r, box_corners, poly_clip_area) is the
 // §13 code of box_geom.h, shared with the NMS kernels, so every decision is bit-identical to the CPU oracle.
 //
-// boxes_iou: a 2-D grid of IOU_TA x IOU_TB pair tiles per scene.  A workgroup computes the corners, areas and
+// boxes_iou: a 2-D grid of IOU_TA x IOU_TB pair tiles per scene.  A workgroup computes the local corners, centres, areas and
 // heights of its tile's boxes once into LDS, then each thread clips one pair with poly_clip_area<256> in
 // thread-interleaved LDS scratch (the NMS mask kernel's layout).  One kernel, a mode argument (BEV / 3-D).
 //
@@ -56,8 +56,8 @@ __device__ __forceinline__ BoxK box_consts(const float *bx, float e) {
 // grid (ceil(Kb / IOU_TB), ceil(Ka / IOU_TA), B); mode 0 = BEV (§13 iou_bev), 1 = 3-D (§19.3)
 __global__ __launch_bounds__(256) void boxes_iou_kernel(const float *__restrict__ a, const float *__restrict__ b, int Ka,
                                                         int Kb, int Da, int Db, int mode, float *__restrict__ iou) {
-    __shared__ float s_ax[IOU_TA][4], s_ay[IOU_TA][4], s_aarea[IOU_TA], s_az[IOU_TA], s_ah[IOU_TA], s_avol[IOU_TA];
-    __shared__ float s_bx[IOU_TB][4], s_by[IOU_TB][4], s_barea[IOU_TB], s_bz[IOU_TB], s_bh[IOU_TB], s_bvol[IOU_TB];
+    __shared__ float s_ax[IOU_TA][4], s_ay[IOU_TA][4], s_ac[IOU_TA][2], s_aarea[IOU_TA], s_az[IOU_TA], s_ah[IOU_TA], s_avol[IOU_TA];
+    __shared__ float s_bx[IOU_TB][4], s_by[IOU_TB][4], s_bc[IOU_TB][2], s_barea[IOU_TB], s_bz[IOU_TB], s_bh[IOU_TB], s_bvol[IOU_TB];
     __shared__ float s_poly[4 * 10 * 256];     // per-thread clipping scratch, thread-interleaved
     const int tid = threadIdx.x, sc = blockIdx.z;
     const int i0 = blockIdx.y * IOU_TA, j0 = blockIdx.x * IOU_TB;
@@ -74,6 +74,8 @@ __global__ __launch_bounds__(256) void boxes_iou_kernel(const float *__restrict_
             float *px = isa ? s_ax[t] : s_bx[t], *py = isa ? s_ay[t] : s_by[t];
 #pragma unroll
             for (int q = 0; q < 4; ++q) { px[q] = cx[q]; py[q] = cy[q]; }
+            float *pc = isa ? s_ac[t] : s_bc[t];
+            pc[0] = bx[0]; pc[1] = bx[1];
             (isa ? s_aarea : s_barea)[t] = area;
             (isa ? s_az : s_bz)[t] = bx[2];
             (isa ? s_ah : s_bh)[t] = bx[5];
@@ -84,7 +86,7 @@ __global__ __launch_bounds__(256) void boxes_iou_kernel(const float *__restrict_
     const int ti = tid / IOU_TB, tj = tid - ti * IOU_TB;
     const int i = i0 + ti, j = j0 + tj;
     if (i >= Ka || j >= Kb) return;
-    const float inter = poly_clip_area<256>(s_ax[ti], s_ay[ti], s_bx[tj], s_by[tj], s_poly + tid);
+    const float inter = poly_clip_area<256>(s_ax[ti], s_ay[ti], s_ac[ti][0] - s_bc[tj][0], s_ac[ti][1] - s_bc[tj][1], s_bx[tj], s_by[tj], s_poly + tid);
     float r;
     if (mode == 0) {
         float den = s_aarea[ti] + s_barea[tj];

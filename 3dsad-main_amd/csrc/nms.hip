@@ -26,7 +26,7 @@ __global__ __launch_bounds__(THREADS) void nms_bev_kernel(const float *__restric
                                                           int32_t *__restrict__ keep,
                                                           int32_t *__restrict__ order,
                                                           int32_t *__restrict__ count) {
-    __shared__ float s_cx[NMS_MAXK][4], s_cy[NMS_MAXK][4], s_area[NMS_MAXK], s_score[NMS_MAXK];
+    __shared__ float s_cx[NMS_MAXK][4], s_cy[NMS_MAXK][4], s_ctr[NMS_MAXK][2], s_area[NMS_MAXK], s_score[NMS_MAXK];
     __shared__ int s_rank2idx[NMS_MAXK];
     __shared__ unsigned long long s_mask[NMS_MAXK][NMS_WORDS];
     __shared__ float s_poly[4 * 10 * THREADS];   // per-thread clipping scratch, thread-interleaved
@@ -37,13 +37,14 @@ __global__ __launch_bounds__(THREADS) void nms_bev_kernel(const float *__restric
 
     // 1. rank among the candidates (score >= threshold): score descending, index ascending
     const int n = rank_candidates<THREADS>(bx, K, score_thr, kp, od, s_score, s_rank2idx, &s_n);
-    // corners and areas in rank order
+    // local corners, centres and areas in rank order
     for (int p = tid; p < n; p += THREADS) {
         const float *b = bx + (size_t)s_rank2idx[p] * 9;
         float cx[4], cy[4];
         box_corners(b, cx, cy);
 #pragma unroll
         for (int k = 0; k < 4; ++k) { s_cx[p][k] = cx[k]; s_cy[p][k] = cy[k]; }
+        s_ctr[p][0] = b[0]; s_ctr[p][1] = b[1];
         s_area[p] = b[3] * b[4];
     }
     __syncthreads();
@@ -53,7 +54,7 @@ __global__ __launch_bounds__(THREADS) void nms_bev_kernel(const float *__restric
 #pragma unroll
         for (int k = 0; k < NMS_WORDS; ++k) w[k] = 0ull;
         for (int q = p + 1; q < n; ++q) {
-            if (pair_suppresses<THREADS>(s_cx[p], s_cy[p], s_area[p], s_cx[q], s_cy[q], s_area[q], iou_thr, s_poly + tid)) {
+            if (pair_suppresses<THREADS>(s_cx[p], s_cy[p], s_ctr[p], s_area[p], s_cx[q], s_cy[q], s_ctr[q], s_area[q], iou_thr, s_poly + tid)) {
 #pragma unroll
                 for (int k = 0; k < NMS_WORDS; ++k)
                     if ((q >> 6) == k) w[k] |= 1ull << (q & 63);
@@ -84,13 +85,13 @@ __global__ __launch_bounds__(THREADS) void nms_bev_kernel(const float *__restric
 }
 
 // ---- three-kernel variant (caller workspace): the K x K suppression matrix is spread over the chip --
-// prep (one workgroup per scene): ranking, corners, areas -> workspace; mask (nms_core.h); walk (one
+// prep (one workgroup per scene): ranking, local corners, centres, areas -> workspace; mask (nms_core.h); walk (one
 // wave per scene).  Same arithmetic as nms_bev_kernel, same keep decisions.
-struct NmsBevLayout {     // per scene: [4] ints (n, pad), rank2idx [K], area [K], cx, cy [K][4], mask [K][NMS_WORDS]; no labels
+struct NmsBevLayout {     // per scene: [4] ints (n, pad), rank2idx [K], area [K], cx, cy [K][4], ctr [K][2], mask [K][NMS_WORDS]; no labels
     typedef NmsWs View;
     static constexpr bool LABELS = false;
     __host__ __device__ static size_t scene_bytes(int K) {
-        return 16 + (size_t)K * 4 * 2 + (size_t)K * 16 * 2 + (size_t)K * NMS_WORDS * 8;
+        return 16 + (size_t)K * 4 * 2 + (size_t)K * 16 * 2 + (size_t)K * 8 + (size_t)K * NMS_WORDS * 8;
     }
     __device__ __forceinline__ static View view(void *base, int scene, int K) {
         unsigned char *q = (unsigned char *)base + (size_t)scene * scene_bytes(K);
@@ -100,6 +101,7 @@ struct NmsBevLayout {     // per scene: [4] ints (n, pad), rank2idx [K], area [K
         w.area = (float *)q; q += (size_t)K * 4;
         w.cx = (float *)q; q += (size_t)K * 16;
         w.cy = (float *)q; q += (size_t)K * 16;
+        w.ctr = (float *)q; q += (size_t)K * 8;
         w.mask = (u64 *)q;
         w.label = nullptr;
         w.W = NMS_WORDS;
@@ -126,6 +128,7 @@ __global__ __launch_bounds__(256) void nms_prep_kernel(const float *__restrict__
         box_corners(b, cx, cy);
 #pragma unroll
         for (int k = 0; k < 4; ++k) { w.cx[p * 4 + k] = cx[k]; w.cy[p * 4 + k] = cy[k]; }
+        w.ctr[p * 2] = b[0]; w.ctr[p * 2 + 1] = b[1];
         w.area[p] = b[3] * b[4];
         w.rank2idx[p] = i;
     }

@@ -4,14 +4,14 @@
 // Included inside each file's anonymous namespace, after box_geom.h (poly_clip_area) and prims.h (u64, readlane_u64).
 #pragma once
 
-// Does box p suppress box q?  IoU of §13 on corners and areas; `scratch` is the thread's slot of the clipping lists in LDS.
+// Does box p suppress box q?  IoU of §13 on local corners, centres (pc, qc: x, y) and areas, clipped in q's frame; `scratch` is the thread's slot of the clipping lists in LDS.
 // The areas come by reference, so each caller decides when they are read: nms_bev_kernel's sit in LDS and are read where the
 // sum needs them, after the clip (read ahead of it they cost that kernel 3 %); the mask kernel loads its global one into a
 // register ahead of the clip, which hides the load (after the clip it costs that kernel 3 %).
 template <int STRIDE>
-__device__ __forceinline__ bool pair_suppresses(const float *pcx, const float *pcy, const float &pa, const float *qcx,
-                                                const float *qcy, const float &qa, float iou_thr, float *scratch) {
-    const float inter = poly_clip_area<STRIDE>(pcx, pcy, qcx, qcy, scratch);
+__device__ __forceinline__ bool pair_suppresses(const float *pcx, const float *pcy, const float *pc, const float &pa, const float *qcx,
+                                                const float *qcy, const float *qc, const float &qa, float iou_thr, float *scratch) {
+    const float inter = poly_clip_area<STRIDE>(pcx, pcy, pc[0] - qc[0], pc[1] - qc[1], qcx, qcy, scratch);
     float den = pa + qa;
     den = den - inter;
     const float iou = den > 0.0f ? inter / den : 0.0f;
@@ -87,7 +87,8 @@ struct NmsWs {
     int *rank2idx;        // [P]
     int *label;           // [P], nullptr without classes
     float *area;          // [P]
-    float *cx, *cy;       // [P][4]
+    float *cx, *cy;       // [P][4] local corners (offsets from the centre)
+    float *ctr;           // [P][2] centre x, y
     u64 *mask;            // [P][W] row p, word k: bit l = the box of rank 64k + l is suppressed by rank p (words k >= p / 64 only)
     int W;                // mask row stride in words
 };
@@ -111,6 +112,7 @@ __global__ __launch_bounds__(256) void nms_mask_kernel(int P, float iou_thr, int
         float pcx[4], pcy[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) { pcx[k] = w.cx[p * 4 + k]; pcy[k] = w.cy[p * 4 + k]; }
+        const float pc[2] = {w.ctr[p * 2], w.ctr[p * 2 + 1]};
         const float pa = w.area[p];
         const int pl = L::LABELS ? w.label[p] : 0;
         for (int k = p >> 6; k < nch; ++k) {
@@ -120,8 +122,9 @@ __global__ __launch_bounds__(256) void nms_mask_kernel(int P, float iou_thr, int
                 float qcx[4], qcy[4];
 #pragma unroll
                 for (int c = 0; c < 4; ++c) { qcx[c] = w.cx[q * 4 + c]; qcy[c] = w.cy[q * 4 + c]; }
+                const float qc[2] = {w.ctr[q * 2], w.ctr[q * 2 + 1]};
                 const float qa = w.area[q];                      // (ahead of the clip)
-                sup = pair_suppresses<256>(pcx, pcy, pa, qcx, qcy, qa, iou_thr, s_poly + tid);
+                sup = pair_suppresses<256>(pcx, pcy, pc, pa, qcx, qcy, qc, qa, iou_thr, s_poly + tid);
             }
             const u64 word = __ballot(sup);
             if (lane == 0) w.mask[(size_t)p * w.W + k] = word;

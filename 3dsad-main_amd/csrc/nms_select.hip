@@ -7,7 +7,7 @@
 //           histogram passes over the scene's scores), exact counts above / at the threshold key, then an index-ordered
 //           compaction: everything above the threshold key plus the LOWEST-INDEX ties at it.  Also initialises keep / order.
 //   rank   (256 selected boxes per workgroup): exact counting rank by (key desc, index asc) with the n packed
-//           (key, ~index) words staged through LDS; writes rank2idx, corners, areas, labels in rank order.
+//           (key, ~index) words staged through LDS; writes rank2idx, local corners, centres, areas, labels in rank order.
 //   mask   (one wave per ranked box): nms_core.h's mask kernel on this file's layout, row stride ceil(P/64) words, labels on.
 //   walk   (one workgroup per scene): chunk_decide (nms_core.h) on wave 0; the words a chunk's kept rows suppress in later
 //           chunks are or-ed into LDS by all four waves (thread k owns word k: no atomics).
@@ -34,7 +34,7 @@ __device__ __forceinline__ int lanes_below(u64 ballot) {      // set bits of `ba
 }
 
 // per scene (8-byte items first; the scene stride is a multiple of 16): hdr [16] ints, sel [P], mask [P][W], cx, cy [P][4],
-// rank2idx, label, area [P], with W = ceil(P / 64)
+// ctr [P][2], rank2idx, label, area [P], with W = ceil(P / 64)
 struct NmsxLayout {
     struct View : NmsWs {
         int *hdr;         // [16]: n, n_above, take, threshold key (n = hdr)
@@ -43,7 +43,7 @@ struct NmsxLayout {
     static constexpr bool LABELS = true;
     __host__ __device__ static size_t scene_bytes(int P) {
         const size_t W = (size_t)(P + 63) / 64;
-        const size_t b = 64 + (size_t)P * 8 + (size_t)P * W * 8 + (size_t)P * 16 * 2 + (size_t)P * 4 * 3;
+        const size_t b = 64 + (size_t)P * 8 + (size_t)P * W * 8 + (size_t)P * 16 * 2 + (size_t)P * 8 + (size_t)P * 4 * 3;
         return sad::al16(b);
     }
     __device__ __forceinline__ static View view(void *base, int scene, int P) {
@@ -55,6 +55,7 @@ struct NmsxLayout {
         w.mask = (u64 *)q; q += (size_t)P * w.W * 8;
         w.cx = (float *)q; q += (size_t)P * 16;
         w.cy = (float *)q; q += (size_t)P * 16;
+        w.ctr = (float *)q; q += (size_t)P * 8;
         w.rank2idx = (int *)q; q += (size_t)P * 4;
         w.label = (int *)q; q += (size_t)P * 4;
         w.area = (float *)q;
@@ -206,6 +207,7 @@ __global__ __launch_bounds__(256) void nmsx_rank_kernel(const float *__restrict_
         box_corners(b, cx, cy);
 #pragma unroll
         for (int k = 0; k < 4; ++k) { w.cx[r * 4 + k] = cx[k]; w.cy[r * 4 + k] = cy[k]; }
+        w.ctr[r * 2] = b[0]; w.ctr[r * 2 + 1] = b[1];
         w.area[r] = b[3] * b[4];
         w.rank2idx[r] = idx;
         w.label[r] = labels ? labels[row] : 0;

@@ -4,7 +4,7 @@
 //
 // roi_targets   two launches, no [R,G] matrix, nothing read back:
 //   pass 1      grid (ceil(R / 16), B), 256 threads: 16 RoIs x 16 slices of the boxes.  The scene's boxes come through LDS in
-//               chunks of GCH: corners, z, h, volume and label, 12 words per box, computed once per workgroup.  A thread clips
+//               chunks of GCH: local corners, centre, z, h, volume and label, 14 words per box, computed once per workgroup.  A thread clips
 //               its RoI against the boxes of its slice that it is eligible for in ascending g with the §19.3 arithmetic of
 //               boxes.hip (box_corners, poly_clip_area<256> in thread-interleaved LDS scratch: the same bits as boxes_iou3d)
 //               and keeps the maximum under a strict >; the 16 slices meet in LDS (largest m, lowest g among equals), so the
@@ -24,7 +24,7 @@ namespace {
 constexpr int ROI_MAXR = 4096, ROI_MAXS = 1024, ROI_MAXG = 1024;
 constexpr int P1_ROIS = 16, P1_SLICES = 16; // pass 1: RoIs per workgroup x slices of the boxes
 constexpr int P1_THREADS = P1_ROIS * P1_SLICES;
-constexpr int GCH = P1_THREADS;            // pass 1: ground-truth boxes per LDS chunk (12 KB), one per thread
+constexpr int GCH = P1_THREADS;            // pass 1: ground-truth boxes per LDS chunk (14 KB), one per thread
 constexpr int P2_THREADS = 256;
 constexpr unsigned DRAW_BASE = 0x80000000u;
 constexpr float PI_F = 3.14159265358979323846f;
@@ -59,7 +59,7 @@ __device__ __forceinline__ int roi_candidates(const RoiP &p, int b) {
 // over ceil(R / 16) workgroups.  A thread steps from one box it is eligible for to the next, so the lanes of a wave clip together
 // whatever their classes.  The slices' (m, j) meet in LDS: the largest m, the lowest j among equals, which is the lowest g overall.
 __global__ __launch_bounds__(P1_THREADS) void roi_match_kernel(const RoiP p) {
-    __shared__ float s_gx[GCH][4], s_gy[GCH][4], s_gz[GCH], s_gh[GCH], s_gvol[GCH];
+    __shared__ float s_gx[GCH][4], s_gy[GCH][4], s_gc[GCH][2], s_gz[GCH], s_gh[GCH], s_gvol[GCH];
     __shared__ int s_glab[GCH];
     __shared__ float s_poly[4 * 10 * P1_THREADS];      // per-thread clipping scratch, thread-interleaved
     __shared__ float s_m[P1_THREADS];
@@ -71,11 +71,13 @@ __global__ __launch_bounds__(P1_THREADS) void roi_match_kernel(const RoiP p) {
     const int r = blockIdx.x * P1_ROIS + (tid - slice * P1_ROIS);
     const bool live = r < nb;
     float ax[4] = {0.f, 0.f, 0.f, 0.f}, ay[4] = {0.f, 0.f, 0.f, 0.f};
-    float za = 0.f, ha = 0.f, avol = 0.f;
+    float acx = 0.f, acy = 0.f, za = 0.f, ha = 0.f, avol = 0.f;
     int alab = 0;
     if (live) {
         const float *bx = p.rois + ((size_t)b * p.R + r) * p.D;
         box_corners(bx, ax, ay);
+        acx = bx[0];
+        acy = bx[1];
         const float area = bx[3] * bx[4];
         avol = area * bx[5];
         za = bx[2];
@@ -99,6 +101,7 @@ __global__ __launch_bounds__(P1_THREADS) void roi_match_kernel(const RoiP p) {
                 box_corners(bx, cx, cy);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) { s_gx[t][q] = cx[q]; s_gy[t][q] = cy[q]; }
+                s_gc[t][0] = bx[0]; s_gc[t][1] = bx[1];
                 const float area = bx[3] * bx[4];
                 s_gvol[t] = area * bx[5];
                 s_gz[t] = bx[2];
@@ -113,7 +116,7 @@ __global__ __launch_bounds__(P1_THREADS) void roi_match_kernel(const RoiP p) {
             }
             if (t >= cnt) break;
             // §19.3, mode 3d, a = the RoI, b = the box: the operations of boxes_iou_kernel in its order
-            const float inter = poly_clip_area<P1_THREADS>(ax, ay, s_gx[t], s_gy[t], s_poly + tid);
+            const float inter = poly_clip_area<P1_THREADS>(ax, ay, acx - s_gc[t][0], acy - s_gc[t][1], s_gx[t], s_gy[t], s_poly + tid);
             const float hb = 0.5f * s_gh[t], zb = s_gz[t];
             const float top = fminf(za + ha, zb + hb), bot = fmaxf(za - ha, zb - hb);
             float oh = top - bot;

@@ -579,8 +579,9 @@ int sad_nms_bev_ws_f32(const float *boxes, int B, int K, float iou_thr, float sc
  * pass K for "no limit".  Shape rule: order has P = min(K, pre_max, post_max) columns.  Limits: 1 <= B <= 65535,
  * B*K < 2^31, min(K, pre_max) <= 16384 (SAD_EUNSUPPORTED above; workspace_bytes then returns 0).
  * Workspace law: sad_nms_boxes_workspace_bytes(B, K, pre_max) bytes, 16-byte aligned, contents irrelevant before and
- * after the call: per scene, with P' = min(K, pre_max), 64 + 52 P' + 8 P' ceil(P'/64) bytes rounded up to 16 (the
- * suppression matrix is P' x ceil(P'/64) words).  keep, order and count are fully written by the call.  Four launches
+ * after the call: per scene, with P' = min(K, pre_max), 64 + 60 P' + 8 P' ceil(P'/64) bytes rounded up to 16 (the
+ * suppression matrix is P' x ceil(P'/64) words; 8 P' of it are the centres the pair test subtracts, SPEC.md §13: always
+ * ask the function, the law has grown before).  keep, order and count are fully written by the call.  Four launches
  * whose dimensions depend on (B, K, pre_max) only; nothing is read back and nothing synchronises. */
 size_t sad_nms_boxes_workspace_bytes(int B, int K, int pre_max);
 int sad_nms_boxes_f32(const float *boxes, int D, const float *scores, const int32_t *labels, int B, int K,

@@ -449,18 +449,17 @@ static void sincos_r(float th, float *s_out, float *c_out) {
     }
 }
 
-static void box_corners(const float *bx, float *cx, float *cy) {
+/* local corners: the offsets of the four corners from the box's own centre (the centre is not added) */
+static void box_corners(const float *bx, float *ox, float *oy) {
     float s, c;
     sincos_r(bx[6], &s, &c);
     const float hl = 0.5f * bx[3], hw = 0.5f * bx[4];
     const float dx[4] = {hl, -hl, -hl, hl}, dy[4] = {hw, hw, -hw, -hw};
     for (int k = 0; k < 4; ++k) {
         float a = c * dx[k], b = s * dy[k];
-        float t = bx[0] + a;
-        cx[k] = t - b;
+        ox[k] = a - b;
         a = s * dx[k]; b = c * dy[k];
-        t = bx[1] + a;
-        cy[k] = t + b;
+        oy[k] = a + b;
     }
 }
 
@@ -513,6 +512,9 @@ static float iou_bev(const float *a, const float *b) {
     float ax[4], ay[4], bx[4], by[4];
     box_corners(a, ax, ay);
     box_corners(b, bx, by);
+    /* the pair is clipped in b's frame: a's vertices are (a.centre - b.centre) + its local corners, b's are its local corners */
+    const float ddx = a[0] - b[0], ddy = a[1] - b[1];
+    for (int k = 0; k < 4; ++k) { ax[k] = ddx + ax[k]; ay[k] = ddy + ay[k]; }
     const float inter = poly_clip_area(ax, ay, bx, by);
     const float aa = a[3] * a[4], ab = b[3] * b[4];
     float den = aa + ab;

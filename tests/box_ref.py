@@ -96,14 +96,20 @@ def roipoint_pool3d(xyz, feat, boxes, e, S):
 
 # ---- IoU ----------------------------------------------------------------------------------------------------
 def corners(box, s, c):
-    """§13 corners (counter-clockwise) of one box row: ([4], [4]) lists of np.float32."""
+    """§13 local corners (counter-clockwise) of one box row, the offsets from its own centre: ([4], [4]) lists of np.float32."""
     hl, hw = HALF * box[3], HALF * box[4]
     dx, dy = (hl, -hl, -hl, hl), (hw, hw, -hw, -hw)
     X, Y = [], []
     for k in range(4):
-        X.append((box[0] + c * dx[k]) - s * dy[k])
-        Y.append((box[1] + s * dx[k]) + c * dy[k])
+        X.append(c * dx[k] - s * dy[k])
+        Y.append(s * dx[k] + c * dy[k])
     return X, Y
+
+
+def pair_inter(a, ca, b, cb):
+    """§13 clipped area of the pair (a, b) in b's frame: a's vertices are (a.centre - b.centre) + its local corners."""
+    ddx, ddy = a[0] - b[0], a[1] - b[1]
+    return clip_area([ddx + x for x in ca[0]], [ddy + y for y in ca[1]], cb[0], cb[1])
 
 
 def clip_area(ax, ay, bx, by):
@@ -147,8 +153,9 @@ def _corner_list(boxes):
 
 def iou_bev_pair(a, b):
     """§13 iou_bev of two box rows, scalar (the check of the clip the 3-D IoU uses)."""
-    (ax, ay), (bx, by) = _corner_list(np.stack([a[:7], b[:7]]))
-    inter = clip_area(ax, ay, bx, by)
+    a, b = np.asarray(a, F), np.asarray(b, F)
+    ca, cb = _corner_list(np.stack([a[:7], b[:7]]))
+    inter = pair_inter(a, ca, b, cb)
     den = (F(a[3]) * F(a[4]) + F(b[3]) * F(b[4])) - inter
     return inter / den if den > ZERO else ZERO
 
@@ -180,7 +187,7 @@ def iou3d_matrix(a, b):
         va = (A[3] * A[4]) * A[5]
         for j in range(b.shape[0]):
             Bx = b[j]
-            inter = clip_area(ca[i][0], ca[i][1], cb[j][0], cb[j][1])
+            inter = pair_inter(A, ca[i], Bx, cb[j])
             hb = HALF * Bx[5]
             top = min(A[2] + ha, Bx[2] + hb)
             bot = max(A[2] - ha, Bx[2] - hb)

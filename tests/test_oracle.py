@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import box_truth
 from conftest import GOLDEN
 
 
@@ -335,34 +336,6 @@ def _random_boxes(seed, B, K, extent=30.0):
     return bx
 
 
-def _iou_float64(a, b):
-    """Independent restatement: float64 corners from numpy sin/cos + Sutherland-Hodgman."""
-    def corners(q):
-        c, s = np.cos(np.float64(q[6])), np.sin(np.float64(q[6]))
-        d = np.array([[1, 1], [-1, 1], [-1, -1], [1, -1]], np.float64) * np.array([q[3], q[4]], np.float64) / 2
-        return np.stack([q[0] + c * d[:, 0] - s * d[:, 1], q[1] + s * d[:, 0] + c * d[:, 1]], 1)
-    poly, clip = corners(a), corners(b)
-    for e in range(4):
-        q0, q1 = clip[e], clip[(e + 1) % 4]
-        out = []
-        for i in range(len(poly)):
-            cur, prev = poly[i], poly[i - 1]
-            cc = (q1[0] - q0[0]) * (cur[1] - q0[1]) - (q1[1] - q0[1]) * (cur[0] - q0[0])
-            cp = (q1[0] - q0[0]) * (prev[1] - q0[1]) - (q1[1] - q0[1]) * (prev[0] - q0[0])
-            if (cc >= 0) != (cp >= 0):
-                out.append(prev + cp / (cp - cc) * (cur - prev))
-            if cc >= 0:
-                out.append(cur)
-        poly = np.array(out) if out else np.zeros((0, 2))
-        if len(poly) == 0:
-            break
-    inter = 0.0
-    if len(poly) >= 3:
-        x, y = poly[:, 0], poly[:, 1]
-        inter = 0.5 * abs(np.sum(x * np.roll(y, -1) - np.roll(x, -1) * y))
-    return inter / (a[3] * a[4] + b[3] * b[4] - inter)
-
-
 def test_sincos_r_accuracy(orc):
     th = np.linspace(-50, 50, 20001).astype(np.float32)
     s, c = orc.sincos_r(th)
@@ -374,7 +347,7 @@ def test_iou_bev_vs_float64_and_known_answers(orc):
     bx = _random_boxes(1, 1, 400, extent=12.0)[0]
     a, b = bx[:200], bx[200:]
     got = orc.iou_bev(a, b)
-    want = np.array([_iou_float64(p, q) for p, q in zip(a, b)])
+    want = np.array([box_truth._iou_float64(p, q) for p, q in zip(a, b)])
     assert (want > 0.05).sum() >= 15                      # the sample really contains overlaps
     np.testing.assert_allclose(got, want, atol=2e-5)
     unit = np.array([[0, 0, 0, 4, 2, 1, 0, 1, 0]], np.float32)

@@ -540,9 +540,7 @@ __global__ __launch_bounds__(GQ_WAVES * 64) __attribute__((amdgpu_waves_per_eu(8
                     const int total = __builtin_popcountll(bc);
                     int first = 0;
                     if (bc) first = __builtin_amdgcn_readlane(jidx, __builtin_ctzll(bc));
-#ifndef SAD_BQ_NOPAD            // (measurement build: the padding stores of the packed path left out — what they cost; consumers that take `cnt` never read them)
                     if (lane >= total && lane < S) out0[c * S + lane] = first;       // (nsample <= 64: one store covers the row)
-#endif
                     tot[c] = total < S ? total : S;
                 }
                 if (prm.cnt[r] && lane < 4 && m0 + lane < M)
@@ -801,11 +799,6 @@ SAD_API int sad_ball_query_grid_f32(const float *xyz, const float *new_xyz, int 
         sad::lds_attr_once(attr_done0, reinterpret_cast<const void *>(&grid_build_kernel<0>), 144 * 1024);
         hipLaunchKernelGGL(grid_build_kernel<0>, dim3(B), dim3(BUILD_T), blds, st, xyz, N, rmax * 1.001f, rmax, (char *)workspace);
     }
-#ifdef SAD_GRID_BUILD_TWICE  // measurement build: the grid build launched twice (idempotent: same tables) — what its time costs the pipelined step
-    if (N <= 4 * BUILD_T) hipLaunchKernelGGL(grid_build_kernel<4>, dim3(B), dim3(BUILD_T), blds, st, xyz, N, rmax * 1.001f, rmax, (char *)workspace);
-    else if (N <= 16 * BUILD_T) hipLaunchKernelGGL(grid_build_kernel<16>, dim3(B), dim3(BUILD_T), blds, st, xyz, N, rmax * 1.001f, rmax, (char *)workspace);
-    else hipLaunchKernelGGL(grid_build_kernel<0>, dim3(B), dim3(BUILD_T), blds, st, xyz, N, rmax * 1.001f, rmax, (char *)workspace);
-#endif
     if (int e = sad::check_launch("sad_ball_query_grid_f32 (build)")) return e;
     const char *ws = (const char *)workspace;
     switch (n_radii) {

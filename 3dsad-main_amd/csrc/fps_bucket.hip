@@ -279,21 +279,6 @@ __device__ __forceinline__ unsigned half_max_u32(unsigned v) {   // max over lan
     return o > v ? o : v;
 }
 
-#ifdef SAD_FPS_STAMPS
-// measurement build: per wave of workgroup 0, cycles (s_memtime) summed over the second half of the steps:
-// [0] skip test, [1] bucket updates + wave best, [2] publish up to the barrier, [3] barrier wait, [4] read + broadcast,
-// [5] steps in which the wave was active, [6] buckets updated, [7] steps
-__device__ unsigned long long g_fpst[16 * 8];
-extern "C" __attribute__((visibility("default"))) int sad_debug_read_fps_stamps(unsigned long long *dst) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_fpst), sizeof(unsigned long long) * 16 * 8);
-}
-#define FPS_T(v) const unsigned long long v = __builtin_amdgcn_s_memtime()
-#define FPS_ACC(slot, expr) do { if (sample) acc_##slot += (expr); } while (0)
-#else
-#define FPS_T(v)
-#define FPS_ACC(slot, expr)
-#endif
-
 template <int NW, int PPT>
 __device__ __forceinline__ void fps_cell_body(const float *__restrict__ xyz, const int *__restrict__ perm_in, int N,
                                               int M, int *__restrict__ idx_out) {
@@ -361,23 +346,11 @@ __device__ __forceinline__ void fps_cell_body(const float *__restrict__ xyz, con
         __syncthreads();
     }
     int b3 = 1;
-#ifdef SAD_FPS_STAMPS
-    unsigned long long acc_0 = 0, acc_1 = 0, acc_2 = 0, acc_3 = 0, acc_4 = 0, acc_5 = 0, acc_6 = 0, acc_7 = 0;
-#endif
     for (int i = 1; i < M; ++i) {
-#ifdef SAD_FPS_STAMPS
-        const bool sample = blockIdx.x == 0 && i >= M / 2;
-#endif
-        FPS_T(ta);
         // all PPT skip tests at once: lane k tests bucket k (a never-active lane has bmax = 0)
         const float dq = sad::d2f(__builtin_amdgcn_fmed3f(cx, blo0, bhi0), __builtin_amdgcn_fmed3f(cy, blo1, bhi1),
                                   __builtin_amdgcn_fmed3f(cz, blo2, bhi2), cx, cy, cz);
         unsigned act = __builtin_amdgcn_readfirstlane((unsigned)__ballot(!(dq >= __builtin_bit_cast(float, bmax))));   // (BMAX_FRESH is a NaN)
-        FPS_T(tb);
-        FPS_ACC(0, tb - ta);
-        FPS_ACC(5, act ? 1 : 0);
-        FPS_ACC(6, __builtin_popcount(act));
-        FPS_ACC(7, 1);
         if (act) {
             // a disturbed wave's chain is the step's critical path: it issues ahead of the three idle siblings on its SIMD
             // (2.87 -> 2.81 ms per 4 096 samples; keeping the priority through the publish: 2.83)
@@ -419,8 +392,6 @@ __device__ __forceinline__ void fps_cell_body(const float *__restrict__ xyz, con
             wz = rdl_f(bz, kb);
         }
         __builtin_amdgcn_s_setprio(0);
-        FPS_T(tc);
-        FPS_ACC(1, tc - tb);
         unsigned glo;
         if constexpr (NW == 1) {
             glo = wk_lo;
@@ -436,14 +407,7 @@ __device__ __forceinline__ void fps_cell_body(const float *__restrict__ xyz, con
                 *reinterpret_cast<float4 *>(&s_wxyz[buf][wave][0]) = r;
                 if (wave == 0) s_gkey[b3n] = 0ull;
             }
-#ifdef SAD_FPS_STAMPS
-            __builtin_amdgcn_s_waitcnt(0xc07f);      // lgkmcnt(0): the publish has left
-#endif
-            FPS_T(td);
-            FPS_ACC(2, td - tc);
             __syncthreads();
-            FPS_T(te);
-            FPS_ACC(3, te - td);
             const u64 gk = s_gkey[b3];
             const float4 rec = *reinterpret_cast<const float4 *>(&s_wxyz[buf][lane & (NW - 1)][0]);
             const unsigned g = __builtin_amdgcn_readfirstlane((unsigned)gk);
@@ -453,20 +417,9 @@ __device__ __forceinline__ void fps_cell_body(const float *__restrict__ xyz, con
             cy = rdl_f(rec.y, slot);
             cz = rdl_f(rec.z, slot);
             b3 = b3n;
-#ifdef SAD_FPS_STAMPS
-            asm volatile("" :: "v"(cx), "v"(cy), "v"(cz));
-#endif
-            FPS_T(tf);
-            FPS_ACC(4, tf - te);
         }
         if (tid == 0) out[i] = (int)(~glo);
     }
-#ifdef SAD_FPS_STAMPS
-    if (blockIdx.x == 0 && lane == 0) {
-        unsigned long long *d = g_fpst + wave * 8;
-        d[0] = acc_0; d[1] = acc_1; d[2] = acc_2; d[3] = acc_3; d[4] = acc_4; d[5] = acc_5; d[6] = acc_6; d[7] = acc_7;
-    }
-#endif
 }
 
 template <int NW, int PPT>
@@ -493,22 +446,6 @@ __global__ __launch_bounds__(NW * 64) void fps_cell_kernel(const float *__restri
 typedef float f4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ unsigned lds_off(const void *p) { return (unsigned)(size_t)p; }   // low half of a flat LDS address
 
-#ifdef SAD_FPS_STAMPS2
-// measurement build of the second form: s_memtime ticks per phase, summed by every wave of workgroup 0 over the steps in
-// which IT held the sampled point (its chain is the step's critical path), second half of the run:
-// [0] barrier -> centre known, [1] skip test, [2] bucket updates, [3] wave best, [4] record, [5] key atomic issued -> barrier passed,
-// [6] such steps, [7] buckets updated in them
-__device__ unsigned long long g_fpst2[16 * 8];
-extern "C" __attribute__((visibility("default"))) int sad_debug_read_fps_stamps2(unsigned long long *dst) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_fpst2), sizeof(unsigned long long) * 16 * 8);
-}
-#define FPS2_T(v) const unsigned long long v = __builtin_amdgcn_s_memtime()
-#define FPS2_ACC(slot, expr) do { if (s.crit) s.acc[slot] += (expr); } while (0)
-#else
-#define FPS2_T(v)
-#define FPS2_ACC(slot, expr)
-#endif
-
 // State of one wave (everything is a register; the struct exists so that the six unrolled step bodies share one text).
 template <int NW, int PPT>
 struct Cell2 {
@@ -526,10 +463,6 @@ struct Cell2 {
     unsigned pending;                         // the other record buffer still holds the previous best
     unsigned a_key, a_rec_mine, a_rec0;       // LDS byte addresses: key slots, own record, record of wave 0
     int wave;
-#ifdef SAD_FPS_STAMPS2
-    unsigned long long acc[8], t_bar;
-    bool crit, sample;
-#endif
 };
 
 // The rare part of a step: bucket updates, the wave's new best, its record.  BUF = record buffer of this step.
@@ -542,8 +475,6 @@ __device__ __forceinline__ void cell2_slow(Cell2<NW, PPT> &s, unsigned act, int 
     constexpr unsigned long long PMASK = PPT >= 32 ? 0xffffffffull : ((1ull << PPT) - 1ull);
     unsigned publish = s.pending;
     s.pending = 0u;
-    FPS2_T(ts0);
-    FPS2_ACC(7, __builtin_popcount(act));
     if (act) {
         __builtin_amdgcn_s_setprio(3);        // the disturbed wave's chain ahead of its idle siblings on the SIMD
         // the wave best must be recomputed when its bucket is updated, or when an updated bucket ends up with the same
@@ -563,26 +494,11 @@ __device__ __forceinline__ void cell2_slow(Cell2<NW, PPT> &s, unsigned act, int 
             const unsigned db = __builtin_bit_cast(unsigned, d), ob = __builtin_bit_cast(unsigned, om);
             const unsigned mb = db < ob ? db : ob;
             s.md[k] = __builtin_bit_cast(float, mb);
-#if defined(SAD_FPS_DUP) && SAD_FPS_DUP == 2      // measurement: the 64-lane reduction a second time
-            { unsigned t = mb ^ 1u; asm volatile("" : "+v"(t)); unsigned r = wave_max_u32_b(t); asm volatile("" :: "s"(r)); }
-#endif
-#ifdef SAD_FPS_KEEP      // (measurement build; NOT the default: see the comment)
-            {   // Round 5: two thirds of the bucket updates leave the bucket's maximum where it was (the sample lowers a few
-                // points near it, not the farthest one).  Min-distances only fall, so if the recorded lane still holds the
-                // recorded value, maximum and lane are unchanged (a lane that ties now tied before, and the recorded lane was
-                // the lowest index among those): three lane reads instead of the 64-lane reduction, ballot and writelanes.
-                // Exact (all FPS tests) and SLOWER here: 2.195 against 2.094 ms per 32 scenes — the wave that holds the sampled
-                // point never takes the shortcut for that point's bucket and pays the three dependent lane reads on the step's
-                // critical chain.  The record-streaming kernel below keeps its version (11.96 against 12.08 ms: its updates
-                // carry four more lane reads and five writelanes, and wait for L2 anyway).
-                const unsigned obm = __builtin_amdgcn_readlane(s.bmax, k);
-                const int obl = (int)__builtin_amdgcn_readlane(s.blane, k);
-                if (__builtin_amdgcn_readlane(mb, obl) == obm) {
-                    top = obm > top ? obm : top;
-                    continue;
-                }
-            }
-#endif
+            // (Round 5: two thirds of the updates leave the bucket's maximum where it was, and skipping the reduction when the
+            // recorded lane still holds the recorded value is exact — and SLOWER here: 2.195 against 2.094 ms per 32 scenes.  The
+            // wave that holds the sampled point never takes the shortcut for that point's bucket and pays the three dependent lane
+            // reads on the step's critical chain.  The record-streaming kernel below keeps its version: 11.96 against 12.08 ms,
+            // its updates carry four more lane reads and five writelanes, and wait for L2 anyway.  Measured in round 5, build removed.)
             const unsigned hi = wave_max_u32_b(mb);
             const unsigned long long tie = __ballot(mb == hi);
             int l = __builtin_ctzll(tie);
@@ -596,8 +512,6 @@ __device__ __forceinline__ void cell2_slow(Cell2<NW, PPT> &s, unsigned act, int 
             s.blane = sad_writelane((unsigned)l, k, s.blane);
             top = hi > top ? hi : top;
         } while (act);
-        FPS2_T(ts1);
-        FPS2_ACC(2, ts1 - ts0);
         if (kb_hit | (top >= s.wk_hi ? 1u : 0u)) {
             const unsigned nh = __builtin_amdgcn_readlane(half_max_u32<PSTEPS>(s.bmax), 0);
             const unsigned long long wt = __ballot(s.bmax == nh) & PMASK;
@@ -619,10 +533,7 @@ __device__ __forceinline__ void cell2_slow(Cell2<NW, PPT> &s, unsigned act, int 
             publish = 3u;                     // new key + record (even if it came out the same: rare, and cheaper than comparing)
         }
         __builtin_amdgcn_s_setprio(0);
-        FPS2_T(ts2);
-        FPS2_ACC(3, ts2 - ts1);
     }
-    FPS2_T(ts3);
     if (publish) {
         // the owner of the wave's best point (lane wl, register slot kb) publishes it from its own registers: every lane reads
         // slot kb, lane wl alone writes (s_and_saveexec: the statement saves the exec mask it finds and restores it)
@@ -645,8 +556,6 @@ __device__ __forceinline__ void cell2_slow(Cell2<NW, PPT> &s, unsigned act, int 
                          : "=&s"(sv) : "s"(s.wlmask), "v"(s.a_rec_mine), "v"(r), "n"(BUF * 256) : "memory", "scc");
         }
     }
-    FPS2_T(ts4);
-    FPS2_ACC(4, ts4 - ts3);
 }
 
 // One sampling step.  BUF / B3: record buffer and key slot of this step (compile-time: the loop is unrolled six times, so
@@ -656,19 +565,10 @@ __device__ __forceinline__ void cell2_slow(Cell2<NW, PPT> &s, unsigned act, int 
 template <int NW, int PPT, int BUF, int B3, bool W0>
 __device__ __forceinline__ void cell2_step(Cell2<NW, PPT> &s, int lane, int *__restrict__ out_i) {
     constexpr int B3N = B3 == 2 ? 0 : B3 + 1;
-    FPS2_T(ta);
-    FPS2_ACC(0, ta - s.t_bar);
-    FPS2_ACC(6, 1);
     const float dq = sad::d2f(__builtin_amdgcn_fmed3f(s.cx, s.blo0, s.bhi0), __builtin_amdgcn_fmed3f(s.cy, s.blo1, s.bhi1),
                               __builtin_amdgcn_fmed3f(s.cz, s.blo2, s.bhi2), s.cx, s.cy, s.cz);
     unsigned act = __builtin_amdgcn_readfirstlane((unsigned)__ballot(!(dq >= __builtin_bit_cast(float, s.bmax))));
-#if defined(SAD_FPS_ABL) && SAD_FPS_ABL == 1
-    act = 0;                                  // ablation: no bucket updates (timing only, wrong results)
-#endif
-    FPS2_T(tb);
-    FPS2_ACC(1, tb - ta);
     if (act | s.pending) cell2_slow<NW, PPT, BUF>(s, act, lane);
-    FPS2_T(tc);
     {
         const u64 key = ((u64)s.khi << 32) | s.klo;
         // (the exec mask found on entry is saved and restored inside the statement; scc is declared clobbered)
@@ -687,9 +587,6 @@ __device__ __forceinline__ void cell2_step(Cell2<NW, PPT> &s, int lane, int *__r
         unsigned gk;                          // low word of the winning key: (index order << 4) | wave
         f4v rec;
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#ifdef SAD_FPS_STAMPS2
-        { FPS2_T(td); FPS2_ACC(5, td - tc); s.t_bar = td; }
-#endif
         {
             unsigned ra;
             asm volatile("ds_read_b32 %0, %3 offset:%5\n\t"
@@ -701,10 +598,6 @@ __device__ __forceinline__ void cell2_step(Cell2<NW, PPT> &s, int lane, int *__r
                          : "=&v"(gk), "=&v"(rec), "=&v"(ra) : "v"(s.a_key), "v"(s.a_rec0), "n"(B3 * 8), "n"(BUF * 256) : "memory");
         }
         s.cx = rec.x; s.cy = rec.y; s.cz = rec.z;
-#ifdef SAD_FPS_STAMPS2
-        asm volatile("" :: "v"(s.cx), "v"(s.cy), "v"(s.cz));
-        s.crit = ((__builtin_amdgcn_readfirstlane(gk) & 15) == (unsigned)s.wave) && s.sample;
-#endif
         if (W0) {
             if (lane == 0) *out_i = (int)(0x0fffffffu - (gk >> 4));
         }
@@ -715,9 +608,6 @@ template <int NW, int PPT, bool W0>
 __device__ __forceinline__ void cell2_loop(Cell2<NW, PPT> &s, int lane, int M, int *__restrict__ out) {
     int i = 1;                                // step i: record buffer i & 1, key slot i % 3  (i = 1: 1, 1)
     for (; i + 6 <= M; i += 6) {
-#ifdef SAD_FPS_STAMPS2
-        s.sample = blockIdx.x == 0 && i >= M / 2;
-#endif
         cell2_step<NW, PPT, 1, 1, W0>(s, lane, out + i);
         cell2_step<NW, PPT, 0, 2, W0>(s, lane, out + i + 1);
         cell2_step<NW, PPT, 1, 0, W0>(s, lane, out + i + 2);
@@ -791,16 +681,8 @@ __global__ __launch_bounds__(NW * 64) void fps_cell2_kernel(const float *__restr
     s.kb = 0; s.wl = 0; s.wk_hi = 0u; s.wlmask = 1ull;
     s.klo = (unsigned)wave; s.khi = 0u;       // (a wave without a real point keeps key 0 | wave and never wins: wave 0 has one)
     s.pending = 1u;
-#ifdef SAD_FPS_STAMPS2
-    for (int q = 0; q < 8; ++q) s.acc[q] = 0;
-    s.t_bar = 0; s.crit = false; s.sample = false;
-#endif
     if (wave == 0) cell2_loop<NW, PPT, true>(s, lane, M, out);
     else cell2_loop<NW, PPT, false>(s, lane, M, out);
-#ifdef SAD_FPS_STAMPS2
-    if (blockIdx.x == 0 && lane == 0)
-        for (int q = 0; q < 8; ++q) g_fpst2[wave * 8 + q] = s.acc[q];
-#endif
 }
 
 // ---- cell-bucket kernel, third form ("several samples per round", round 5) ------------------------------------------
@@ -822,20 +704,6 @@ __global__ __launch_bounds__(NW * 64) void fps_cell2_kernel(const float *__restr
 // round takes 5 samples on average (tools/probe/fps_rounds.py; 16 384 -> 4 096 in ~810 rounds instead of 4 095).
 // Same buckets, same box test, same tie rules as the other forms; indices are bit-exact (tests/test_gpu_ops.py).
 constexpr int MP_KMAX = 8;                    // samples per round (cap)
-#ifdef SAD_FPS_STAMPS3
-// measurement build: s_memtime ticks per phase, per wave of workgroup 0, summed over the rounds of the second half of the run:
-// [0] box tests, [1] bucket updates, [2] top-2 + publish, [3] wait at the first barrier, [4] ranking, [5] wait at the second
-// barrier, [6] prefix + samples, [7] rounds, [8] buckets updated, [9] rounds with a top-2 recompute, [10] samples
-__device__ unsigned long long g_fpst3[16 * 12];
-extern "C" __attribute__((visibility("default"))) int sad_debug_read_fps_stamps3(unsigned long long *dst) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_fpst3), sizeof(unsigned long long) * 16 * 12);
-}
-#define FPS3_T(v) const unsigned long long v = __builtin_amdgcn_s_memtime()
-#define FPS3_ACC(slot, expr) do { if (sample3) acc3[slot] += (expr); } while (0)
-#else
-#define FPS3_T(v)
-#define FPS3_ACC(slot, expr)
-#endif
 
 template <int NW, int PPT>
 __global__ __launch_bounds__(NW * 64) void fps_cell3_kernel(const float *__restrict__ xyz, const int *__restrict__ perm_in,
@@ -917,17 +785,7 @@ __global__ __launch_bounds__(NW * 64) void fps_cell3_kernel(const float *__restr
         for (int i = 0; i < MP_KMAX; ++i) { cx[i] = p0x; cy[i] = p0y; cz[i] = p0z; }
     }
     int P = 1, t = 1;
-#ifdef SAD_FPS_STAMPS3
-    unsigned long long acc3[12];
-    for (int q = 0; q < 12; ++q) acc3[q] = 0;
-#endif
     while (t < M) {
-#ifdef SAD_FPS_STAMPS3
-        const bool sample3 = blockIdx.x == 0 && t >= M / 2;
-#endif
-        FPS3_T(t0);
-        FPS3_ACC(7, 1);
-        FPS3_ACC(10, P);
         // ---- apply the round's samples: box tests (lane k tests bucket k), then the disturbed buckets ---------------
         const float bmf = __builtin_bit_cast(float, bmax);
         bool any = false;
@@ -947,11 +805,8 @@ __global__ __launch_bounds__(NW * 64) void fps_cell3_kernel(const float *__restr
             }
         }
         unsigned rest = __builtin_amdgcn_readfirstlane((unsigned)__ballot(any));
-        FPS3_T(t1);
-        FPS3_ACC(0, t1 - t0);
         if (rest) {
             const bool hit = fresh || ((((rest >> kb) | (rest >> kb2)) & 1u) != 0u);
-            FPS3_ACC(8, __builtin_popcount(rest));
             do {
                 // two disturbed buckets per pass (the second repeats the first when only one is left: the update is idempotent),
                 // so that the two dependent chains — distances, minimum, 64-lane maximum, lane of the maximum — interleave
@@ -997,10 +852,7 @@ __global__ __launch_bounds__(NW * 64) void fps_cell3_kernel(const float *__restr
                 bmax = sad_writelane(h1, k1, bmax);
                 blane = sad_writelane((unsigned)l1, k1, blane);
             } while (rest);
-            FPS3_T(t2);
-            FPS3_ACC(1, t2 - t1);
             if (hit) {
-                FPS3_ACC(9, 1);
                 // the wave's best point: best bucket (ties: lowest index), the lane recorded for it
                 auto bucket_of = [&](unsigned top, int excl, int &bk, int &bl, unsigned &bn) {
                     unsigned long long wt = __ballot(bmax == top && lane != excl) & PMASK;
@@ -1060,14 +912,9 @@ __global__ __launch_bounds__(NW * 64) void fps_cell3_kernel(const float *__restr
                     *reinterpret_cast<f4v *>(&s_rec[2 * wave][0]) = f4v{q1x, q1y, q1z, 0.f};
                     *reinterpret_cast<f4v *>(&s_rec[2 * wave + 1][0]) = f4v{q2x, q2y, q2z, 0.f};
                 }
-                FPS3_T(t3);
-                FPS3_ACC(2, t3 - t2);
             }
         }
-        FPS3_T(t4);
         __syncthreads();
-        FPS3_T(t5);
-        FPS3_ACC(3, t5 - t4);
         // ---- every wave ranks its two candidates in the table and tests them against the higher-ranked entries ------
         unsigned tkhi = 0u, tklo = 0u;
         float tx = 0.f, ty = 0.f, tz = 0.f;
@@ -1098,11 +945,7 @@ __global__ __launch_bounds__(NW * 64) void fps_cell3_kernel(const float *__restr
                 if (r2 < (unsigned)MP_KMAX) *reinterpret_cast<f4v *>(&s_cen[r2][0]) = f4v{q2x, q2y, q2z, __builtin_bit_cast(float, n2)};
             }
         }
-        FPS3_T(t6);
-        FPS3_ACC(4, t6 - t5);
         __syncthreads();
-        FPS3_T(t7);
-        FPS3_ACC(5, t7 - t6);
         // ---- the prefix: every wave derives the same P; the samples come sorted from the table ---------------------------
         const unsigned res = lane < 2 * NW ? s_res[lane] : (63u | (1u << 8));
         const f4v cen = *reinterpret_cast<const f4v *>(&s_cen[lane & (MP_KMAX - 1)][0]);     // lane i (< MP_KMAX): sample i of the round
@@ -1122,13 +965,7 @@ __global__ __launch_bounds__(NW * 64) void fps_cell3_kernel(const float *__restr
         const float cenw = cen.w;                 // (hipcc: a bit_cast applied directly to a vector element reads element 0)
         if (wave == 0 && lane < P) out[t + lane] = (int)(~__builtin_bit_cast(unsigned, cenw));
         t += P;
-        FPS3_T(t8);
-        FPS3_ACC(6, t8 - t7);
     }
-#ifdef SAD_FPS_STAMPS3
-    if (blockIdx.x == 0 && lane == 0)
-        for (int q = 0; q < 12; ++q) g_fpst3[wave * 12 + q] = acc3[q];
-#endif
 }
 
 template <int NW, int PPT>
@@ -1304,11 +1141,6 @@ __global__ __launch_bounds__(1024) void fps_cellg_kernel(const float4 *__restric
 // loops, each touching one 32-wide vector only: with "if (k < 32) md0[k] ... else md1[k - 32] ..." around the read and
 // again around the write, hipcc copied a whole 32-register vector into a temporary and back on every update
 // (32 v_mov_b64: the first form of this kernel paid that too)
-#ifdef SAD_FPS_NOKEEP
-#define SAD_FPS_KEEP_ON false
-#else
-#define SAD_FPS_KEEP_ON true
-#endif
 #define CELLG2_UPD(MD, KI, KS)                                                                                        \
     {                                                                                                                 \
         const float4 r = rec[(KS) * 1024];                                                                            \
@@ -1323,7 +1155,7 @@ __global__ __launch_bounds__(1024) void fps_cellg_kernel(const float4 *__restric
         const unsigned obm = __builtin_amdgcn_readlane(bmax, KS);                                                     \
         const unsigned obn = __builtin_amdgcn_readlane(bidx, KS);                                                     \
         const unsigned long long own = __ballot(n == obn);                                                            \
-        const bool keep = SAD_FPS_KEEP_ON && own != 0ull &&                                                           \
+        const bool keep = own != 0ull &&                                                                              \
                           __builtin_amdgcn_readlane(mb, (int)__builtin_ctzll(own | (1ull << 63))) == obm;             \
         if (keep) {                                                                                                   \
             top = obm > top ? obm : top;                                                                              \

@@ -32,29 +32,18 @@ using sad::BfRegMulti;
 constexpr int WHOLE_BIT = 1 << 30;
 using sad::CONT_BIT;            // split pooling (common.h): the row's group began in an earlier tile
 using sad::GID_MASK;
-#ifndef SAD_BR_RS
-#define SAD_BR_RS 8      // (16: sa1 82 vs 72 us, sa2 47 vs 41, cluster 112 vs 108, sa3 112 vs 115 — the smaller ring / image lets more workgroups share a CU)
-#endif
-#ifndef SAD_BR_PFD
-#define SAD_BR_PFD 4
-#endif
-#ifndef SAD_BR_DMA
-#define SAD_BR_DMA 1     // the weight ring is filled by LDS-DMA (global_load_lds_dwordx4), three stages ahead; 0 = through registers, two ahead
-#endif
-constexpr int RS = SAD_BR_RS;        // fragments (1 KB each) per ring stage
-constexpr int RNS = SAD_BR_DMA ? 4 : 3;      // ring slots: being read / complete / (DMA: in flight) / being written
+constexpr int RS = 8;                // fragments (1 KB each) per ring stage (16: sa1 82 vs 72 us, sa2 47 vs 41, cluster 112 vs 108, sa3 112 vs 115 — the smaller ring / image lets more workgroups share a CU)
+constexpr int RNS = 4;               // ring slots: being read / complete / in flight / being written — the ring is filled by LDS-DMA (global_load_lds_dwordx4), three stages ahead
 constexpr int RING_F4 = RNS * RS * 64;
-constexpr int PFD_DEFAULT = SAD_BR_PFD;   // ring reads run this many fragments ahead of the MFMA that consumes them
-#ifndef SAD_BR_F2
-#define SAD_BR_F2 2      // (with the LDS-DMA ring: two workgroups of 256 registers, no spills — a spill reload is a vector-memory load whose wait, a
-#endif                   // vmcnt(0), drains the DMA issued for three stages ahead; 3 x 168 registers with 12 spilled: +0.3 % / +0.5 % on the KITTI / nuScenes-shaped step)
-#ifndef SAD_BR_PFD2
-#define SAD_BR_PFD2 2
-#endif
+constexpr int PFD_DEFAULT = 4;       // ring reads run this many fragments ahead of the MFMA that consumes them
+// Workgroups per CU of the SA3 family (with the LDS-DMA ring: two workgroups of 256 registers, no spills — a spill reload is a vector-memory load whose wait, a
+// vmcnt(0), drains the DMA issued for three stages ahead; 3 x 168 registers with 12 spilled: +0.3 % / +0.5 % on the KITTI / nuScenes-shaped step)
+constexpr int F2_WGS = 2;
+constexpr int PFD_F2 = 2;            // read-ahead of the SA3 family
 // SA3 family, round 4 (weights through registers): three workgroups per CU (168 registers) with reads two fragments ahead — 107 us against 121
 // with two workgroups of 207 registers and four ahead on the KITTI-shaped batch (three workgroups at four ahead: 113, 19 registers spilled
-// instead of 10).  Round 5 (LDS-DMA ring): two workgroups again, see SAD_BR_F2
-__host__ __device__ constexpr int pfd_of(int family) { return family == 2 ? SAD_BR_PFD2 : PFD_DEFAULT; }
+// instead of 10).  Round 5 (LDS-DMA ring): two workgroups again, see F2_WGS
+__host__ __device__ constexpr int pfd_of(int family) { return family == 2 ? PFD_F2 : PFD_DEFAULT; }
 // Staged pooled output.  A wave owns 4 KB of LDS: STAGE_F floats = slots x CB channels, slot = ordinal of a group inside
 // the tile, CB = 128 / 64 / 32 channels per block for tiles with <= 8 / 16 / 32 groups.  EVERY row of an output tile
 // max-combines into its group's slot with one LDS atomic per register (ds_max_u32 on the bit patterns: values are >= +0
@@ -62,7 +51,7 @@ __host__ __device__ constexpr int pfd_of(int family) { return family == 2 ? SAD_
 // leaves as one row of CB channels: coalesced 16-byte stores (64 lanes cover 256 / CB groups), an atomic max only for the
 // first / last group of a tile when it continues in another tile.  The first version walked the 16 registers with a
 // running max and stored 128 bytes per (group end, lane half, output tile): 16 exec-masked branches per output tile cost
-// ~2 700 cycles against 512 of MFMAs (tools/probe/bf16_stamps.py), and half-tile atomics ran at the memory pipeline's
+// ~2 700 cycles against 512 of MFMAs (profiles/r05_bf16_chain_phase_stamps.txt), and half-tile atomics ran at the memory pipeline's
 // instruction rate.
 constexpr int STAGE_F = 1024;        // floats of pooled-output staging per wave
 __host__ __device__ constexpr int stage_cb(int no2) { return no2 * 32 < 128 ? no2 * 32 : 128; }
@@ -83,15 +72,6 @@ __device__ __forceinline__ bf16x8 pack8(const f32x16 &t, int s) {
     }
     return v;
 }
-
-#ifdef SAD_BR_STAMPS   // measurement build only (tools/probe/bf16_stamps.py): s_memtime sums per phase over a wave's tiles
-__device__ unsigned long long g_brst[1024 * 16];
-#define SAD_BSTAMP(var) const unsigned long long var = __builtin_amdgcn_s_memtime()
-#define SAD_BACC(i, t1, t0) do { if (blockIdx.x < 256 && lane == 0) g_brst[(blockIdx.x * 4 + wave) * 16 + (i)] += (t1) - (t0); } while (0)
-#else
-#define SAD_BSTAMP(var)
-#define SAD_BACC(i, t1, t0)
-#endif
 
 struct Ring {
     float4 *ring;       // [RNS][RS][64 lanes]
@@ -142,7 +122,6 @@ __device__ __forceinline__ void br_tile(const BfRegChain &c, const int tile, con
     constexpr int FPW = RS / NW;
     constexpr bool ROLL2 = (KS2 % RS == 0) && NO2 > 4;      // layer-2 tiles span whole stages: loop over them stays rolled
     const int r = lane & 31, h = lane >> 5;
-    SAD_BSTAMP(ts0);
     // ---- rows: lane r carries packed row pi(r) of the tile (its row-map entries were fetched during the previous tile) ----
     const int src = rows.src;
     const int grp = rows.gvq & GID_MASK;
@@ -196,13 +175,10 @@ __device__ __forceinline__ void br_tile(const BfRegChain &c, const int tile, con
     float4 *const ring = rs.ring;
     int slot = rs.slot;
     int srel = 0;
-    static_assert(FPW == 2 || FPW == 4, "two or four fragments per wave and stage");   // (FPW == 2: T2, T3 stay unused; SAD_BR_DMA: all four)
-    [[maybe_unused]] float4 T0, T1, T2, T3;         // this wave's fragments of stage srel + 2, in flight (named: an array
-    T2 = T3 = make_float4(0.f, 0.f, 0.f, 0.f);      // captured by the lambdas below may end up in scratch)
+    static_assert(FPW == 2 || FPW == 4, "two or four fragments per wave and stage");
     const unsigned ulane = (unsigned)lane;
     auto stage_begin = [&]() {
         if constexpr (STATICW) return;
-#if SAD_BR_DMA
         // this wave's fragments of stage srel + 3 (the last three stages of an item: the first three of the next) straight into the slot
         // that was read in the previous stage — every wave has passed that stage's barrier behind its reads
         const int s3 = srel + 3;
@@ -211,39 +187,15 @@ __device__ __forceinline__ void br_tile(const BfRegChain &c, const int tile, con
         const unsigned dst = (unsigned)(size_t)ring + (unsigned)(ws * RS + FPW * wave) * 1024u;
 #pragma unroll
         for (int e = 0; e < FPW; ++e) glds16(sp + e * 64 + ulane, dst + e * 1024u);
-#else
-        const int s2 = srel + 2;
-        const float4 *sp = s2 < NSTG ? sbase + (size_t)(s2 * RS + FPW * wave) * 64 : nbase + (size_t)((s2 - NSTG) * RS + FPW * wave) * 64;
-        T0 = sp[ulane];
-        T1 = (sp + 64)[ulane];
-        if constexpr (FPW == 4) {
-            T2 = (sp + 128)[ulane];
-            T3 = (sp + 192)[ulane];
-        }
-#endif
     };
     auto stage_end = [&]() {
         if constexpr (STATICW) return;
-#if SAD_BR_DMA
         // retire the DMA issued one stage ago (stage srel + 2: the next stage reads ahead into it), leave this stage's in flight; anything
         // else this wave has in the queue behind it (gather loads, pooled-row stores) only makes the wait longer, never shorter
         wait_vm<FPW>();
         __syncthreads();                            // (lgkmcnt(0) + s_barrier: the compiler knows of no DMA)
         slot = slot + 1 == RNS ? 0 : slot + 1;
         ++srel;
-#else
-        const int ws = slot + 2 >= RNS ? slot + 2 - RNS : slot + 2;
-        float4 *wp = ring + (ws * RS + FPW * wave) * 64 + lane;
-        wp[0] = T0;
-        wp[64] = T1;
-        if constexpr (FPW == 4) {
-            wp[128] = T2;
-            wp[192] = T3;
-        }
-        __syncthreads();
-        slot = slot + 1 == RNS ? 0 : slot + 1;
-        ++srel;
-#endif
     };
     // fragment at position pp of this tile's stream, read while position p0 is being consumed (pp >= p0)
     auto frag_at = [&](int pp, int p0) -> float4 {
@@ -281,7 +233,6 @@ __device__ __forceinline__ void br_tile(const BfRegChain &c, const int tile, con
         x1[2 * o] = pack8(acc, 0);
         x1[2 * o + 1] = pack8(acc, 1);
     }
-    SAD_BSTAMP(ts1);
     bf16x8 x2[KS2];
     // ---- layer 1 ----------------------------------------------------------------------------------------------
 #pragma unroll
@@ -329,10 +280,8 @@ __device__ __forceinline__ void br_tile(const BfRegChain &c, const int tile, con
             pi.soff[i] = (slot << (pi.cbs + 2)) + 4 * r;
         }
     }
-    SAD_BSTAMP(ts2);
     // ---- layer 2: D[row, cout] = X . W^T, pooled over the rows of each group -------------------------------------
     auto l2_tile = [&](const int o, const int p0) {   // p0: position of the tile's first fragment (modulo the stage size when rolled)
-        SAD_BSTAMP(tk0);
         f32x16 acc;
         {
             const float bv = sb2[o * 32 + r];
@@ -346,22 +295,11 @@ __device__ __forceinline__ void br_tile(const BfRegChain &c, const int tile, con
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2[ks], as_bf(a[p % PFD]), acc, 0, 0, 0);
             BR_NEXT(p);
         }
-#ifdef SAD_BR_STAMPS
-        asm volatile("" : "+v"(acc));
-        SAD_BSTAMP(tk1);
-        SAD_BACC(6, tk1, tk0);
-#endif
         // register i of this lane half = row 16h + i of the tile, channel 32 o + r
-#ifdef SAD_BR_ABL       // measurement builds (tools/probe/build_variant.sh): 1 no pooling atomics, 2 no flush, 3 neither (wrong results)
-        if (SAD_BR_ABL == 3) { asm volatile("" :: "v"(acc)); return; }
-#endif
         if (pi.ngroups > 0) {
             const int nobm = (1 << (pi.cbs - 5)) - 1;               // output tiles per block - 1
             const int ob = o & nobm;
             char *sp = reinterpret_cast<char *>(stage) + 128 * ob;
-#ifdef SAD_BR_ABL
-            if (SAD_BR_ABL == 1) { asm volatile("" :: "v"(acc)); } else
-#endif
             if (pi.kind == 1) {
                 // each half of the tile lies inside one group: a plain max chain across the registers, one LDS atomic per half
                 float m = relu1(acc[0]);
@@ -378,9 +316,6 @@ __device__ __forceinline__ void br_tile(const BfRegChain &c, const int tile, con
                     atomicMax(reinterpret_cast<unsigned *>(sp + pi.soff[i]), __builtin_bit_cast(unsigned, v));      // ds_max_u32
                 }
             }
-#ifdef SAD_BR_ABL
-            if (SAD_BR_ABL == 2) return;
-#endif
             if (ob == nobm) {
                 // block complete: every group leaves as one row of CB channels, then its slot is zero again
                 const int cbs = pi.cbs;
@@ -412,18 +347,10 @@ __device__ __forceinline__ void br_tile(const BfRegChain &c, const int tile, con
                 for (int s0 = 0; s0 < pi.ngroups; s0 += 64 >> (cbs - 2)) {       // (wave-uniform)
                     const int sidx = s0 + (lane >> (cbs - 2));
                     float4 *src = reinterpret_cast<float4 *>(stage + (s0 << cbs)) + lane;
-#if defined(SAD_BR_ABL) && SAD_BR_ABL == 4      // (4: plain stores where a group continues in another tile, 5: no global stores at all)
-                    const bool whole = true;
-#else
                     const bool whole = (sidx > 0 || pi.whole_first) && (sidx < pi.ngroups - 1 || pi.whole_last);
-#endif
                     if (sidx < pi.ngroups && whole) {
                         const float4 v = *src;
                         *src = make_float4(0.f, 0.f, 0.f, 0.f);
-#if defined(SAD_BR_ABL) && SAD_BR_ABL == 5
-                        asm volatile("" :: "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
-                        continue;
-#endif
                         float *orow = c_out + (long long)(pi.g_first + sidx) * ldo + col_off + ch;
                         if (vec_out && ch + 3 < cout_last) {
                             *reinterpret_cast<float4 *>(orow) = v;
@@ -447,15 +374,10 @@ __device__ __forceinline__ void br_tile(const BfRegChain &c, const int tile, con
                         if (ch0 + cc < cout_last) atomic_max_pos(orow + cc, v);
                     }
                 };
-#if !defined(SAD_BR_ABL) || SAD_BR_ABL != 4
                 if (!pi.whole_first) combine(0);
                 if (!pi.whole_last && pi.ngroups > 1) combine(pi.ngroups - 1);
-#endif
             }
         }
-#ifdef SAD_BR_STAMPS
-        { SAD_BSTAMP(tk2); SAD_BACC(7, tk2, tk1); }
-#endif
     };
     if constexpr (ROLL2) {
         static_assert(RS % PFD == 0 && KS2 % RS == 0, "a rolled tile must start at the same position modulo the stage and the read queue");
@@ -469,16 +391,6 @@ __device__ __forceinline__ void br_tile(const BfRegChain &c, const int tile, con
 #undef BR_BEGIN
 #undef BR_NEXT
     rs.slot = slot;
-#ifdef SAD_BR_STAMPS
-    {
-        SAD_BSTAMP(ts3);
-        SAD_BACC(0, ts1, ts0);      // rows, gather, layer 0
-        SAD_BACC(1, ts2, ts1);      // layer 1
-        SAD_BACC(2, ts3, ts2);      // layer 2 + pooling
-        SAD_BACC(3, 1, 0);          // tiles
-        SAD_BACC(4, (unsigned long long)P, 0ull);   // fragments
-    }
-#endif
 }
 
 // Shapes (sad::bfreg_shape_id):  KS0, NO0, NO1, NO2
@@ -510,7 +422,7 @@ __device__ __forceinline__ void run_br(const BfRegChain &c, int shape, int tile,
 constexpr int BR_NW = 4;
 
 template <int FAMILY, bool SPLIT>
-__global__ __launch_bounds__(BR_NW * 64, FAMILY == 0 ? 4 : (FAMILY == 1 ? 3 : (FAMILY == 2 ? SAD_BR_F2 : 2))) void mlp_bf16_reg_kernel(const BfRegMulti mp) {
+__global__ __launch_bounds__(BR_NW * 64, FAMILY == 0 ? 4 : (FAMILY == 1 ? 3 : (FAMILY == 2 ? F2_WGS : 2))) void mlp_bf16_reg_kernel(const BfRegMulti mp) {
     constexpr int NW = BR_NW;
     constexpr int FPW = RS / NW;
     constexpr bool STATICW = FAMILY == 0;
@@ -554,28 +466,16 @@ __global__ __launch_bounds__(BR_NW * 64, FAMILY == 0 ? 4 : (FAMILY == 1 ? 3 : (F
             for (int i = tid; i < n4; i += NW * 64) ring[wo + i] = sp[i];
             wo += n4;
         }
-    } else if (item < nitems) {   // prologue: stages 0 and 1 of the first item (DMA: 0, 1 and 2)
+    } else if (item < nitems) {   // prologue: stages 0, 1 and 2 of the first item
         const float4 *sp = stream_of(item) + (size_t)(FPW * wave) * 64;
-#if SAD_BR_DMA
 #pragma unroll
         for (int s = 0; s < 3; ++s)
 #pragma unroll
             for (int e = 0; e < FPW; ++e) glds16(sp + (size_t)(s * RS + e) * 64 + ulane, (unsigned)(size_t)ring + (unsigned)(s * RS + FPW * wave + e) * 1024u);
         wait_vm<0>();
-#else
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int e = 0; e < FPW; ++e) ring[(s * RS + FPW * wave + e) * 64 + lane] = (sp + (size_t)(s * RS + e) * 64)[ulane];
-#endif
     }
     __syncthreads();                                // (also: the biases are in place)
     Ring rs{ring, 0};
-#ifdef SAD_BR_STAMPS
-    const unsigned long long tk0 = __builtin_amdgcn_s_memtime(), tr0 = __builtin_amdgcn_s_memrealtime();
-    if (blockIdx.x < 256 && lane == 0)
-        for (int i = 0; i < 16; ++i) g_brst[(blockIdx.x * 4 + wave) * 16 + i] = 0;
-#endif
     auto chain_of = [&](int it) { return __builtin_amdgcn_readfirstlane(it < t0 ? 0 : (it < t1 ? 1 : 2)); };
     auto tile_of = [&](int it, int ci) { return (it - (ci == 0 ? 0 : (ci == 1 ? t0 : t1))) * NW + wave; };
     auto total_of = [&](int ci) { return ci == 0 ? tot0 : (ci == 1 ? tot1 : tot2); };
@@ -594,15 +494,7 @@ __global__ __launch_bounds__(BR_NW * 64, FAMILY == 0 ? 4 : (FAMILY == 1 ? 3 : (F
         run_br<FAMILY, NW, SPLIT>(mp.c[ci], mp.shape[ci], tile_of(item, ci), sbias + (ci == 0 ? 0 : (ci == 1 ? b1 : b2)), lane, wave, rs,
                            stream_of(item), stream_of(nit), stage, total_of(ci), rows, mp.c[nci], tile_of(nit, nci), total_of(nci));
     }
-#if SAD_BR_DMA
     if constexpr (!STATICW) wait_vm<0>();             // (no DMA may land in this workgroup's LDS after it has gone)
-#endif
-#ifdef SAD_BR_STAMPS
-    if (blockIdx.x < 256 && lane == 0) {
-        g_brst[(blockIdx.x * 4 + wave) * 16 + 12] = __builtin_amdgcn_s_memtime() - tk0;
-        g_brst[(blockIdx.x * 4 + wave) * 16 + 13] = __builtin_amdgcn_s_memrealtime() - tr0;
-    }
-#endif
 }
 
 // fragment stream of one chain in consumption order (see the header): layer 0 in natural k order, layers 1 and 2 in the
@@ -733,9 +625,3 @@ int launch_bfreg(const BfRegMulti &mp, hipStream_t st) {
 }
 
 }  // namespace sad
-
-#ifdef SAD_BR_STAMPS
-extern "C" __attribute__((visibility("default"))) int sad_debug_read_br_stamps(unsigned long long *dst) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_brst), sizeof(unsigned long long) * 1024 * 16);
-}
-#endif

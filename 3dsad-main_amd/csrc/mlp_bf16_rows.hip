@@ -24,9 +24,7 @@ typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 using sad::BfRowsJob;
 
 constexpr int KC = 4;                 // k-steps (of 16) per chunk
-#ifndef SAD_ROWS_DX
-#define SAD_ROWS_DX 2      // row-queue depth of layers with more than two chunks (3: slower on every aggregation, 224 - 256 registers)
-#endif
+constexpr int DEEP_DX = 2;            // row-queue depth of layers with more than two chunks (3: slower on every aggregation, 224 - 256 registers)
 
 __device__ __forceinline__ bf16x8 cvt8(const float4 a, const float4 b) {
     bf16x8 v;
@@ -40,15 +38,6 @@ __device__ __forceinline__ bf16x8 cvt8(const float4 a, const float4 b) {
 __device__ __forceinline__ float4 max_pos_bf16x8(const float4 a, const float4 b) {
     return __builtin_bit_cast(float4, __builtin_elementwise_max(__builtin_bit_cast(u16x8, a), __builtin_bit_cast(u16x8, b)));
 }
-
-#ifdef SAD_ROWS_STAMPS   // measurement build only (tools/probe/rows_stamps.py): s_memtime sums per phase over a wave's chunks
-__device__ unsigned long long g_rowst[1024 * 8];
-#define SAD_RSTAMP(var) const unsigned long long var = __builtin_amdgcn_s_memtime()
-#define SAD_RACC(i, t1, t0) do { if (blockIdx.x < 1024 / (int)(blockDim.x / 64) && lane == 0) g_rowst[(blockIdx.x * (blockDim.x / 64) + wave) * 8 + (i)] += (t1) - (t0); } while (0)
-#else
-#define SAD_RSTAMP(var)
-#define SAD_RACC(i, t1, t0)
-#endif
 
 // NT = channel tiles (of 32) per item: 4, or 2 for layers with at most 64 output channels
 // XCONT (with XBF16): the rows are SPLIT-POOLED (common.h BfRowsJob; mlp_bf16_reg.hip): row g of the chain behind a column range is the
@@ -73,14 +62,6 @@ __global__ __launch_bounds__(256) void bf16_rows_kernel(const BfRowsJob jb) {
     const int rb = xcd + 8 * (slot / ncb), cb = slot % ncb;
     if (rb >= nrb) return;
     const int nt = jb.ct - cb * NT < NT ? jb.ct - cb * NT : NT;        // channel tiles of this item (1..4)
-#ifdef SAD_ROWS_STAMPS
-    if (blockIdx.x < 256 && lane == 0)
-        for (int i = 0; i < 8; ++i) g_rowst[(blockIdx.x * 4 + wave) * 8 + i] = 0;
-#endif
-    SAD_RSTAMP(tk0);
-#ifdef SAD_ROWS_STAMPS
-    const unsigned long long tr0 = __builtin_amdgcn_s_memrealtime();
-#endif
     const long long row = (long long)rb * 128 + wave * 32 + r;
     const bool live = row < jb.rows;
     const long long rowc = live ? row : jb.rows - 1;
@@ -241,26 +222,13 @@ __global__ __launch_bounds__(256) void bf16_rows_kernel(const BfRowsJob jb) {
                 if (c < NC) {                               // (workgroup-uniform)
                     const float4 *cur = lds + (i & 1) * STAGE_F4;
                     bf16x8 x[KC];
-                    SAD_RSTAMP(ta);
     #pragma unroll
                     for (int s = 0; s < KC; ++s)
                         x[s] = XCONT ? __builtin_bit_cast(bf16x8, max_pos_bf16x8(xq[i % DX].a[s], xq[i % DX].b[s]))
                                      : (XBF16 ? __builtin_bit_cast(bf16x8, xq[i % DX].a[s]) : cvt8(xq[i % DX].a[s], xq[i % DX].b[s]));
-#ifdef SAD_ROWS_STAMPS
-                    asm volatile("" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]));
-#endif
-                    SAD_RSTAMP(tb);
                     const int cx = c + DX < NC ? c + DX : NC - 1, cw = c + 2 < NC ? c + 2 : NC - 1;
-    #if defined(SAD_ROWS_ABL) && SAD_ROWS_ABL == 1       // measurement builds: 1 the rows are loaded once, 2 the weights are loaded once (wrong results)
-                    if (c == 0) xq[i % DX] = load_x(cx);
-    #else
                     xq[i % DX] = load_x(cx);
-    #endif
-    #if defined(SAD_ROWS_ABL) && SAD_ROWS_ABL == 2
-                    wq[i & 1] = load_w(0);
-    #else
                     wq[i & 1] = load_w(cw);
-    #endif
                     // A full chunk of a full item (every chunk but possibly the last, every item but those of a ragged last channel block) runs
                     // WITHOUT per-product conditions: with them every MFMA sat behind its own branch, LDS read and lgkmcnt(0) — ~200 cycles per
                     // 32-cycle product.  The fragments of k-step s + 1 are read while the products of k-step s run.
@@ -291,27 +259,13 @@ __global__ __launch_bounds__(256) void bf16_rows_kernel(const BfRowsJob jb) {
                             }
                         }
                     }
-#ifdef SAD_ROWS_STAMPS
-    #pragma unroll
-                    for (int t = 0; t < NT; ++t) asm volatile("" : "+v"(acc[t]));
-#endif
-                    SAD_RSTAMP(tc);
                     if (c + 1 < NC) store_w(wq[(i + 1) & 1], lds + ((i + 1) & 1) * STAGE_F4);      // (chunk c + 1: loaded during chunk c - 1)
-#ifdef SAD_ROWS_STAMPS
-                    __builtin_amdgcn_s_waitcnt(0);
-#endif
-                    SAD_RSTAMP(td);
                     __syncthreads();
-                    SAD_RSTAMP(te);
-                    SAD_RACC(0, tb, ta); SAD_RACC(1, tc, tb); SAD_RACC(2, td, tc); SAD_RACC(3, te, td); SAD_RACC(4, 1, 0);
                 }
             }
         }
     }
     // ---- epilogue: lane = row, registers 4q .. 4q+3 = channels 32 t + 8 q + 4 h .. + 3 ----
-#ifdef SAD_ROWS_STAMPS
-    { SAD_RSTAMP(tk1); SAD_RACC(5, tk1, tk0); SAD_RACC(6, __builtin_amdgcn_s_memrealtime(), tr0); }
-#endif
     if (!live) return;
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
@@ -352,7 +306,7 @@ __global__ __launch_bounds__(256) void bf16_rows_kernel(const BfRowsJob jb) {
 
 
 // ---- second form (round 5): a tiled GEMM fed by LDS-DMA ------------------------------------------------------------------------------
-// What the phase stamps of the kernel above said on the aggregation layers (tools/probe/rows_stamps.py, cluster.agg 8 192 x 1 536 -> 512):
+// What the phase stamps of the kernel above said on the aggregation layers (profiles/r05_rows1_phase_stamps.txt, cluster.agg 8 192 x 1 536 -> 512):
 // ~2 200 cycles per 64-deep chunk against 512 of MFMAs — the fragment-shaped row loads (every instruction touches 32 lines for 32 bytes
 // each), the register-staged weights (four loads + four ds_write per wave and chunk, waited for in the middle of the chunk) and a
 // write -> barrier -> read turn-around of the LDS at every chunk.  This form moves both operands global -> LDS with global_load_lds_dwordx4
@@ -384,15 +338,7 @@ __global__ __launch_bounds__(512) void bf16_rows2_kernel(const BfRowsJob jb) {
     constexpr int XB = 128 * 128;                     //                   row tile (128 rows x 64 k of bf16)
     constexpr int SB = WB + XB + (XCONT ? XB : 0);    //                   + continuation tile
     constexpr int PW = KC * TW / 8;                   // weight pieces (1 KB) per wave and chunk
-#if defined(SAD_ROWS2_WHATIF) && SAD_ROWS2_WHATIF == 1
-    constexpr int PV = PW + (XCONT ? 2 : 0);
-#elif defined(SAD_ROWS2_WHATIF) && SAD_ROWS2_WHATIF == 2
-    constexpr int PV = 2 + (XCONT ? 2 : 0);
-#elif defined(SAD_ROWS2_WHATIF) && SAD_ROWS2_WHATIF == 3
-    constexpr int PV = (XCONT ? 2 : 0);
-#else
     constexpr int PV = PW + 2 + (XCONT ? 2 : 0);      // DMA instructions per wave and chunk
-#endif
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem2[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int rw = wave & 3, cw = wave >> 2;
@@ -403,12 +349,6 @@ __global__ __launch_bounds__(512) void bf16_rows2_kernel(const BfRowsJob jb) {
     const int xcd = g & 7, slot = g >> 3;
     const int rb = xcd + 8 * (slot / ncb), cb = slot % ncb;
     if (rb >= nrb) return;                            // (workgroup-uniform)
-#ifdef SAD_ROWS_STAMPS
-    if (blockIdx.x < 128 && lane == 0)
-        for (int i = 0; i < 8; ++i) g_rowst[(blockIdx.x * 8 + wave) * 8 + i] = 0;
-    const unsigned long long tr0 = __builtin_amdgcn_s_memrealtime();
-#endif
-    SAD_RSTAMP(tk0);
     const unsigned lds0 = (unsigned)(size_t)smem2;
     // ---- DMA sources of this lane ------------------------------------------------------------------------------------------------
     const char *wsrc[PW];
@@ -436,14 +376,10 @@ __global__ __launch_bounds__(512) void bf16_rows2_kernel(const BfRowsJob jb) {
     const int drow0 = 8 * wave + (lane >> 3), drow1 = drow0 + 64;              // the tile rows of this lane's two DMA pieces
     auto issue_wx = [&](int c) __attribute__((always_inline)) {   // the DMA of chunk c into stage c % 3: weight fragments and row tile
         const unsigned st = lds0 + (unsigned)(c % 3) * SB;
-#if !defined(SAD_ROWS2_WHATIF) || (SAD_ROWS2_WHATIF != 2 && SAD_ROWS2_WHATIF != 3)      // (measurement builds: 1 = no row tile, 2 = no weights, 3 = neither — wrong results, what the bytes cost)
 #pragma unroll
         for (int i = 0; i < PW; ++i) glds16(wsrc[i] + (size_t)c * (KC * 1024), st + wdst[i]);
-#endif
-#if !defined(SAD_ROWS2_WHATIF) || (SAD_ROWS2_WHATIF != 1 && SAD_ROWS2_WHATIF != 3)
 #pragma unroll
         for (int i = 0; i < 2; ++i) glds16(xsrc[i] + (size_t)c * 128, st + xdst[i]);
-#endif
     };
     // the first two chunks' weights and rows are on their way before anything below waits for memory (the continuation tables, the bias)
     issue_wx(0);
@@ -520,11 +456,9 @@ __global__ __launch_bounds__(512) void bf16_rows2_kernel(const BfRowsJob jb) {
     const unsigned xoff = WB + xrow * 128, xsw = (unsigned)(xrow & 7);
 #pragma unroll 1
     for (int c = 0; c < NC; ++c) {
-        SAD_RSTAMP(ta);
         // (the two waves of a SIMD — w and w + 4 — taking turns, one issuing its DMA while the other multiplies, was measured: no faster, the
         // largest layers 7 - 12 % slower)
         if (c + 2 < NC) { issue_wx(c + 2); issue_c(c + 2); }
-        SAD_RSTAMP(tb);
         const unsigned char *st = smem2 + (c % 3) * SB;
         // the chunk's four B fragments first (row r of the tile, columns 2 s + h), then the weight fragments one k-step ahead of their MFMAs
         float4 bf[KC];
@@ -558,10 +492,6 @@ __global__ __launch_bounds__(512) void bf16_rows2_kernel(const BfRowsJob jb) {
 #pragma unroll
             for (int s = 0; s < KC; ++s) bf[s] = max_pos_bf16x8(bf[s], bc[s]);
         }
-#ifdef SAD_ROWS_STAMPS
-        asm volatile("s_waitcnt lgkmcnt(0)");
-#endif
-        SAD_RSTAMP(tc);
         float4 wf[2][NTW];
 #pragma unroll
         for (int j = 0; j < NTW; ++j) wf[0][j] = *reinterpret_cast<const float4 *>(st + ((cw * NTW + j) * 64 + lane) * 16);
@@ -577,23 +507,12 @@ __global__ __launch_bounds__(512) void bf16_rows2_kernel(const BfRowsJob jb) {
                 acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wf[s & 1][j]), __builtin_bit_cast(bf16x8, bf[s]), acc[j], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
-#ifdef SAD_ROWS_STAMPS
-#pragma unroll
-        for (int j = 0; j < NTW; ++j) asm volatile("" : "+v"(acc[j]));
-#endif
-        SAD_RSTAMP(td);
         if (c + 1 < NC) {
             // retire chunk c + 1's DMA (chunk c + 2's stays in flight), retire this chunk's LDS reads, publish
             if (c + 2 < NC) wait_vm<PV>(); else wait_vm<0>();
-            SAD_RSTAMP(te);
             __syncthreads();
-            SAD_RSTAMP(tf);
-            SAD_RACC(0, tb, ta); SAD_RACC(1, tc, tb); SAD_RACC(2, td, tc); SAD_RACC(3, te, td); SAD_RACC(7, tf, te); SAD_RACC(4, 1, 0);
         }
     }
-#ifdef SAD_ROWS_STAMPS
-    { SAD_RSTAMP(tk1); SAD_RACC(5, tk1, tk0); SAD_RACC(6, __builtin_amdgcn_s_memrealtime(), tr0); }
-#endif
     // ---- epilogue: lane = row, registers 4q .. 4q+3 = channels 32 t + 8 q + 4 h .. + 3 (as in the first form) ----
     const long long row = (long long)rb * 128 + rw * 32 + r;
     if (row >= jb.rows) return;
@@ -673,34 +592,24 @@ int launch_bf16_rows(const BfRowsJob &job, hipStream_t st) {
     // occupancy instead: sa1.agg (1 024 workgroups, two chunks) 26 -> 32 us, and at 32 nuScenes-shaped scenes (1 024 workgroups per layer)
     // cluster.agg 160 -> 180, sa3.agg 86 -> 100, sa2.agg 64 -> 69 us.
     const int cus = sad::device_cus();
-#ifdef SAD_ROWS_DEEP_ALWAYS      // measurement builds: the queued loop for every layer of more than two chunks, whatever the grid
-    const bool deep = (jb.ks + KC - 1) / KC > 2 && cus > 0;
-#else
     const bool deep = (jb.ks + KC - 1) / KC > 2 && grid <= 2LL * cus;
-#endif
 #define SAD_ROWS_LAUNCH(XB, NTV, DXV) hipLaunchKernelGGL((bf16_rows_kernel<XB, NTV, DXV>), dim3((unsigned)grid), dim3(256), 0, st, jb)
     if (jb.n_pool) {
         if (!jb.x_bf16) return fail(SAD_EINVAL, "sad_mlp_chain_bf16: split-pooled rows are bf16");
 #define SAD_ROWS_LAUNCH_C(NTV, DXV) hipLaunchKernelGGL((bf16_rows_kernel<true, NTV, DXV, true>), dim3((unsigned)grid), dim3(256), 0, st, jb)
-        if (nt == 4) { if (deep) SAD_ROWS_LAUNCH_C(4, SAD_ROWS_DX); else SAD_ROWS_LAUNCH_C(4, 0); }
-        else { if (deep) SAD_ROWS_LAUNCH_C(2, SAD_ROWS_DX); else SAD_ROWS_LAUNCH_C(2, 0); }
+        if (nt == 4) { if (deep) SAD_ROWS_LAUNCH_C(4, DEEP_DX); else SAD_ROWS_LAUNCH_C(4, 0); }
+        else { if (deep) SAD_ROWS_LAUNCH_C(2, DEEP_DX); else SAD_ROWS_LAUNCH_C(2, 0); }
 #undef SAD_ROWS_LAUNCH_C
     } else
     if (nt == 4) {
-        if (jb.x_bf16) { if (deep) SAD_ROWS_LAUNCH(true, 4, SAD_ROWS_DX); else SAD_ROWS_LAUNCH(true, 4, 0); }
-        else { if (deep) SAD_ROWS_LAUNCH(false, 4, SAD_ROWS_DX); else SAD_ROWS_LAUNCH(false, 4, 0); }
+        if (jb.x_bf16) { if (deep) SAD_ROWS_LAUNCH(true, 4, DEEP_DX); else SAD_ROWS_LAUNCH(true, 4, 0); }
+        else { if (deep) SAD_ROWS_LAUNCH(false, 4, DEEP_DX); else SAD_ROWS_LAUNCH(false, 4, 0); }
     } else {
-        if (jb.x_bf16) { if (deep) SAD_ROWS_LAUNCH(true, 2, SAD_ROWS_DX); else SAD_ROWS_LAUNCH(true, 2, 0); }
-        else { if (deep) SAD_ROWS_LAUNCH(false, 2, SAD_ROWS_DX); else SAD_ROWS_LAUNCH(false, 2, 0); }
+        if (jb.x_bf16) { if (deep) SAD_ROWS_LAUNCH(true, 2, DEEP_DX); else SAD_ROWS_LAUNCH(true, 2, 0); }
+        else { if (deep) SAD_ROWS_LAUNCH(false, 2, DEEP_DX); else SAD_ROWS_LAUNCH(false, 2, 0); }
     }
 #undef SAD_ROWS_LAUNCH
     return check_launch("sad_mlp_chain_bf16 (plain-row layer)");
 }
 
 }  // namespace sad
-
-#ifdef SAD_ROWS_STAMPS
-extern "C" __attribute__((visibility("default"))) int sad_debug_read_rows_stamps(unsigned long long *dst) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_rowst), sizeof(unsigned long long) * 1024 * 8);
-}
-#endif

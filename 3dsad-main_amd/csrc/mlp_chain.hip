@@ -24,9 +24,7 @@ using namespace sad::chain;
 
 #include "prims.h"       // f32x16, atomic_max_pos
 
-#ifndef SAD_MLP_BDEPTH
-#define SAD_MLP_BDEPTH 2
-#endif
+constexpr int B_DEPTH = 2;    // B ring depth asked for (4 applies to row tiles of RW <= 2 only: see mma_ktile)
 
 // LDS activation image of a tile of R rows.  Channels are grouped in k-blocks of 8; inside a block
 // the even channels (plane 0) and the odd channels (plane 1) are separate [row][4] arrays, so lane
@@ -63,9 +61,7 @@ __device__ __forceinline__ float group_max(float v, int steps) {
 // Software pipeline written out by hand (hipcc otherwise sinks each load to its use): a ring of
 // four A registers refilled right after use (L2 latency covered by three k-steps of MFMAs) and two
 // B registers (LDS latency covered by one k-step).
-#ifndef SAD_MLP_ADEPTH
-#define SAD_MLP_ADEPTH 4   // k-steps of weight fragments in flight per accumulator chain
-#endif
+constexpr int A_DEPTH = 4;    // k-steps of weight fragments in flight per accumulator chain
 
 template <int RW>
 struct BFrag { float4 v[RW]; };
@@ -103,7 +99,7 @@ __device__ __forceinline__ void mma_ktile(f32x16 (&acc)[RW], const float4 *__res
     float4 a[D];
 #pragma unroll
     for (int u = 0; u < D; ++u) a[u] = lda(af, u, n4);
-    constexpr int BD = SAD_MLP_BDEPTH <= 2 || RW > 2 ? 2 : 4;   // B ring depth (LDS prefetch distance)
+    constexpr int BD = B_DEPTH <= 2 || RW > 2 ? 2 : 4;   // B ring depth (LDS prefetch distance)
     BFrag<RW> b[BD];
 #pragma unroll
     for (int u = 0; u < BD; ++u) b[u] = ldb<RW>(bp, u, n4, kbs);
@@ -438,12 +434,12 @@ __device__ __forceinline__ void mlp_chain_body(const MlpParams &p, const int blo
                         if constexpr (CW == 2) {
                             if (haves[CW - 1]) {
                                 const float4 *af1 = frags + ((size_t)ocs[CW - 1] * nT4 + (k0 >> 3)) * 64 + lane;
-                                mma_ktile2<SAD_MLP_ADEPTH>(accs[0][0], accs[CW - 1][0], af, af1, (k1 - k0) >> 3, bp, PS >> 1);
+                                mma_ktile2<A_DEPTH>(accs[0][0], accs[CW - 1][0], af, af1, (k1 - k0) >> 3, bp, PS >> 1);
                             } else {
-                                mma_ktile<RW, SAD_MLP_ADEPTH>(accs[0], af, (k1 - k0) >> 3, bp, PS >> 1);
+                                mma_ktile<RW, A_DEPTH>(accs[0], af, (k1 - k0) >> 3, bp, PS >> 1);
                             }
                         } else {
-                            mma_ktile<RW, SAD_MLP_ADEPTH>(accs[0], af, (k1 - k0) >> 3, bp, PS >> 1);
+                            mma_ktile<RW, A_DEPTH>(accs[0], af, (k1 - k0) >> 3, bp, PS >> 1);
                         }
                     }
                 }

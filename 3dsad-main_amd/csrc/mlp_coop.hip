@@ -34,22 +34,6 @@ constexpr int RING_F4 = NS * S * 64; // float4 in the ring
 // pooled-output staging per wave (floats): 8 slots of a tile's COUT channels (groups ending inside one tile)
 __host__ __device__ constexpr int pool_floats(int family) { return family == 2 ? 8 * 256 : 8 * 128; }
 
-#ifdef SAD_COOP_STAMPS   // measurement build only (tools/probe/coop_stamps.py): s_memtime at the phase boundaries of a tile
-__device__ unsigned long long g_cstamps[64 * 16];
-__device__ unsigned long long g_call[2048 * 4];     // per workgroup: start / end (s_memrealtime), items, hardware id
-#define SAD_CSTAMP(i)                                                                                              \
-    do {                                                                                                           \
-        if (blockIdx.x < 16 && lane == 0) g_cstamps[(blockIdx.x * 4 + wave) * 16 + (i)] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
-#define SAD_CACC(i, t0)                                                                                            \
-    do {                                                                                                           \
-        if (blockIdx.x < 16 && lane == 0) g_cstamps[(blockIdx.x * 4 + wave) * 16 + (i)] += __builtin_amdgcn_s_memtime() - (t0); \
-    } while (0)
-#else
-#define SAD_CSTAMP(i)
-#define SAD_CACC(i, t0)
-#endif
-
 struct RingState {
     float4 *ring;        // workgroup-shared: [NS][S][64 lanes]
     int slot;            // ring slot of the stage being consumed (wave-uniform)
@@ -67,7 +51,6 @@ __device__ __forceinline__ void coop_tile(const RegChain &c, const int tile, con
     constexpr int NSTG = (P + S - 1) / S;
     constexpr bool ROLL2 = NG2 % S == 0;   // layer-2 tiles span whole stages: the loop over them can stay rolled
     const int j = lane & 31, h = lane >> 5;
-    SAD_CSTAMP(0);
     const int total = c.rowtab[0];
     int q = tile * 32 + j;
     const bool live = q < total;
@@ -171,11 +154,7 @@ __device__ __forceinline__ void coop_tile(const RegChain &c, const int tile, con
                 float ops[4];
                 xfix(xq[n % 3], r, ops);
                 t = mma4(t, a[p % 2], ops);
-#ifdef SAD_COOP_NOGATHER     // measurement build (wrong results): the feature rows are gathered for layer 0's FIRST output tile only
-                if (n + 3 < NT0) xq[n % 3] = xload((n + 3) % NT0);
-#else
                 if (n + 3 < NX) xq[n % 3] = xload((n + 3) % NT0);
-#endif
             } else {
                 const int i = r - NT0;
                 acc1[i >> 2] = mma4(acc1[i >> 2], a[p % 2], bt + 4 * (i & 3));
@@ -190,7 +169,6 @@ __device__ __forceinline__ void coop_tile(const RegChain &c, const int tile, con
             if (m == S - 1) stage_end();
         }
     }
-    SAD_CSTAMP(1);
 #pragma unroll
     for (int o1 = 0; o1 < NO1; ++o1) {
         const f32x16 u = relu16(acc1[o1]);
@@ -198,14 +176,7 @@ __device__ __forceinline__ void coop_tile(const RegChain &c, const int tile, con
         for (int g = 0; g < 4; ++g) to_operands(u[4 * g], u[4 * g + 1], u[4 * g + 2], u[4 * g + 3], in2 + 16 * o1 + 4 * g);
     }
     const PoolMasks pm = pool_masks(key);
-    SAD_CSTAMP(2);
-#ifdef SAD_COOP_STAMPS
-    if (blockIdx.x < 16 && lane == 0) { g_cstamps[(blockIdx.x * 4 + wave) * 16 + 5] = 0; g_cstamps[(blockIdx.x * 4 + wave) * 16 + 6] = 0; }
-#endif
     auto l2_tile = [&](const int o, const int p0) {   // p0: position of the tile's first fragment (modulo the stage size when rolled)
-#ifdef SAD_COOP_STAMPS
-        const unsigned long long tk = __builtin_amdgcn_s_memtime();
-#endif
         f32x16 t2 = bias_tile(sb2 + o * 32, h);
 #pragma unroll
         for (int i = 0; i < NG2; ++i) {
@@ -217,13 +188,8 @@ __device__ __forceinline__ void coop_tile(const RegChain &c, const int tile, con
             __builtin_amdgcn_sched_barrier(0);
             if (m == S - 1) stage_end();
         }
-        SAD_CACC(5, tk);
-#ifdef SAD_COOP_STAMPS
-        const unsigned long long tp = __builtin_amdgcn_s_memtime();
-#endif
         if (sg.lds) pool_stage<COUT>(relu16(t2), pm, tail, sg, o, h);
         else pool_store(relu16(t2), pm, tail, whole, orow, o, h, c);
-        SAD_CACC(6, tp);
     };
     if constexpr (ROLL2) {
 #pragma unroll 1
@@ -232,10 +198,8 @@ __device__ __forceinline__ void coop_tile(const RegChain &c, const int tile, con
 #pragma unroll
         for (int o = 0; o < NO2; ++o) l2_tile(o, TOT + o * NG2);
     }
-    SAD_CSTAMP(3);
     if (P % S != 0) stage_end();                   // the padded last stage
     if (sg.lds) stage_flush<COUT>(sg, grp, whole, lane, c);
-    SAD_CSTAMP(4);
     rs.slot = slot;
 }
 
@@ -316,22 +280,6 @@ __global__ __launch_bounds__(WAVES * 64, FAMILY == 2 ? 2 : 3) void mlp_coop_kern
     __syncthreads();                                // (also: the biases are in place)
     int item = s_next[0], nxt = s_next[1];
     __syncthreads();                                // s_next is written again at the end of the first item
-#ifdef SAD_COOP_STAMPS
-    if (blockIdx.x < 2048 && tid == 0) {
-        g_call[blockIdx.x * 4 + 0] = __builtin_amdgcn_s_memrealtime();
-        g_call[blockIdx.x * 4 + 1] = 0;
-        g_call[blockIdx.x * 4 + 2] = 0;
-        unsigned hw, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        g_call[blockIdx.x * 4 + 3] = ((unsigned long long)(xcc & 0xF) << 32) | hw;
-    }
-    if (blockIdx.x < 16 && lane == 0) {
-        g_cstamps[(blockIdx.x * 4 + wave) * 16 + 8] = __builtin_amdgcn_s_memtime();
-        g_cstamps[(blockIdx.x * 4 + wave) * 16 + 10] = __builtin_amdgcn_s_memrealtime();
-        g_cstamps[(blockIdx.x * 4 + wave) * 16 + 12] = 0;
-    }
-#endif
     const unsigned ulane = (unsigned)lane;
     auto stream_of = [&](int it) -> const float4 * {
         const int ci = it < t0 ? 0 : (it < t1 ? 1 : 2);
@@ -382,18 +330,8 @@ __global__ __launch_bounds__(WAVES * 64, FAMILY == 2 ? 2 : 3) void mlp_coop_kern
             if (tid == 0 && mp.nq == 8) atomicAdd(Q.q + sad::ITEMQ_REFILLS, 1);   // test instrumentation (common.h)
             __syncthreads();
         }
-#ifdef SAD_COOP_STAMPS
-        if (blockIdx.x < 16 && lane == 0) g_cstamps[(blockIdx.x * 4 + wave) * 16 + 12] += 1;
-#endif
     }
     if (tid == 0 && mp.nq) sad::itemq_done(Q, (int)gridDim.x);    // the last workgroup out re-arms the queues for the next launch
-#ifdef SAD_COOP_STAMPS
-    if (blockIdx.x < 2048 && tid == 0) g_call[blockIdx.x * 4 + 1] = __builtin_amdgcn_s_memrealtime();
-    if (blockIdx.x < 16 && lane == 0) {
-        g_cstamps[(blockIdx.x * 4 + wave) * 16 + 9] = __builtin_amdgcn_s_memtime();
-        g_cstamps[(blockIdx.x * 4 + wave) * 16 + 11] = __builtin_amdgcn_s_memrealtime();
-    }
-#endif
 }
 
 }  // namespace
@@ -454,12 +392,3 @@ int launch_coop(const RegMulti &mp, hipStream_t st) {
 }
 
 }  // namespace sad
-
-#ifdef SAD_COOP_STAMPS
-extern "C" __attribute__((visibility("default"))) int sad_debug_read_coop_stamps(unsigned long long *dst) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_cstamps), sizeof(unsigned long long) * 64 * 16);
-}
-extern "C" __attribute__((visibility("default"))) int sad_debug_read_coop_all(unsigned long long *dst) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_call), sizeof(unsigned long long) * 2048 * 4);
-}
-#endif

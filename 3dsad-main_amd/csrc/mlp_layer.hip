@@ -40,10 +40,7 @@ using sad::LayerMulti;
 // two LDS stages (weights copied as they are packed, activations turned into operand order by the loading wave),
 // wave (wy, wx) of the 2 x 2 grid computes row tiles {2wy, 2wy+1} x output tiles {2wx, 2wx+1}: 16 MFMAs per
 // k-group from four ds_read_b128, and 8 MFMAs per global load instead of 3.2.
-#ifndef SAD_LAYER_KC
-#define SAD_LAYER_KC 2
-#endif
-constexpr int KC = SAD_LAYER_KC;                    // k-groups per LDS stage (2 or 4)
+constexpr int KC = 2;                               // k-groups per LDS stage (2 or 4)
 constexpr int STAGE_F4 = KC * 8 * 64;               // float4 per stage: KC x (4 weight + 4 activation fragments) x 64 lanes
 
 __device__ __forceinline__ int job_rows(const LayerJob &jb) { return jb.rowtab ? jb.rowtab[0] : jb.rows; }
@@ -106,13 +103,7 @@ __device__ __forceinline__ Chunk load_chunk_of(const LayerJob &jb, const unsigne
             const int cc = ch < 0 ? 0 : (ch < jb.cpr ? ch : jb.cpr - 1);
             gb[u] = *reinterpret_cast<const float4 *>(xb + (size_t)(xoff + 16u * (unsigned)cc));
         } else {
-#if defined(SAD_LAYER_WHATIF) && SAD_LAYER_WHATIF >= 3      // measurement build (wrong results): no activation loads at all (a fused chain reads them from LDS)
-            gb[u] = make_float4(0.25f, 0.5f, 0.75f, 1.f);
-#elif defined(SAD_LAYER_WHATIF) && SAD_LAYER_WHATIF == 2    // every activation load hits row 0 (cache hits: the issue cost stays, the bytes go)
-            gb[u] = *reinterpret_cast<const float4 *>((xb + (size_t)g * 32) + (size_t)(16u * (unsigned)h));
-#else
             gb[u] = *reinterpret_cast<const float4 *>((xb + (size_t)g * 32) + (size_t)(xoff + 16u * (unsigned)h));
-#endif
         }
     }
     return Chunk{ga[0], ga[1], ga[KC > 2 ? 2 : 0], ga[KC > 2 ? 3 : 0], gb[0], gb[1], gb[KC > 2 ? 2 : 0], gb[KC > 2 ? 3 : 0]};
@@ -219,10 +210,6 @@ __device__ __forceinline__ Prefetched gemm_item(const LayerMulti &lm, const Laye
     store_chunk(nxt, 0, lds);
     if (NC == 1) publish_next();
     __syncthreads();
-#if defined(SAD_LAYER_WHATIF) && SAD_LAYER_WHATIF == 4
-    float4 wnx[2], xnx[2];
-    wnx[0] = wnx[1] = xnx[0] = xnx[1] = make_float4(0.f, 0.f, 0.f, 0.f);
-#endif
 #pragma unroll 1
     for (int c = 0; c < NC; ++c) {
         float4 *cur = lds + (c & 1) * STAGE_F4;
@@ -263,20 +250,11 @@ __device__ __forceinline__ Prefetched gemm_item(const LayerMulti &lm, const Laye
         }
         // one k-group = 2 weight + 2 activation fragments from LDS -> 16 MFMAs; reads run one k-group ahead
         float4 wa[2][2], xa[2][2];
-#if defined(SAD_LAYER_WHATIF) && SAD_LAYER_WHATIF == 4      // measurement build (racy, wrong results): the chunk's first fragments were read BEFORE the barrier (what a three-stage ring would allow)
-        if (c == 0) {
-#endif
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             wa[0][i] = cur[(0 * 8 + 2 * wx + i) * 64 + lane];
             xa[0][i] = cur[(0 * 8 + 4 + 2 * wy + i) * 64 + lane];
         }
-#if defined(SAD_LAYER_WHATIF) && SAD_LAYER_WHATIF == 4
-        } else {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) { wa[0][i] = wnx[i]; xa[0][i] = xnx[i]; }
-        }
-#endif
 #pragma unroll
         for (int u = 0; u < KC; ++u) {
             if (u + 1 < KC) {
@@ -297,16 +275,6 @@ __device__ __forceinline__ Prefetched gemm_item(const LayerMulti &lm, const Laye
         }
         if (c + 1 < NC) store_chunk(nxt, c + 1, lds + ((c + 1) & 1) * STAGE_F4);
         if (c + 2 == NC) publish_next();
-#if defined(SAD_LAYER_WHATIF) && SAD_LAYER_WHATIF == 4
-        {
-            const float4 *nx = lds + ((c + 1) & 1) * STAGE_F4;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                wnx[i] = nx[(0 * 8 + 2 * wx + i) * 64 + lane];
-                xnx[i] = nx[(0 * 8 + 4 + 2 * wy + i) * 64 + lane];
-            }
-        }
-#endif
         __syncthreads();
     }
     if (jb.relu) {
@@ -324,11 +292,7 @@ __device__ __forceinline__ Prefetched gemm_item(const LayerMulti &lm, const Laye
         const int j = lane & 31;
         if constexpr (!LAST) {
             // hidden layer: row-major output, 16 bytes per lane (padded channels are exact zeros)
-#if defined(SAD_LAYER_WHATIF) && SAD_LAYER_WHATIF >= 1      // measurement build: the hidden activations are not stored (one sentinel row keeps the code alive)
-            if (ri.live && ri.q == 0x7FFFFFF0) {
-#else
             if (ri.live) {
-#endif
                 float *yrow = jb.y + (long long)ri.q * jb.ldy + (ob * 4 + 2 * wx) * 32 + 4 * h;
 #pragma unroll
                 for (int oc = 0; oc < 2; ++oc)

@@ -36,31 +36,13 @@ namespace {
 
 #include "reg_common.h"
 
-#ifndef SAD_REG_RING
-#define SAD_REG_RING 4
-#endif
-constexpr int RING = SAD_REG_RING;   // weight fragments in flight per wave
-#ifndef SAD_REG_RING2
-#define SAD_REG_RING2 8
-#endif
+constexpr int RING = 4;          // weight fragments in flight per wave
 // ... and in the last layer, whose tiles end with stores / atomic max merges: vector-memory operations
 // retire in order, so a fragment load issued behind an atomic (in flight ~3000 cycles when every CU
 // issues them) is not usable before it; with 8 k-groups fetched BEFORE the epilogue of the previous
 // tile, the loads that queue behind its atomics are first needed ~4000 cycles later.
-constexpr int RING2 = SAD_REG_RING2;
+constexpr int RING2 = 8;
 constexpr int WAVES = 4;         // waves per workgroup (independent; they only share the bias copy)
-
-
-#ifdef SAD_REG_STAMPS    // measurement build only (tools/probe/reg_stamps.py): s_memtime at the phase boundaries of a tile
-__device__ unsigned long long g_stamps[64 * 64];
-#define SAD_STAMP(i)                                                                                  \
-    do {                                                                                              \
-        if (blockIdx.x < 16 && (threadIdx.x & 63) == 0 && tile < 16 * 1024)                            \
-            g_stamps[((blockIdx.x * 4 + (threadIdx.x >> 6)) & 63) * 64 + (i)] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
-#else
-#define SAD_STAMP(i)
-#endif
 
 // A-fragment array of one layer: fragment k (64 lanes x 16 B) at base[k * 64 + lane], base wave-uniform
 struct Frags {
@@ -123,15 +105,10 @@ __device__ __forceinline__ void reg_tile(const RegChain &c, const int tile, cons
     static_assert(NG2 <= 4 * NO1 && NG1 <= 4 * NO0, "layer widths must chain");
     constexpr bool FULL1 = NG1 == 4 * NO0;          // layer 1 reads every channel of layer 0's padded output
     const int j = lane & 31, h = lane >> 5;
-    SAD_STAMP(0);
-    SAD_STAMP(40 + 2 * (tile / (int)(gridDim.x * WAVES) < 10 ? tile / (int)(gridDim.x * WAVES) : 10));
     const int total = c.rowtab[0];
     int q = tile * 32 + j;
     const bool live = q < total;
     if (!live) q = total - 1;                      // rows past the end repeat the last row and store nothing
-#ifdef SAD_REG_NOGATHER     // measurement build: every tile reads the first 32 rows (hot in L1)
-    q = j;
-#endif
     const int src = c.row_src[q];
     const int gv = c.row_gid[q];
     const int grp = gv & (WHOLE_BIT - 1);
@@ -209,7 +186,6 @@ __device__ __forceinline__ void reg_tile(const RegChain &c, const int tile, cons
         float4 ring[D];
 #pragma unroll
         for (int u = 0; u < D; ++u) ring[u] = item(u);
-        SAD_STAMP(1);
         f32x16 t;
         float bt[16];
         float4 lb[2];                                      // LDS operand ring (IN0_LDS)
@@ -237,9 +213,7 @@ __device__ __forceinline__ void reg_tile(const RegChain &c, const int tile, cons
             }
             ring[g % D] = g + D < TOT ? item(g + D) : f2(g + D - TOT);   // (layer-2 fragment i' = g + D - TOT: slot (R0 + i') % D)
             __builtin_amdgcn_sched_barrier(0);             // keep each refill right behind the MFMAs that freed its slot
-            if (r == 0 && o < 4) SAD_STAMP(2 + 2 * o);
             if (r == NT0 - 1) {
-                SAD_STAMP(3 + 2 * o);
                 t = relu16(t);
 #pragma unroll
                 for (int a = 0; a < 4; ++a) to_operands(t[4 * a], t[4 * a + 1], t[4 * a + 2], t[4 * a + 3], bt + 4 * a);
@@ -251,9 +225,7 @@ __device__ __forceinline__ void reg_tile(const RegChain &c, const int tile, cons
 #pragma unroll
             for (int a = 0; a < 4; ++a) to_operands(u[4 * a], u[4 * a + 1], u[4 * a + 2], u[4 * a + 3], in2 + 16 * o1 + 4 * a);
         }
-        SAD_STAMP(10);
         const PoolMasks pm = pool_masks(key);
-        SAD_STAMP(11);
         // layer 2: a ring of RING2 slots; fragment i of a tile lives in slot i % RING2.  The first RING of
         // tile 0 were fetched by the loop above (into ring[(R0 + i) % RING]), the rest are fetched here.
         constexpr int D2 = NG2 % RING2 == 0 ? RING2 : RING;
@@ -271,14 +243,10 @@ __device__ __forceinline__ void reg_tile(const RegChain &c, const int tile, cons
                 ring2[i % D2] = i + D2 < NG2 ? cur(i + D2) : nxt(i + D2 - NG2);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if (o < 8) SAD_STAMP(12 + 2 * o);
             if (sg.lds) pool_stage<COUT>(relu16(t2), pm, tail, sg, o, h);
             else pool_store(relu16(t2), pm, tail, whole, orow, o, h, c);
-            if (o < 8) SAD_STAMP(13 + 2 * o);
         }
         if (sg.lds) stage_flush<COUT>(sg, grp, whole, lane, c);
-        SAD_STAMP(30);
-        SAD_STAMP(41 + 2 * (tile / (int)(gridDim.x * WAVES) < 10 ? tile / (int)(gridDim.x * WAVES) : 10));
     } else {
         // ---- simple variant (narrow chains: few MFMAs per block, latency is covered by many waves per SIMD) ----
 #pragma unroll 1
@@ -359,10 +327,6 @@ __device__ __forceinline__ void reg_body(const RegMulti &mp) {
     // [families 1, 2: per wave a private image of the layer-0 operands, 9 / 17 k-groups x 64 lanes x 16 B] then
     // per chain the bias blocks of the three layers
     extern __shared__ __attribute__((aligned(16))) float smem[];
-#ifdef SAD_REG_STAMPS
-    if (blockIdx.x < 16 && (threadIdx.x & 63) == 0) g_stamps[((blockIdx.x * 4 + (threadIdx.x >> 6)) & 63) * 64 + 63] = __builtin_amdgcn_s_memtime();
-    if (blockIdx.x == 0 && threadIdx.x == 0) g_stamps[62] = gridDim.x;
-#endif
     constexpr int IN0_F4 = in0_f4(FAMILY);
     float *sbias = smem + WAVES * IN0_F4 * 4;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -464,9 +428,3 @@ int launch_reg(const RegMulti &mp, hipStream_t st) {
 }
 
 }  // namespace sad
-
-#ifdef SAD_REG_STAMPS
-extern "C" __attribute__((visibility("default"))) int sad_debug_read_stamps(unsigned long long *dst) {
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_stamps), sizeof(unsigned long long) * 64 * 64);
-}
-#endif

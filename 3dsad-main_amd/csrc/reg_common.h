@@ -86,9 +86,6 @@ __device__ __forceinline__ PoolMasks pool_masks(int key) {   // key >= 1 for liv
 // read-after-write wait states are covered by the other registers' work (a register-by-register scan is a
 // chain of ten dependent instructions per register: ~4000 cycles per tile instead of ~700).
 __device__ __forceinline__ f32x16 seg_max16(f32x16 t, const PoolMasks &pm) {
-#ifdef SAD_NOSCAN           // measurement build: no pooling arithmetic (wrong results)
-    return t;
-#endif
     unsigned x[16];
 #pragma unroll
     for (int g = 0; g < 16; ++g) {
@@ -121,23 +118,7 @@ __device__ __forceinline__ f32x16 seg_max16(f32x16 t, const PoolMasks &pm) {
 // that continue in another tile; outputs are >= 0 and the buffer starts at zero)
 __device__ __forceinline__ void pool_store(f32x16 t, const PoolMasks &pm, bool tail, bool whole, float *orow, int o, int h,
                                            const RegChain &c) {
-#ifdef SAD_REG_NOPOOL       // measurement build: no pooling, one store per tile keeps the chain alive
-    if (t[0] == 123.f) orow[0] = t[0];
-    return;
-#endif
     t = seg_max16(t, pm);
-#ifdef SAD_REG_NOSTORE      // measurement build: pooling arithmetic only
-    {
-        float s = 0.f;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) s += t[g];
-        if (s == 123.456f) orow[0] = s;
-        return;
-    }
-#endif
-#ifdef SAD_REG_NOATOMIC     // measurement build: plain stores where the product merges with an atomic max (wrong results)
-    whole = true;
-#endif
     if (tail) {
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
@@ -170,20 +151,7 @@ struct Stage {
 
 template <int COUT>
 __device__ __forceinline__ void pool_stage(f32x16 t, const PoolMasks &pm, bool tail, const Stage &sg, int o, int h) {
-#ifdef SAD_REG_NOPOOL       // measurement build (as in pool_store): no pooling, no staging; the comparison keeps the chain alive
-    if (t[0] == 123.f) sg.lds[0] = t[0];
-    return;
-#endif
     t = seg_max16(t, pm);
-#ifdef SAD_REG_NOSTORE      // measurement build (as in pool_store): the pooling arithmetic only, nothing staged or stored
-    {
-        float s = 0.f;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) s += t[g];
-        if (s == 123.456f) sg.lds[0] = s;
-        return;
-    }
-#endif
     if (tail) {
         float *d = sg.lds + sg.slot * COUT + o * 32 + 4 * h;
 #pragma unroll
@@ -194,9 +162,6 @@ __device__ __forceinline__ void pool_stage(f32x16 t, const PoolMasks &pm, bool t
 
 template <int COUT>
 __device__ __forceinline__ void stage_flush(const Stage &sg, int grp, bool whole, int lane, const RegChain &c) {
-#if defined(SAD_REG_NOPOOL) || defined(SAD_REG_NOSTORE)
-    return;
-#endif
     unsigned rem = sg.tails;
     for (int s = 0; s < sg.ngroups; ++s) {                 // wave-uniform loop over the groups that end in this tile
         const int p = __builtin_ctz(rem);

@@ -1,7 +1,7 @@
 """bench.py with every untimed torch.cuda.Event replaced by a HIP event created with hipEventDisableSystemFence (no
 system-scope release when the event is recorded): what the fences of the step's cross-stream events cost.  Measurement only.
-SAD_LIGHT=0 keeps torch's events (control, same wrapper code path); SAD_FAKE2 as in bench_fake_gather2.py selects a gather
-pattern without a collective (unset: bench.py's own gather object).
+SAD_LIGHT=0 keeps torch's events (control, same wrapper code path); SAD_FAKE2 (any value) replaces the gather by
+its stream pattern without a collective (unset: bench.py's own gather object).
 usage: [SAD_BENCH_FORCE_DIST=1] SAD_LIGHT=1 python tools/probe/bench_light_events.py <bench.py arguments>"""
 import ctypes
 import os

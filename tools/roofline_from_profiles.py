@@ -3,7 +3,7 @@
 
     python tools/roofline_from_profiles.py profiles/r02_serial_kernel_trace.csv profiles/r02_bench.json
 
-Inputs (both produced by tools/profile_r02.sh and committed under profiles/):
+Inputs (both committed under profiles/; profiles/README.md says how each round produced them):
   * a kernel trace (rocprofv3 --kernel-trace, trimmed to name / start / end / grid by the script) of
     `bench.py --main-streams 1 --no-overlap --geometry-file ...`: ONE stream, nothing overlapped, no autotune
     launches, so every kernel interval is a kernel duration and the trace holds only steady-state steps;

@@ -31,6 +31,7 @@ _LAZY = {
     "AnchorHeadLoss": "dense_head", "CenterHeadLoss": "dense_head",
     "roi_targets": "ops", "roi_targets_workspace": "ops", "roi_decode": "ops", "ProposalTargetLayer": "roi_head",
     "roi_head_loss": "ops", "RoIHeadLoss": "roi_head",
+    "rotated_iou_loss": "ops", "boxes_iou_aligned": "ops", "RotatedIoULoss": "iou_loss", "RoIIoULoss": "roi_head",
     "point_targets": "ops", "point_head_loss": "ops", "point_head_loss_workspace": "ops",
     "PointTargetAssigner": "point_head", "PointHeadLoss": "point_head",
     "roi_grid_points": "ops", "voxel_query": "ops", "voxel_query_workspace": "ops", "VoxelRoIPool": "voxel_roi_pool",

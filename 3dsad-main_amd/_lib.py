@@ -225,6 +225,22 @@ class PointHeadLossArgs(ctypes.Structure):
     ]
 
 
+IOU_MODES = {"bev": 0, "3d": 1}               # SAD_IOU_BEV, SAD_IOU_3D
+IOU_LOSS_KINDS = {"iou": 0, "diou": 1}        # SAD_IOU_LOSS_*
+IOU_CODES = {"box": 0, "roi": 1}              # SAD_IOU_CODE_*
+
+
+class RotatedIouLossArgs(ctypes.Structure):
+    """``struct sad_rotated_iou_loss_args`` (include/sad_amd.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("pred", vp), ("target", vp), ("weight", vp), ("rois", vp),
+        ("N", ctypes.c_int), ("Dp", ctypes.c_int), ("Dt", ctypes.c_int), ("Dr", ctypes.c_int),
+        ("mode", ctypes.c_int), ("kind", ctypes.c_int), ("code", ctypes.c_int), ("need_grad", ctypes.c_int),
+        ("loss", vp), ("iou", vp), ("grad", vp), ("decoded", vp),
+    ]
+
+
 GRAD_FEAT, GRAD_XYZ, GRAD_NEW_XYZ, GRAD_PARAMS = 1, 2, 4, 8      # SAD_GRAD_*
 
 
@@ -367,6 +383,7 @@ SIGNATURES = {
     "sad_mlp_grad_workspace_bytes": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_size_t),
                                                                           ctypes.POINTER(ctypes.c_size_t)]),
     "sad_mlp_grad_f32": (ctypes.c_int, [ctypes.POINTER(MlpGradArgs), vp]),
+    "sad_rotated_iou_loss_f32": (ctypes.c_int, [ctypes.POINTER(RotatedIouLossArgs), vp]),
 }
 
 _lib = None

@@ -354,6 +354,28 @@ class PointHeadLoss(_HeadLoss):
     table = ((0, ((None, 0), (7, 1))), (1, ((3, 2), (3, 3))))
 
 
+class RotatedIoULoss(torch.autograd.Function):
+    """``apply(pred [...,Dp], target [...,Dt], weight [...] | None, rois [...,D] | None, cfg) -> (loss [...], iou [...])``
+    (SPEC.md §34), differentiable in ``pred``; ``cfg`` = the operator's ``mode`` / ``kind`` / ``code``.  The forward runs
+    ``ops.rotated_iou_loss`` and saves its ``grad``; the backward returns ``grad · g[..., None]`` (torch multiplies; zero in the
+    columns of ``pred`` beyond the seventh) and ``None`` for target, weight and rois.  ``iou`` is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, pred, target, weight, rois, cfg):
+        loss, iou, grad = ops.rotated_iou_loss(pred, target, weight, rois=rois, need_grad=True, **cfg)
+        ctx.save_for_backward(grad)
+        ctx.mark_non_differentiable(iou)
+        ctx.extra = pred.shape[-1] - 7
+        return loss, iou
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss, _grad_iou):
+        (grad,) = ctx.saved_tensors
+        g = grad * grad_loss[..., None]
+        return (torch.nn.functional.pad(g, (0, ctx.extra)) if ctx.extra else g), None, None, None, None
+
+
 def _layers_of(params):
     """(W_1 .. W_L, b_1 .. b_L) -> [(W_l, b_l)]."""
     L = len(params) // 2

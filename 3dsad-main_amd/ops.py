@@ -1813,6 +1813,79 @@ def roi_head_loss(rcnn_cls: torch.Tensor, rcnn_reg: torch.Tensor, cls_target: to
     return outs
 
 
+def rotated_iou_loss_output_spec(lead: tuple, need_grad: bool, decoded: bool) -> tuple:
+    """((name, shape, dtype), ...) of ``rotated_iou_loss``' outputs for pairs of leading shape ``lead``, what its ``out=`` tuple
+    is checked against."""
+    f32, lead = torch.float32, tuple(lead)
+    spec = [("loss", lead, f32), ("iou", lead, f32)]
+    if need_grad:
+        spec.append(("grad", lead + (7,), f32))
+    if decoded:
+        spec.append(("decoded", lead + (7,), f32))
+    return tuple(spec)
+
+
+def _box_rows(t: torch.Tensor, name: str, lead: Optional[tuple] = None) -> torch.Tensor:
+    """Box rows [..., D >= 7] of the strict policy (at least one leading axis; ``lead``: the leading shape they must have)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: expected a torch.Tensor")
+    want = "[..., D] with D >= 7 and at least one leading axis" if lead is None else f"[..., D] with leading shape {tuple(lead)} and D >= 7"
+    shape = (None,) * max(t.dim(), 2) if lead is None else tuple(lead) + (None,)
+    _strict(t, name, torch.float32, shape, want)
+    if t.shape[-1] < 7 or t.numel() == 0:
+        raise ValueError(f"{name}: expected {want}, got {tuple(t.shape)}")
+    return t
+
+
+def rotated_iou_loss(pred: torch.Tensor, target: torch.Tensor, weight: Optional[torch.Tensor] = None, *, mode: str = "3d",
+                     kind: str = "iou", code: str = "box", rois: Optional[torch.Tensor] = None, need_grad: bool = True,
+                     decoded: bool = False, out: Optional[tuple] = None) -> tuple:
+    """Rotated IoU loss of aligned pairs with its analytic gradient (SPEC.md §34).  pred [...,Dp], target [...,Dt] f32 box rows
+    (D >= 7, seven columns read) of one leading shape, weight [...] f32 or None -> (loss [...], iou [...] [, grad [...,7]]
+    [, decoded [...,7]]).  ``iou`` is the rotated IoU of the pair (``mode`` "bev" or "3d"), bit-equal to the diagonal of
+    ``boxes_iou_bev`` / ``boxes_iou3d``; ``loss = weight * (1 - iou)``, ``kind="diou"`` adds the squared centre distance over the
+    squared diagonal of the box aligned with the target's axes around both boxes; ``grad`` is d loss / d pred, the target is a
+    constant.  A row of weight 0 gives loss = grad = 0 whatever its boxes hold.  ``code="roi"``: pred is a RoI head's
+    ``rcnn_reg``, target ``roi_targets``' ``gt_local`` and ``rois`` [...,D] (``rois_s``) is required; the box is decoded in the
+    RoI's frame, ``grad`` is with respect to the residuals and ``decoded=True`` returns the box.  One launch, no workspace, no
+    synchronisation, bit-identical from call to call.  ``out``: the tuple to write into."""
+    _box_rows(pred, "pred")
+    lead = tuple(pred.shape[:-1])
+    if pred.numel() // pred.shape[-1] >= 2 ** 31:
+        raise ValueError(f"pred: {pred.numel() // pred.shape[-1]} pairs (fewer than 2^31 supported)")
+    _box_rows(target, "target", lead)
+    if weight is not None:
+        _strict(weight, "weight", torch.float32, lead)
+    for name, v, table in (("mode", mode, _lib.IOU_MODES), ("kind", kind, _lib.IOU_LOSS_KINDS), ("code", code, _lib.IOU_CODES)):
+        if v not in table:
+            raise ValueError(f"{name}: expected one of {sorted(table)}, got {v!r}")
+    if (rois is not None) != (code == "roi"):
+        raise ValueError('rois must be given with code="roi" and only then')
+    if decoded and code != "roi":
+        raise ValueError('decoded: the decoded box is an output of code="roi" only')
+    if rois is not None:
+        _box_rows(rois, "rois", lead)
+    dev = _head_devices((("pred", pred), ("target", target), ("weight", weight), ("rois", rois)))
+    outs = _outputs(rotated_iou_loss_output_spec(lead, bool(need_grad), bool(decoded)), out, dev, "pred")
+    a = _lib.RotatedIouLossArgs()
+    a.struct_size = ctypes.sizeof(_lib.RotatedIouLossArgs)
+    a.pred, a.target, a.weight, a.rois = pred.data_ptr(), target.data_ptr(), _ptr(weight), _ptr(rois)
+    a.N, a.Dp, a.Dt, a.Dr = pred.numel() // pred.shape[-1], pred.shape[-1], target.shape[-1], rois.shape[-1] if rois is not None else 0
+    a.mode, a.kind, a.code, a.need_grad = _lib.IOU_MODES[mode], _lib.IOU_LOSS_KINDS[kind], _lib.IOU_CODES[code], int(bool(need_grad))
+    a.loss, a.iou = outs[0].data_ptr(), outs[1].data_ptr()
+    a.grad = outs[2].data_ptr() if need_grad else None
+    a.decoded = outs[-1].data_ptr() if decoded else None
+    with _timed("rotated_iou_loss", f"{mode}{kind}N{a.N}"):
+        check(lib().sad_rotated_iou_loss_f32(ctypes.byref(a), _stream()), "sad_rotated_iou_loss_f32")
+    return outs
+
+
+def boxes_iou_aligned(a: torch.Tensor, b: torch.Tensor, mode: str = "3d") -> torch.Tensor:
+    """Rotated IoU of the aligned pairs (a_i, b_i) (SPEC.md §34): a [...,Da], b [...,Db] -> iou [...], the diagonal of
+    ``boxes_iou_bev`` / ``boxes_iou3d`` without the matrix.  ``rotated_iou_loss``' launch with ``need_grad=False``."""
+    return rotated_iou_loss(a, b, mode=mode, need_grad=False)[1]
+
+
 POINT_OUTPUTS = ("labels", "match", "centerness", "shift_target", "size_target", "reg_target")
 
 

@@ -2,7 +2,8 @@
 trains on, their matched ground truth in the RoI's frame with the residual code, the decode of that code at inference, and
 the loss on those targets.  ``ProposalTargetLayer`` holds the sampling configuration only and has no parameters; the pooling
 and the head's layers are the caller's.  No gradients pass through it: its outputs are targets.  ``RoIHeadLoss`` is the loss
-of the head's two predictions against them, differentiable in the predictions."""
+of the head's two predictions against them, differentiable in the predictions; ``RoIIoULoss`` (SPEC.md §34) is the rotated
+IoU / DIoU loss of the box residuals against the same targets."""
 from collections import namedtuple
 from typing import Optional
 
@@ -59,6 +60,10 @@ class ProposalTargetLayer(nn.Module):
         """The loss module on this layer's targets: ``RoIHeadLoss(**cfg)``."""
         return RoIHeadLoss(**cfg)
 
+    def iou_loss(self, **cfg) -> "RoIIoULoss":
+        """The rotated IoU loss on this layer's targets: ``RoIIoULoss(**cfg)``."""
+        return RoIIoULoss(**cfg)
+
 
 class RoIHeadLoss(nn.Module):
     """Losses of a RoI head (``ops.roi_head_loss``, SPEC.md §29): the configuration only, no parameters.  ``cls_weight``,
@@ -87,3 +92,29 @@ class RoIHeadLoss(nn.Module):
         loss, self.num = _Fn.apply(rcnn_cls.view(B, S), rcnn_reg.view(B, S, 7), targets.cls_target, targets.reg_valid,
                                    targets.reg_target, rois, gt_local, self.cfg)
         return loss
+
+
+class RoIIoULoss(nn.Module):
+    """Rotated IoU loss of a RoI head's box residuals (``ops.rotated_iou_loss`` with ``code="roi"``, SPEC.md §34): the
+    configuration only, no parameters.  ``forward(rcnn_reg, targets) -> loss [B]``: ``1 - IoU`` (``kind="diou"``: plus the
+    centre-distance term) of the box decoded in the RoI's frame against ``targets.gt_local``, over the rows with
+    ``reg_valid != 0``, summed per scene and divided by ``max(n_reg, 1)`` (``normalize=False``: not divided), differentiable in
+    ``rcnn_reg``, which may come as [B,S,7] or [B*S,7]: a contiguous view, never copied.  ``targets`` is the ``RoiTargets`` of
+    ``ProposalTargetLayer``, read where it is.  The module keeps the call's detached ``iou`` [B,S] (of every row, valid or
+    not) as its attribute ``iou`` until the next call: the target of an IoU-prediction branch."""
+
+    def __init__(self, mode: str = "3d", kind: str = "iou", normalize: bool = True):
+        super().__init__()
+        self.cfg = dict(mode=mode, kind=kind, code="roi")
+        self.normalize = bool(normalize)
+        self.iou = None
+
+    def forward(self, rcnn_reg: torch.Tensor, targets: RoiTargets) -> torch.Tensor:
+        from .autograd import RotatedIoULoss as _Fn
+        B, S = targets.reg_valid.shape
+        if rcnn_reg.numel() != B * S * 7 or rcnn_reg.shape[-1] != 7 or not rcnn_reg.is_contiguous():
+            raise ValueError(f"rcnn_reg: expected contiguous predictions for {B} x {S} RoIs ([B,S,7] or [B*S,7]), got {tuple(rcnn_reg.shape)}")
+        valid = targets.reg_valid != 0
+        loss, self.iou = _Fn.apply(rcnn_reg.view(B, S, 7), targets.gt_local, valid.to(torch.float32), targets.rois_s, self.cfg)
+        loss = loss.sum(1)
+        return loss / valid.sum(1).clamp(min=1).to(torch.float32) if self.normalize else loss

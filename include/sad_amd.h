@@ -987,6 +987,39 @@ int sad_mlp_grad_workspace_bytes(int B, int M, int S, int grouped, int has_cnt, 
                                  size_t *full_bytes);
 int sad_mlp_grad_f32(const sad_mlp_grad_args *args, sad_stream_t stream);
 
+/* SPEC.md §34 (additions of ABI 4 as well).  Rotated IoU losses of ALIGNED pairs, pred[i] against target[i], with the analytic
+ * gradient with respect to pred.  pred[N,Dp], target[N,Dt]: box rows of D >= 7 floats as in §19 (seven columns are read, row
+ * stride D); weight[N] or NULL.  iou[N] = §19.3's IoU of the pair (mode SAD_IOU_BEV / SAD_IOU_3D), equal to the diagonal entry
+ * of sad_boxes_iou_f32 bit for bit.  loss[N] = weight * (1 - iou), kind SAD_IOU_LOSS_DIOU adds rho^2 / c^2 (the squared centre
+ * distance over the squared diagonal of the box aligned with the TARGET's axes around both footprints; with z and the height
+ * intervals in mode 3-D).  grad[N,7] = d loss / d pred (given iff need_grad != 0); the target is a constant.  A row with
+ * weight == 0 gives loss = grad = +0 whatever its boxes hold, iou as computed.
+ * code SAD_IOU_CODE_ROI: pred is a RoI head's residual rcnn_reg, target is §28.1's gt_local, rois[N,Dr] (columns 3..5 are read)
+ * is required; the box is decoded in the RoI's frame as §29's corner loss decodes it, grad is with respect to the residuals and
+ * decoded[N,7] (or NULL) receives the box.  With SAD_IOU_CODE_BOX rois and decoded are NULL.
+ * One launch, one lane per pair, no workspace, no memset, no atomics; outputs are fully written; nothing is read back, nothing
+ * synchronises; two calls are bit-equal.  |yaw| >= 1e4 and a non-finite box in a row of non-zero weight are undefined behaviour.
+ * A NULL required pointer, a wrong struct_size, N < 1, D < 7, another mode, kind or code, rois given or missing against code,
+ * decoded with SAD_IOU_CODE_BOX, grad given or missing against need_grad: SAD_EINVAL. */
+#define SAD_IOU_LOSS_IOU 0
+#define SAD_IOU_LOSS_DIOU 1
+#define SAD_IOU_CODE_BOX 0
+#define SAD_IOU_CODE_ROI 1
+typedef struct sad_rotated_iou_loss_args {
+    size_t struct_size;   /* = sizeof(sad_rotated_iou_loss_args) */
+    const float *pred;             /* [N,Dp] */
+    const float *target;           /* [N,Dt] */
+    const float *weight;           /* [N] or NULL */
+    const float *rois;             /* [N,Dr] or NULL */
+    int N, Dp, Dt, Dr;
+    int mode, kind, code, need_grad;
+    float *loss;          /* [N] */
+    float *iou;           /* [N] */
+    float *grad;          /* [N,7] or NULL */
+    float *decoded;       /* [N,7] or NULL */
+} sad_rotated_iou_loss_args;
+int sad_rotated_iou_loss_f32(const sad_rotated_iou_loss_args *args, sad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,8 @@ _LAZY = {
     "SAModuleMSG": "sa_module", "SAModule": "sa_module", "sa_module": "sa_module", "SAModuleMSGTrain": "sa_module",
     "SharedMLP": "shared_mlp", "BranchGroup": "shared_mlp", "grouped_mlp_grad": "mlp", "mlp_rows_grad": "mlp",
     "candidates": "ops", "candidates_grad": "ops", "prefix_rows_grad": "ops", "SADDetectorTrain": "detector_train",
+    "global_augment": "ops", "gt_paste": "ops", "gt_paste_workspace": "ops", "gt_paste_rows": "ops",
+    "GTDatabase": "augment", "GTSampler": "augment", "GlobalAugment": "augment", "TrainAugment": "augment",
     "SADDetector": "detector", "IngestPipeline": "pipeline",
     "shard_range": "dist", "all_gather_boxes": "dist", "run_sharded": "dist",
 }

@@ -241,6 +241,39 @@ class RotatedIouLossArgs(ctypes.Structure):
     ]
 
 
+class GlobalAugmentArgs(ctypes.Structure):
+    """``struct sad_global_augment_args`` (include/sad_amd.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("points", vp), ("offsets", vp), ("gt_boxes", vp),
+        ("B", ctypes.c_int), ("N", ctypes.c_int), ("total", ctypes.c_int), ("Cp", ctypes.c_int), ("G", ctypes.c_int), ("D", ctypes.c_int),
+        ("seed", ctypes.c_uint),
+        ("flip_x", ctypes.c_int), ("flip_y", ctypes.c_int), ("with_velocity", ctypes.c_int),
+        ("rot_lo", ctypes.c_float), ("rot_hi", ctypes.c_float), ("scale_lo", ctypes.c_float), ("scale_hi", ctypes.c_float),
+        ("translate", ctypes.c_float * 3),
+        ("points_out", vp), ("boxes_out", vp), ("params", vp),
+    ]
+
+
+PASTE_MAX_CLASSES = 16                         # SAD_PASTE_MAX_CLASSES
+
+
+class GtPasteArgs(ctypes.Structure):
+    """``struct sad_gt_paste_args`` (include/sad_amd.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("points", vp), ("offsets", vp), ("gt_boxes", vp), ("gt_labels", vp),
+        ("db_points", vp), ("db_offsets", vp), ("db_boxes", vp), ("params", vp),
+        ("B", ctypes.c_int), ("total", ctypes.c_int), ("Cp", ctypes.c_int), ("G", ctypes.c_int), ("D", ctypes.c_int), ("C", ctypes.c_int),
+        ("Ndb", ctypes.c_int), ("max_obj_points", ctypes.c_int), ("with_velocity", ctypes.c_int),
+        ("class_offsets", ctypes.c_int * (PASTE_MAX_CLASSES + 1)), ("sample_num", ctypes.c_int * PASTE_MAX_CLASSES),
+        ("seed", ctypes.c_uint), ("remove_extra_width", ctypes.c_float),
+        ("R", ctypes.c_longlong),
+        ("keep", vp), ("db_index", vp), ("boxes_out", vp), ("labels_out", vp), ("num_pasted", vp), ("out_points", vp),
+        ("out_offsets", vp), ("workspace", vp),
+    ]
+
+
 GRAD_FEAT, GRAD_XYZ, GRAD_NEW_XYZ, GRAD_PARAMS = 1, 2, 4, 8      # SAD_GRAD_*
 
 
@@ -384,6 +417,9 @@ SIGNATURES = {
                                                                           ctypes.POINTER(ctypes.c_size_t)]),
     "sad_mlp_grad_f32": (ctypes.c_int, [ctypes.POINTER(MlpGradArgs), vp]),
     "sad_rotated_iou_loss_f32": (ctypes.c_int, [ctypes.POINTER(RotatedIouLossArgs), vp]),
+    "sad_global_augment_f32": (ctypes.c_int, [ctypes.POINTER(GlobalAugmentArgs), vp]),
+    "sad_gt_paste_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
+    "sad_gt_paste_f32": (ctypes.c_int, [ctypes.POINTER(GtPasteArgs), vp]),
 }
 
 _lib = None

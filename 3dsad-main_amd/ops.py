@@ -1389,8 +1389,8 @@ def center_decode(hm: torch.Tensor, reg: torch.Tensor, height: torch.Tensor, dim
     return boxes, scores, labels
 
 
-def _gt_inputs(gt_boxes: torch.Tensor, gt_labels: torch.Tensor, min_d: int = 7) -> Tuple[int, int, int, torch.device]:
-    """(B, G, D, device) of gt_boxes [B,G,D] f32 / gt_labels [B,G] int32, both contiguous on the current GPU."""
+def _gt_shapes(gt_boxes: torch.Tensor, gt_labels: torch.Tensor, min_d: int = 7) -> Tuple[int, int, int]:
+    """(B, G, D) of gt_boxes [B,G,D] f32 / gt_labels [B,G] int32, both contiguous; judged before any device."""
     for t, name, dt in ((gt_boxes, "gt_boxes", torch.float32), (gt_labels, "gt_labels", torch.int32)):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{name}: expected a torch.Tensor")
@@ -1405,6 +1405,12 @@ def _gt_inputs(gt_boxes: torch.Tensor, gt_labels: torch.Tensor, min_d: int = 7) 
         raise ValueError(f"gt_boxes: at most 1024 boxes per scene (got G = {G})")
     if not gt_boxes.is_contiguous() or not gt_labels.is_contiguous():
         raise ValueError("gt_boxes / gt_labels: must be contiguous")
+    return B, G, D
+
+
+def _gt_inputs(gt_boxes: torch.Tensor, gt_labels: torch.Tensor, min_d: int = 7) -> Tuple[int, int, int, torch.device]:
+    """(B, G, D, device) of gt_boxes [B,G,D] f32 / gt_labels [B,G] int32, both contiguous on the current GPU."""
+    B, G, D = _gt_shapes(gt_boxes, gt_labels, min_d)
     return B, G, D, _head_devices((("gt_boxes", gt_boxes), ("gt_labels", gt_labels)))
 
 
@@ -2189,6 +2195,179 @@ def voxel_query(coors: torch.Tensor, offsets: torch.Tensor, spatial_shape, voxel
     with _timed("voxel_query", f"n{Nv}m{B * M}s{S}"):
         check(lib().sad_voxel_query_f32(ctypes.byref(a), _stream()), "sad_voxel_query_f32")
     return idx, cnt
+
+
+PASTE_MAX_SLOTS = 512          # Q of SPEC.md §35.2
+
+
+def augment_seed(seed: int, step: int) -> int:
+    """The seed of call number ``step`` (SPEC.md §35): §17's hash of (seed, step), as ``ProposalTargetLayer.call_seed``."""
+    from . import io as _io
+    return int(_io._h(int(seed), int(step), 0))
+
+
+def _range2(v, name: str) -> Tuple[float, float]:
+    lo, hi = (v if isinstance(v, (tuple, list)) else (-v, v))
+    lo, hi = _f32(lo), _f32(hi)
+    if not lo <= hi:
+        raise ValueError(f"{name}: expected (lo, hi) with lo <= hi, got {v!r}")
+    return lo, hi
+
+
+def _aug_points(points: torch.Tensor, offsets: Optional[torch.Tensor]):
+    """Ragged ``points [total,Cp]`` + ``offsets [B+1]`` int32, or padded ``points [B,N,Cp]`` with ``offsets=None`` ->
+    (shape, B, N, total, Cp): contiguous f32, judged before any device."""
+    if offsets is None:
+        _strict(points, "points", torch.float32, (None, None, None), "[B,N,Cp] (or [total,Cp] with offsets)")
+        B, N, Cp = points.shape
+        total = B * N
+    else:
+        _strict(points, "points", torch.float32, (None, None), "[total,Cp] with offsets")
+        _strict(offsets, "offsets", torch.int32, (None,), "[B+1]")
+        (total, Cp), B, N = points.shape, offsets.shape[0] - 1, 0
+    if B < 1 or Cp < 3:
+        raise ValueError(f"points: expected at least one scene and Cp >= 3 columns, got {tuple(points.shape)}")
+    if total * Cp >= 1 << 31:
+        raise ValueError("points: too many rows")
+    return tuple(points.shape), B, N, total, Cp
+
+
+def global_augment_output_spec(points_shape: tuple, B: int, G: int, D: int) -> tuple:
+    """((name, shape, dtype), ...) of ``global_augment``'s outputs, what its ``out=`` tuple is checked against."""
+    f32 = torch.float32
+    return (("points_out", tuple(points_shape), f32), ("boxes_out", (B, G, D), f32), ("params", (B, 8), f32))
+
+
+def global_augment(points: torch.Tensor, offsets: Optional[torch.Tensor], gt_boxes: torch.Tensor, *, seed: int = 0, step: int = 0,
+                   flip_x: bool = True, flip_y: bool = False, rot_range=(-0.78539816, 0.78539816), scale_range=(0.95, 1.05),
+                   translate_range=(0.0, 0.0, 0.0), with_velocity: bool = False, out: Optional[tuple] = None) -> tuple:
+    """One random flip / rotation / scale / translation per scene, on points and boxes (SPEC.md §35.1).  points [total,Cp] +
+    offsets [B+1] int32, or points [B,N,Cp] with ``offsets=None``; gt_boxes [B,G,D>=7] ->
+    (points_out, boxes_out [B,G,D], params [B,8] = (flips, theta, cos, sin, scale, tx, ty, tz)).  The draws are §17's hash of
+    (seed mixed with step, scene); ``flip_x`` / ``flip_y`` allow the flip, which one hash bit decides.  Order: flip about x
+    (y = -y), flip about y, rotate, scale, translate; ``with_velocity`` (D >= 9) carries columns 7, 8 as a vector.  Every other
+    column is a bit copy; every box row is transformed, padding included.  One launch, no synchronisation."""
+    shape, B, N, total, Cp = _aug_points(points, offsets)
+    _strict(gt_boxes, "gt_boxes", torch.float32, (B, None, None), f"[{B},G,D] with D >= 7")
+    G, D = gt_boxes.shape[1:]
+    if D < 7:
+        raise ValueError(f"gt_boxes: box rows need at least 7 fields, got {D}")
+    if G > 1024:
+        raise ValueError(f"gt_boxes: at most 1024 boxes per scene (got G = {G})")
+    if with_velocity and D < 9:
+        raise ValueError(f"with_velocity: needs box rows of D >= 9 columns (got {D})")
+    rot, sc = _range2(rot_range, "rot_range"), _range2(scale_range, "scale_range")
+    tr = [_f32(v) for v in translate_range]
+    if len(tr) != 3 or min(tr) < 0.0:
+        raise ValueError(f"translate_range: expected three values >= 0, got {translate_range!r}")
+    if not sc[0] > 0.0:
+        raise ValueError(f"scale_range: expected 0 < lo <= hi, got {scale_range!r}")
+    if max(abs(rot[0]), abs(rot[1])) >= 1e4:
+        raise ValueError("rot_range: |angle| must be below 1e4")
+    dev = _head_devices((("points", points), ("offsets", offsets), ("gt_boxes", gt_boxes)))
+    outs = _outputs(global_augment_output_spec(shape, B, G, D), out, dev, "points")
+    a = _lib.GlobalAugmentArgs()
+    a.struct_size = ctypes.sizeof(_lib.GlobalAugmentArgs)
+    a.points, a.offsets, a.gt_boxes = points.data_ptr(), _ptr(offsets), gt_boxes.data_ptr() if G else None
+    a.B, a.N, a.total, a.Cp, a.G, a.D = B, N, total, Cp, G, D
+    a.seed = augment_seed(seed, step)
+    a.flip_x, a.flip_y, a.with_velocity = int(bool(flip_x)), int(bool(flip_y)), int(bool(with_velocity))
+    a.rot_lo, a.rot_hi, a.scale_lo, a.scale_hi = rot[0], rot[1], sc[0], sc[1]
+    a.translate[:] = tr
+    a.points_out, a.boxes_out, a.params = outs[0].data_ptr(), outs[1].data_ptr() if G else None, outs[2].data_ptr()
+    with _timed("global_augment", f"n{total}G{G}"):
+        check(lib().sad_global_augment_f32(ctypes.byref(a), _stream()), "sad_global_augment_f32")
+    return outs
+
+
+PASTE_OUTPUTS = ("keep", "db_index", "boxes_out", "labels_out", "num_pasted", "out_points", "out_offsets")
+
+
+def gt_paste_rows(total: int, B: int, Q: int, max_obj_points: int) -> int:
+    """The least row count of ``gt_paste``'s ``out_points``: total + B * Q * max_obj_points (SPEC.md §35.2)."""
+    return int(total) + int(B) * int(Q) * int(max_obj_points)
+
+
+def gt_paste_output_spec(B: int, G: int, D: int, Q: int, Cp: int, R: int) -> tuple:
+    """((name, shape, dtype), ...) of ``gt_paste``'s outputs, what its ``out=`` tuple is checked against."""
+    i32, f32 = torch.int32, torch.float32
+    return (("keep", (B, Q), i32), ("db_index", (B, Q), i32), ("boxes_out", (B, G + Q, D), f32), ("labels_out", (B, G + Q), i32),
+            ("num_pasted", (B,), i32), ("out_points", (R, Cp), f32), ("out_offsets", (B + 1,), i32))
+
+
+def gt_paste_workspace(B: int, Q: int, total: int, device) -> torch.Tensor:
+    """The workspace of ``gt_paste(..., workspace=...)`` for a caller that keeps it."""
+    nbytes = lib().sad_gt_paste_workspace_bytes(int(B), int(Q), int(total))
+    if not nbytes:
+        raise ValueError(f"gt_paste_workspace: need 1 <= B <= 65535, 1 <= Q <= {PASTE_MAX_SLOTS} and total >= 0 (got {B}, {Q}, {total})")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def gt_paste(points: torch.Tensor, offsets: torch.Tensor, gt_boxes: torch.Tensor, gt_labels: torch.Tensor, db_points: torch.Tensor,
+             db_offsets: torch.Tensor, db_boxes: torch.Tensor, class_offsets: Sequence[int], *, sample_num: Sequence[int],
+             max_obj_points: int, seed: int = 0, step: int = 0, remove_extra_width: float = 0.0, params: Optional[torch.Tensor] = None,
+             with_velocity: bool = False, out: Optional[tuple] = None, workspace: Optional[torch.Tensor] = None) -> tuple:
+    """Ground-truth database sampling (SPEC.md §35.2).  points [total,Cp] + offsets [B+1] int32, padded gt_boxes [B,G,D] /
+    gt_labels [B,G] int32; the database on the device: db_points [.,Cp], db_offsets [Ndb+1] int32, db_boxes [Ndb,D], entries
+    sorted by class with the host list ``class_offsets`` [C+1]; ``sample_num`` [C] = the "fill up to" count per class, Q = its sum
+    (<= 512).  -> (keep [B,Q], db_index [B,Q], boxes_out [B,G+Q,D], labels_out [B,G+Q], num_pasted [B], out_points [R,Cp],
+    out_offsets [B+1]): accepted greedily in slot order where the candidate overlaps no valid ground-truth box and no accepted
+    earlier slot in bird's-eye view; the scene points inside an accepted box (enlarged by ``remove_extra_width``) are dropped,
+    the objects' points come first, then the survivors in file order.  ``out_points`` has R >= total + B*Q*max_obj_points rows,
+    those at or beyond out_offsets[B] are not written.  ``params`` [B,8] (from ``global_augment``): that transform is applied
+    as the rows are stored.  Four launches, no synchronisation, bit-identical from call to call."""
+    _, B, _, total, Cp = _aug_points(points, offsets)
+    if isinstance(gt_boxes, torch.Tensor) and gt_boxes.dim() == 3 and gt_boxes.shape[0] != B:
+        raise ValueError(f"gt_boxes: expected {B} scenes like offsets, got {gt_boxes.shape[0]}")
+    _, G, D = _gt_shapes(gt_boxes, gt_labels)
+    class_offsets, sample_num = [int(v) for v in class_offsets], [int(v) for v in sample_num]
+    C = len(sample_num)
+    if not 1 <= C <= _lib.PASTE_MAX_CLASSES or len(class_offsets) != C + 1:
+        raise ValueError(f"sample_num / class_offsets: expected C and C + 1 entries with 1 <= C <= {_lib.PASTE_MAX_CLASSES}")
+    if min(sample_num) < 0 or sum(sample_num) < 1:
+        raise ValueError(f"sample_num: expected counts >= 0 with a sum >= 1, got {sample_num}")
+    Q = sum(sample_num)
+    if Q > PASTE_MAX_SLOTS:
+        raise ValueError(f"sample_num: Q = {Q} candidate slots per scene, at most {PASTE_MAX_SLOTS} are supported")
+    _strict(db_points, "db_points", torch.float32, (None, Cp), f"[.,{Cp}]: the database must have the scene's {Cp} point columns")
+    _strict(db_boxes, "db_boxes", torch.float32, (None, D), f"[Ndb,{D}]: the database must have the ground truth's {D} box columns")
+    Ndb = db_boxes.shape[0]
+    _strict(db_offsets, "db_offsets", torch.int32, (Ndb + 1,))
+    if Ndb < 1 or class_offsets[0] != 0 or class_offsets[-1] != Ndb or any(a > b for a, b in zip(class_offsets, class_offsets[1:])):
+        raise ValueError(f"class_offsets: expected an ascending list from 0 to Ndb = {Ndb}, got {class_offsets}")
+    if with_velocity and D < 9:
+        raise ValueError(f"with_velocity: needs box rows of D >= 9 columns (got {D})")
+    if params is not None:
+        _strict(params, "params", torch.float32, (B, 8))
+    Pmax, e = int(max_obj_points), _f32(remove_extra_width)
+    if Pmax < 0 or not e >= 0.0:
+        raise ValueError("max_obj_points and remove_extra_width must be >= 0")
+    need = gt_paste_rows(total, B, Q, Pmax)
+    R = need
+    if out is not None and len(out) == len(PASTE_OUTPUTS) and isinstance(out[5], torch.Tensor) and out[5].dim() == 2:
+        R = out[5].shape[0]
+        if R < need:
+            raise ValueError(f"out_points: {R} rows, needs total + B*Q*max_obj_points = {need}")
+    if need * Cp >= 1 << 31:
+        raise ValueError("out_points: too many rows")
+    dev = _head_devices((("points", points), ("offsets", offsets), ("gt_boxes", gt_boxes), ("gt_labels", gt_labels), ("db_points", db_points),
+                         ("db_offsets", db_offsets), ("db_boxes", db_boxes), ("params", params)))
+    outs = _outputs(gt_paste_output_spec(B, G, D, Q, Cp, R), out, dev, "points")
+    workspace = _workspace(lib().sad_gt_paste_workspace_bytes(B, Q, total), workspace, dev, "ops.gt_paste_workspace", 16)
+    a = _lib.GtPasteArgs()
+    a.struct_size = ctypes.sizeof(_lib.GtPasteArgs)
+    a.points, a.offsets = points.data_ptr(), offsets.data_ptr()
+    a.gt_boxes, a.gt_labels = (gt_boxes.data_ptr(), gt_labels.data_ptr()) if G else (None, None)
+    a.db_points, a.db_offsets, a.db_boxes, a.params = db_points.data_ptr(), db_offsets.data_ptr(), db_boxes.data_ptr(), _ptr(params)
+    a.B, a.total, a.Cp, a.G, a.D, a.C, a.Ndb, a.max_obj_points, a.with_velocity = B, total, Cp, G, D, C, Ndb, Pmax, int(bool(with_velocity))
+    a.class_offsets[:C + 1], a.sample_num[:C] = class_offsets, sample_num
+    a.seed, a.remove_extra_width, a.R = augment_seed(seed, step), e, R
+    for n, t in zip(PASTE_OUTPUTS, outs):
+        setattr(a, n, t.data_ptr())
+    a.workspace = workspace.data_ptr()
+    with _timed("gt_paste", f"n{total}G{G}Q{Q}"):
+        check(lib().sad_gt_paste_f32(ctypes.byref(a), _stream()), "sad_gt_paste_f32")
+    return outs
 
 
 # The fused MLP chains (PackedMLP / PackedMLPBf16, grouped_multi, rowscan_multi, the autotuner) live in mlp.py; they belong

@@ -1020,6 +1020,70 @@ typedef struct sad_rotated_iou_loss_args {
 } sad_rotated_iou_loss_args;
 int sad_rotated_iou_loss_f32(const sad_rotated_iou_loss_args *args, sad_stream_t stream);
 
+/* SPEC.md §35 (additions of ABI 4 as well).  Training augmentation on the device, reproducible from `seed` (the caller mixes its
+ * step counter into it): every draw is §17's integer hash h(seed, scene, index) on index ranges of its own.
+ *
+ * §35.1 sad_global_augment_f32: one flip / rotation / scale / translation per scene, applied to the scene's points and box rows.
+ * points[total,Cp] ragged with offsets[B+1], or offsets == NULL: B scenes of N rows each (total = B*N); Cp >= 3, columns 3..
+ * are copied.  gt_boxes[B,G,D] rows of D >= 7 floats as in §19 (G >= 0); with_velocity (needs D >= 9) treats columns 7, 8 as a
+ * vector: flipped, rotated and scaled, not translated.  Every box row is transformed, padding included; yaw is not wrapped.
+ * params[B,8] = (flips, theta, cos, sin, scale, tx, ty, tz), flips = flip_x + 2 * flip_y as a float.  One launch.
+ *
+ * §35.2 sad_gt_paste_f32: ground-truth database sampling.  The database: db_points[.,Cp], db_offsets[Ndb+1], db_boxes[Ndb,D],
+ * entries sorted by class, class c = entries class_offsets[c] .. class_offsets[c+1]-1 (host array, C <= 16 classes).  Q = the sum
+ * of sample_num[c] candidate slots per scene (Q <= 512, else SAD_EUNSUPPORTED); a slot is accepted greedily in slot order iff it
+ * is active and its BEV IoU with every valid ground-truth row and every accepted earlier slot is not > 0.  Outputs: keep[B,Q],
+ * db_index[B,Q] (-1 = inactive), boxes_out[B,G+Q,D] / labels_out[B,G+Q] (the G rows, the accepted boxes in slot order, zero rows
+ * with label -1), num_pasted[B], out_points[R,Cp] (per scene: the accepted objects' points, then the scene's points outside
+ * every accepted box enlarged by remove_extra_width, in file order) and out_offsets[B+1]; rows at or beyond out_offsets[B] are
+ * not written.  R >= total + B*Q*max_obj_points (SAD_EINVAL otherwise); an object's rows beyond max_obj_points are not pasted.
+ * params != NULL: §35.1's transform is applied to every stored point and every row of boxes_out.  Four launches, no float
+ * atomics, nothing read back, two calls bit-equal.  workspace: sad_gt_paste_workspace_bytes(B, Q, total) bytes, 16-byte aligned. */
+typedef struct sad_global_augment_args {
+    size_t struct_size;   /* = sizeof(sad_global_augment_args) */
+    const float *points;           /* [total,Cp] */
+    const int32_t *offsets;        /* [B+1] or NULL */
+    const float *gt_boxes;         /* [B,G,D] or NULL when G == 0 */
+    int B, N, total, Cp, G, D;
+    unsigned seed;
+    int flip_x, flip_y, with_velocity;
+    float rot_lo, rot_hi, scale_lo, scale_hi;
+    float translate[3];
+    float *points_out;             /* [total,Cp] */
+    float *boxes_out;              /* [B,G,D] or NULL when G == 0 */
+    float *params;                 /* [B,8] */
+} sad_global_augment_args;
+int sad_global_augment_f32(const sad_global_augment_args *args, sad_stream_t stream);
+
+#define SAD_PASTE_MAX_CLASSES 16
+typedef struct sad_gt_paste_args {
+    size_t struct_size;   /* = sizeof(sad_gt_paste_args) */
+    const float *points;           /* [total,Cp] */
+    const int32_t *offsets;        /* [B+1] */
+    const float *gt_boxes;         /* [B,G,D] or NULL when G == 0 */
+    const int32_t *gt_labels;      /* [B,G] or NULL when G == 0 */
+    const float *db_points;        /* [.,Cp] */
+    const int32_t *db_offsets;     /* [Ndb+1] */
+    const float *db_boxes;         /* [Ndb,D] */
+    const float *params;           /* [B,8] or NULL */
+    int B, total, Cp, G, D, C, Ndb, max_obj_points, with_velocity;
+    int class_offsets[SAD_PASTE_MAX_CLASSES + 1];
+    int sample_num[SAD_PASTE_MAX_CLASSES];
+    unsigned seed;
+    float remove_extra_width;
+    long long R;                   /* rows of out_points */
+    int32_t *keep;                 /* [B,Q] */
+    int32_t *db_index;             /* [B,Q] */
+    float *boxes_out;              /* [B,G+Q,D] */
+    int32_t *labels_out;           /* [B,G+Q] */
+    int32_t *num_pasted;           /* [B] */
+    float *out_points;             /* [R,Cp] */
+    int32_t *out_offsets;          /* [B+1] */
+    void *workspace;
+} sad_gt_paste_args;
+size_t sad_gt_paste_workspace_bytes(int B, int Q, int total);   /* 0 outside 1 <= B <= 65535, 1 <= Q <= 512, total >= 0 */
+int sad_gt_paste_f32(const sad_gt_paste_args *args, sad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -217,8 +217,7 @@ __global__ __launch_bounds__(AUG_T) void paste_select_kernel(const PasteArgs p) 
     // ---- cnt_b(c): the valid ground-truth rows per class; the scene's first workgroup of the point pass
     for (int g = tid; g < G; g += AUG_T) {
         const int cls = gl[g];
-        const float *r = gt + (size_t)g * D;
-        if (cls >= 0 && cls < p.C && r[3] > 0.0f && r[4] > 0.0f && r[5] > 0.0f) atomicAdd(&s_cnt[cls], 1);
+        if (gt_row_valid(cls, p.C, gt + (size_t)g * D)) atomicAdd(&s_cnt[cls], 1);
     }
     {
         int nb = 0;
@@ -239,13 +238,7 @@ __global__ __launch_bounds__(AUG_T) void paste_select_kernel(const PasteArgs p) 
         int d = -1;
         if (active) {
             d = p.coff[c] + (int)(h17(p.seed, (unsigned)b, AUG_DRAW_PASTE + (unsigned)q) % (unsigned)nc);
-            const float *row = p.dbb + (size_t)d * D;
-            float cx[4], cy[4];
-            box_corners(row, cx, cy);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { s_cx[q][k] = cx[k]; s_cy[q][k] = cy[k]; }
-            s_ctr[q][0] = row[0]; s_ctr[q][1] = row[1];
-            s_area[q] = row[3] * row[4];
+            box_footprint(p.dbb + (size_t)d * D, s_cx[q], s_cy[q], s_ctr[q], s_area[q]);
         } else {
             atomicOr(&s_rem[q >> 6], 1ull << (q & 63));
         }
@@ -259,16 +252,9 @@ __global__ __launch_bounds__(AUG_T) void paste_select_kernel(const PasteArgs p) 
         if (tid < tn) {
             const int g = g0 + tid, cls = gl[g];
             const float *r = gt + (size_t)g * D;
-            const bool ok = cls >= 0 && cls < p.C && r[3] > 0.0f && r[4] > 0.0f && r[5] > 0.0f;
+            const bool ok = gt_row_valid(cls, p.C, r);
             g_ok[tid] = ok;
-            if (ok) {
-                float cx[4], cy[4];
-                box_corners(r, cx, cy);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { g_cx[tid][k] = cx[k]; g_cy[tid][k] = cy[k]; }
-                g_ctr[tid][0] = r[0]; g_ctr[tid][1] = r[1];
-                g_area[tid] = r[3] * r[4];
-            }
+            if (ok) box_footprint(r, g_cx[tid], g_cy[tid], g_ctr[tid], g_area[tid]);
         }
         __syncthreads();
         for (int i = tid; i < Q * tn; i += AUG_T) {
@@ -328,6 +314,7 @@ __global__ __launch_bounds__(AUG_T) void paste_select_kernel(const PasteArgs p) 
         p.ws.acc_start(b)[rank] = start;
         p.ws.acc_db(b)[rank] = d;
         float *k8 = p.ws.consts(b) + (size_t)rank * 8;
+        // BoxK's fields in its order, box_consts written out
         float s, c;
         sincos_r(row[6], s, c);
         const float e2 = 2.0f * p.e;

@@ -1,8 +1,9 @@
-// Rotated-box geometry of SPEC.md §13, shared by the NMS kernels (nms.hip), the box operators (boxes.hip) and the RoI head
-// (roi_head.hip, roi_loss.hip): the reproducible sin/cos, the box corners, the Sutherland-Hodgman clipped area and the RoI's local anchor.  Binary32, no contraction
-// (the library is built with -ffp-contract=off), so the CPU oracle and every kernel agree bit for bit.
+// Rotated-box geometry of SPEC.md §13, §19.1, §19.3 and §28.1, ONE definition per formula, for every box kernel (DESIGN.md names the
+// few sites that keep a written-out copy, and why).  Binary32, no contraction (-ffp-contract=off), one rounding per written
+// operation: the CPU oracle and every kernel agree bit for bit.
 #pragma once
 #include "common.h"
+#include <math.h>
 
 namespace {
 
@@ -28,6 +29,16 @@ __device__ __forceinline__ void sincos_r(float th, float &s_out, float &c_out) {
     c_out = q == 0 ? C : (q == 1 ? -S : (q == 2 ? -C : S));
 }
 
+// §13 a world offset into a box's frame (c, s: cos and sin of its yaw), and back
+__device__ __forceinline__ void to_frame(float dx, float dy, float c, float s, float &lx, float &ly) {
+    lx = (dx * c) + (dy * s);
+    ly = (dy * c) - (dx * s);
+}
+__device__ __forceinline__ void from_frame(float lx, float ly, float c, float s, float &x, float &y) {
+    x = (lx * c) - (ly * s);
+    y = (lx * s) + (ly * c);
+}
+
 // §13 local corners: the four corner offsets of a box from its own centre, counter-clockwise.  The centre is not added: a pair
 // is clipped in the frame of its second box (poly_clip_area), so the IoU does not depend on where the scene lies.
 __device__ __forceinline__ void box_corners(const float *bx, float *ox, float *oy) {
@@ -44,14 +55,67 @@ __device__ __forceinline__ void box_corners(const float *bx, float *ox, float *o
     }
 }
 
-// §19.1 inside(p, box, e) on the box's constants: centre, half extents of the enlarged box, cos, sin (boxes.hip, point_head.hip)
+// §13 a box for the pair test: local corners, centre (x, y) and area, written where the caller keeps them
+__device__ __forceinline__ void box_footprint(const float *bx, float *cx, float *cy, float *ctr, float &area) {
+    float ox[4], oy[4];
+    box_corners(bx, ox, oy);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { cx[k] = ox[k]; cy[k] = oy[k]; }
+    ctr[0] = bx[0]; ctr[1] = bx[1];
+    area = bx[3] * bx[4];
+}
+// §19.3 ... and z, height, volume
+__device__ __forceinline__ void box_footprint3d(const float *bx, float *cx, float *cy, float *ctr, float &z, float &h, float &vol) {
+    float area;
+    box_footprint(bx, cx, cy, ctr, area);
+    z = bx[2]; h = bx[5];
+    vol = area * bx[5];
+}
+
+// §13 IoU from the intersection and the areas (§19.3: inter * oh and the volumes), by reference: the caller decides when they are
+// read (pair_suppresses); sum and den go out for iou_loss.hip's gradient
+__device__ __forceinline__ float iou_of(float inter, const float &a, const float &b, float &sum, float &den) {
+    sum = a + b; den = sum - inter;
+    return den > 0.0f ? inter / den : 0.0f;
+}
+__device__ __forceinline__ float iou_of(float inter, const float &a, const float &b) { float s, d; return iou_of(inter, a, b, s, d); }
+// §19.3 the z overlap of two boxes (heights, then centres), clamped at 0; the tops and bottoms go out as well
+__device__ __forceinline__ float height_overlap(float ha, float hb, float za, float zb, float &topa, float &topb, float &bota,
+                                                float &botb) {
+    const float hha = 0.5f * ha, hhb = 0.5f * hb;
+    topa = za + hha; topb = zb + hhb; bota = za - hha; botb = zb - hhb;
+    const float oh = fminf(topa, topb) - fmaxf(bota, botb);
+    return oh > 0.0f ? oh : 0.0f;
+}
+__device__ __forceinline__ float height_overlap(float ha, float hb, float za, float zb) {
+    float t[4];
+    return height_overlap(ha, hb, za, zb, t[0], t[1], t[2], t[3]);
+}
+
+// §19.1 per-box constants of inside(p, box, e): centre, half extents of the enlarged box, cos, sin
+struct BoxK { float cx, cy, cz, hl, hw, hh, c, s; };
+__device__ __forceinline__ BoxK box_consts(const float *bx, float e) {
+    BoxK k;
+    float s, c;
+    sincos_r(bx[6], s, c);
+    const float e2 = 2.0f * e;
+    const float L = bx[3] + e2, W = bx[4] + e2, H = bx[5] + e2;
+    k.cx = bx[0]; k.cy = bx[1]; k.cz = bx[2];
+    k.hl = 0.5f * L; k.hw = 0.5f * W; k.hh = 0.5f * H;
+    k.c = c; k.s = s;
+    return k;
+}
+// a ground-truth row that counts (§31.1, §35): a class in [0, C) and three positive extents
+__device__ __forceinline__ bool gt_row_valid(int cls, int C, const float *r) {
+    return cls >= 0 && cls < C && r[3] > 0.0f && r[4] > 0.0f && r[5] > 0.0f;
+}
+
+// §19.1 inside(p, box, e) on the box's constants
 __device__ __forceinline__ bool inside(float px, float py, float pz, float cx, float cy, float cz, float hl, float hw,
                                        float hh, float c, float s) {
     const float dx = px - cx, dy = py - cy, dz = pz - cz;
-    const float a = dx * c, b = dy * s;
-    const float lx = a + b;
-    const float a2 = dy * c, b2 = dx * s;
-    const float ly = a2 - b2;
+    float lx, ly;
+    to_frame(dx, dy, c, s, lx, ly);
     return fabsf(dz) <= hh && fabsf(lx) < hl && fabsf(ly) < hw;
 }
 
@@ -59,11 +123,19 @@ __device__ __forceinline__ bool inside(float px, float py, float pz, float cx, f
 struct RoiAnchor { float la, wa, ha, dg; };
 __device__ __forceinline__ RoiAnchor roi_anchor(const float *roi) {
     RoiAnchor a;
-    a.la = fmaxf(roi[3], 1e-5f);
-    a.wa = fmaxf(roi[4], 1e-5f);
-    a.ha = fmaxf(roi[5], 1e-5f);
+    a.la = fmaxf(roi[3], 1e-5f); a.wa = fmaxf(roi[4], 1e-5f); a.ha = fmaxf(roi[5], 1e-5f);
     a.dg = sqrtf((a.la * a.la) + (a.wa * a.wa));
     return a;
+}
+// §28.1 the residual code in the RoI's frame: t -> o[0 .. 5], centre and extents (o may be t); lv, the box in that frame -> tv
+__device__ __forceinline__ void roi_decode_local(const float *t, const RoiAnchor &a, float *o) {
+    o[0] = t[0] * a.dg; o[1] = t[1] * a.dg; o[2] = t[2] * a.ha;
+    o[3] = expf(t[3]) * a.la; o[4] = expf(t[4]) * a.wa; o[5] = expf(t[5]) * a.ha;
+}
+__device__ __forceinline__ void roi_encode_local(const float *lv, const RoiAnchor &a, float *tv) {
+    tv[0] = lv[0] / a.dg; tv[1] = lv[1] / a.dg; tv[2] = lv[2] / a.ha;
+    tv[3] = logf(fmaxf(lv[3], 1e-5f) / a.la); tv[4] = logf(fmaxf(lv[4], 1e-5f) / a.wa); tv[5] = logf(fmaxf(lv[5], 1e-5f) / a.ha);
+    tv[6] = lv[6];
 }
 
 // area of (box a) ∩ (box b) in b's frame: a's vertices are (ddx, ddy) + its local corners, with (ddx, ddy) = a.centre - b.centre

@@ -1,6 +1,6 @@
 // Box operators (SPEC.md §19): pairwise BEV / 3-D IoU, points_in_boxes and roipoint_pool3d — the box-level
-// operators a detector's users reach for after NMS.  Geometry (sincos_r, box_corners, poly_clip_area) is the
-// §13 code of box_geom.h, shared with the NMS kernels, so every decision is bit-identical to the CPU oracle.
+// operators a detector's users reach for after NMS.  The geometry (corners, the clip, inside() and its constants) is
+// box_geom.h's, shared with every other box kernel, so every decision is bit-identical to the CPU oracle.
 //
 // boxes_iou: a 2-D grid of IOU_TA x IOU_TB pair tiles per scene.  A workgroup computes the local corners, centres, areas and
 // heights of its tile's boxes once into LDS, then each thread clips one pair with poly_clip_area<256> in
@@ -28,30 +28,6 @@ constexpr int RP_TILE = 1024;              // points per LDS tile (12 KiB)
 constexpr int RP_BPW = 4;                  // boxes per wave at most
 constexpr int RP_SEL_INTS = 8192;          // LDS for the selected indices of a workgroup's boxes (32 KiB): S <= 8192
 
-// SPEC §19.1 per-box constants of inside(p, box, e): centre, half extents of the enlarged box, cos, sin
-struct BoxK {
-    float cx, cy, cz, hl, hw, hh, c, s;
-};
-
-__device__ __forceinline__ BoxK box_consts(const float *bx, float e) {
-    BoxK k;
-    float s, c;
-    sincos_r(bx[6], s, c);
-    const float e2 = 2.0f * e;
-    const float L = bx[3] + e2, W = bx[4] + e2, H = bx[5] + e2;
-    k.cx = bx[0];
-    k.cy = bx[1];
-    k.cz = bx[2];
-    k.hl = 0.5f * L;
-    k.hw = 0.5f * W;
-    k.hh = 0.5f * H;
-    k.c = c;
-    k.s = s;
-    return k;
-}
-
-// (inside, the predicate itself: box_geom.h, shared with point_head.hip)
-
 // ---- pairwise IoU -------------------------------------------------------------------------------------------
 // grid (ceil(Kb / IOU_TB), ceil(Ka / IOU_TA), B); mode 0 = BEV (§13 iou_bev), 1 = 3-D (§19.3)
 __global__ __launch_bounds__(256) void boxes_iou_kernel(const float *__restrict__ a, const float *__restrict__ b, int Ka,
@@ -67,6 +43,7 @@ __global__ __launch_bounds__(256) void boxes_iou_kernel(const float *__restrict_
         const int k = (isa ? i0 : j0) + t, K = isa ? Ka : Kb;
         if (k < K) {
             const float *bx = isa ? a + ((size_t)sc * Ka + k) * Da : b + ((size_t)sc * Kb + k) * Db;
+            // box_footprint3d and, below, height_overlap and iou_of, written out
             float cx[4], cy[4];
             box_corners(bx, cx, cy);
             const float area = bx[3] * bx[4];

@@ -59,8 +59,7 @@ __device__ __forceinline__ float reg_row(const AncL &p, const float *r, const fl
             float sp, cp, st, ct;
             sincos_r(r[6], sp, cp);
             sincos_r(t[6], st, ct);
-            d = ((sp * ct) - (cp * st)) * p.cw[6];
-            extra = (cp * ct) + (sp * st);
+            d = sin_diff(sp, cp, st, ct, p.cw[6], extra);
         } else {
             d = (r[j] - t[j]) * p.cw[j];
         }

@@ -1,7 +1,6 @@
 // Rotated IoU losses (SPEC.md §34): the IoU of ALIGNED pairs (pred[i] against target[i]) in bird's-eye view or 3-D, the IoU / DIoU
-// loss on it and the analytic gradient with respect to the pred's seven columns, in one launch.  The value is §19.3's: the same
-// box_corners, the same centre difference, the same poly_clip_area<256> in thread-interleaved LDS as boxes_iou_kernel, so iou
-// equals that operator's diagonal bit for bit.
+// loss on it and the analytic gradient with respect to the pred's seven columns, in one launch.  The value is §19.3's, from
+// box_geom.h's helpers: iou equals the diagonal of boxes_iou_* bit for bit.
 //
 // The gradient does not differentiate the clip.  The target is fixed, so the intersection I changes only where the boundary of
 // P ∩ T lies on an edge of P: dI = ∮ (v·n) ds over those pieces, and the normal velocity of P's boundary is linear along an edge.
@@ -88,8 +87,7 @@ __global__ __launch_bounds__(IL_THREADS) void iou_loss_kernel(const IouL p) {
     }
     if (p.roi) {                                        // §34 code = roi: the box decoded in the RoI's frame, as §29's corner loss
         const RoiAnchor an = roi_anchor(p.rois + i * p.Dr);
-        P[0] = P[0] * an.dg; P[1] = P[1] * an.dg; P[2] = P[2] * an.ha;
-        P[3] = expf(P[3]) * an.la; P[4] = expf(P[4]) * an.wa; P[5] = expf(P[5]) * an.ha;
+        roi_decode_local(P, an, P);
         jac[0] = an.dg; jac[1] = an.dg; jac[2] = an.ha; jac[3] = P[3]; jac[4] = P[4]; jac[5] = P[5];
         if (p.dec) {
 #pragma unroll
@@ -110,9 +108,7 @@ __global__ __launch_bounds__(IL_THREADS) void iou_loss_kernel(const IouL p) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         cor[k] = tx[k]; cor[4 + k] = ty[k]; cor[8 + k] = cx[k]; cor[12 + k] = cy[k];
-        const float vx = ddx + cx[k], vy = ddy + cy[k];
-        X[k] = (vx * ct) + (vy * st);
-        Y[k] = (vy * ct) - (vx * st);
+        to_frame(ddx + cx[k], ddy + cy[k], ct, st, X[k], Y[k]);
     }
     const float inter = poly_clip_area<IL_THREADS>(cor + 8, cor + 12, ddx, ddy, cor, cor + 4, s_poly + tid);
     // ---- edge pass: the length of each pred edge inside the target and the parameter of its midpoint
@@ -129,26 +125,19 @@ __global__ __launch_bounds__(IL_THREADS) void iou_loss_kernel(const IouL p) {
     const float u0 = hl - (tm[0] * l), v1 = hw - (tm[1] * w), u2 = (tm[2] * l) - hl, v3 = (tm[3] * w) - hw;
     const float dIt = ((ln[0] * u0) + (ln[1] * v1)) - ((ln[2] * u2) + (ln[3] * v3));
     // ---- the IoU of §19.3 and the quotient rule
-    float iou, nx, ny, nz, nl, nw, nh, nt, den;
+    float iou, nx, ny, nz, nl, nw, nh, nt, S, den;
     bool live;
     float topP = 0.0f, topT = 0.0f, botP = 0.0f, botT = 0.0f;
     if (p.mode == SAD_IOU_BEV) {
-        const float S = (l * w) + (gl * gw);
-        den = S - inter;
-        iou = den > 0.0f ? inter / den : 0.0f;
+        iou = iou_of(inter, l * w, gl * gw, S, den);
         live = inter > 0.0f && den > 0.0f;
         nx = dIx * S; ny = dIy * S; nz = 0.0f; nh = 0.0f; nt = dIt * S;
         nl = (dIl * S) - (inter * w);
         nw = (dIw * S) - (inter * l);
     } else {
-        const float ha = 0.5f * h, hb = 0.5f * gh;
-        topP = z + ha; topT = gz + hb; botP = z - ha; botT = gz - hb;
-        float oh = fminf(topP, topT) - fmaxf(botP, botT);
-        oh = oh > 0.0f ? oh : 0.0f;
+        const float oh = height_overlap(h, gh, z, gz, topP, topT, botP, botT);
         const float i3 = inter * oh;
-        const float S = ((l * w) * h) + ((gl * gw) * gh);
-        den = S - i3;
-        iou = den > 0.0f ? i3 / den : 0.0f;
+        iou = iou_of(i3, (l * w) * h, (gl * gw) * gh, S, den);
         live = inter > 0.0f && oh > 0.0f && den > 0.0f;
         const float tp = topP < topT ? 1.0f : 0.0f, bp = botP > botT ? 1.0f : 0.0f;      // a tie is the target's
         nx = (dIx * oh) * S; ny = (dIy * oh) * S; nt = (dIt * oh) * S;

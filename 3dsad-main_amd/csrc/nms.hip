@@ -37,7 +37,7 @@ __global__ __launch_bounds__(THREADS) void nms_bev_kernel(const float *__restric
 
     // 1. rank among the candidates (score >= threshold): score descending, index ascending
     const int n = rank_candidates<THREADS>(bx, K, score_thr, kp, od, s_score, s_rank2idx, &s_n);
-    // local corners, centres and areas in rank order
+    // local corners, centres and areas in rank order (box_footprint, written out here and in nms_prep_kernel: DESIGN.md)
     for (int p = tid; p < n; p += THREADS) {
         const float *b = bx + (size_t)s_rank2idx[p] * 9;
         float cx[4], cy[4];

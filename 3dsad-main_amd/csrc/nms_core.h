@@ -1,7 +1,7 @@
 // What the rotated-box NMS pipelines share (SPEC.md §13, §23): nms_bev_kernel and nms_prep / mask / walk (nms.hip), nmsx_select /
 // rank / mask / walk (nms_select.hip).  §23 promises identical keep decisions, so the pair test, the candidate ranking, the
 // decision chain of a chunk of 64 ranks, the per-scene workspace view and the mask kernel have ONE definition each, here.
-// Included inside each file's anonymous namespace, after box_geom.h (poly_clip_area) and prims.h (u64, readlane_u64).
+// Included inside each file's anonymous namespace, after box_geom.h (poly_clip_area, iou_of) and prims.h (u64, readlane_u64).
 #pragma once
 
 // Does box p suppress box q?  IoU of §13 on local corners, centres (pc, qc: x, y) and areas, clipped in q's frame; `scratch` is the thread's slot of the clipping lists in LDS.
@@ -12,10 +12,7 @@ template <int STRIDE>
 __device__ __forceinline__ bool pair_suppresses(const float *pcx, const float *pcy, const float *pc, const float &pa, const float *qcx,
                                                 const float *qcy, const float *qc, const float &qa, float iou_thr, float *scratch) {
     const float inter = poly_clip_area<STRIDE>(pcx, pcy, pc[0] - qc[0], pc[1] - qc[1], qcx, qcy, scratch);
-    float den = pa + qa;
-    den = den - inter;
-    const float iou = den > 0.0f ? inter / den : 0.0f;
-    return iou > iou_thr;
+    return iou_of(inter, pa, qa) > iou_thr;
 }
 
 // One workgroup of THREADS threads ranks a scene of K <= 512 boxes (scores in column 7 of 9): keep = 0, order = -1, then an

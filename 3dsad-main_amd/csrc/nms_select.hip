@@ -203,12 +203,7 @@ __global__ __launch_bounds__(256) void nmsx_rank_kernel(const float *__restrict_
         const int idx = (int)~(unsigned)cj;
         const size_t row = (size_t)blockIdx.y * K + (size_t)idx;
         const float *b = boxes + row * D;
-        float cx[4], cy[4];
-        box_corners(b, cx, cy);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { w.cx[r * 4 + k] = cx[k]; w.cy[r * 4 + k] = cy[k]; }
-        w.ctr[r * 2] = b[0]; w.ctr[r * 2 + 1] = b[1];
-        w.area[r] = b[3] * b[4];
+        box_footprint(b, w.cx + r * 4, w.cy + r * 4, w.ctr + r * 2, w.area[r]);
         w.rank2idx[r] = idx;
         w.label[r] = labels ? labels[row] : 0;
     }

@@ -84,13 +84,14 @@ __global__ __launch_bounds__(PH_THREADS) void point_targets_kernel(const PtT p) 
             for (int j = 0; j < 7; ++j) r[j] = row[j];
             cls = p.gl[(size_t)b * p.G + g];
         }
-        const bool ok = cls >= 0 && cls < p.C && r[3] > 0.0f && r[4] > 0.0f && r[5] > 0.0f;
+        const bool ok = gt_row_valid(cls, p.C, r);
         const u64 m = __ballot(ok);
         const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
         if (lane == 0) wcnt[wave] = __popcll(m);
         __syncthreads();
         int at = n + rank;
         for (int w = 0; w < wave; ++w) at += wcnt[w];
+        // (not BoxK: the band test needs the raw extents)
         if (ok) {                                       // (at < n + 256 <= G <= PH_MAXG)
             float s, c;
             sincos_r(r[6], s, c);
@@ -132,7 +133,8 @@ __global__ __launch_bounds__(PH_THREADS) void point_targets_kernel(const PtT p) 
         }
         // centre-ness at q, in the box's frame (lx, ly, dz: §19.1's)
         const float dx = q[0] - a.x, dy = q[1] - a.y, dz = q[2] - a.z;
-        const float lx = (dx * bb.z) + (dy * bb.w), ly = (dy * bb.z) - (dx * bb.w);
+        float lx, ly;
+        to_frame(dx, dy, bb.z, bb.w, lx, ly);
         const float rx = axis_ratio(0.5f * a.w, lx), ry = axis_ratio(0.5f * bb.x, ly), rz = axis_ratio(0.5f * bb.y, dz);
         cent = cbrtf((rx * ry) * rz);
 #pragma unroll
@@ -172,8 +174,7 @@ __device__ __forceinline__ float reg_row(const PtL &p, float *r, const float *t,
             float sp, cp, st, ct;
             sincos_r(r[6], sp, cp);
             sincos_r(t[6], st, ct);
-            d = ((sp * ct) - (cp * st)) * p.cw[6];
-            extra = (cp * ct) + (sp * st);
+            d = sin_diff(sp, cp, st, ct, p.cw[6], extra);
         } else if (j >= 3) {
             pass = r[j] >= -2.0f && r[j] <= 2.0f;
             d = (clampf(r[j], 2.0f) - t[j]) * p.cw[j];

@@ -186,3 +186,10 @@ __device__ __forceinline__ float smooth_l1(float d, float beta, float &sg) {
     sg = quad ? d / beta : (float)((d > 0.0f) - (d < 0.0f));
     return quad ? ((0.5f * a) * a) / beta : a - (0.5f * beta);
 }
+
+// §27.1 the sine-difference yaw term: sin(p - t) * cw6 for smooth_l1, and extra = cos(p - t), the factor its gradient picks up
+__device__ __forceinline__ float sin_diff(float sp, float cp, float st, float ct, float cw6, float &extra) {
+    const float d = ((sp * ct) - (cp * st)) * cw6;
+    extra = (cp * ct) + (sp * st);
+    return d;
+}

@@ -5,8 +5,8 @@
 // roi_targets   two launches, no [R,G] matrix, nothing read back:
 //   pass 1      grid (ceil(R / 16), B), 256 threads: 16 RoIs x 16 slices of the boxes.  The scene's boxes come through LDS in
 //               chunks of GCH: local corners, centre, z, h, volume and label, 14 words per box, computed once per workgroup.  A thread clips
-//               its RoI against the boxes of its slice that it is eligible for in ascending g with the §19.3 arithmetic of
-//               boxes.hip (box_corners, poly_clip_area<256> in thread-interleaved LDS scratch: the same bits as boxes_iou3d)
+//               its RoI against the boxes of its slice that it is eligible for in ascending g with §19.3's helpers of box_geom.h
+//               (poly_clip_area<256> in thread-interleaved LDS scratch): boxes_iou3d's value (tests/test_gpu_box_identities.py),
 //               and keeps the maximum under a strict >; the 16 slices meet in LDS (largest m, lowest g among equals), so the
 //               lowest g wins; (m, j) go to the workspace.
 //   pass 2      one workgroup per scene.  Candidates r < n_b are classified (fg / hard / easy) by exact float compares and
@@ -71,17 +71,10 @@ __global__ __launch_bounds__(P1_THREADS) void roi_match_kernel(const RoiP p) {
     const int r = blockIdx.x * P1_ROIS + (tid - slice * P1_ROIS);
     const bool live = r < nb;
     float ax[4] = {0.f, 0.f, 0.f, 0.f}, ay[4] = {0.f, 0.f, 0.f, 0.f};
-    float acx = 0.f, acy = 0.f, za = 0.f, ha = 0.f, avol = 0.f;
+    float ac[2] = {0.f, 0.f}, az = 0.f, ah = 0.f, avol = 0.f;
     int alab = 0;
     if (live) {
-        const float *bx = p.rois + ((size_t)b * p.R + r) * p.D;
-        box_corners(bx, ax, ay);
-        acx = bx[0];
-        acy = bx[1];
-        const float area = bx[3] * bx[4];
-        avol = area * bx[5];
-        za = bx[2];
-        ha = 0.5f * bx[5];
+        box_footprint3d(p.rois + ((size_t)b * p.R + r) * p.D, ax, ay, ac, az, ah, avol);
         if (p.roi_labels) alab = p.roi_labels[(size_t)b * p.R + r];
     }
     const bool any_class = p.roi_labels == nullptr;
@@ -96,16 +89,7 @@ __global__ __launch_bounds__(P1_THREADS) void roi_match_kernel(const RoiP p) {
             const int lab = p.gl[row];
             s_glab[t] = lab;
             if (lab >= 0) {                             // a padding row is never eligible: its fields are not read
-                const float *bx = p.gt + row * p.Dg;
-                float cx[4], cy[4];
-                box_corners(bx, cx, cy);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) { s_gx[t][q] = cx[q]; s_gy[t][q] = cy[q]; }
-                s_gc[t][0] = bx[0]; s_gc[t][1] = bx[1];
-                const float area = bx[3] * bx[4];
-                s_gvol[t] = area * bx[5];
-                s_gz[t] = bx[2];
-                s_gh[t] = bx[5];
+                box_footprint3d(p.gt + row * p.Dg, s_gx[t], s_gy[t], s_gc[t], s_gz[t], s_gh[t], s_gvol[t]);
             }
         }
         __syncthreads();
@@ -115,16 +99,10 @@ __global__ __launch_bounds__(P1_THREADS) void roi_match_kernel(const RoiP p) {
                 if (lab >= 0 && (any_class || lab == alab)) break;
             }
             if (t >= cnt) break;
-            // §19.3, mode 3d, a = the RoI, b = the box: the operations of boxes_iou_kernel in its order
-            const float inter = poly_clip_area<P1_THREADS>(ax, ay, acx - s_gc[t][0], acy - s_gc[t][1], s_gx[t], s_gy[t], s_poly + tid);
-            const float hb = 0.5f * s_gh[t], zb = s_gz[t];
-            const float top = fminf(za + ha, zb + hb), bot = fmaxf(za - ha, zb - hb);
-            float oh = top - bot;
-            oh = oh > 0.0f ? oh : 0.0f;
-            const float i3 = inter * oh;
-            float den = avol + s_gvol[t];
-            den = den - i3;
-            const float v = den > 0.0f ? i3 / den : 0.0f;
+            // §19.3, mode 3d, a = the RoI, b = the box
+            const float inter = poly_clip_area<P1_THREADS>(ax, ay, ac[0] - s_gc[t][0], ac[1] - s_gc[t][1], s_gx[t], s_gy[t], s_poly + tid);
+            const float oh = height_overlap(ah, s_gh[t], az, s_gz[t]);
+            const float v = iou_of(inter * oh, avol, s_gvol[t]);
             if (j < 0 || v > m) { m = v; j = g0 + t; }  // strict: a tie stays with the lowest g of the slice
         }
     }
@@ -155,8 +133,6 @@ __device__ __forceinline__ float local_heading(float gyaw, float rr) {
     if (o > PI_F) o = o - TWO_PI_F;
     return fminf(fmaxf(o, -HALF_PI_F), HALF_PI_F);
 }
-
-// (roi_anchor, the local anchor of a RoI: box_geom.h, shared with roi_loss.hip)
 
 __global__ __launch_bounds__(P2_THREADS) void roi_sample_kernel(const RoiP p) {
     __shared__ u64 keys[ROI_MAXR];                      // the fg keys, sorted (32 KB)
@@ -265,18 +241,10 @@ __global__ __launch_bounds__(P2_THREADS) void roi_sample_kernel(const RoiP p) {
             float s, c;
             sincos_r(rv[6], s, c);
             const float dx = g[0] - rv[0], dy = g[1] - rv[1], dz = g[2] - rv[2];
-            const float lx = (dx * c) + (dy * s);
-            const float ly = (dy * c) - (dx * s);
-            const float hd = local_heading(g[6], rv[6]);
-            lv[0] = lx; lv[1] = ly; lv[2] = dz; lv[3] = g[3]; lv[4] = g[4]; lv[5] = g[5]; lv[6] = hd;
-            const RoiAnchor a = roi_anchor(rv);
-            tv[0] = lx / a.dg;
-            tv[1] = ly / a.dg;
-            tv[2] = dz / a.ha;
-            tv[3] = logf(fmaxf(g[3], 1e-5f) / a.la);
-            tv[4] = logf(fmaxf(g[4], 1e-5f) / a.wa);
-            tv[5] = logf(fmaxf(g[5], 1e-5f) / a.ha);
-            tv[6] = hd;
+            to_frame(dx, dy, c, s, lv[0], lv[1]);
+            lv[2] = dz; lv[3] = g[3]; lv[4] = g[4]; lv[5] = g[5];
+            lv[6] = local_heading(g[6], rv[6]);
+            roi_encode_local(lv, roi_anchor(rv), tv);
         }
 #pragma unroll
         for (int q = 0; q < 7; ++q) { rs[q] = rv[q]; gloc[q] = lv[q]; rt[q] = tv[q]; }
@@ -291,15 +259,16 @@ __global__ __launch_bounds__(256) void roi_decode_kernel(const float *__restrict
     const float *roi = rois + (size_t)i * D, *t = reg + (size_t)i * 7;
     float *o = boxes + (size_t)i * 7;
     const RoiAnchor a = roi_anchor(roi);
-    float s, c;
+    float s, c, d[6], x, y;
     sincos_r(roi[6], s, c);
-    const float lx = t[0] * a.dg, ly = t[1] * a.dg, lz = t[2] * a.ha;
-    o[0] = ((lx * c) - (ly * s)) + roi[0];
-    o[1] = ((lx * s) + (ly * c)) + roi[1];
-    o[2] = lz + roi[2];
-    o[3] = expf(t[3]) * a.la;
-    o[4] = expf(t[4]) * a.wa;
-    o[5] = expf(t[5]) * a.ha;
+    roi_decode_local(t, a, d);
+    from_frame(d[0], d[1], c, s, x, y);
+    o[0] = x + roi[0];
+    o[1] = y + roi[1];
+    o[2] = d[2] + roi[2];
+    o[3] = d[3];
+    o[4] = d[4];
+    o[5] = d[5];
     o[6] = t[6] + roi[6];
 }
 

@@ -49,8 +49,8 @@ __device__ __forceinline__ float reg_row(const RoiL &p, const float *r, const fl
 
 // §29 corner loss of one row in the RoI's frame: t = residuals, an = the RoI's anchor, gt = gt_local -> the term and gradients
 __device__ __forceinline__ float corner_row(const float *t, const RoiAnchor &an, const float *gt, float wq, float *g) {
-    const float px = t[0] * an.dg, py = t[1] * an.dg, pz = t[2] * an.ha;
-    const float pl = expf(t[3]) * an.la, pw = expf(t[4]) * an.wa, ph = expf(t[5]) * an.ha;
+    float d[6]; roi_decode_local(t, an, d);
+    const float px = d[0], py = d[1], pz = d[2], pl = d[3], pw = d[4], ph = d[5];
     float sp, cp, sg, cg;
     sincos_r(t[6], sp, cp);
     sincos_r(gt[6], sg, cg);
@@ -61,10 +61,11 @@ __device__ __forceinline__ float corner_row(const float *t, const RoiAnchor &an,
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         const float ox = SX[k] * hl, oy = SY[k] * hw, oz = SZ[k] * hh;
-        const float rx = (ox * cp) - (oy * sp), ry = (ox * sp) + (oy * cp);
+        float rx, ry, grx, gry;
+        from_frame(ox, oy, cp, sp, rx, ry);
         const float X = rx + px, Y = ry + py, Z = oz + pz;
         const float gox = SX[k] * ghl, goy = SY[k] * ghw, goz = SZ[k] * ghh;
-        const float grx = (gox * cg) - (goy * sg), gry = (gox * sg) + (goy * cg);
+        from_frame(gox, goy, cg, sg, grx, gry);
         const float ex = X - (grx + gt[0]), ey = Y - (gry + gt[1]), ez = Z - (goz + gt[2]);
         const float fx = X - (gt[0] - grx), fy = Y - (gt[1] - gry);
         const float d0 = sqrtf(((ex * ex) + (ey * ey)) + (ez * ez));

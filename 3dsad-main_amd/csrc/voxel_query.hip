@@ -105,10 +105,11 @@ __global__ __launch_bounds__(256) void roi_grid_points_kernel(const float *__res
     const float lx = ((((float)ix + 0.5f) / Gf) * roi[3]) - (0.5f * roi[3]);
     const float ly = ((((float)iy + 0.5f) / Gf) * roi[4]) - (0.5f * roi[4]);
     const float lz = ((((float)iz + 0.5f) / Gf) * roi[5]) - (0.5f * roi[5]);
-    float s, c;
+    float s, c, x, y;
     sincos_r(roi[6], s, c);
-    o[0] = ((lx * c) - (ly * s)) + roi[0];
-    o[1] = ((lx * s) + (ly * c)) + roi[1];
+    from_frame(lx, ly, c, s, x, y);
+    o[0] = x + roi[0];
+    o[1] = y + roi[1];
     o[2] = lz + roi[2];
 }
 

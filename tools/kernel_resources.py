@@ -12,7 +12,7 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 
 
 def kernels(name):
-    obj = os.path.join(ROOT, "3dsad-main_amd", "csrc", name + ".o")
+    obj = name if name.endswith(".o") else os.path.join(ROOT, "3dsad-main_amd", "csrc", name + ".o")
     with tempfile.TemporaryDirectory() as td:
         fat, co = os.path.join(td, "x.fat"), os.path.join(td, "x.co")
         subprocess.check_call([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", obj])

@@ -45,6 +45,7 @@ _LAZY = {
     "candidates": "ops", "candidates_grad": "ops", "prefix_rows_grad": "ops", "SADDetectorTrain": "detector_train",
     "global_augment": "ops", "gt_paste": "ops", "gt_paste_workspace": "ops", "gt_paste_rows": "ops",
     "GTDatabase": "augment", "GTSampler": "augment", "GlobalAugment": "augment", "TrainAugment": "augment",
+    "det_match": "ops", "det_ap": "ops", "det_ap_workspace": "ops", "DetectionEval": "evaluate",
     "SADDetector": "detector", "IngestPipeline": "pipeline",
     "shard_range": "dist", "all_gather_boxes": "dist", "run_sharded": "dist",
 }

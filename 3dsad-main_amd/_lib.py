@@ -274,6 +274,33 @@ class GtPasteArgs(ctypes.Structure):
     ]
 
 
+DET_METRICS = {"iou_bev": 0, "iou3d": 1, "dist": 2}      # SAD_DET_*
+
+
+class DetMatchArgs(ctypes.Structure):
+    """``struct sad_det_match_args`` (include/sad_amd.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("det_boxes", vp), ("det_scores", vp), ("det_labels", vp), ("det_count", vp),
+        ("gt_boxes", vp), ("gt_labels", vp), ("gt_ignore", vp), ("thr", vp),
+        ("B", ctypes.c_int), ("K", ctypes.c_int), ("D", ctypes.c_int), ("G", ctypes.c_int), ("Dg", ctypes.c_int),
+        ("C", ctypes.c_int), ("T", ctypes.c_int), ("metric", ctypes.c_int),
+        ("code", vp), ("match", vp), ("value", vp), ("gt_det", vp), ("n_gt", vp),
+    ]
+
+
+class DetApArgs(ctypes.Structure):
+    """``struct sad_det_ap_args`` (include/sad_amd.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_size_t),
+        ("keys", vp), ("perm", vp), ("code", vp), ("n_gt", vp),
+        ("N", ctypes.c_longlong),
+        ("C", ctypes.c_int), ("T", ctypes.c_int), ("points", ctypes.c_int), ("first", ctypes.c_int),
+        ("floor", ctypes.c_float),
+        ("ap", vp), ("prec", vp), ("max_recall", vp), ("n_det", vp),
+    ]
+
+
 GRAD_FEAT, GRAD_XYZ, GRAD_NEW_XYZ, GRAD_PARAMS = 1, 2, 4, 8      # SAD_GRAD_*
 
 
@@ -420,6 +447,9 @@ SIGNATURES = {
     "sad_global_augment_f32": (ctypes.c_int, [ctypes.POINTER(GlobalAugmentArgs), vp]),
     "sad_gt_paste_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
     "sad_gt_paste_f32": (ctypes.c_int, [ctypes.POINTER(GtPasteArgs), vp]),
+    "sad_det_match_f32": (ctypes.c_int, [ctypes.POINTER(DetMatchArgs), vp]),
+    "sad_det_ap_keys_f32": (ctypes.c_int, [vp, vp, ctypes.c_longlong, ctypes.c_int, vp, vp]),
+    "sad_det_ap_f32": (ctypes.c_int, [ctypes.POINTER(DetApArgs), vp]),
 }
 
 _lib = None

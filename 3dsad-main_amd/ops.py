@@ -2370,6 +2370,128 @@ def gt_paste(points: torch.Tensor, offsets: torch.Tensor, gt_boxes: torch.Tensor
     return outs
 
 
+DET_MATCH_OUTPUTS = ("code", "match", "value", "gt_det", "n_gt")
+DET_AP_OUTPUTS = ("ap", "prec", "max_recall", "n_det")
+
+
+def det_match_output_spec(B: int, K: int, G: int, C: int, T: int) -> tuple:
+    """((name, shape, dtype), ...) of ``det_match``'s outputs, what its ``out=`` tuple is checked against."""
+    i32, f32 = torch.int32, torch.float32
+    return (("code", (B, K, T), i32), ("match", (B, K, T), i32), ("value", (B, K, T), f32), ("gt_det", (B, G, T), i32), ("n_gt", (B, C), i32))
+
+
+def det_match(det_boxes: torch.Tensor, det_scores: torch.Tensor, det_labels: torch.Tensor, det_count: Optional[torch.Tensor],
+              gt_boxes: torch.Tensor, gt_labels: torch.Tensor, gt_ignore: Optional[torch.Tensor], thr: torch.Tensor, *,
+              metric: str = "iou3d", out: Optional[tuple] = None) -> tuple:
+    """Score-ordered assignment of detections to ground truth, per scene (SPEC.md §36.1).  det_boxes [B,K,D>=7] f32 rows
+    (cx,cy,cz,l,w,h,yaw,...), det_scores [B,K] f32, det_labels [B,K] int32, det_count [B] int32 or ``None`` (the rows beyond
+    ``det_count[b]`` are never read: the gathered output of ``nms_boxes`` goes in as it is), gt_boxes [B,G,Dg>=7] / gt_labels
+    [B,G] int32 (outside [0, C): padding), gt_ignore [B,G] int32 or ``None``, thr [C,T] f32 on the device ->
+    (code [B,K,T] int32, match [B,K,T] int32, value [B,K,T] f32, gt_det [B,G,T] int32, n_gt [B,C] int32).
+    Live detections (k < det_count, 0 <= label < C) are walked in §23's rank order, independently per threshold column: the best
+    accepted box of the class that is neither ignored nor taken wins (code 1); else the best accepted ignored box absorbs the
+    detection (code -1, never taken); else a false positive (code 0, match -1, value 0).  ``metric``: ``"iou3d"`` / ``"iou_bev"``
+    (§19.3's bits, accepted iff v > thr) or ``"dist"`` (centre distance, accepted iff v < thr).  A row that is not live gets
+    (-1, -1, 0).  K, G <= 1024, C <= 64, T <= 8.  One launch, no workspace, no synchronisation; two calls are bit-equal."""
+    if metric not in _lib.DET_METRICS:
+        raise ValueError(f"metric: expected 'iou3d', 'iou_bev' or 'dist', got {metric!r}")
+    _strict(det_boxes, "det_boxes", torch.float32, (None, None, None), "[B,K,D] with B, K >= 1 and D >= 7")
+    B, K, D = det_boxes.shape
+    if B < 1 or K < 1 or D < 7:
+        raise ValueError(f"det_boxes: expected [B,K,D] with B, K >= 1 and D >= 7, got {tuple(det_boxes.shape)}")
+    if K > 1024:
+        raise ValueError(f"det_boxes: at most 1024 detections per scene (got K = {K})")
+    if B > 65535:
+        raise ValueError(f"det_boxes: at most 65535 scenes (got B = {B})")
+    _strict(det_scores, "det_scores", torch.float32, (B, K))
+    _strict(det_labels, "det_labels", torch.int32, (B, K))
+    if det_count is not None:
+        _strict(det_count, "det_count", torch.int32, (B,))
+    if isinstance(gt_boxes, torch.Tensor) and gt_boxes.dim() == 3 and gt_boxes.shape[0] != B:
+        raise ValueError(f"gt_boxes: expected {B} scenes like det_boxes, got {gt_boxes.shape[0]}")
+    _, G, Dg = _gt_shapes(gt_boxes, gt_labels)
+    if gt_ignore is not None:
+        _strict(gt_ignore, "gt_ignore", torch.int32, (B, G))
+    _strict(thr, "thr", torch.float32, (None, None), "[C,T] with 1 <= C <= 64 and 1 <= T <= 8")
+    C, T = thr.shape
+    if not (1 <= C <= 64 and 1 <= T <= 8):
+        raise ValueError(f"thr: expected [C,T] with 1 <= C <= 64 and 1 <= T <= 8, got {tuple(thr.shape)}")
+    dev = _head_devices((("det_boxes", det_boxes), ("det_scores", det_scores), ("det_labels", det_labels), ("det_count", det_count),
+                         ("gt_boxes", gt_boxes), ("gt_labels", gt_labels), ("gt_ignore", gt_ignore), ("thr", thr)))
+    outs = _outputs(det_match_output_spec(B, K, G, C, T), out, dev, "det_boxes")
+    a = _lib.DetMatchArgs()
+    a.struct_size = ctypes.sizeof(_lib.DetMatchArgs)
+    a.det_boxes, a.det_scores, a.det_labels, a.det_count = det_boxes.data_ptr(), det_scores.data_ptr(), det_labels.data_ptr(), _ptr(det_count)
+    a.gt_boxes, a.gt_labels, a.gt_ignore = (gt_boxes.data_ptr(), gt_labels.data_ptr(), _ptr(gt_ignore)) if G else (None, None, None)
+    a.thr = thr.data_ptr()
+    a.B, a.K, a.D, a.G, a.Dg, a.C, a.T, a.metric = B, K, D, G, Dg, C, T, _lib.DET_METRICS[metric]
+    for n, t in zip(DET_MATCH_OUTPUTS, outs):
+        setattr(a, n, t.data_ptr() if t.numel() else None)
+    with _timed("det_match", f"{metric}K{K}G{G}C{C}T{T}"):
+        check(lib().sad_det_match_f32(ctypes.byref(a), _stream()), "sad_det_match_f32")
+    return outs
+
+
+def det_ap_output_spec(C: int, T: int, points: int = 40, first: int = 1) -> tuple:
+    """((name, shape, dtype), ...) of ``det_ap``'s outputs, what its ``out=`` tuple is checked against."""
+    f32 = torch.float32
+    return (("ap", (C, T), f32), ("prec", (C, T, points - first + 1), f32), ("max_recall", (C, T), f32), ("n_det", (C, T), torch.int32))
+
+
+def det_ap_workspace(N: int, device) -> torch.Tensor:
+    """The workspace of ``det_ap(..., workspace=...)`` for a caller that keeps it: the N sort keys."""
+    return torch.empty(max(8 * int(N), 8), dtype=torch.uint8, device=device)
+
+
+def det_ap(scores: torch.Tensor, labels: torch.Tensor, code: torch.Tensor, n_gt: torch.Tensor, *, points: int = 40, first: int = 1,
+           floor: float = 0.0, out: Optional[tuple] = None, workspace: Optional[torch.Tensor] = None) -> tuple:
+    """Precision / recall and AP over accumulated rows (SPEC.md §36.2).  scores [N] f32, labels [N] int32, code [N,T] int32
+    (``det_match``'s, rows flattened), n_gt [C] int32 -> (ap [C,T] f32, prec [C,T,points-first+1] f32, max_recall [C,T] f32, n_det
+    [C,T] int32).  For (c, t) the rows of class c with code != -1, by (score descending, row ascending), give the running
+    precision and recall; ``prec[c,t,k-first]`` is the precision envelope at the first row whose recall reaches k / points
+    (0 when none does), ``ap`` the mean of max(prec - floor, 0) over k = first .. points, divided by 1 - floor; -1 for a class
+    without ground truth.  (40, 1, 0) is KITTI R40, (10, 0, 0) R11, (100, 11, 0.1) nuScenes' recall and precision floors.  The
+    order comes from one stable ``torch.sort`` on a key the library writes; everything else is two launches.  N * T < 2^31,
+    points <= 128.  No synchronisation; two calls are bit-equal."""
+    points, first, floor = int(points), int(first), _f32(floor)
+    if not 1 <= points <= 128:
+        raise ValueError(f"points: expected 1 .. 128, got {points}")
+    if not 0 <= first <= points:
+        raise ValueError(f"first: expected 0 .. points, got {first}")
+    if not 0.0 <= floor < 1.0:
+        raise ValueError(f"floor: expected a value in [0, 1), got {floor}")
+    _strict(scores, "scores", torch.float32, (None,), "[N]")
+    N = scores.shape[0]
+    _strict(labels, "labels", torch.int32, (N,))
+    _strict(code, "code", torch.int32, (N, None), f"[N,T] with N = {N} and 1 <= T <= 8")
+    T = code.shape[1]
+    if not 1 <= T <= 8:
+        raise ValueError(f"code: expected [N,T] with 1 <= T <= 8, got {tuple(code.shape)}")
+    _strict(n_gt, "n_gt", torch.int32, (None,), "[C] with 1 <= C <= 64")
+    C = n_gt.shape[0]
+    if not 1 <= C <= 64:
+        raise ValueError(f"n_gt: expected [C] with 1 <= C <= 64, got {tuple(n_gt.shape)}")
+    if N * T >= 1 << 31:
+        raise ValueError(f"code: N * T must stay below 2^31 (got {N} x {T})")
+    dev = _head_devices((("scores", scores), ("labels", labels), ("code", code), ("n_gt", n_gt)))
+    outs = _outputs(det_ap_output_spec(C, T, points, first), out, dev, "scores")
+    workspace = _workspace(max(8 * N, 8), workspace, dev, "ops.det_ap_workspace", 8)
+    keys = workspace[:8 * N].view(torch.int64)
+    with _timed("det_ap", f"N{N}C{C}T{T}"):
+        check(lib().sad_det_ap_keys_f32(scores.data_ptr(), labels.data_ptr(), N, C, keys.data_ptr(), _stream()), "sad_det_ap_keys_f32")
+        _unrecordable("det_ap: torch.sort")
+        skeys, perm = torch.sort(keys, stable=True)
+        a = _lib.DetApArgs()
+        a.struct_size = ctypes.sizeof(_lib.DetApArgs)
+        a.keys, a.perm, a.code = (skeys.data_ptr(), perm.data_ptr(), code.data_ptr()) if N else (None, None, None)
+        a.n_gt = n_gt.data_ptr()
+        a.N, a.C, a.T, a.points, a.first, a.floor = N, C, T, points, first, floor
+        for n, t in zip(DET_AP_OUTPUTS, outs):
+            setattr(a, n, t.data_ptr())
+        check(lib().sad_det_ap_f32(ctypes.byref(a), _stream()), "sad_det_ap_f32")
+    return outs
+
+
 # The fused MLP chains (PackedMLP / PackedMLPBf16, grouped_multi, rowscan_multi, the autotuner) live in mlp.py; they belong
 # to this operator surface, so their public names are re-exported here (the same objects).
 from .mlp import (GroupedCall, PackedMLP, PackedMLPBf16, check_workspace, choose_stage_assignment, cont_buffer,  # noqa: E402,F401

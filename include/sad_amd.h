@@ -1084,6 +1084,67 @@ typedef struct sad_gt_paste_args {
 size_t sad_gt_paste_workspace_bytes(int B, int Q, int total);   /* 0 outside 1 <= B <= 65535, 1 <= Q <= 512, total >= 0 */
 int sad_gt_paste_f32(const sad_gt_paste_args *args, sad_stream_t stream);
 
+/* SPEC.md §36 (additions of ABI 4 as well).  Detection evaluation on the device.
+ *
+ * §36.1 sad_det_match_f32: per scene, the live detections (k < det_count[b] clamped to [0,K], or K without det_count, and
+ * 0 <= det_labels < C) are walked in §23's rank order (score descending, index ascending) and assigned to the ground truth of
+ * their class, independently for each of the T thresholds thr[C,T] (device memory).  The pair value is §19.3's IoU (metric
+ * SAD_DET_IOU_BEV / SAD_DET_IOU3D, detection as a, ground truth as b: sad_boxes_iou_f32's bits; accepted iff v > thr, larger is
+ * better) or the centre distance sqrtf(dx*dx + dy*dy) (SAD_DET_DIST: accepted iff v < thr, smaller is better).  The best
+ * accepted box that is not ignored and not yet taken at t wins (lowest g on a tie): code 1, match g, value v, gt_det[g,t] = k;
+ * else the best accepted ignored box absorbs the detection: code -1, match g, value v (ignored boxes are never taken); else
+ * code 0, match -1, value 0.  A row that is not live gets (-1, -1, 0) and is never read beyond det_count.  A ground-truth label
+ * outside [0, C) is padding; gt_det is -1 where nothing took the box; n_gt[B,C] counts the valid boxes that are not ignored.
+ * G = 0 comes with NULL gt pointers.  One launch, one workgroup per scene, no workspace, no atomics on memory, every output
+ * fully written, nothing read back; two calls are bit-equal.  K, G <= 1024, C <= 64, T <= 8, B <= 65535, else
+ * SAD_EUNSUPPORTED.  NaN in any value that is read is undefined behaviour.
+ *
+ * §36.2 sad_det_ap_keys_f32 / sad_det_ap_f32: AP over N accumulated rows (scores[N], labels[N], code[N,T]).  keys[N] is the
+ * composite key (class, or C for a label outside [0, C)) << 32 | descending-ordered score bits, -0 as +0; the caller sorts it
+ * STABLY and passes the sorted keys with the permutation (int64 each).  For (c, t) the rows of class c with code != -1 in
+ * that order give tp_i, fp_i, rec_i = (float)tp_i / (float)n_gt[c], prec_i = (float)tp_i / (float)(tp_i + fp_i), env_i =
+ * max_{j >= i} prec_j; for k = first .. points, prec[c,t,k - first] = env at the first i with rec_i >= (float)k / (float)points,
+ * or 0; ap = (sum_k fmaxf(s_k - floor, 0)) / ((float)(points - first + 1) * (1.0f - floor)), summed in ascending k;
+ * max_recall = the last rec_i (0 without rows), n_det = the rows counted.  n_gt[c] == 0: ap = -1, prec = 0, max_recall = 0.
+ * N * T < 2^31, points <= 128, C <= 64, T <= 8, else SAD_EUNSUPPORTED; 0 <= first <= points, 0 <= floor < 1. */
+#define SAD_DET_IOU_BEV 0
+#define SAD_DET_IOU3D 1
+#define SAD_DET_DIST 2
+typedef struct sad_det_match_args {
+    size_t struct_size;   /* = sizeof(sad_det_match_args) */
+    const float *det_boxes;        /* [B,K,D] */
+    const float *det_scores;       /* [B,K] */
+    const int32_t *det_labels;     /* [B,K] */
+    const int32_t *det_count;      /* [B] or NULL */
+    const float *gt_boxes;         /* [B,G,Dg] or NULL when G == 0 */
+    const int32_t *gt_labels;      /* [B,G] or NULL when G == 0 */
+    const int32_t *gt_ignore;      /* [B,G] or NULL */
+    const float *thr;              /* [C,T] */
+    int B, K, D, G, Dg, C, T, metric;
+    int32_t *code;                 /* [B,K,T] */
+    int32_t *match;                /* [B,K,T] */
+    float *value;                  /* [B,K,T] */
+    int32_t *gt_det;               /* [B,G,T] or NULL when G == 0 */
+    int32_t *n_gt;                 /* [B,C] */
+} sad_det_match_args;
+int sad_det_match_f32(const sad_det_match_args *args, sad_stream_t stream);
+int sad_det_ap_keys_f32(const float *scores, const int32_t *labels, long long N, int C, long long *keys, sad_stream_t stream);
+typedef struct sad_det_ap_args {
+    size_t struct_size;   /* = sizeof(sad_det_ap_args) */
+    const long long *keys;         /* [N] sorted */
+    const long long *perm;         /* [N] the permutation that sorted them */
+    const int32_t *code;           /* [N,T] */
+    const int32_t *n_gt;           /* [C] */
+    long long N;
+    int C, T, points, first;
+    float floor;
+    float *ap;                     /* [C,T] */
+    float *prec;                   /* [C,T,points - first + 1] */
+    float *max_recall;             /* [C,T] */
+    int32_t *n_det;                /* [C,T] */
+} sad_det_ap_args;
+int sad_det_ap_f32(const sad_det_ap_args *args, sad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,7 +39,7 @@ _LAZY = {
     "sparse_conv_index": "ops", "sparse_conv": "ops", "sparse_to_dense": "ops", "PackedSparseWeight": "ops",
     "sparse_conv_index_transpose": "ops", "sparse_conv_grad_weight": "ops", "sparse_conv_grad_input": "ops",
     "sparse_max_pool": "ops", "sparse_max_pool_grad": "ops", "SparseMaxPool3d": "spconv", "SparseInverseConv3d": "spconv",
-    "SparseTensor": "spconv", "SubMConv3d": "spconv", "SparseConv3d": "spconv", "SparseSequential": "spconv",
+    "SparseTensor": "spconv", "Rulebook": "spconv", "SubMConv3d": "spconv", "SparseConv3d": "spconv", "SparseSequential": "spconv",
     "SAModuleMSG": "sa_module", "SAModule": "sa_module", "sa_module": "sa_module", "SAModuleMSGTrain": "sa_module",
     "SharedMLP": "shared_mlp", "BranchGroup": "shared_mlp", "grouped_mlp_grad": "mlp", "mlp_rows_grad": "mlp",
     "candidates": "ops", "candidates_grad": "ops", "prefix_rows_grad": "ops", "SADDetectorTrain": "detector_train",

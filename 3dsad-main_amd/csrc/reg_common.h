@@ -36,6 +36,24 @@ __device__ __forceinline__ f32x16 mma4(f32x16 acc, const float4 a, const float *
     return acc;
 }
 
+// columns c0 .. c0 + 3 of row `row` of base[][ld] for a 16-byte LDS store: zero for no row (row < 0) and beyond the `valid` columns; one
+// 16-byte load when `vec` (16-byte aligned rows, valid % 4 == 0), guarded scalar loads otherwise
+__device__ __forceinline__ float4 row_quad(const float *base, long long row, int ld, int c0, int valid, int vec) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (row >= 0 && c0 < valid) {
+        const float *src = base + (size_t)row * ld + c0;
+        if (vec) {
+            v = *reinterpret_cast<const float4 *>(src);
+        } else {
+            v.x = src[0];
+            if (c0 + 1 < valid) v.y = src[1];
+            if (c0 + 2 < valid) v.z = src[2];
+            if (c0 + 3 < valid) v.w = src[3];
+        }
+    }
+    return v;
+}
+
 __device__ __forceinline__ f32x16 bias_tile(const float *sb, int h) {   // sb: 32 biases of the tile (LDS)
     f32x16 t;
 #pragma unroll

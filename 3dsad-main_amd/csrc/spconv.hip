@@ -235,20 +235,8 @@ __global__ __launch_bounds__(256) void spconv_kernel(const ConvJob jb) {
         for (int idx = tid; idx < TR * CQ; idx += 256) {
             const int r = idx / CQ, q = idx - r * CQ;
             const int n = s_nbr[r * Kvol + kk];
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             const int c0 = 4 * q;
-            if (n >= 0 && c0 < jb.Cin) {
-                const float *src = jb.feat + (size_t)n * jb.Cin + c0;
-                if (jb.vec_in) {
-                    v = *reinterpret_cast<const float4 *>(src);
-                } else {
-                    v.x = src[0];
-                    if (c0 + 1 < jb.Cin) v.y = src[1];
-                    if (c0 + 2 < jb.Cin) v.z = src[2];
-                    if (c0 + 3 < jb.Cin) v.w = src[3];
-                }
-            }
-            *reinterpret_cast<float4 *>(s_x + r * LDX + c0) = v;
+            *reinterpret_cast<float4 *>(s_x + r * LDX + c0) = row_quad(jb.feat, n, jb.Cin, c0, jb.Cin, jb.vec_in);
         }
         __syncthreads();
         bool any = false;
@@ -348,7 +336,7 @@ __global__ __launch_bounds__(VX_THREADS) void dense_write_kernel(const float *__
 // ---- host side ----------------------------------------------------------------------------------------------------------
 using sad::al16;
 using sad::blocks_for;
-constexpr int SP_MAX_C = 256;
+#include "spconv_limits.h"
 
 // kernel / stride / padding / shapes of §21: subm ignores stride and padding (1 and K / 2)
 int sp_geo(const char *fn, const int *shape, const int *kernel, const int *stride, const int *padding, int subm, SpGeo &g) {
@@ -407,7 +395,7 @@ inline long long sp_max_sites(int Nv, const SpGeo &g) {
 int sp_sizes_ok(const char *fn, long long Nv, int B, const SpGeo &g, int subm) {
     SAD_REQUIRE(B >= 1 && B <= 65535, "%s: B must be in 1 .. 65535 (got %d)", fn, B);
     SAD_REQUIRE(Nv >= 0 && Nv <= (1 << 30), "%s: Nv must be in 0 .. 2^30 (got %lld)", fn, Nv);
-    if (Nv * g.Kvol >= (1LL << 31)) return sad::fail(SAD_EUNSUPPORTED, "%s: Nv * Kvol = %lld must be below 2^31", fn, Nv * g.Kvol);
+    if (int rc = sp_rows_ok(fn, "Nv", Nv, g.Kvol)) return rc;
     if (!subm && sp_max_sites((int)Nv, g) > (1LL << 30)) return sad::fail(SAD_EUNSUPPORTED, "%s: more than 2^30 possible output sites", fn);
     return SAD_OK;
 }
@@ -436,13 +424,6 @@ int launch_conv(const ConvJob &jb, hipStream_t st) {
     return sad::check_launch("sad_spconv_f32");
 }
 
-int sp_channels_ok(const char *fn, int Kvol, int Cin, int Cout) {
-    SAD_REQUIRE(Kvol >= 1 && Cin >= 1 && Cout >= 1, "%s: Kvol, Cin, Cout must be >= 1 (got %d, %d, %d)", fn, Kvol, Cin, Cout);
-    if (Kvol > 27) return sad::fail(SAD_EUNSUPPORTED, "%s: Kvol = %d (at most 27 = 3 x 3 x 3)", fn, Kvol);
-    if (Cin > SP_MAX_C || Cout > SP_MAX_C) return sad::fail(SAD_EUNSUPPORTED, "%s: Cin = %d, Cout = %d (at most %d each)", fn, Cin, Cout, SP_MAX_C);
-    return SAD_OK;
-}
-
 }  // namespace
 
 SAD_API int sad_spconv_workspace_bytes(int Nv, int B, const int *kernel, const int *stride, int subm, size_t *out) {
@@ -459,7 +440,7 @@ SAD_API int sad_spconv_workspace_bytes(int Nv, int B, const int *kernel, const i
 SAD_API int sad_spconv_index_subm(const int32_t *coors, const int32_t *offsets, int Nv, int B, const int *spatial_shape, const int *kernel,
                                   int32_t *nbr, void *workspace, sad_stream_t stream) {
     SAD_REQUIRE(offsets && workspace && spatial_shape && (Nv == 0 || (coors && nbr)), "sad_spconv_index_subm: NULL pointer");
-    SAD_REQUIRE(((uintptr_t)workspace & 15) == 0, "sad_spconv_index_subm: workspace must be 16-byte aligned");
+    SAD_REQUIRE(aligned16(workspace), "sad_spconv_index_subm: workspace must be 16-byte aligned");
     SpGeo g;
     if (int rc = sp_geo("sad_spconv_index_subm", spatial_shape, kernel, nullptr, nullptr, 1, g)) return rc;
     if (int rc = sp_sizes_ok("sad_spconv_index_subm", Nv, B, g, 1)) return rc;
@@ -475,7 +456,7 @@ SAD_API int sad_spconv_index_subm(const int32_t *coors, const int32_t *offsets, 
 SAD_API int sad_spconv_index_count(const int32_t *coors, const int32_t *offsets, int Nv, int B, const int *spatial_shape, const int *kernel,
                                    const int *stride, const int *padding, int32_t *out_offsets, void *workspace, sad_stream_t stream) {
     SAD_REQUIRE(offsets && out_offsets && workspace && spatial_shape && (Nv == 0 || coors), "sad_spconv_index_count: NULL pointer");
-    SAD_REQUIRE(((uintptr_t)workspace & 15) == 0, "sad_spconv_index_count: workspace must be 16-byte aligned");
+    SAD_REQUIRE(aligned16(workspace), "sad_spconv_index_count: workspace must be 16-byte aligned");
     SpGeo g;
     if (int rc = sp_geo("sad_spconv_index_count", spatial_shape, kernel, stride, padding, 0, g)) return rc;
     if (int rc = sp_sizes_ok("sad_spconv_index_count", Nv, B, g, 0)) return rc;
@@ -500,11 +481,11 @@ SAD_API int sad_spconv_index_fill(const int32_t *coors, const int32_t *offsets, 
     SAD_REQUIRE(offsets && out_offsets && workspace && spatial_shape && (Nv == 0 || coors) && (capacity == 0 || (out_coors && nbr)),
                 "sad_spconv_index_fill: NULL pointer");
     SAD_REQUIRE(capacity >= 0, "sad_spconv_index_fill: capacity must be >= 0 (got %d)", capacity);
-    SAD_REQUIRE(((uintptr_t)workspace & 15) == 0, "sad_spconv_index_fill: workspace must be 16-byte aligned");
+    SAD_REQUIRE(aligned16(workspace), "sad_spconv_index_fill: workspace must be 16-byte aligned");
     SpGeo g;
     if (int rc = sp_geo("sad_spconv_index_fill", spatial_shape, kernel, stride, padding, 0, g)) return rc;
     if (int rc = sp_sizes_ok("sad_spconv_index_fill", Nv, B, g, 0)) return rc;
-    if ((long long)capacity * g.Kvol >= (1LL << 31)) return sad::fail(SAD_EUNSUPPORTED, "sad_spconv_index_fill: capacity * Kvol must be below 2^31");
+    if (int rc = sp_rows_ok("sad_spconv_index_fill", "capacity", capacity, g.Kvol)) return rc;
     if (capacity == 0) return SAD_OK;
     const SpWs w = sp_ws(workspace, Nv, g, 0);
     const hipStream_t st = (hipStream_t)stream;
@@ -520,7 +501,7 @@ SAD_API int sad_spconv_index_fill(const int32_t *coors, const int32_t *offsets, 
 }
 
 SAD_API size_t sad_spconv_packed_floats(int Kvol, int Cin, int Cout) {
-    if (Kvol < 1 || Kvol > 27 || Cin < 1 || Cout < 1 || Cin > SP_MAX_C || Cout > SP_MAX_C) return 0;
+    if (Kvol < 1 || Kvol > SP_MAX_KVOL || Cin < 1 || Cout < 1 || Cin > SP_MAX_C || Cout > SP_MAX_C) return 0;
     const size_t nct = ((size_t)Cout + 31) / 32, KG = ((size_t)Cin + 7) / 8;
     return 32 * nct + (size_t)Kvol * nct * KG * 256;
 }
@@ -528,7 +509,7 @@ SAD_API size_t sad_spconv_packed_floats(int Kvol, int Cin, int Cout) {
 SAD_API int sad_spconv_pack_f32(const float *W, const float *bias, int Kvol, int Cin, int Cout, float *packed, sad_stream_t stream) {
     SAD_REQUIRE(W && packed, "sad_spconv_pack_f32: NULL pointer");
     if (int rc = sp_channels_ok("sad_spconv_pack_f32", Kvol, Cin, Cout)) return rc;
-    SAD_REQUIRE(((uintptr_t)packed & 15) == 0, "sad_spconv_pack_f32: packed must be 16-byte aligned");
+    SAD_REQUIRE(aligned16(packed), "sad_spconv_pack_f32: packed must be 16-byte aligned");
     const int nct = (Cout + 31) / 32, KG = (Cin + 7) / 8;
     const unsigned long long n = std::max<unsigned long long>((unsigned long long)Kvol * nct * KG * 64, 32ull * nct);
     hipLaunchKernelGGL(spconv_pack_kernel, dim3(blocks_for(n, VX_THREADS)), dim3(VX_THREADS), 0, (hipStream_t)stream, W, bias, Kvol, Cin, Cout, KG, nct,
@@ -541,26 +522,16 @@ SAD_API int sad_spconv_f32(const float *feat, const int32_t *nbr, const float *p
     SAD_REQUIRE(packed && (No == 0 || (nbr && out)) && (Nv == 0 || feat), "sad_spconv_f32: NULL pointer");
     SAD_REQUIRE(Nv >= 0 && No >= 0, "sad_spconv_f32: Nv and No must be >= 0 (got %d, %d)", Nv, No);
     if (int rc = sp_channels_ok("sad_spconv_f32", Kvol, Cin, Cout)) return rc;
-    if ((long long)No * Kvol >= (1LL << 31)) return sad::fail(SAD_EUNSUPPORTED, "sad_spconv_f32: No * Kvol must be below 2^31");
-    SAD_REQUIRE(((uintptr_t)packed & 15) == 0, "sad_spconv_f32: packed must be 16-byte aligned");
+    if (int rc = sp_rows_ok("sad_spconv_f32", "No", No, Kvol)) return rc;
+    SAD_REQUIRE(aligned16(packed), "sad_spconv_f32: packed must be 16-byte aligned");
     if (No == 0) return SAD_OK;
-    ConvJob jb;
-    jb.feat = feat;
-    jb.nbr = nbr;
-    jb.packed = packed;
-    jb.residual = residual;
-    jb.out = out;
-    jb.Nv = Nv;
-    jb.No = No;
-    jb.Kvol = Kvol;
-    jb.Cin = Cin;
-    jb.Cout = Cout;
+    ConvJob jb = {feat, nbr, packed, residual, out, Nv, No, Kvol, Cin, Cout};
     jb.KG = (Cin + 7) / 8;
     jb.nct = (Cout + 31) / 32;
     jb.LDX = 8 * jb.KG + 4;           // (16-byte aligned rows, four banks apart)
     jb.relu = relu != 0;
-    jb.vec_in = Cin % 4 == 0 && ((uintptr_t)feat & 15) == 0;
-    jb.vec_out = Cout % 4 == 0 && ((uintptr_t)out & 15) == 0 && (!residual || ((uintptr_t)residual & 15) == 0);
+    jb.vec_in = Cin % 4 == 0 && aligned16(feat);
+    jb.vec_out = Cout % 4 == 0 && aligned16(out) && aligned16(residual);
     const hipStream_t st = (hipStream_t)stream;
     if (jb.nct == 1) return launch_conv<4, 1, 1>(jb, st);     // 128 rows x 32 channels
     if (jb.nct == 2) return launch_conv<2, 1, 1>(jb, st);     //  64 rows x 64

@@ -24,7 +24,8 @@ namespace {
 #include "reg_common.h"
 
 using sad::blocks_for;
-constexpr int SG_MAX_C = 256, SG_TR = 64, SG_MAX_TILES = 1024, SG_BIAS_ROWS = 1024;
+#include "spconv_limits.h"
+constexpr int SG_TR = 64, SG_MAX_TILES = 1024, SG_BIAS_ROWS = 1024;
 
 // ---- transposed rulebook ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(VX_THREADS) void spt_fill_kernel(int32_t *__restrict__ nbrT, unsigned n, int32_t *__restrict__ collisions) {
@@ -137,19 +138,8 @@ __global__ __launch_bounds__(256) void spconv_grad_w_kernel(const GradJob jb) {
                 const long long row = row0 + r;
                 int n = row < jb.No ? jb.nbr[row * Kvol + kk] : -1;
                 if (n >= jb.Nv) n = -1;
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (n >= 0 && c0 < vci) {
-                    const float *src = jb.feat + (size_t)n * jb.Cin + ci0 + c0;
-                    if (jb.vec_f) {                              // (Cin % 4 == 0: vci is a multiple of 4 too)
-                        v = *reinterpret_cast<const float4 *>(src);
-                    } else {
-                        v.x = src[0];
-                        if (c0 + 1 < vci) v.y = src[1];
-                        if (c0 + 2 < vci) v.z = src[2];
-                        if (c0 + 3 < vci) v.w = src[3];
-                    }
-                }
-                *reinterpret_cast<float4 *>(s_f + r * LDF + c0) = v;
+                // (vec_f: Cin % 4 == 0, so vci is a multiple of 4 too)
+                *reinterpret_cast<float4 *>(s_f + r * LDF + c0) = row_quad(jb.feat + ci0, n, jb.Cin, c0, vci, jb.vec_f);
             }
             for (int idx = tid; idx < SG_TR * CQG; idx += 256) {
                 const int r = idx / CQG, c0 = 4 * (idx - r * CQG);
@@ -205,13 +195,6 @@ int launch_grad_w(const GradJob &jb, unsigned nranges, unsigned nblk, hipStream_
     return sad::check_launch("sad_spconv_grad_weight_f32");
 }
 
-int sg_channels_ok(const char *fn, int Kvol, int Cin, int Cout) {
-    SAD_REQUIRE(Kvol >= 1 && Cin >= 1 && Cout >= 1, "%s: Kvol, Cin, Cout must be >= 1 (got %d, %d, %d)", fn, Kvol, Cin, Cout);
-    if (Kvol > 27) return sad::fail(SAD_EUNSUPPORTED, "%s: Kvol = %d (at most 27 = 3 x 3 x 3)", fn, Kvol);
-    if (Cin > SG_MAX_C || Cout > SG_MAX_C) return sad::fail(SAD_EUNSUPPORTED, "%s: Cin = %d, Cout = %d (at most %d each)", fn, Cin, Cout, SG_MAX_C);
-    return SAD_OK;
-}
-
 inline int pow2_tiles(int t) { return t >= 3 ? 4 : t; }          // 1, 2, 3, 4 tiles -> 1, 2, 4, 4
 inline int lds_stride(int width) { return (width / 32) % 2 ? width : width + 32; }   // = 32 mod 64 floats
 
@@ -220,10 +203,9 @@ inline int lds_stride(int width) { return (width / 32) % 2 ? width : width + 32;
 SAD_API int sad_spconv_index_transpose(const int32_t *nbr, int No, int Nv, int Kvol, int32_t *nbrT, int32_t *collisions, sad_stream_t stream) {
     SAD_REQUIRE(collisions && (No == 0 || nbr) && (Nv == 0 || nbrT), "sad_spconv_index_transpose: NULL pointer");
     SAD_REQUIRE(No >= 0 && Nv >= 0, "sad_spconv_index_transpose: No and Nv must be >= 0 (got %d, %d)", No, Nv);
-    SAD_REQUIRE(Kvol >= 1, "sad_spconv_index_transpose: Kvol must be >= 1 (got %d)", Kvol);
-    if (Kvol > 27) return sad::fail(SAD_EUNSUPPORTED, "sad_spconv_index_transpose: Kvol = %d (at most 27 = 3 x 3 x 3)", Kvol);
-    if ((long long)No * Kvol >= (1LL << 31) || (long long)Nv * Kvol >= (1LL << 31))
-        return sad::fail(SAD_EUNSUPPORTED, "sad_spconv_index_transpose: No * Kvol and Nv * Kvol must be below 2^31");
+    if (int rc = sp_kvol_ok("sad_spconv_index_transpose", Kvol)) return rc;
+    if (int rc = sp_rows_ok("sad_spconv_index_transpose", "No", No, Kvol)) return rc;
+    if (int rc = sp_rows_ok("sad_spconv_index_transpose", "Nv", Nv, Kvol)) return rc;
     const hipStream_t st = (hipStream_t)stream;
     const unsigned nT = (unsigned)Nv * (unsigned)Kvol, n = (unsigned)No * (unsigned)Kvol;
     const unsigned fb = std::min(blocks_for(nT, VX_THREADS), 16384u);
@@ -239,7 +221,7 @@ SAD_API int sad_spconv_grad_weight_workspace_bytes(int No, int Kvol, int Cin, in
     SAD_REQUIRE(out, "sad_spconv_grad_weight_workspace_bytes: NULL out");
     *out = 0;
     SAD_REQUIRE(No >= 0, "sad_spconv_grad_weight_workspace_bytes: No must be >= 0 (got %d)", No);
-    if (int rc = sg_channels_ok("sad_spconv_grad_weight_workspace_bytes", Kvol, Cin, Cout)) return rc;
+    if (int rc = sp_channels_ok("sad_spconv_grad_weight_workspace_bytes", Kvol, Cin, Cout)) return rc;
     return SAD_OK;                                               // the partials meet in grad_W itself (float atomics): no scratch
 }
 
@@ -248,8 +230,8 @@ SAD_API int sad_spconv_grad_weight_f32(const float *feat, const int32_t *nbr, co
     (void)workspace;
     SAD_REQUIRE((grad_W || grad_bias) && (No == 0 || g) && (!grad_W || ((No == 0 || nbr) && (Nv == 0 || feat))), "sad_spconv_grad_weight_f32: NULL pointer");
     SAD_REQUIRE(Nv >= 0 && No >= 0, "sad_spconv_grad_weight_f32: Nv and No must be >= 0 (got %d, %d)", Nv, No);
-    if (int rc = sg_channels_ok("sad_spconv_grad_weight_f32", Kvol, Cin, Cout)) return rc;
-    if ((long long)No * Kvol >= (1LL << 31)) return sad::fail(SAD_EUNSUPPORTED, "sad_spconv_grad_weight_f32: No * Kvol must be below 2^31");
+    if (int rc = sp_channels_ok("sad_spconv_grad_weight_f32", Kvol, Cin, Cout)) return rc;
+    if (int rc = sp_rows_ok("sad_spconv_grad_weight_f32", "No", No, Kvol)) return rc;
     const hipStream_t st = (hipStream_t)stream;
     if ((grad_W && hipMemsetAsync(grad_W, 0, (size_t)Kvol * Cout * Cin * sizeof(float), st) != hipSuccess) ||
         (grad_bias && hipMemsetAsync(grad_bias, 0, (size_t)Cout * sizeof(float), st) != hipSuccess))
@@ -261,16 +243,7 @@ SAD_API int sad_spconv_grad_weight_f32(const float *feat, const int32_t *nbr, co
         hipLaunchKernelGGL(spg_bias_kernel, dim3(blocks_for((unsigned long long)No, SG_BIAS_ROWS)), dim3(256), 0, st, g, No, Cout, CP, grad_bias);
     }
     if (Nv == 0 || !grad_W) return sad::check_launch("sad_spconv_grad_weight_f32");      // (grad_W == NULL: a frozen weight pays for the column sums only)
-    GradJob jb;
-    jb.feat = feat;
-    jb.nbr = nbr;
-    jb.g = g;
-    jb.gw = grad_W;
-    jb.Nv = Nv;
-    jb.No = No;
-    jb.Kvol = Kvol;
-    jb.Cin = Cin;
-    jb.Cout = Cout;
+    GradJob jb = {feat, nbr, g, grad_W, Nv, No, Kvol, Cin, Cout};
     const int ncot = (Cout + 31) / 32, ncit = (Cin + 31) / 32;   // 32-channel tiles, 1 .. 8 each
     const int ncb = (ncot + 3) / 4;
     jb.nib = (ncit + 3) / 4;
@@ -289,8 +262,8 @@ SAD_API int sad_spconv_grad_weight_f32(const float *feat, const int32_t *nbr, co
     const int target = knob > 0 ? knob : std::max(1, 2 * sad::device_cus() / nblk);
     jb.tiles_per_wg = std::min(SG_MAX_TILES, std::max(1, (jb.ntiles + target - 1) / target));
     const unsigned nranges = (unsigned)((jb.ntiles + jb.tiles_per_wg - 1) / jb.tiles_per_wg);
-    jb.vec_f = Cin % 4 == 0 && ((uintptr_t)feat & 15) == 0;
-    jb.vec_g = Cout % 4 == 0 && ((uintptr_t)g & 15) == 0;
+    jb.vec_f = Cin % 4 == 0 && aligned16(feat);
+    jb.vec_g = Cout % 4 == 0 && aligned16(g);
     if (NT == 1) return launch_grad_w<1>(jb, nranges, (unsigned)nblk, st);
     if (NT == 2) return launch_grad_w<2>(jb, nranges, (unsigned)nblk, st);
     return launch_grad_w<4>(jb, nranges, (unsigned)nblk, st);

@@ -20,6 +20,7 @@
 
 namespace {
 
+#include "spconv_limits.h"
 constexpr int SP_THREADS = 256, SP_GROUP = 4, SP_MIN_ROWS = 16, SP_MAX_ROWS = 256, SP_ITEMS = 1024;
 
 // the tile's index rows -> LDS (entries of rows beyond `rows_total` are never read)
@@ -158,14 +159,12 @@ inline int tile_rows(long long rows, int CQ) {
 
 int pool_args_ok(const char *fn, int Nv, int No, int Kvol, int C) {
     SAD_REQUIRE(Nv >= 0 && No >= 0, "%s: Nv and No must be >= 0 (got %d, %d)", fn, Nv, No);
-    SAD_REQUIRE(Kvol >= 1 && C >= 1, "%s: Kvol and C must be >= 1 (got %d, %d)", fn, Kvol, C);
-    if (Kvol > 27) return sad::fail(SAD_EUNSUPPORTED, "%s: Kvol = %d (at most 27 = 3 x 3 x 3)", fn, Kvol);
+    SAD_REQUIRE(C >= 1, "%s: C must be >= 1 (got %d)", fn, C);
+    if (int rc = sp_kvol_ok(fn, Kvol)) return rc;
     if ((long long)Nv * C >= (1LL << 31) || (long long)No * C >= (1LL << 31))
         return sad::fail(SAD_EUNSUPPORTED, "%s: Nv * C and No * C must be below 2^31 (got %d, %d rows of %d)", fn, Nv, No, C);
     return SAD_OK;
 }
-
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 

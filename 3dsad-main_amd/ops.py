@@ -919,6 +919,17 @@ def sparse_conv_index(coors: torch.Tensor, offsets: torch.Tensor, spatial_shape,
     return out_coors, out_offsets, nbr
 
 
+# the limits of the sparse-convolution family (csrc/spconv_limits.h): 1 <= Kvol <= 27 (3 x 3 x 3), 1 <= Cin, Cout <= 256
+SPARSE_MAX_KVOL, SPARSE_MAX_C = 27, 256
+
+
+def _sparse_limits(what: str, kvol: int, cin: Optional[int] = None, cout: Optional[int] = None) -> None:
+    if not 1 <= kvol <= SPARSE_MAX_KVOL:
+        raise ValueError(f"{what}: Kvol = {kvol} must be in 1 .. {SPARSE_MAX_KVOL}")
+    if cin is not None and not (1 <= cin <= SPARSE_MAX_C and 1 <= cout <= SPARSE_MAX_C):
+        raise ValueError(f"{what}: channels must be in 1 .. {SPARSE_MAX_C}, got {cin} -> {cout}")
+
+
 class PackedSparseWeight:
     """``W [Kvol,Cout,Cin]`` (+ ``bias [Cout]``) in the fragment layout the convolution kernel reads (``sad_spconv_pack_f32``);
     BatchNorm is folded into W and bias beforehand, as for ``PackedMLP``."""
@@ -930,11 +941,10 @@ class PackedSparseWeight:
             bias = _need(bias, "bias", torch.float32, 1)
             if bias.shape[0] != self.cout or bias.device != weight.device:
                 raise ValueError("bias: [Cout] on the device of weight expected")
-        if not (1 <= self.kvol <= 27):
-            raise ValueError(f"weight: Kvol = {self.kvol} must be in 1 .. 27")
+        _sparse_limits("weight", self.kvol)
         n = lib().sad_spconv_packed_floats(self.kvol, self.cin, self.cout)
         if n == 0:
-            raise RuntimeError(f"sparse_conv: Cin = {self.cin}, Cout = {self.cout} unsupported (1 .. 256 each)")
+            raise RuntimeError(f"sparse_conv: Cin = {self.cin}, Cout = {self.cout} unsupported (1 .. {SPARSE_MAX_C} each)")
         self.has_bias = bias is not None
         self.packed = torch.empty((n,), dtype=torch.float32, device=weight.device)
         check(lib().sad_spconv_pack_f32(weight.data_ptr(), _ptr(bias), self.kvol, self.cin, self.cout,
@@ -983,8 +993,7 @@ def sparse_conv_index_transpose(nbr: torch.Tensor, Nv: int):
     No, Kvol = nbr.shape
     if Nv < 0:
         raise ValueError(f"Nv={Nv} must be >= 0")
-    if not (1 <= Kvol <= 27):
-        raise ValueError(f"nbr: Kvol = {Kvol} must be in 1 .. 27")
+    _sparse_limits("nbr", Kvol)
     nbrT = torch.empty((Nv, Kvol), dtype=torch.int32, device=nbr.device)
     collisions = torch.empty((), dtype=torch.int32, device=nbr.device)
     with _timed("spconv_index", f"transpose n{No}k{Kvol}"):
@@ -1008,8 +1017,7 @@ def sparse_conv_grad_weight(feat: torch.Tensor, nbr: torch.Tensor, g: torch.Tens
         raise ValueError(f"g: one row per row of nbr expected, got {tuple(g.shape)} for nbr {tuple(nbr.shape)}")
     if nbr.device != dev or g.device != dev:
         raise ValueError("feat, nbr and g must be on one device")
-    if not (1 <= kvol <= 27 and 1 <= cin <= 256 and 1 <= cout <= 256):
-        raise ValueError(f"Kvol = {kvol} must be in 1 .. 27, Cin = {cin} and Cout = {cout} in 1 .. 256")
+    _sparse_limits("sparse_conv_grad_weight", kvol, cin, cout)
     if not (bias or weight):
         raise ValueError("sparse_conv_grad_weight: nothing asked for (bias=False, weight=False)")
     nbytes = _bytes("sad_spconv_grad_weight_workspace_bytes", No, kvol, cin, cout)
@@ -1038,8 +1046,7 @@ def sparse_conv_grad_input(g: torch.Tensor, nbrT: torch.Tensor, weight) -> torch
 
 
 def _pool_sizes(Nv: int, No: int, Kvol: int, C: int, what: str) -> None:
-    if not (1 <= Kvol <= 27):
-        raise ValueError(f"{what}: Kvol = {Kvol} must be in 1 .. 27")
+    _sparse_limits(what, Kvol)
     if C < 1:
         raise ValueError(f"{what}: at least one channel expected")
     if Nv * C >= 2 ** 31 or No * C >= 2 ** 31:

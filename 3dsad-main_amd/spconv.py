@@ -4,15 +4,16 @@ decoder side of a sparse U-Net: ``SparseMaxPool3d`` (§22.1) and ``SparseInverse
 its partner layer (named by ``indice_key``) came from, by that layer's own rulebook.
 
 A ``SparseTensor`` is ``feat [Nv,C]`` f32, ``coors [Nv,3]`` int32 (z,y,x), ``offsets [B+1]`` int32 (all on the GPU) and a host
-``spatial_shape`` (Gz,Gy,Gx).  It carries a rulebook cache: layers that name the same ``indice_key`` (the submanifold layers of
-one resolution) build ``nbr`` once.  The forward is deterministic and equal to the reference restatement under ``==``; there is
-no CPU path.
+``spatial_shape`` (Gz,Gy,Gx).  It carries a rulebook cache, ``rulebooks``: one ``Rulebook`` record per ``indice_key``, shared by
+every tensor derived from it (``derive``), so layers that name the same key (the submanifold layers of one resolution) build
+``nbr`` once; a layer without a key builds an uncached record.  The forward is deterministic and equal to the reference
+restatement under ``==``; there is no CPU path.
 
 Training (SPEC.md §21.4).  Parameters are created with ``requires_grad=False`` and the layers then run the plain forward
 under ``no_grad``; ``module.requires_grad_(True)`` (or an input whose ``feat`` requires grad) routes a layer through
 ``autograd.SparseConv``: grad_W / grad_bias by the weight-gradient kernel (float atomics: within the §21.4 bound, not bit-equal
 from run to run), grad_feat by the forward kernel over the transposed rulebook, which is built at the first backward that needs
-it and cached per ``indice_key`` beside the rulebook (``SparseTensor.transposed``; its collision count is read back once).
+it and kept on the layer's ``Rulebook`` (``Rulebook.transposed()``; its collision count is read back once).
 ``dense()`` / ``bev()`` are differentiable the same way.  A scene that holds a coordinate twice has no gradient through a
 submanifold layer (``ValueError`` in backward); ``from_voxels`` never produces one."""
 from typing import Optional, Sequence
@@ -24,9 +25,28 @@ from . import autograd, ops
 from .shared_mlp import wants_grad
 
 
+class Rulebook:
+    """What one layer geometry made of one input tensor.  ``geometry`` = (subm, in_shape, kernel, stride, padding); ``in_coors`` /
+    ``in_offsets`` are the input's own tensor objects, which an inverse layer (§22.3) hands on."""
+
+    def __init__(self, geometry, in_coors, in_offsets, out_coors, out_offsets, nbr, out_shape, nbrT=None, collisions=None):
+        self.geometry, self.in_coors, self.in_offsets = geometry, in_coors, in_offsets
+        self.out_coors, self.out_offsets, self.nbr, self.out_shape = out_coors, out_offsets, nbr, out_shape
+        self.nbrT, self.collisions = nbrT, collisions
+
+    def transposed(self):
+        """(nbrT, collisions): the transposed rulebook of §21.4, built (one synchronisation) for whichever asks first, the backward
+        of the layer that owns the rulebook or the forward of its inverse, then kept."""
+        if self.nbrT is None:
+            with torch.no_grad():
+                self.nbrT, col = ops.sparse_conv_index_transpose(self.nbr, self.in_coors.shape[0])
+            self.collisions = int(col.item())
+        return self.nbrT, self.collisions
+
+
 class SparseTensor:
     def __init__(self, feat: torch.Tensor, coors: torch.Tensor, offsets: torch.Tensor, spatial_shape: Sequence[int],
-                 rulebooks: Optional[dict] = None, transposed: Optional[dict] = None, sources: Optional[dict] = None):
+                 rulebooks: Optional[dict] = None):
         if feat.dim() != 2 or coors.dim() != 2 or coors.shape[1] != 3 or coors.shape[0] != feat.shape[0]:
             raise ValueError(f"feat [Nv,C] and coors [Nv,3] expected, got {tuple(feat.shape)} and {tuple(coors.shape)}")
         if offsets.dim() != 1 or offsets.shape[0] < 2:
@@ -35,13 +55,7 @@ class SparseTensor:
             raise ValueError(f"spatial_shape = (Gz,Gy,Gx), all >= 1, expected, got {spatial_shape!r}")
         self.feat, self.coors, self.offsets = feat, coors, offsets
         self.spatial_shape = tuple(int(g) for g in spatial_shape)
-        # indice_key -> (geometry, in_coors, out_coors, out_offsets, nbr, out_shape); shared by every tensor derived from this one
-        self.rulebooks = {} if rulebooks is None else rulebooks
-        # indice_key -> (nbr, nbrT, collisions): the transposed rulebook of §21.4, made by the first backward that needs it; shared likewise
-        self.transposed = {} if transposed is None else transposed
-        # indice_key -> (in_offsets,): what an inverse layer (§22.3) needs of its partner's INPUT tensor beside the rulebook entry
-        # (which holds in_coors and, in its geometry, the input's spatial_shape); shared likewise
-        self.sources = {} if sources is None else sources
+        self.rulebooks = {} if rulebooks is None else rulebooks     # indice_key -> Rulebook; shared by every tensor derived from this one
 
     @property
     def batch_size(self) -> int:
@@ -63,8 +77,13 @@ class SparseTensor:
         return cls(feat.reshape(B * V, C)[keep].to(torch.float32).contiguous(), coors.reshape(B * V, 3)[keep].to(torch.int32).contiguous(),
                    offsets, spatial_shape)
 
+    def derive(self, feat: torch.Tensor, coors=None, offsets=None, spatial_shape=None) -> "SparseTensor":
+        """A tensor that shares this one's rulebook cache; what is not given is this one's."""
+        return SparseTensor(feat, self.coors if coors is None else coors, self.offsets if offsets is None else offsets,
+                            self.spatial_shape if spatial_shape is None else spatial_shape, self.rulebooks)
+
     def replace_feature(self, feat: torch.Tensor) -> "SparseTensor":
-        return SparseTensor(feat, self.coors, self.offsets, self.spatial_shape, self.rulebooks, self.transposed, self.sources)
+        return self.derive(feat)
 
     def dense(self) -> torch.Tensor:
         """-> [B,C,Gz,Gy,Gx], zero where no voxel is (§21.3); differentiable with respect to ``feat`` (§21.4)."""
@@ -79,35 +98,20 @@ class SparseTensor:
         return d.view(B, C * Gz, Gy, Gx)
 
 
-def _rulebook(x: SparseTensor, indice_key, subm: bool, kernel_size, stride, padding):
-    """(out_coors, out_offsets, nbr, out_shape) of a layer geometry on ``x``, built once per ``indice_key``."""
+def _rulebook(x: SparseTensor, indice_key, subm: bool, kernel_size, stride, padding) -> Rulebook:
+    """The ``Rulebook`` of a layer geometry on ``x``, built once per ``indice_key`` (uncached without one)."""
     geo = (subm, x.spatial_shape, kernel_size, stride, padding)
-    hit = x.rulebooks.get(indice_key) if indice_key is not None else None
-    if hit is not None:
-        if hit[0] != geo or hit[1] is not x.coors:
+    rb = x.rulebooks.get(indice_key) if indice_key is not None else None
+    if rb is not None:
+        if rb.geometry != geo or rb.in_coors is not x.coors:
             raise ValueError(f"indice_key {indice_key!r} was built for another geometry or another sparse tensor")
-        x.sources.setdefault(indice_key, (x.offsets,))
-        return hit[2:]
+        return rb
     out_shape = ops.sparse_conv_geometry(x.spatial_shape, kernel_size, stride, padding, subm)[4]
-    out_coors, out_offsets, nbr = ops.sparse_conv_index(x.coors, x.offsets, x.spatial_shape, kernel_size, stride, padding, subm)
+    rb = Rulebook(geo, x.coors, x.offsets, *ops.sparse_conv_index(x.coors, x.offsets, x.spatial_shape, kernel_size, stride, padding, subm),
+                  out_shape)
     if indice_key is not None:
-        x.rulebooks[indice_key] = (geo, x.coors, out_coors, out_offsets, nbr, out_shape)
-        x.sources[indice_key] = (x.offsets,)
-    return out_coors, out_offsets, nbr, out_shape
-
-
-def _transposed(x: SparseTensor, indice_key, nbr: torch.Tensor, Nv: int):
-    """(nbrT, collisions) of the rulebook ``nbr`` over ``Nv`` input rows; cached under ``indice_key`` (one synchronisation at the
-    build), whichever layer asks first: the backward of the layer that owns the rulebook or the forward of its inverse."""
-    hit = x.transposed.get(indice_key) if indice_key is not None else None
-    if hit is not None and hit[0] is nbr:
-        return hit[1:]
-    with torch.no_grad():
-        nbrT, col = ops.sparse_conv_index_transpose(nbr, Nv)
-    col = int(col.item())
-    if indice_key is not None:
-        x.transposed[indice_key] = (nbr, nbrT, col)
-    return nbrT, col
+        x.rulebooks[indice_key] = rb
+    return rb
 
 
 class _SparseConvBase(nn.Module):
@@ -119,11 +123,10 @@ class _SparseConvBase(nn.Module):
         # (shape checks on fixed sizes; the layer's own geometry is checked here so that a bad layer fails at construction)
         _, self.kernel_size, self.stride, self.padding, _ = ops.sparse_conv_geometry((3, 3, 3), kernel_size, stride, padding, self.subm)
         self.in_channels, self.out_channels = int(in_channels), int(out_channels)
-        if not (1 <= self.in_channels <= 256 and 1 <= self.out_channels <= 256):
-            raise ValueError(f"channels must be in 1 .. 256, got {in_channels} -> {out_channels}")
+        kvol = self.kernel_size[0] * self.kernel_size[1] * self.kernel_size[2]
+        ops._sparse_limits(type(self).__name__, kvol, self.in_channels, self.out_channels)
         self.relu = bool(relu)
         self.indice_key = indice_key
-        kvol = self.kernel_size[0] * self.kernel_size[1] * self.kernel_size[2]
         self.weight = nn.Parameter(torch.empty((kvol, self.out_channels, self.in_channels), dtype=torch.float32), requires_grad=False)
         self.bias = nn.Parameter(torch.zeros((self.out_channels,), dtype=torch.float32), requires_grad=False) if bias else None
         nn.init.uniform_(self.weight, -(kvol * in_channels) ** -0.5, (kvol * in_channels) ** -0.5)
@@ -150,11 +153,7 @@ class _SparseConvBase(nn.Module):
             self._packed_t = (key, ops.PackedSparseWeight(self.weight.data.transpose(1, 2).contiguous(), None))
         return self._packed_t[1]
 
-    def transposed(self, x: SparseTensor, nbr: torch.Tensor):
-        """(nbrT, collisions) of this layer's rulebook on ``x``; cached under ``indice_key`` (one synchronisation at the build)."""
-        return _transposed(x, self.indice_key, nbr, x.feat.shape[0])
-
-    def rulebook(self, x: SparseTensor):
+    def rulebook(self, x: SparseTensor) -> Rulebook:
         return _rulebook(x, self.indice_key, self.subm, self.kernel_size, self.stride, self.padding)
 
     def forward(self, x: SparseTensor, residual: Optional[torch.Tensor] = None) -> SparseTensor:
@@ -162,13 +161,12 @@ class _SparseConvBase(nn.Module):
             raise ValueError(f"{self.in_channels} input channels expected, got {x.feat.shape[1]}")
         train = wants_grad(x.feat, self.weight, self.bias, residual)
         with torch.no_grad():
-            out_coors, out_offsets, nbr, out_shape = self.rulebook(x)
+            rb = self.rulebook(x)
             if not train:
-                out = ops.sparse_conv(x.feat, nbr, self.packed(), None, residual, self.relu)
+                out = ops.sparse_conv(x.feat, rb.nbr, self.packed(), None, residual, self.relu)
         if train:
-            out = autograd.sparse_conv(x.feat, self.weight, self.bias, residual, nbr, self.relu, lambda: self.transposed(x, nbr),
-                                       self.packed(), self.packed_t)
-        return SparseTensor(out, out_coors, out_offsets, out_shape, x.rulebooks, x.transposed, x.sources)
+            out = autograd.sparse_conv(x.feat, self.weight, self.bias, residual, rb.nbr, self.relu, rb.transposed, self.packed(), self.packed_t)
+        return x.derive(out, rb.out_coors, rb.out_offsets, rb.out_shape)
 
     def extra_repr(self) -> str:
         return (f"{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, padding={self.padding}, "
@@ -205,39 +203,35 @@ class SparseInverseConv3d(_SparseConvBase):
         super().__init__(in_channels, out_channels, kernel_size, 1, 0, bias, relu, indice_key)
         self.stride = self.padding = None          # the partner's, found with its rulebook
 
-    def rulebook(self, x: SparseTensor):
-        """-> (in_coors, in_offsets, in_shape, nbr) of the partner layer's rulebook, after the checks of §22.3."""
+    def rulebook(self, x: SparseTensor) -> Rulebook:
+        """-> the partner layer's rulebook, after the checks of §22.3."""
         key = self.indice_key
-        hit = x.rulebooks.get(key)
-        if hit is None:
+        rb = x.rulebooks.get(key)
+        if rb is None:
             raise ValueError(f"SparseInverseConv3d: no rulebook under indice_key {key!r} (the strided layer it inverts must run first, on "
                              "a tensor this one derives from)")
-        (subm, in_shape, kernel_size, _, _), in_coors, out_coors, _, nbr, _ = hit
+        subm, _, kernel_size, _, _ = rb.geometry
         if subm:
             raise ValueError(f"SparseInverseConv3d: indice_key {key!r} names a submanifold rulebook; a strided layer is expected")
         if kernel_size != self.kernel_size:
             raise ValueError(f"SparseInverseConv3d: kernel_size {self.kernel_size} differs from {kernel_size} of indice_key {key!r}")
-        if x.coors is not out_coors:
+        if x.coors is not rb.out_coors:
             raise ValueError(f"SparseInverseConv3d: the input is not the tensor that the layer of indice_key {key!r} produced")
-        src = x.sources.get(key)
-        if src is None:
-            raise ValueError(f"SparseInverseConv3d: the input carries the rulebook of indice_key {key!r} but not its partner's offsets "
-                             "(a SparseTensor built by hand must be given the `sources` dict beside `rulebooks`)")
-        return in_coors, src[0], in_shape, nbr
+        return rb
 
     def forward(self, x: SparseTensor, residual: Optional[torch.Tensor] = None) -> SparseTensor:
         if x.feat.shape[1] != self.in_channels:
             raise ValueError(f"{self.in_channels} input channels expected, got {x.feat.shape[1]}")
-        in_coors, in_offsets, in_shape, nbr = self.rulebook(x)
+        rb = self.rulebook(x)
         train = wants_grad(x.feat, self.weight, self.bias, residual)
         with torch.no_grad():
-            nbrT, collisions = _transposed(x, self.indice_key, nbr, in_coors.shape[0])
+            nbrT, collisions = rb.transposed()
             if not train:
                 out = ops.sparse_conv(x.feat, nbrT, self.packed(), None, residual, self.relu)
         if train:
             # (the roles of §21.4 swapped: the rulebook of this convolution is nbrT, and its transpose is nbr when nothing collided)
-            out = autograd.sparse_conv(x.feat, self.weight, self.bias, residual, nbrT, self.relu, (nbr, collisions), self.packed(), self.packed_t)
-        return SparseTensor(out, in_coors, in_offsets, in_shape, x.rulebooks, x.transposed, x.sources)
+            out = autograd.sparse_conv(x.feat, self.weight, self.bias, residual, nbrT, self.relu, (rb.nbr, collisions), self.packed(), self.packed_t)
+        return x.derive(out, rb.in_coors, rb.in_offsets, rb.geometry[1])
 
     def extra_repr(self) -> str:
         return (f"{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, indice_key={self.indice_key!r}, "
@@ -255,21 +249,18 @@ class SparseMaxPool3d(nn.Module):
                                                                                       kernel_size if stride is None else stride, padding, False)
         self.indice_key = indice_key
 
-    def rulebook(self, x: SparseTensor):
+    def rulebook(self, x: SparseTensor) -> Rulebook:
         return _rulebook(x, self.indice_key, False, self.kernel_size, self.stride, self.padding)
-
-    def transposed(self, x: SparseTensor, nbr: torch.Tensor):
-        return _transposed(x, self.indice_key, nbr, x.feat.shape[0])
 
     def forward(self, x: SparseTensor) -> SparseTensor:
         train = wants_grad(x.feat)
         with torch.no_grad():
-            out_coors, out_offsets, nbr, out_shape = self.rulebook(x)
+            rb = self.rulebook(x)
             if not train:
-                out = ops.sparse_max_pool(x.feat, nbr)[0]
+                out = ops.sparse_max_pool(x.feat, rb.nbr)[0]
         if train:
-            out = autograd.sparse_max_pool(x.feat, nbr, lambda: self.transposed(x, nbr))
-        return SparseTensor(out, out_coors, out_offsets, out_shape, x.rulebooks, x.transposed, x.sources)
+            out = autograd.sparse_max_pool(x.feat, rb.nbr, rb.transposed)
+        return x.derive(out, rb.out_coors, rb.out_offsets, rb.out_shape)
 
     def extra_repr(self) -> str:
         return f"kernel_size={self.kernel_size}, stride={self.stride}, padding={self.padding}, indice_key={self.indice_key!r}"

@@ -144,12 +144,12 @@ def test_sequential_layer_by_layer_and_rulebook_cache(dev, orc):
     _eq_f(y.feat, f, "SparseSequential")
     cached = x0.rulebooks["subm1"]
     rebuilt = ops.sparse_conv_index(x0.coors, x0.offsets, G, 3, subm=True)
-    assert torch.equal(cached[4], rebuilt[2]) and cached[2] is x0.coors
+    assert torch.equal(cached.nbr, rebuilt[2]) and cached.out_coors is x0.coors
     y1 = net[1](net[0](x0))
     assert x0.rulebooks["subm1"] is cached and y1.coors is x0.coors
     d = x0.rulebooks["down1"]
     r2 = ops.sparse_conv_index(x0.coors, x0.offsets, G, 3, 2, 1)
-    assert torch.equal(d[2], r2[0]) and torch.equal(d[3], r2[1]) and torch.equal(d[4], r2[2])
+    assert torch.equal(d.out_coors, r2[0]) and torch.equal(d.out_offsets, r2[1]) and torch.equal(d.nbr, r2[2])
     with pytest.raises(ValueError):
         SubMConv3d(16, 16, (1, 3, 3), indice_key="subm1").to(dev)(net[0](x0))          # the key belongs to another geometry
     # residual input of a layer

@@ -248,7 +248,7 @@ def _net(dev):
 def test_autograd_sequential_end_to_end(dev, orc, monkeypatch):
     import torch
     from sad_amd import ops
-    from sad_amd.spconv import SparseTensor
+    from sad_amd.spconv import Rulebook, SparseTensor
     coors, off, G = sc.FAMILIES["synth"][0]()
     net = _net(dev).requires_grad_(True)
     feat = sc.make_feat(len(coors), 4, 9)
@@ -282,10 +282,10 @@ def test_autograd_sequential_end_to_end(dev, orc, monkeypatch):
         assert col == 0
         grad = gref.grad_input(g, nbrT, W)
     _eq_f(x0.feat.grad, grad, "input gradient")
-    # the transposed rulebooks sit beside the rulebooks, whose entries and keys are what they were
-    assert sorted(x0.rulebooks) == ["down1", "subm1", "subm2"] and sorted(x0.transposed) == ["down1", "subm1", "subm2"]
-    assert all(len(v) == 6 for v in x0.rulebooks.values())
-    cachedT = {k: v[1] for k, v in x0.transposed.items()}
+    # the transposed rulebooks sit on the records of the rulebooks, whose keys are what they were
+    assert sorted(x0.rulebooks) == ["down1", "subm1", "subm2"]
+    assert all(isinstance(v, Rulebook) and v.nbrT is not None for v in x0.rulebooks.values())
+    cachedT = {k: v.nbrT for k, v in x0.rulebooks.items()}
     _eq_int(cachedT["subm1"], gref.index_transpose_vec(steps[0][2], len(coors))[0], "cached nbrT")
     # a second backward on a fresh forward reuses them; frozen parameters cost no weight-gradient call, an input without
     # requires_grad no input-gradient call for the first layer
@@ -300,7 +300,7 @@ def test_autograd_sequential_end_to_end(dev, orc, monkeypatch):
     net(x0).feat.sum().backward()
     assert calls == {"w": 3, "i": 3, "t": 0}, calls
     assert net[1].weight.grad is None and net[1].bias.grad is None and net[0].weight.grad is not None
-    assert all(x0.transposed[k][1] is cachedT[k] for k in cachedT)
+    assert all(x0.rulebooks[k].nbrT is cachedT[k] for k in cachedT)
     # an in-place weight update between two forwards is seen (the packs are re-made), with and without gradients
     before = net(x0).feat.detach().clone()
     with torch.no_grad():
@@ -312,7 +312,7 @@ def test_autograd_sequential_end_to_end(dev, orc, monkeypatch):
         _eq_f(net[0](x0).feat, f1, "layer 0 after an in-place update (no_grad)")
     assert not torch.equal(net(x0).feat.detach(), before)
     # ... and by the packed W^T of the input gradient
-    xg = SparseTensor(_t(feat, dev, True), x0.coors, x0.offsets, G, x0.rulebooks, x0.transposed)
+    xg = SparseTensor(_t(feat, dev, True), x0.coors, x0.offsets, G, x0.rulebooks)
     go = sc.make_feat(len(coors), 16, 3)
     net[0](xg).feat.backward(_t(go, dev))
     g = gref.relu_mask(go, f1, True)
@@ -329,7 +329,7 @@ def test_default_path_untouched_and_non_default_stream(dev, orc):
     feat = sc.make_feat(len(coors), 4, 2)
     x = SparseTensor(_t(feat, dev), _t(coors, dev), _t(off, dev), G)
     y = net[0](x)
-    assert y.feat.requires_grad is False and y.feat.grad_fn is None and not x.transposed
+    assert y.feat.requires_grad is False and y.feat.grad_fn is None and all(v.nbrT is None for v in x.rulebooks.values())
     nbr = ref.index_vec(coors, off, G, (3, 3, 3), subm=True)[2]
     _eq_f(y.feat, ref.conv(feat, nbr, net[0].weight.cpu().numpy(), net[0].bias.cpu().numpy(), None, True), "default path")
     assert x.dense().requires_grad is False

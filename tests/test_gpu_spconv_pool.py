@@ -218,7 +218,7 @@ def test_collisions_refuse_backward_not_forward(dev):
     y.feat.backward(_t(go, dev))
     nbr = ref.index_vec(coors, off, G, (3, 3, 3), (2, 2, 2), (1, 1, 1))[2]
     nbrT, col = gref.index_transpose_vec(nbr, len(coors))
-    assert col == 0 and x.transposed["p"][2] == 0
+    assert col == 0 and x.rulebooks["p"].collisions == 0
     _eq_bits(x.feat.grad, pref.max_pool_grad_loop(go, pref.max_pool_vec(feat, nbr)[1], nbrT), "layer backward on duplicates (strided)")
 
 
@@ -288,6 +288,11 @@ def test_inverse_conv_every_channel_pair(dev, orc, cin, cout):
 
 
 # ---- layers ----------------------------------------------------------------------------------------------------------
+def _with_nbrT(x):
+    """The keys whose record holds a transposed rulebook."""
+    return sorted(k for k, v in x.rulebooks.items() if v.nbrT is not None)
+
+
 def _count(monkeypatch, mod, fn, calls):
     real = getattr(mod, fn)
     monkeypatch.setattr(mod, fn, lambda *a, **k: (calls.__setitem__(fn, calls.get(fn, 0) + 1), real(*a, **k))[1])
@@ -296,7 +301,7 @@ def _count(monkeypatch, mod, fn, calls):
 def test_layer_pairing(dev, orc, monkeypatch):
     import torch
     from sad_amd import ops
-    from sad_amd.spconv import SparseConv3d, SparseInverseConv3d, SparseMaxPool3d, SparseTensor, SubMConv3d
+    from sad_amd.spconv import Rulebook, SparseConv3d, SparseInverseConv3d, SparseMaxPool3d, SparseTensor, SubMConv3d
     coors, off, G = sc.FAMILIES["random030"][0]()
     Nv = len(coors)
     feat = sc.make_feat(Nv, 4, 0)
@@ -322,23 +327,23 @@ def test_layer_pairing(dev, orc, monkeypatch):
         inv(x1.replace_feature(torch.zeros((Nv, 32), device=dev)))
     with pytest.raises(ValueError, match="input channels"):
         inv(x2.replace_feature(torch.zeros((x2.feat.shape[0], 8), device=dev)))
-    assert not x0.transposed
+    assert _with_nbrT(x0) == []
     calls = {}
     _count(monkeypatch, ops, "sparse_conv_index", calls)
     _count(monkeypatch, ops, "sparse_conv_index_transpose", calls)
     y = inv(x3)
     assert y.coors is x0.coors and y.offsets is x0.offsets and y.spatial_shape == x0.spatial_shape and y.feat.shape == (Nv, 16)
-    assert y.rulebooks is x0.rulebooks and y.transposed is x0.transposed and y.sources is x0.sources
+    assert y.rulebooks is x0.rulebooks
     z = again(y)
     assert calls == {"sparse_conv_index_transpose": 1}, calls    # no new rulebook: the submanifold key of this resolution is a hit
-    assert sorted(x0.rulebooks) == ["down1", "subm1", "subm2"] and all(len(v) == 6 for v in x0.rulebooks.values())
-    assert sorted(x0.transposed) == ["down1"] and x0.transposed["down1"][0] is x0.rulebooks["down1"][4]
+    assert sorted(x0.rulebooks) == ["down1", "subm1", "subm2"] and all(isinstance(v, Rulebook) for v in x0.rulebooks.values())
+    assert _with_nbrT(x0) == ["down1"] and x0.rulebooks["down1"].collisions == 0
     # the values: the reference chain
     oc, oo, nbr_d = ref.index_vec(coors, off, G, (2, 2, 2), (2, 2, 2), (0, 0, 0))
     nbr_s = ref.index_vec(coors, off, G, (3, 3, 3), subm=True)[2]
     nbrT_d, col = gref.index_transpose_vec(nbr_d, Nv)
     assert col == 0 and (nbrT_d < 0).all(1).any()
-    _eq_int(x0.transposed["down1"][1], nbrT_d, "cached nbrT")
+    _eq_int(x0.rulebooks["down1"].nbrT, nbrT_d, "cached nbrT")
     np_ = lambda m: (m.weight.detach().cpu().numpy(), None if m.bias is None else m.bias.detach().cpu().numpy())
     want = pref.inverse_conv(x3.feat.cpu().numpy(), nbrT_d, *np_(inv), None, True)
     _eq_f(y.feat, want, "inverse layer")
@@ -349,13 +354,13 @@ def test_layer_pairing(dev, orc, monkeypatch):
     for m in (subm, down, subm2, inv, again):
         m.requires_grad_(True)
     calls.clear()
-    x0g = SparseTensor(_t(feat, dev, True), x0.coors, x0.offsets, G, x0.rulebooks, x0.transposed, x0.sources)
+    x0g = SparseTensor(_t(feat, dev, True), x0.coors, x0.offsets, G, x0.rulebooks)
     out = again(inv(subm2(down(subm(x0g)))))
     assert calls == {}, calls                                    # down1's nbrT is there already; the others wait for the backward
     out.feat.sum().backward()
     assert calls == {"sparse_conv_index_transpose": 2}, calls    # subm1, subm2; down1 reused by the encoder's backward
-    assert sorted(x0.transposed) == ["down1", "subm1", "subm2"] and x0g.feat.grad is not None
-    # a pool as the partner; a hand-built tensor without `sources` is refused with a message
+    assert _with_nbrT(x0) == ["down1", "subm1", "subm2"] and x0g.feat.grad is not None
+    # a pool as the partner; a hand-built tensor that carries the cache goes through the inverse layer like the layer's own
     pool = SparseMaxPool3d(2, indice_key="pool1")
     assert pool.stride == (2, 2, 2) and pool.padding == (0, 0, 0) and not list(pool.parameters())
     xp = pool(x1)
@@ -365,13 +370,43 @@ def test_layer_pairing(dev, orc, monkeypatch):
     yp = invp(xp)
     assert yp.coors is x0.coors
     _eq_f(yp.feat, pref.inverse_conv(xp.feat.cpu().numpy(), nbrT_d, np_(invp)[0]), "inverse of a pool")
-    with pytest.raises(ValueError, match="sources"):
-        invp(SparseTensor(xp.feat, xp.coors, xp.offsets, xp.spatial_shape, xp.rulebooks, xp.transposed))
+    yh = invp(SparseTensor(xp.feat, xp.coors, xp.offsets, xp.spatial_shape, xp.rulebooks))
+    assert yh.coors is x0.coors and yh.offsets is x0.offsets
+    _eq_bits(yh.feat, yp.feat.cpu().numpy(), "inverse of a pool, hand-built input")
     # a pool and a convolution of one geometry may share a key
     shared = SparseMaxPool3d(2, 2, 0, indice_key="down1")
     calls.clear()
     xs = shared(x1)
     assert calls == {} and xs.coors is x2.coors
+
+
+def test_layers_without_a_key_build_each_table_once(dev, orc, monkeypatch):
+    """indice_key=None: an uncached record per forward, one rulebook and one transposed rulebook per layer, nothing left in the cache."""
+    import torch
+    from sad_amd import ops
+    from sad_amd.spconv import SparseConv3d, SparseTensor, SubMConv3d
+    coors, off, G = sc.FAMILIES["random030"][0]()
+    feat = sc.make_feat(len(coors), 4, 6)
+    torch.manual_seed(4)
+    calls = {}
+    _count(monkeypatch, ops, "sparse_conv_index", calls)
+    _count(monkeypatch, ops, "sparse_conv_index_transpose", calls)
+    for layer in (SubMConv3d(4, 8, 3), SparseConv3d(4, 8, 2, 2, 0)):
+        layer = layer.to(dev).requires_grad_(True)
+        x = SparseTensor(_t(feat, dev, True), _t(coors, dev), _t(off, dev), G)
+        calls.clear()
+        y = layer(x)
+        assert calls == {"sparse_conv_index": 1}, calls
+        y.feat.sum().backward()
+        assert calls == {"sparse_conv_index": 1, "sparse_conv_index_transpose": 1}, calls
+        assert x.rulebooks == {} and y.rulebooks is x.rulebooks
+        nbr = ref.index_vec(coors, off, G, layer.kernel_size, layer.stride, layer.padding, layer.subm)[2]
+        W, b = _wb(layer)
+        out = ref.conv(feat, nbr, W, b)
+        _eq_f(y.feat, out, "layer without a key")
+        nbrT, col = gref.index_transpose_vec(nbr, len(coors))
+        assert col == 0
+        _eq_f(x.feat.grad, gref.grad_input(np.ones(out.shape, F), nbrT, W), "input gradient without a key")
 
 
 def _unet(dev):
@@ -446,7 +481,7 @@ def _unet_reference(net, feat, coors, off, G, lossw):
 
 def _run_unet(dev, coors, off, G, seed, stream=None):
     import torch
-    from sad_amd.spconv import SparseTensor
+    from sad_amd.spconv import Rulebook, SparseTensor
     net = _unet(dev).requires_grad_(True)
     feat = sc.make_feat(len(coors), 4, seed)
     lossw = np.random.default_rng(seed).integers(-2, 3, (len(coors), 8)).astype(F)
@@ -467,8 +502,8 @@ def _run_unet(dev, coors, off, G, seed, stream=None):
         _within(net[li].weight.grad, gw, mag, n, f"U-Net layer {li} grad_W")
         if net[li].bias is not None:
             _within(net[li].bias.grad, gb, magb, rows, f"U-Net layer {li} grad_bias")
-    assert sorted(x0.rulebooks) == ["down1", "down2", "subm1", "subm2", "subm3"] and all(len(v) == 6 for v in x0.rulebooks.values())
-    assert sorted(x0.transposed) == sorted(x0.rulebooks)
+    assert sorted(x0.rulebooks) == ["down1", "down2", "subm1", "subm2", "subm3"] and all(isinstance(v, Rulebook) for v in x0.rulebooks.values())
+    assert _with_nbrT(x0) == sorted(x0.rulebooks)
     return net, x0, y
 
 

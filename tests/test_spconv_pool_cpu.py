@@ -169,7 +169,10 @@ def test_layers_construct_and_refuse_without_a_gpu(sad):
     assert sad.SparseMaxPool3d is SparseMaxPool3d and sad.SparseInverseConv3d is SparseInverseConv3d and sad.sparse_max_pool is ops.sparse_max_pool
     assert callable(autograd.sparse_max_pool)
     x = SparseTensor(torch.zeros((2, 4)), torch.zeros((2, 3), dtype=torch.int32), torch.tensor([0, 2], dtype=torch.int32), (4, 4, 4))
-    assert x.sources == {} and x.replace_feature(x.feat).sources is x.sources
+    assert x.rulebooks == {} and x.replace_feature(x.feat).rulebooks is x.rulebooks
+    for gone in ("transposed", "sources"):
+        with pytest.raises(TypeError):
+            SparseTensor(x.feat, x.coors, x.offsets, (4, 4, 4), {}, **{gone: {}})
     with pytest.raises(ValueError, match="no rulebook"):
         SparseInverseConv3d(4, 4, 3, "k")(x)
     with pytest.raises(RuntimeError, match="no CPU path"):

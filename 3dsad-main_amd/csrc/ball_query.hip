@@ -18,19 +18,60 @@ struct BQParams {
     int32_t *cnt[SAD_MAX_RADII];   // optional: number of accepted points per centroid, capped at nsample
 };
 
-constexpr int BQ_WAVES = 4;
+constexpr int BQ_WAVES = 8;
+constexpr int BQ_CW = 2;             // centroids of a wave
+constexpr int BQ_BLOCK = BQ_WAVES * BQ_CW;
+constexpr int BQ_STAGE_MAX = 2048;   // staged form: three planes of ceil64(N) floats, at most 24 KB of LDS
+constexpr int BQ_STAGE_LOADS = BQ_STAGE_MAX / (BQ_WAVES * 64);
 
-template <int NR, int CW>
+// STAGED: the workgroup copies its scene into LDS once (planes x | y | z of Np = ceil64(N) floats, the tail holds
+// NaN, which no radius accepts) and the scan reads LDS only; the next chunk's reads are issued before the current
+// chunk's tests.  !STAGED (N > BQ_STAGE_MAX): the chunks come straight from global memory.
+// Per centroid and chunk one ballot against the centroid's widest r^2 gates the per-radius blocks.
+// Eight waves of two centroids: with the scene in LDS a chunk read is cheap, and the scan is a chain of ballots, scalar
+// tests and branches that only more resident waves hide (DESIGN.md §3.2 has the shapes that were measured).
+template <int NR, int CW, bool STAGED>
 __global__ __launch_bounds__(BQ_WAVES * 64) void ball_query_kernel(
     const float *__restrict__ xyz, const float *__restrict__ new_xyz,
     const float *__restrict__ radius_pc, BQParams prm, int N, int M) {
+    extern __shared__ float bq_lds[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int b = blockIdx.y;
-    const int m0 = (blockIdx.x * BQ_WAVES + wave) * CW;
     const float *p = xyz + (size_t)b * N * 3;
+    const int Np = (N + 63) & ~63;
+    const float *sx = bq_lds, *sy = bq_lds + Np, *sz = bq_lds + 2 * Np;
 
-    float cx[CW], cy[CW], cz[CW], r2[CW][NR];
+    if (STAGED) {
+        // point j by thread j mod 512: a wave reads 768 contiguous bytes per step; every load is issued before the first store
+        float vx[BQ_STAGE_LOADS], vy[BQ_STAGE_LOADS], vz[BQ_STAGE_LOADS];
+#pragma unroll
+        for (int k = 0; k < BQ_STAGE_LOADS; ++k) {
+            if (k * BQ_WAVES * 64 >= Np) break;          // workgroup-uniform
+            const int j = k * BQ_WAVES * 64 + (int)threadIdx.x;
+            const int jj = j < N ? j : N - 1;
+            vx[k] = p[jj * 3 + 0];
+            vy[k] = p[jj * 3 + 1];
+            vz[k] = p[jj * 3 + 2];
+        }
+#pragma unroll
+        for (int k = 0; k < BQ_STAGE_LOADS; ++k) {
+            if (k * BQ_WAVES * 64 >= Np) break;
+            const int j = k * BQ_WAVES * 64 + (int)threadIdx.x;
+            if (j < Np) {
+                const bool real = j < N;
+                bq_lds[j] = real ? vx[k] : __builtin_nanf("");
+                bq_lds[Np + j] = real ? vy[k] : __builtin_nanf("");
+                bq_lds[2 * Np + j] = real ? vz[k] : __builtin_nanf("");
+            }
+        }
+        __syncthreads();
+    }
+
+    const int m0 = (blockIdx.x * BQ_WAVES + wave) * CW;
+    if (m0 >= M) return;      // wave-uniform; no barrier follows
+
+    float cx[CW], cy[CW], cz[CW], r2[CW][NR], rw[CW];
     int cnt[CW][NR], first[CW][NR];
     bool active[CW];
     int ndone = 0;
@@ -42,30 +83,50 @@ __global__ __launch_bounds__(BQ_WAVES * 64) void ball_query_kernel(
         cx[c] = q[0];
         cy[c] = q[1];
         cz[c] = q[2];
+        rw[c] = -__builtin_inff();
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
             float rad = prm.radii[r];
             if (radius_pc) rad = rad * radius_pc[(size_t)b * M + m];
             r2[c][r] = rad * rad;
+            rw[c] = r2[c][r] > rw[c] ? r2[c][r] : rw[c];      // the widest r^2; a NaN one never wins and accepts nothing
             first[c][r] = 0;
             cnt[c][r] = active[c] ? 0 : prm.nsample[r];
             if (!active[c]) ++ndone;
         }
     }
 
+    float px, py, pz;
+    if (STAGED) {
+        px = sx[lane];
+        py = sy[lane];
+        pz = sz[lane];
+    }
     for (int base = 0; base < N && ndone < CW * NR; base += 64) {
         const int j = base + lane;
-        const bool valid = j < N;
-        const int jj = valid ? j : N - 1;
-        const float px = p[jj * 3 + 0], py = p[jj * 3 + 1], pz = p[jj * 3 + 2];
+        const bool valid = STAGED || j < N;
+        float qx, qy, qz;
+        if (STAGED) {
+            const int jn = base + 64 < Np ? j + 64 : j;      // the next chunk (the last one reads itself again)
+            qx = sx[jn];
+            qy = sy[jn];
+            qz = sz[jn];
+        } else {
+            const int jj = valid ? j : N - 1;
+            px = p[jj * 3 + 0];
+            py = p[jj * 3 + 1];
+            pz = p[jj * 3 + 2];
+        }
 #pragma unroll
         for (int c = 0; c < CW; ++c) {
             const float d = sad::d2f(px, py, pz, cx[c], cy[c], cz[c]);
+            if (__ballot(valid && (d < rw[c])) == 0ull) continue;      // wave-uniform: no radius of this centroid accepts a point of the chunk
 #pragma unroll
             for (int r = 0; r < NR; ++r) {
+                if (cnt[c][r] >= prm.nsample[r]) continue;      // wave-uniform: full
                 const bool in = valid && (d < r2[c][r]);
                 const unsigned long long mask = __ballot(in);
-                if (mask != 0ull && cnt[c][r] < prm.nsample[r]) {  // wave-uniform
+                if (mask != 0ull) {  // wave-uniform
                     const int slot = cnt[c][r] + __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
                     if (in && slot < prm.nsample[r])
                         prm.idx[r][((size_t)b * M + (m0 + c)) * prm.nsample[r] + slot] = j;
@@ -74,6 +135,11 @@ __global__ __launch_bounds__(BQ_WAVES * 64) void ball_query_kernel(
                     if (cnt[c][r] >= prm.nsample[r]) ++ndone;
                 }
             }
+        }
+        if (STAGED) {
+            px = qx;
+            py = qy;
+            pz = qz;
         }
     }
     // SPEC.md §3 padding: remaining slots repeat the first accepted index (0 if none).
@@ -94,10 +160,10 @@ __global__ __launch_bounds__(BQ_WAVES * 64) void ball_query_kernel(
 template <int NR>
 void launch_bq(const float *xyz, const float *new_xyz, const float *radius_pc, const BQParams &prm,
                int B, int N, int M, hipStream_t st) {
-    constexpr int CW = 4;
-    dim3 grid((M + BQ_WAVES * CW - 1) / (BQ_WAVES * CW), B);
-    hipLaunchKernelGGL((ball_query_kernel<NR, CW>), grid, dim3(BQ_WAVES * 64), 0, st, xyz, new_xyz,
-                       radius_pc, prm, N, M);
+    dim3 grid((M + BQ_BLOCK - 1) / BQ_BLOCK, B);
+    const size_t lds = N <= BQ_STAGE_MAX ? (size_t)3 * ((N + 63) & ~63) * sizeof(float) : 0;
+    auto kernel = N <= BQ_STAGE_MAX ? ball_query_kernel<NR, BQ_CW, true> : ball_query_kernel<NR, BQ_CW, false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(BQ_WAVES * 64), lds, st, xyz, new_xyz, radius_pc, prm, N, M);
 }
 
 // ---- kNN: one wave per centroid; lane i holds the i-th best (d2, j) so far -------------------
